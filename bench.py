@@ -3,6 +3,14 @@
 Headline benchmark: signal samples/sec/GPU at chunk=10000, batch=512 (BASELINE.json `metric`).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model hac|fast|sup|sup_lstm] [--decoder viterbi|beam] [--quantize]
+                    [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline needs: set up, warm up, time the resident leg (below: the median of its regions of exactly K
+steps each), print the JSON line. Everything else
+(the H2D leg, roofline, per_call_1, cpu_baseline + parity, e2e, other_configs, config1_ctc) runs under `--full`; without it those
+keys of the line are null. `--dump-outputs DIR` writes what the last timed step computed - the decoder planes of its batch of --batch
+chunks (beam: sequence, qstring, moves; viterbi: path, moves), float32 - to DIR/<name>.npy; the inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 One "step" = one pass of the hot path over one synthetic batch: fp16 signal [512, 10000] -> HIP encoder (conv x3,
 LSTM x5, LinearCRFEncoder) -> HIP CRF decode -> int8 moves / sequence / qstring on the host. THREE distinct batches rotate
@@ -11,7 +19,7 @@ through the steps. Weights are seeded random-init tensors of the named architect
 Two kinds of timed region, each of EXACTLY K steps bracketed by barrier + synchronize, MAX over ranks:
   * `value` / `ms_per_step`: input batches already resident in HBM when the region starts (the bench contract: a PCIe-inclusive
     rate is never `value`);
-  * `with_h2d` / `value_with_h2d`: the same steps with each batch copied pinned-host -> device on a copy stream inside the step
+  * `with_h2d` / `value_with_h2d` (`--full`): the same steps with each batch copied pinned-host -> device on a copy stream inside the step
     ("H2D of fp16 signal included"). The copy of call k+1 overlaps the kernels of call k; the FIRST call's batch is
     staged before the clock starts, as the product's reader thread has it (crf/basecall.py). This leg runs FIRST.
 With the driver's flags (--steps 20) a region is five engine calls = 0.24 s, and one hiccup moved its mean by 46 % (round 5: 17.30 ms
@@ -21,7 +29,7 @@ at most 5) and the MEDIAN region is reported; every region's figure is in `regio
 The warm-up is W steps AND at least --warmup-seconds of engine calls (clocks, instruction caches and the allocator settle in
 about a second; a 20-step run used to be timed cold: mean 20.3 ms against a median of 16.3).
 
-More legs in the same JSON line (rank 0, N = 1 only; each bounded to a few seconds):
+More legs in the same JSON line (`--full` only; rank 0, N = 1 only; each bounded to a few seconds):
   per_call_1    -- the reference's call shape: ONE batch of 512 chunks per engine call (what `--per-call 1` or a short input runs; the
                    product path groups batches into the default leg's calls of 2048 chunks), with the roofline of the kernel that serves it
   other_configs -- the other BASELINE.json configurations (fast 512 x 10000, sup transformer 256 x 12000, sup LSTM-1024
@@ -31,7 +39,7 @@ N > 1: `python bench.py --gpus N` spawns N ranks itself (one process per GPU, RC
 under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` the ranks come from the environment. Read
 chunks shard embarrassingly, every rank runs the same per-GPU workload, no data-path collective -> "scaling": "weak".
 
-The JSON line also carries
+With `--full` the JSON line also carries
   roofline     -- dominant kernel's algorithmic FLOP/s from HIP-event timings on the engine stream (kernels running alone)
   cpu_baseline -- the CPU oracle (PyTorch-CPU fp32 restatement of bonito/nn.py + C Viterbi) on a bounded sample (rank 0, N=1)
 """
@@ -107,7 +115,15 @@ def parse(argv=None):
     ap.add_argument("--no-h2d-leg", action="store_true", help="skip the second timed region (H2D inside the step)")
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE",
                     help="library tuning option (bh_set_option), e.g. beam_fork=1; for A/B runs, not part of the contract")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the H2D leg, roofline, per_call_1, cpu_baseline + parity, e2e, "
+                         "other_configs, config1_ctc (off: set up, warm up, time the resident leg, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the decoder's int8 planes of its batch, "
+                         "as float32) to DIR/<name>.npy")
     a = ap.parse_args(argv)
+    if not a.full:            # a plain run times the headline only
+        a.no_h2d_leg = a.no_side_legs = a.no_cpu_baseline = True
     a.batch = a.batch or (256 if a.model in ("sup", "sup_lstm") else 512)
     a.chunk = a.chunk or (12000 if a.model == "sup" else 20000 if a.model == "sup_lstm" else 10000)
     lanes_given = a.lanes > 0
@@ -382,7 +398,7 @@ def other_configs(a, hard_timeout=240.0):
             continue
         # every child carries its own small CPU-oracle sample (`parity`: config 5 = 256 x 20000 on BOTH candidate graphs included) and
         # runs ONE timed region: the steps of these legs are long enough (sup: 12 x 60 ms) or many enough (fast: 384)
-        cmd = [sys.executable, os.path.abspath(__file__)] + flags + ["--no-h2d-leg", "--no-side-legs", "--repeats", "1",
+        cmd = [sys.executable, os.path.abspath(__file__)] + flags + ["--full", "--no-h2d-leg", "--no-side-legs", "--repeats", "1",
                                                                      "--parity-chunks", str(OTHER_PARITY_CHUNKS.get(name, 2)),
                                                                      "--warmup-seconds", "1.0", "--decoder", a.decoder]
         log("other config: " + " ".join(flags))
@@ -502,6 +518,36 @@ def config1_leg(hard_timeout=120.0):
         return {"error": "exceeded %.0f s" % hard_timeout}
 
 
+def input_batches(a, dev, rank=0):
+    """The N_BATCHES seeded fp16 input batches of the timed legs (one engine call of a.call_batch chunks each); timed call i runs
+    batch i % N_BATCHES."""
+    import torch
+    gen = torch.Generator(device=dev).manual_seed(25 + rank)
+    return [torch.randn(a.call_batch, 1, a.chunk, generator=gen, device=dev).half() for _ in range(N_BATCHES)]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, planes, decoder, batch):
+    """`--dump-outputs DIR`: the decoder planes of the last timed engine call (CPU int8 [N, T] each, as `run` returns them) cut to the
+    last step = its last `batch` chunks, written as float32 DIR/<name>.npy. Beam search fills (sequence, qstring, moves); Viterbi writes
+    only planes 1 and 2 (path, moves). Above 64 MB in all, a fixed seeded sample of chunks (rows) is written instead."""
+    import numpy as np
+    named = [("sequence", planes[0]), ("qstring", planes[1]), ("moves", planes[2])] if decoder == "beam" else \
+            [("path", planes[1]), ("moves", planes[2])]
+    named = [(k, v[-batch:].numpy()) for k, v in named]
+    n, t = named[0][1].shape
+    rows = np.arange(n)
+    if n * t * 4 * len(named) > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES // (t * 4 * len(named)))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in named:
+        np.save(os.path.join(dirname, k + ".npy"), v[rows].astype(np.float32))
+    return [k for k, _ in named], len(rows)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N copies of this command, one per GPU, wired up like
     torch.distributed.run does (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT); rank 0 prints the JSON line."""
@@ -618,8 +664,7 @@ def main():
     model = build_model(a.model, a.call_batch, a.chunk)
     model.use_koi(batchsize=a.call_batch, chunksize=a.chunk, quantize=a.quantize)
     model = model.half().to(dev)
-    gen = torch.Generator(device=dev).manual_seed(25 + rank)
-    signals = [torch.randn(a.call_batch, 1, a.chunk, generator=gen, device=dev).half() for _ in range(N_BATCHES)]
+    signals = input_batches(a, dev, rank)
     host_signals = [s.cpu().pin_memory() for s in signals]
     copy_stream = torch.cuda.Stream(dev)
 
@@ -706,9 +751,11 @@ def main():
     def run(steps, h2d=False, marks=None, reset=True):
         """`steps` engine calls (a.per_call batches each) of the hot path, software-pipelined: inside a lane encoder(i+1) overlaps
         decode(i) on two HIP streams, and the lanes run round-robin. Every step's int8 outputs are on the host when this
-        returns. `marks`: list that receives one timing event per step, recorded behind the step's decode + D2H."""
+        returns, and the planes of the LAST call submitted are returned. `marks`: list that receives one timing event per step,
+        recorded behind the step's decode + D2H."""
         if reset:
             reset_lanes()
+        last = None
         for i in range(steps):
             ln = lanes[i % len(lanes)]
             nxt = i + len(lanes)                   # this lane's next step
@@ -719,7 +766,7 @@ def main():
             with torch.cuda.stream(ln.dec_stream):
                 ln.dec_stream.wait_event(ev)
                 sc.record_stream(ln.dec_stream)
-                ln.tickets[k] = ln.decs[k].submit(sc)
+                ln.tickets[k] = last = ln.decs[k].submit(sc)
                 if marks is not None:
                     m = torch.cuda.Event(enable_timing=True)
                     m.record(ln.dec_stream)
@@ -729,7 +776,9 @@ def main():
         for ln in lanes:
             for tk in ln.tickets:
                 if tk is not None:
-                    out = tk.result()
+                    res = tk.result()
+                    if tk is last:
+                        out = res
         return out
 
     def barrier():
@@ -742,6 +791,8 @@ def main():
         for ln in lanes:
             ln.model._hip.check()
 
+    last_planes = {}          # leg (h2d or not) -> decoder planes of the last call of its latest region
+
     def timed(h2d):
         """ONE timed region of exactly a.steps steps -> (elapsed seconds MAX over ranks, median ms per step, per-call ms list)."""
         calls = a.steps // a.per_call
@@ -751,7 +802,7 @@ def main():
         barrier()
         marks = []
         t0 = time.perf_counter()
-        run(calls, h2d, marks, reset=False)           # exactly a.steps batches
+        last_planes[h2d] = run(calls, h2d, marks, reset=False)          # exactly a.steps batches
         barrier()
         el = time.perf_counter() - t0
         el = parallel.max_over_ranks(el, device="cpu" if oversubscribed else dev)
@@ -792,6 +843,9 @@ def main():
     log("timed leg 2 (inputs resident in HBM), %d region(s) of %d steps" % (a.repeats, a.steps))
     elapsed, med, regs = timed_leg(False, "resident")
     log("timed legs done: %.2f ms/step (median step %.2f ms)" % (1e3 * elapsed / a.steps, med))
+    if a.dump_outputs and rank == 0:
+        names, rows = dump_outputs(a.dump_outputs, last_planes[False], a.decoder, a.batch)
+        log("last step's outputs (%d chunks): %s -> %s" % (rows, ", ".join(names), a.dump_outputs))
 
     # ---- roofline leg: per-kernel-class HIP-event timings on the engine's stream (after the timed regions)
     def roofline_of(mdl, dec, sigs, call_batch, per_call, pipelined=None):
@@ -886,7 +940,7 @@ def main():
 
     roof = None
     breakdown = None
-    if rank == 0:
+    if rank == 0 and a.full:
         roof, breakdown = roofline_of(model, decs[0], signals, a.call_batch, a.per_call,
                                       pipelined=lambda: run(max(4 * len(lanes), min(a.steps // a.per_call, 12)), not a.no_h2d_leg))
 
@@ -933,7 +987,8 @@ def main():
         lanes, a.per_call, a.call_batch = lanes_main, per_call_main, call_batch_main
 
     if rank == 0:
-        log("roofline leg done; cpu baseline + parity")
+        if a.full:
+            log("roofline leg done; cpu baseline + parity")
         samples = a.batch * a.chunk * a.steps * world
         cpu = par = None
         if not (a.no_cpu_baseline or world > 1):

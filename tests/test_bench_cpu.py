@@ -61,6 +61,45 @@ def test_batches_per_engine_call(bench, monkeypatch):
     assert parsed("--model", "sup", "--steps", "7").per_call == 1
 
 
+def test_plain_run_leaves_the_side_legs_to_full(bench, monkeypatch):
+    """A plain run times the headline only - no H2D leg, no side legs, no CPU baseline - unless --full asks for them."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "20", "--warmup", "5"])
+    a = bench.parse()
+    assert not a.full and a.no_h2d_leg and a.no_side_legs and a.no_cpu_baseline and a.dump_outputs is None and a.steps == 20
+    assert a.repeats == 4                   # the headline is the median of regions of exactly --steps steps, as under --full
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and not (a.no_h2d_leg or a.no_side_legs or a.no_cpu_baseline) and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-side-legs", "--steps", "20"])
+    a = bench.parse()
+    assert a.no_side_legs and not a.no_h2d_leg and a.repeats == 4    # five engine calls per region, >= 16 calls per leg
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "20", "--repeats", "3"])
+    assert bench.parse().repeats == 3
+
+
+def test_dump_outputs_writes_the_last_step_as_float32(bench, tmp_path, monkeypatch):
+    """--dump-outputs: the last --batch chunks of the last engine call's planes, as float32; Viterbi fills path and moves only; above the
+    size limit a fixed seeded sample of chunks."""
+    import numpy as np
+    import torch
+    planes = torch.randint(-128, 128, (3, 2048, 50), generator=torch.Generator().manual_seed(1), dtype=torch.int8)
+    names, rows = bench.dump_outputs(str(tmp_path / "b"), (planes[0], planes[1], planes[2]), "beam", 512)
+    assert names == ["sequence", "qstring", "moves"] and rows == 512
+    for i, n in enumerate(names):
+        v = np.load(str(tmp_path / "b" / (n + ".npy")))
+        assert v.dtype == np.float32 and np.array_equal(v, planes[i, -512:].numpy().astype(np.float32))
+    names, _ = bench.dump_outputs(str(tmp_path / "v"), (planes[0], planes[1], planes[2]), "viterbi", 512)
+    assert names == ["path", "moves"] and sorted(os.listdir(tmp_path / "v")) == ["moves.npy", "path.npy"]
+    assert np.array_equal(np.load(str(tmp_path / "v" / "path.npy")), planes[1, -512:].numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100 * 50 * 4 * 3)
+    _, rows = bench.dump_outputs(str(tmp_path / "s1"), (planes[0], planes[1], planes[2]), "beam", 512)
+    bench.dump_outputs(str(tmp_path / "s2"), (planes[0], planes[1], planes[2]), "beam", 512)
+    one, two = (np.load(str(tmp_path / s / "moves.npy")) for s in ("s1", "s2"))
+    assert rows == 100 and one.shape == (100, 50) and np.array_equal(one, two)
+    last = planes[2, -512:].numpy().astype(np.float32)
+    assert all((last == r).all(axis=1).any() for r in one)          # every sampled row is a row of the last step
+
+
 def test_pmc_traffic_table_names_the_roofline_kernel(bench):
     table = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
     entry = table["lstm_layer_wg_kernel"]

@@ -575,14 +575,14 @@ def test_basecall_lanes_give_identical_results():
 
 
 def test_bench_default_mode_runs_and_reports_the_contract_fields():
-    """`python bench.py` in its default mode (hac, four batches per engine call, paired recurrent kernel), shortened: one JSON line on
+    """`python bench.py --full` in its default mode (hac, four batches per engine call, paired recurrent kernel), shortened: one JSON line on
     stdout with the contract's fields, the roofline of the kernel the engine says it runs, no exchange timeout."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "8", "--warmup", "4", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "8", "--warmup", "4", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

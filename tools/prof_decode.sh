@@ -1,12 +1,12 @@
 #!/bin/bash
 # Decode stage alone under rocprofv3: kernel trace (per-kernel time) + SQ counter passes of tools/decode_bench.py.
-#   usage: bash tools/prof_decode.sh <tag> [N T C] [viterbi]     (FETCH_SIZE / WRITE_SIZE: KiB per dispatch, own passes)     outputs: gpurun_out/prof_<tag>/decode_{kernel_stats.csv,sq_counters.txt}
+#   usage: bash tools/prof_decode.sh <tag> [N T C] [viterbi]     (FETCH_SIZE / WRITE_SIZE: KiB per dispatch, own passes)     outputs: $OUT/prof_<tag>/decode_{kernel_stats.csv,sq_counters.txt}, default out/
 TAG=${1:-r05}
 shift
 ARGS=${@:-2048 1667 1024}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
-OUT=$R/gpurun_out/prof_$TAG
+OUT=${OUT:-$R/out}/prof_$TAG
 mkdir -p $OUT
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o dec -- python $R/tools/decode_bench.py $ARGS > $OUT/decode_bench.log 2>&1
 python $R/tools/rocprof_summary.py $(find $OUT/trace -name "*.db" | head -1) $OUT/decode_kernel_stats.csv | head -8

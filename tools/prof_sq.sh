@@ -1,13 +1,13 @@
 #!/bin/bash
 # SQ counters of the recurrent kernel (where do a wave's cycles go: matrix pipe busy, vector ALU issuing, waiting), one rocprofv3 --pmc pass
-# each over one 1024-chunk step (tools/profile_step.py), summarised per kernel into gpurun_out/prof_<tag>/sq_counters.txt.
+# each over one 1024-chunk step (tools/profile_step.py), summarised per kernel into $OUT/prof_<tag>/sq_counters.txt (default out/).
 #   usage: bash tools/prof_sq.sh <tag> [profile_step.py arguments, default: --batch 1024 (hac)]
 TAG=${1:-r03}
 shift
 PS=${@:---batch 1024}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
-OUT=$R/gpurun_out/prof_$TAG
+OUT=${OUT:-$R/out}/prof_$TAG
 mkdir -p $OUT
 rocprofv3 -L 2>/dev/null | grep -o "SQ_[A-Z_0-9]*" | sort -u > $OUT/sq_counter_names.txt
 : > $OUT/sq_counters.txt
