@@ -3,9 +3,9 @@ import sys
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
 from bonito_amd import __version__
-from bonito_amd.cli import basecaller
+from bonito_amd.cli import basecaller, evaluate
 
-modules = ["basecaller"]
+modules = ["basecaller", "evaluate"]
 
 
 def main(argv=None):
@@ -15,7 +15,7 @@ def main(argv=None):
     sub.required = True
     for name in modules:
         mod = globals()[name]
-        p = sub.add_parser(name, parents=[mod.argparser()])
+        p = sub.add_parser(name, parents=[mod.argparser()], description=mod.argparser().description)
         p.set_defaults(func=mod.main)
     args = parser.parse_args(argv)
     args._argv = list(sys.argv[1:] if argv is None else argv)[1:]      # the sub-command's own arguments (multi-GPU re-launch)

@@ -75,6 +75,51 @@ class CTC_CRF:
         """Log partition function per chunk of koi-layout scores [N, T, 4S] (reference crf/model.py:47-52)."""
         return hip_decode.logz(scores.contiguous(), blank_score)
 
+    def normalise(self, scores):
+        """scores - logZ / T on the reference layout [T, N, 5S] (reference crf/model.py:54-55). The koi layout keeps its stay
+        score outside the tensor, so it cannot be normalised in place; ``ctc_loss`` never needs the normalised copy."""
+        if scores.shape[-1] != self.n_score():
+            raise ValueError("normalise needs the reference layout [T, N, %d]" % self.n_score())
+        logz = hip_decode.logz_any(scores, self.state_len).to(scores.dtype)
+        return scores - logz[:, None] / len(scores)
+
+    def prepare_ctc_scores(self, scores, targets):
+        """The plain torch gather of the reference (crf/model.py:110-124), kept for API parity and for tests: the HIP scans gather
+        the same edges inside the kernel and never build these [T, N, L] tensors."""
+        targets = torch.clamp(targets - 1, 0)
+        T, N, C = scores.shape
+        scores = scores.to(torch.float32)
+        n = targets.size(1) - (self.state_len - 1)
+        stay_indices = sum(
+            targets[:, i:n + i] * self.n_base ** (self.state_len - i - 1)
+            for i in range(self.state_len)
+        ) * len(self.alphabet)
+        move_indices = stay_indices[:, 1:] + targets[:, :n - 1] + 1
+        stay_scores = scores.gather(2, stay_indices.expand(T, -1, -1))
+        move_scores = scores.gather(2, move_indices.expand(T, -1, -1))
+        return stay_scores, move_scores
+
+    def ctc_loss(self, scores, targets, target_lengths, loss_clip=None, reduction="mean", normalise_scores=True,
+                 blank_score=None):
+        """-ln P(target | scores) / target_length per chunk (reference crf/model.py:126-139), forward value only.
+        scores: the reference layout [T, N, 5S], or the engine layout [N, T, 4S] with ``blank_score``; cuda fp16 (fp32 is
+        rounded to fp16). With ``normalise_scores`` no normalised copy is written: normalisation subtracts logZ / T from each
+        of the T edges of every path, so the loss is -(seq_logz(raw) - logZ(raw)) / target_length."""
+        if reduction not in ("mean", "none", None):
+            raise ValueError("Unknown reduction type {}".format(reduction))
+        logz = hip_decode.seq_logz(scores, targets, target_lengths, self.state_len, blank_score).double()
+        if normalise_scores:
+            logz = logz - hip_decode.logz_any(scores, self.state_len, blank_score)
+        loss = (-(logz / target_lengths.to(logz.device))).float()
+        if loss_clip:
+            loss = torch.clamp(loss, 0.0, loss_clip)
+        return loss.mean() if reduction == "mean" else loss
+
+    def ctc_viterbi_alignments(self, scores, targets, target_lengths, blank_score=None):
+        """Forced alignment (reference crf/model.py:141-143) -> int32 [N, T] on the CPU: the chain position (index of the
+        target's k-mer) occupied after every step; see ``bonito_amd.decode.seq_viterbi`` for the definition."""
+        return hip_decode.seq_viterbi(scores, targets, target_lengths, self.state_len, blank_score)[0]
+
 
 def conv(c_in, c_out, ks, stride=1, bias=False, activation=None, norm=None):
     return Convolution(c_in, c_out, ks, stride=stride, padding=ks // 2, bias=bias, activation=activation, norm=norm)
@@ -185,6 +230,29 @@ class SeqdistModel(Module):
 
     def decode(self, x):
         return self.decode_batch(x.unsqueeze(0))[0]
+
+    def head_blank_score(self):
+        """The fixed stay score of the CRF head (``LinearCRFEncoder.blank_score``), or None for a learned blank column."""
+        for m in self.encoder.modules():
+            if isinstance(m, LinearCRFEncoder):
+                return m.blank_score
+        return None
+
+    def loss(self, scores, targets, target_lengths, **kwargs):
+        """CTC-CRF loss of labelled chunks (reference crf/model.py:204-207), forward value only. ``scores``: this model's
+        engine output [N, T, 4S] (the head's blank score is filled in) or the reference layout [T, N, 5S]."""
+        if self.target_projection is not None:
+            targets = self.target_projection.to(targets.device)[targets.long()]
+        if scores.shape[-1] != self.seqdist.n_score():
+            kwargs.setdefault("blank_score", self.head_blank_score())
+        return self.seqdist.ctc_loss(scores, targets, target_lengths, **kwargs)
+
+    def seq_logprob(self, scores, sequences, blank_score=None):
+        """ln P(sequence | scores) per chunk of engine scores [N, T, 4S] -> CPU float64 [N]; ``sequences``: strings or a decoder's
+        int8 sequence plane. See ``bonito_amd.decode.seq_logprob``."""
+        if blank_score is None:
+            blank_score = self.head_blank_score()
+        return hip_decode.seq_logprob(scores, sequences, 2.0 if blank_score is None else blank_score)
 
     def to_dict(self, include_weights=False):
         if include_weights:

@@ -1466,6 +1466,35 @@ extern "C" int bh_crf_logz(const void* scores, int N, int T, int state_len, floa
     BH_REQUIRE(scores && workspace && logz, "crf_logz: null pointer");
     return bh_k_crf_logz(scores, N, T, state_len, blank_score, workspace, logz, (hipStream_t)stream);
 }
+extern "C" size_t bh_crf_seq_workspace(int N, int T, int Lmax, int state_len) {
+    return bh_k_crf_seq_workspace(N, T, Lmax, state_len);
+}
+extern "C" int bh_crf_seq_logz(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
+                               long stride_t, const void* targets, int Lmax, int target_bytes, const int32_t* target_lengths,
+                               void* workspace, float* logz_out, void* stream) {
+    BH_REQUIRE(scores && targets && target_lengths && workspace && logz_out, "crf_seq_logz: null pointer");
+    return bh_k_crf_seq(scores, N, T, state_len, layout_5s, blank_score, stride_n, stride_t, targets, target_bytes, Lmax,
+                        target_lengths, workspace, logz_out, nullptr, 0, (hipStream_t)stream);
+}
+extern "C" int bh_crf_seq_logz_free(const void* scores, int N, int T, int state_len, float blank_score, long stride_n, long stride_t,
+                                    const void* targets, int Lmax, int target_bytes, const int32_t* target_lengths, void* workspace,
+                                    float* logz_out, void* stream) {
+    BH_REQUIRE(scores && targets && target_lengths && workspace && logz_out, "crf_seq_logz_free: null pointer");
+    return bh_k_crf_seq(scores, N, T, state_len, 0, blank_score, stride_n, stride_t, targets, target_bytes, Lmax, target_lengths,
+                        workspace, logz_out, nullptr, 2, (hipStream_t)stream);
+}
+extern "C" int bh_crf_seq_viterbi(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
+                                  long stride_t, const void* targets, int Lmax, int target_bytes, const int32_t* target_lengths,
+                                  void* workspace, int32_t* align_out, float* best_out, void* stream) {
+    BH_REQUIRE(scores && targets && target_lengths && workspace && align_out && best_out, "crf_seq_viterbi: null pointer");
+    return bh_k_crf_seq(scores, N, T, state_len, layout_5s, blank_score, stride_n, stride_t, targets, target_bytes, Lmax,
+                        target_lengths, workspace, best_out, align_out, 1, (hipStream_t)stream);
+}
+extern "C" int bh_crf_logz_dense(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
+                                 long stride_t, float* logz_out, void* stream) {
+    BH_REQUIRE(scores && logz_out, "crf_logz_dense: null pointer");
+    return bh_k_crf_logz_dense(scores, N, T, state_len, layout_5s, blank_score, stride_n, stride_t, logz_out, (hipStream_t)stream);
+}
 extern "C" int bh_signal_normalise(const int16_t* raw, const long* offsets, const float* cal_scale, const float* cal_offset, int n_reads,
                                    int strategy, double quantile_a, double quantile_b, double shift_mult, double scale_mult,
                                    double fixed_shift, double fixed_scale, int do_trim, double* shift, double* scale, int* weak,

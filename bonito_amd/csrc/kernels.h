@@ -51,6 +51,14 @@ int bh_k_crf_viterbi(const void* scores, int N, int T, int state_len, int layout
 int bh_k_crf_revcomp(const void* in, void* out, int N, int T, int state_len, int layout_5s, long s_n, long s_t,
                      hipStream_t stream);
 
+// seqdist.hip (mode 0: Log scan, 1: Max scan + traceback, 2: Log scan with a free start)
+size_t bh_k_crf_seq_workspace(int N, int T, int Lmax, int state_len);
+int bh_k_crf_seq(const void* scores, int N, int T, int state_len, int layout_5s, float blank, long s_n, long s_t,
+                 const void* targets, int target_bytes, int Lmax, const int* lens, void* workspace, float* out, int* align,
+                 int mode, hipStream_t stream);
+int bh_k_crf_logz_dense(const void* scores, int N, int T, int state_len, int layout_5s, float blank, long s_n, long s_t,
+                        float* out, hipStream_t stream);
+
 // beam.hip
 size_t bh_k_beam_workspace(int N, int T, int state_len);
 int bh_k_crf_logz(const void* scores, int N, int T, int state_len, float blank, void* workspace, double* logz_out,

@@ -232,3 +232,164 @@ def posterior_viterbi(scores, blank_score=2.0):
 def set_option(name, value):
     """Process-wide engine knob (bh_set_option), e.g. set_option("beam_fork", 0)."""
     _lib.check(_lib.lib().bh_set_option(name.encode(), int(value)), "bh_set_option")
+
+
+# ---- sequence likelihood and forced alignment (csrc/seqdist.hip) -------------------------------------------------------------
+
+def seq_layout(scores, state_len, blank_score=None):
+    """(N, T, layout_5s, stride_n, stride_t) of a score tensor for the bh_crf_seq_* entry points: the reference layout
+    [T, N, 5S] (expand_blanks, crf/model.py:49) or the engine's koi layout [N, T, 4S], which needs `blank_score`.
+    Strided / offset views are passed as they are (element strides); only the score axis must be dense."""
+    S = 4 ** int(state_len)
+    if scores.dim() != 3 or scores.shape[-1] not in (4 * S, 5 * S):
+        raise ValueError("scores of shape %s are neither [T, N, %d] nor [N, T, %d] (state_len %d)"
+                         % (tuple(scores.shape), 5 * S, 4 * S, state_len))
+    if scores.shape[-1] == 5 * S:
+        T, N = scores.shape[:2]
+        return N, T, 1, scores.stride(1), scores.stride(0)
+    if blank_score is None:
+        raise ValueError("koi-layout scores [N, T, %d] need blank_score" % (4 * S))
+    N, T = scores.shape[:2]
+    return N, T, 0, scores.stride(0), scores.stride(1)
+
+
+def check_targets(targets, target_lengths, state_len, free_start=False):
+    """Argument checks of the sequence scans, on the host and before anything is launched: labels in 0..4, every length within
+    [state_len, Lmax] (a free-start row may be shorter, down to 0). Returns (targets int8/int32 [N, Lmax], lengths int32 [N])."""
+    if targets.dim() != 2 or target_lengths.dim() != 1 or targets.shape[0] != target_lengths.shape[0]:
+        raise ValueError("targets must be [N, Lmax] and target_lengths [N]")
+    if targets.dtype not in (torch.int8, torch.int32):
+        if targets.dtype.is_floating_point:
+            raise TypeError("targets must be integer labels, got %s" % targets.dtype)
+        targets = targets.to(torch.int32)
+    lengths = target_lengths.to(torch.int32)
+    lo, hi = (int(lengths.min()), int(lengths.max())) if lengths.numel() else (0, 0)
+    if not free_start and lo < state_len:
+        raise ValueError("target length %d is shorter than state_len %d" % (lo, state_len))
+    if lo < 0 or hi > targets.shape[1]:
+        raise ValueError("target lengths must lie in 0..%d (got %d..%d)" % (targets.shape[1], lo, hi))
+    if targets.numel() and (int(targets.min()) < 0 or int(targets.max()) > 4):
+        raise ValueError("target labels must lie in 0..4")
+    return targets, lengths
+
+
+def _seq_call(scores, targets, target_lengths, state_len, blank_score, mode):
+    if scores.requires_grad:
+        from bonito_amd.nn import NoTorchCompute
+        raise NoTorchCompute("the sequence scans are forward values only: scores with requires_grad have no backward here")
+    N, T, five, s_n, s_t = seq_layout(scores, state_len, blank_score)
+    if mode == "free" and five:
+        raise ValueError("the free-start sum is defined on koi-layout scores [N, T, 4S]")
+    targets, lengths = check_targets(targets, target_lengths, state_len, free_start=(mode == "free"))
+    if targets.shape[0] != N:
+        raise ValueError("%d target rows for %d chunks" % (targets.shape[0], N))
+    if not scores.is_cuda:
+        raise _lib.HipEngineError("scores must live on a HIP device (no CPU fallback)")
+    if scores.dtype != torch.float16:
+        scores = scores.to(torch.float16)
+        N, T, five, s_n, s_t = seq_layout(scores, state_len, blank_score)
+    if scores.stride(2) != 1:
+        scores = scores.contiguous()
+        N, T, five, s_n, s_t = seq_layout(scores, state_len, blank_score)
+    lib = _lib.lib()
+    dev = scores.device
+    Lmax = int(targets.shape[1])
+    if Lmax == 0:                                   # (free start, every row empty)
+        targets, Lmax = torch.zeros((N, 1), dtype=torch.int8), 1
+    targets = targets.to(dev).contiguous()
+    lengths = lengths.to(dev).contiguous()
+    nbytes = lib.bh_crf_seq_workspace(N, T, Lmax, state_len)
+    if nbytes == 0:
+        raise ValueError("unsupported shape: Lmax + 1 - state_len = %d positions (limit 4096), state_len %d (1..5)"
+                         % (Lmax + 1 - state_len, state_len))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(N, dtype=torch.float32, device=dev)
+    blank = float(blank_score if blank_score is not None else 0.0)
+    tb = targets.element_size()
+    with torch.cuda.device(dev):
+        st = _lib.stream_ptr(dev)
+        if mode == "log":
+            _lib.check(lib.bh_crf_seq_logz(_lib.ptr(scores), N, T, state_len, five, blank, s_n, s_t, _lib.ptr(targets), Lmax, tb,
+                                           _lib.ptr(lengths), _lib.ptr(ws), _lib.ptr(out), st), "bh_crf_seq_logz")
+            return out
+        if mode == "free":
+            _lib.check(lib.bh_crf_seq_logz_free(_lib.ptr(scores), N, T, state_len, blank, s_n, s_t, _lib.ptr(targets), Lmax, tb,
+                                                _lib.ptr(lengths), _lib.ptr(ws), _lib.ptr(out), st), "bh_crf_seq_logz_free")
+            return out
+        align = torch.empty((N, T), dtype=torch.int32, device=dev)
+        _lib.check(lib.bh_crf_seq_viterbi(_lib.ptr(scores), N, T, state_len, five, blank, s_n, s_t, _lib.ptr(targets), Lmax, tb,
+                                          _lib.ptr(lengths), _lib.ptr(ws), _lib.ptr(align), _lib.ptr(out), st), "bh_crf_seq_viterbi")
+        return align, out
+
+
+def seq_logz(scores, targets, target_lengths, state_len, blank_score=None, free_start=False):
+    """koi.ctc.logZ_cu of the chain of CTC_CRF.prepare_ctc_scores (crf/model.py:110-130), gathered inside the kernel:
+    ln of the sum over every alignment of the target, fp32 -> device float32 [N] (-inf where the target cannot fit into T steps).
+    free_start=True (koi layout): the sum also runs over every start state - the numerator of ln P(sequence | scores)."""
+    return _seq_call(scores, targets, target_lengths, int(state_len), blank_score, "free" if free_start else "log")
+
+
+def seq_viterbi(scores, targets, target_lengths, state_len, blank_score=None):
+    """Forced alignment (koi.ctc.viterbi_alignments, crf/model.py:143): (align int32 [N, T], best float32 [N]) on the CPU.
+    align[n, t] = the chain position (k-mer index of the target) occupied after step t; ties resolve to stay; rows whose
+    target cannot fit into T steps are -1 with best = -inf. The compact form is this project's own definition (koi is closed)."""
+    align, best = _seq_call(scores, targets, target_lengths, int(state_len), blank_score, "max")
+    return align.cpu(), best.cpu()
+
+
+def logz_any(scores, state_len, blank_score=None):
+    """CTC_CRF.logZ per chunk for either layout -> device float64 [N]: bh_crf_logz for contiguous koi-layout scores, the dense
+    fp32 scan of csrc/seqdist.hip (bh_crf_logz_dense) for the reference layout [T, N, 5S] and for strided views."""
+    N, T, five, s_n, s_t = seq_layout(scores, state_len, blank_score)
+    if not scores.is_cuda:
+        raise _lib.HipEngineError("scores must live on a HIP device (no CPU fallback)")
+    if scores.dtype != torch.float16:
+        scores = scores.to(torch.float16)
+    if scores.stride(2) != 1:
+        scores = scores.contiguous()
+    N, T, five, s_n, s_t = seq_layout(scores, state_len, blank_score)
+    lib = _lib.lib()
+    dev = scores.device
+    with torch.cuda.device(dev):
+        if not five and scores.is_contiguous():
+            ws = torch.empty(lib.bh_beam_search_workspace(N, T, state_len), dtype=torch.uint8, device=dev)
+            out = torch.empty(N, dtype=torch.float64, device=dev)
+            _lib.check(lib.bh_crf_logz(_lib.ptr(scores), N, T, state_len, float(blank_score), _lib.ptr(ws), _lib.ptr(out),
+                                       _lib.stream_ptr(dev)), "bh_crf_logz")
+            return out
+        out = torch.empty(N, dtype=torch.float32, device=dev)
+        _lib.check(lib.bh_crf_logz_dense(_lib.ptr(scores), N, T, state_len, five, float(blank_score or 0.0), s_n, s_t,
+                                         _lib.ptr(out), _lib.stream_ptr(dev)), "bh_crf_logz_dense")
+        return out.double()
+
+
+def encode_sequences(sequences):
+    """Strings over ACGT, or a decoder's int8 plane [N, T] (ASCII bases, 0 = nothing emitted: beam_search's `sequence`,
+    path_to_sequence's output) -> (targets int8 [N, Lmax] with labels 1..4 and 0 padding, lengths int32 [N]), CPU tensors."""
+    lut = np.zeros(256, np.int8)
+    lut[np.frombuffer(b"ACGT", np.uint8)] = (1, 2, 3, 4)
+    if isinstance(sequences, (torch.Tensor, np.ndarray)):
+        plane = sequences.cpu().numpy() if isinstance(sequences, torch.Tensor) else sequences
+        rows = [r[r != 0].astype(np.uint8) for r in plane]
+    else:
+        rows = [np.frombuffer(s.encode() if isinstance(s, str) else bytes(s), np.uint8) for s in sequences]
+    Lmax = max([len(r) for r in rows] + [1])
+    targets = np.zeros((len(rows), Lmax), np.int8)
+    for i, r in enumerate(rows):
+        lab = lut[r]
+        if (lab == 0).any():
+            raise ValueError("sequence %d holds bytes outside ACGT" % i)
+        targets[i, :len(r)] = lab
+    return torch.from_numpy(targets), torch.tensor([len(r) for r in rows], dtype=torch.int32)
+
+
+def seq_logprob(scores, sequences, blank_score=2.0):
+    """ln P(sequence | scores) per chunk of koi-layout scores cuda fp16 [N, T, 4S] -> CPU float64 [N]: the model's exact sequence
+    likelihood (what oracle.crf_ref.seq_logprob computes on the CPU), a decoder-independent figure for any called sequence.
+    Built as  bh_crf_seq_logz_free - bh_crf_logz:  the numerator sums over every alignment of the sequence AND every start
+    state (the loss's chain fixes the first k-mer instead; the free start has a kernel entry of its own)."""
+    sl = state_len_of(scores.shape[-1])
+    targets, lengths = encode_sequences(sequences)
+    num = seq_logz(scores, targets, lengths, sl, blank_score, free_start=True)
+    den = logz_any(scores, sl, blank_score)
+    return (num.double() - den).cpu()

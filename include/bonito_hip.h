@@ -12,9 +12,12 @@
  *   bh_beam_search
  *        koi.decode.beam_search(scores, beam_width, beam_cut, scale, offset, blank_score)
  *                                                                              bonito/crf/basecall.py:36-40
- *   bh_crf_viterbi / bh_crf_logz / bh_crf_posteriors
+ *   bh_crf_viterbi / bh_crf_logz / bh_crf_posterior_viterbi
  *        koi.ctc.{logZ_cu_sparse, fwd_scores_cu_sparse, bwd_scores_cu_sparse}, SequenceDist.posteriors
  *        behind CTC_CRF.logZ / viterbi / decode_batch                          bonito/crf/model.py:47-67,98-103,196-199
+ *   bh_crf_seq_logz / bh_crf_seq_viterbi (+ bh_crf_seq_logz_free, bh_crf_logz_dense)
+ *        koi.ctc.{logZ_cu, viterbi_alignments} behind CTC_CRF.ctc_loss / ctc_viterbi_alignments, SeqdistModel.loss
+ *                                                                              bonito/crf/model.py:126-143,204-207
  *   bh_ctc_greedy_decode / bh_ctc_beam_search
  *        fast_ctc_decode.viterbi_search / beam_search                          bonito/ctc/model.py:39-46
  *   bh_linear, bh_conv1d_*, bh_lstm_layer, ...  (operator level, used by the parity tests)
@@ -175,6 +178,46 @@ int bh_crf_reverse_complement(const void* in, void* out, int N, int T, int state
  * workspace: bh_beam_search_workspace(N, T, state_len) bytes. */
 int bh_crf_logz(const void* scores, int N, int T, int state_len, float blank_score, void* workspace, double* logz,
                 void* stream);
+
+/* ---- CTC-CRF sequence likelihood and forced alignment (csrc/seqdist.hip) ------------------------------------------
+ * The chain of CTC_CRF.prepare_ctc_scores (crf/model.py:110-124): targets[N][Lmax] hold labels 1..4, 0 = padding, as int8
+ * (target_bytes = 1) or int32 (target_bytes = 4); target_lengths[N] int32; all on the device. With k = state_len a row of len
+ * labels is a chain of n = len + 1 - k positions, position j = the k-mer targets0[j .. j+k), targets0 = max(targets - 1, 0).
+ * scores: fp16 with element strides (stride_n, stride_t) and layout_5s as in bh_crf_viterbi, so the reference's [T][N][5S]
+ * tensor and the engine's [N][T][4S] tensor (+ blank_score) both go in without a copy. The stay / move edge scores are gathered
+ * from the score rows inside the kernel; no [T][N][L] tensor is materialised.
+ * Supported range (an error, never a truncation): 1 <= state_len <= 5, T >= 1, state_len <= Lmax, Lmax + 1 - state_len <= 4096.
+ * Lengths live on the device: a row with len < state_len or len > Lmax yields NaN (callers check lengths on the host).
+ * workspace: bh_crf_seq_workspace(N, T, Lmax, state_len) bytes (0 = unsupported shape), shared by the three scans below.
+ *
+ * bh_crf_seq_logz: koi.ctc.logZ_cu (crf/model.py:130). Log semiring, alpha_0 = [0, -inf, ...],
+ *   alpha_{t+1}[j] = logaddexp(alpha_t[j] + stay_t[j], alpha_t[j-1] + move_t[j-1]); logz_out[N] = alpha_T[n-1], fp32 like the
+ *   reference's scores.to(float32); -inf where n - 1 > T.
+ * bh_crf_seq_viterbi: koi.ctc.viterbi_alignments (crf/model.py:143). The same scan in the Max semiring with a one-bit traceback.
+ *   align_out[N][T] int32 = the chain position occupied AFTER each step: it starts from position 0 before step 0, never
+ *   decreases, rises by at most 1 per step and ends at n - 1; best_out[N] = the path score. TIES RESOLVE TO STAY (a cell is
+ *   entered by its move edge only when that candidate is strictly greater). A row with n - 1 > T has best = -inf and
+ *   align = -1 throughout. koi is closed and the reference never calls ctc_viterbi_alignments, so the form koi returns is
+ *   unknown: this compact form is this project's own definition.
+ * bh_crf_seq_logz_free: the same Log scan with a FREE START, koi layout only: ln of the sum over every start state and every
+ *   alignment that emits exactly the row's bases - the numerator of ln P(sequence | scores) (bh_crf_logz is the denominator).
+ *   The first k emissions run through dense levels (states whose leading digits still belong to the unknown start state) in a
+ *   kernel of their own, which feeds position 0 of the chain; rows shorter than state_len (0 included) are valid here.
+ * bh_crf_logz_dense: CTC_CRF.logZ (crf/model.py:47-52) in fp32 for either layout with strides -> logz_out[N] float. This is what
+ *   ctc_loss(normalise_scores=True) uses for the [T][N][5S] layout (a dense device scan, not a host-side expansion);
+ *   bh_crf_logz serves the contiguous koi layout. */
+size_t bh_crf_seq_workspace(int N, int T, int Lmax, int state_len);
+int bh_crf_seq_logz(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
+                    long stride_t, const void* targets, int Lmax, int target_bytes, const int32_t* target_lengths,
+                    void* workspace, float* logz_out, void* stream);
+int bh_crf_seq_viterbi(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
+                       long stride_t, const void* targets, int Lmax, int target_bytes, const int32_t* target_lengths,
+                       void* workspace, int32_t* align_out, float* best_out, void* stream);
+int bh_crf_seq_logz_free(const void* scores, int N, int T, int state_len, float blank_score, long stride_n, long stride_t,
+                         const void* targets, int Lmax, int target_bytes, const int32_t* target_lengths, void* workspace,
+                         float* logz_out, void* stream);
+int bh_crf_logz_dense(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
+                      long stride_t, float* logz_out, void* stream);
 
 /* Signal ingest on the device: replaces Read.__init__'s numpy work (bonito/reader.py:122-166 normalisation + trim, the pA
  * scaling of bonito/pod5.py:52-67) and util.chunk + the fp16 cast (bonito/util.py:142-161, crf/basecall.py:31) for raw
