@@ -186,7 +186,7 @@ __global__ __launch_bounds__(512) void attention_kernel(AttnArgs p) {
 // transposed exactly once per head (the block-per-workgroup kernel above re-stages ~3x the rows and re-applies the
 // rotation each time), and the 128 new rows of the next block travel through registers while the current block computes.
 // Block b (queries 128b..128b+127) reads keys 128b-128 .. 128b+271 (wave w: 18 tiles of 16 from 128b-128+16w), all tile
-// boundaries are multiples of 16 so a tile never straddles the ring wrap. Needs wl + wr <= 256 and wl <= 128.
+// boundaries are multiples of 16 so a tile never straddles the ring wrap. Needs wl <= 128 and wr <= 144 (bh_k_attention_ring_serves, kernels.h).
 typedef float float8_t __attribute__((ext_vector_type(8)));
 constexpr int RING = 512;
 constexpr int RVS = RING + 4;                  // V^T row stride (halves): 4-bank skew between d rows
@@ -707,7 +707,7 @@ int bh_k_attention(const void* qkv, void* out, const float* cos_sin, int N, int 
                    int win_left, int win_right, hipStream_t stream) {
     using namespace bh;
     BH_REQUIRE(head_dim == 64, "attention: only head_dim 64 is implemented (got %d)", head_dim);
-    BH_REQUIRE(win_left >= 0 && win_right >= 0, "attention: a finite window (left, right) is required");
+    BH_REQUIRE(win_left >= 0 && win_right >= 0, "attention: a finite window (left, right) is required (got (%d, %d))", win_left, win_right);
     BH_REQUIRE(N > 0 && T > 0 && nhead > 0, "attention: empty problem");
     const int need = (16 + win_left + win_right + 15) / 16;      // key tiles one wave can see
     AttnArgs a{(const half_t*)qkv, (half_t*)out, cos_sin, N, T, nhead, win_left, win_right, 0.125f};
@@ -738,8 +738,8 @@ int bh_k_attention_prerotated(const void* qkv, void* out, int N, int T, int nhea
                               hipStream_t stream) {
     using namespace bh;
     BH_REQUIRE(head_dim == 64, "attention: only head_dim 64 is implemented (got %d)", head_dim);
-    BH_REQUIRE(win_left >= 0 && win_right >= 0 && win_left <= 128 && win_left + win_right <= 256,
-               "attention (ring): window (%d, %d) outside the supported range", win_left, win_right);
+    BH_REQUIRE(bh_k_attention_ring_serves(win_left, win_right),
+               "attention (ring): window (%d, %d) outside the supported range (left <= 128, right <= 144)", win_left, win_right);
     BH_REQUIRE(N > 0 && T > 0 && nhead > 0, "attention: empty problem");
     AttnRingArgs a{(const half_t*)qkv, (half_t*)out, N, T, nhead, win_left, win_right, 1};
     // twelve waves (blocks of 192 queries) where the chunk is long enough to fill them; "attn_waves" 8 / 12 forces a geometry

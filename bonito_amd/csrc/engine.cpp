@@ -807,10 +807,12 @@ extern "C" int bh_encoder_describe(const bh_encoder_t* e, char* buf, size_t n) {
             }
             case BH_LAYER_LINEAR_CRF: snprintf(line, sizeof(line), "%d linearcrfencoder %d->%d: gemm\n", li, d.in_size, d.out_size); break;
             case BH_LAYER_LINEAR: snprintf(line, sizeof(line), "%d linear %d->%d: gemm\n", li, d.in_size, d.out_size); break;
-            case BH_LAYER_TRANSFORMER:
+            case BH_LAYER_TRANSFORMER: {
+                const bool ring = e->attn_ring && bh_k_attention_ring_serves(d.win_left, d.win_right);      // as bh_encoder_forward dispatches
                 snprintf(line, sizeof(line), "%d transformer d%d h%d ff%d: gemm (Wqkv%s, out_proj, fc1 SwiGLU, fc2) + %s + rmsnorm_residual_kernel\n",
-                         li, d.in_size, d.nhead, d.dim_ff, e->attn_ring ? " + rotary" : "", e->attn_ring ? "attention_ring_kernel" : "attention_kernel");
+                         li, d.in_size, d.nhead, d.dim_ff, ring ? " + rotary" : "", ring ? "attention_ring_kernel" : "attention_kernel");
                 break;
+            }
             case BH_LAYER_UPSAMPLE: snprintf(line, sizeof(line), "%d linearupsample x%d: gemm\n", li, d.scale_factor); break;
             case BH_LAYER_CLAMP: snprintf(line, sizeof(line), "%d clamp: fused into the previous layer's epilogue\n", li); break;
             case BH_LAYER_DWCONV: snprintf(line, sizeof(line), "%d dwconv k%d: dwconv_kernel\n", li, d.winlen); break;
@@ -1097,7 +1099,7 @@ extern "C" int bh_encoder_forward(bh_encoder_t* e, const void* signal, int N, in
                 // roofline can name a kernel - the projections and norms around them share the two older classes
                 // default: rotary + softmax scale in the Wqkv epilogue, persistent ring-buffer attention kernel; the
                 // block-per-workgroup kernel (rotation applied while staging) serves wider windows and "attn_ring" = 0
-                const bool ring = e->attn_ring && d.win_left <= 128 && d.win_left + d.win_right <= 256;
+                const bool ring = e->attn_ring && bh_k_attention_ring_serves(d.win_left, d.win_right);
                 {
                     ProfSpan span(e, st, BH_PROF_ATTENTION);
                     if (ring)

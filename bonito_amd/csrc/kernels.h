@@ -99,6 +99,12 @@ int bh_k_linear_qkv_rotary(const void* X, const void* W, const float* bias, void
                            int T, float qscale, hipStream_t stream);
 int bh_k_attention_prerotated(const void* qkv, void* out, int N, int T, int nhead, int head_dim, int win_left, int win_right,
                               hipStream_t stream);
+// The windows the ring kernels serve - the ONE statement of it: the launcher's guard and the engine's dispatch both call this. A wave's 18
+// key tiles start 128 keys left of its first query and end 159 keys right of it, and its last query is the first + 15: 128 to the left,
+// 159 - 15 = 144 to the right (the staged rows of a block end at its last query + 144 as well). Everything else is bh_k_attention's.
+inline bool bh_k_attention_ring_serves(int win_left, int win_right) {
+    return win_left >= 0 && win_right >= 0 && win_left <= 128 && win_right <= 144;
+}
 // signal.hip
 int bh_k_signal_normalise(const int16_t* raw, const long* offs, const float* cal_scale, const float* cal_offset, int R,
                           int strategy, double qa, double qb, double shift_mult, double scale_mult, double fixed_shift,
