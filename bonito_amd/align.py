@@ -1,0 +1,177 @@
+"""
+Pairwise local alignment on the device: the engine's counterpart of ``parasail.sw_trace_striped_32(seq, ref, 8, 4, dnafull)``, the one
+call behind the reference's read accuracy (bonito/cli/evaluate.py:37-67 ``align``, bonito/util.py:346-368 ``accuracy``).
+
+``sw_align`` is the batched entry (kernel: csrc/align.hip through ``bh_sw_align``); ``align`` / ``AlignResult`` carry the reference's
+names. The definition, with its tie-breaks, is in DESIGN.md section 6. There is no host fallback.
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from bonito_amd import _lib
+from bonito_amd.decode import encode_sequences
+
+OPS = "=XID"                                     # op codes of bh_sw_align's runs: (length << 2) | op
+MAX_LEN = 4096
+# Traceback bits cost ceil(seq / 512) * (ref + 63) * 256 bytes per pair (8.1 MiB at 4096 x 4096, 0.42 MiB for a 10 000-sample chunk's
+# ~ 800 bases). 1 GiB holds 126 pairs of the largest size or about 2 400 chunks in one launch, and stays small beside the 288 GB card.
+DEFAULT_WORKSPACE_BUDGET = 1 << 30
+COLUMNS = ("score", "num_correct", "num_mismatches", "num_insertions", "num_deletions",
+           "align_ref_start", "align_ref_end", "align_seq_start", "align_seq_end", "num_runs")
+
+
+@dataclass
+class AlignResult:
+    """One pair; the reference's fields (cli/evaluate.py:22-34) plus the score and, when asked for, the CIGAR. A pair with nothing
+    in common (score 0, an empty sequence among them) has counts 0, starts 0, ends -1, an empty CIGAR and accuracy 0."""
+    accuracy: float = 0
+    num_correct: int = 0
+    num_mismatches: int = 0
+    num_insertions: int = 0
+    num_deletions: int = 0
+    ref_len: int = 0
+    seq_len: int = 0
+    align_ref_start: int = 0
+    align_ref_end: int = -1
+    align_seq_start: int = 0
+    align_seq_end: int = -1
+    score: int = 0
+    cigar: str = None
+
+
+def accuracy_of(num_correct, num_mismatches, num_insertions, num_deletions):
+    """num_correct / (all alignment columns), 0 where nothing aligned; arrays or scalars."""
+    c = np.asarray(num_correct, np.float64)
+    total = c + np.asarray(num_mismatches) + np.asarray(num_insertions) + np.asarray(num_deletions)
+    return np.divide(c, total, out=np.zeros_like(total, dtype=np.float64), where=total > 0)
+
+
+class SwBatch:
+    """Results of one ``sw_align`` call in the caller's order: ``table`` int32 [n, 10] (``COLUMNS``), ``seq_len`` / ``ref_len``,
+    ``cigar`` (list of strings, or None); every column is an attribute, ``batch[i]`` is an ``AlignResult``."""
+
+    def __init__(self, table, seq_len, ref_len, cigar=None):
+        self.table = np.asarray(table, np.int32).reshape(-1, len(COLUMNS))
+        self.seq_len = np.asarray(seq_len, np.int32)
+        self.ref_len = np.asarray(ref_len, np.int32)
+        self.cigar = cigar
+
+    def __len__(self):
+        return self.table.shape[0]
+
+    def __getattr__(self, name):
+        if name in COLUMNS:
+            return self.table[:, COLUMNS.index(name)]
+        raise AttributeError(name)
+
+    @property
+    def accuracy(self):
+        return accuracy_of(self.num_correct, self.num_mismatches, self.num_insertions, self.num_deletions)
+
+    def __getitem__(self, i):
+        row = [int(v) for v in self.table[i]]
+        return AlignResult(
+            accuracy=float(accuracy_of(*row[1:5])), num_correct=row[1], num_mismatches=row[2], num_insertions=row[3],
+            num_deletions=row[4], ref_len=int(self.ref_len[i]), seq_len=int(self.seq_len[i]), align_ref_start=row[5],
+            align_ref_end=row[6], align_seq_start=row[7], align_seq_end=row[8], score=row[0],
+            cigar=None if self.cigar is None else self.cigar[i])
+
+
+def runs_to_cigar(runs):
+    """uint32 runs of bh_sw_align -> '12=1X3=...'."""
+    return "".join("%d%s" % (int(r) >> 2, OPS[int(r) & 3]) for r in runs)
+
+
+def _encode(x, what):
+    """strings / an ASCII plane (decode.encode_sequences) or a code plane (integers 0..4, 0 = padding after the bases)
+    -> (int8 codes [n, L] CPU tensor, int32 lengths numpy)."""
+    if isinstance(x, (torch.Tensor, np.ndarray)):
+        plane = x.cpu().numpy() if isinstance(x, torch.Tensor) else x
+        if plane.ndim != 2:
+            raise ValueError("%s: a plane must be [n, L]" % what)
+        if plane.size == 0 or int(plane.max()) <= 4:
+            if plane.size and int(plane.min()) < 0:
+                raise ValueError("%s: codes must be 0..4" % what)
+            lens = (plane != 0).sum(axis=1).astype(np.int32)
+            if ((plane != 0) != (np.arange(plane.shape[1])[None, :] < lens[:, None])).any():
+                raise ValueError("%s: padding (0) inside a row of codes" % what)
+            return torch.from_numpy(np.ascontiguousarray(plane.astype(np.int8))), lens
+    codes, lens = encode_sequences(x)
+    return codes, lens.numpy().astype(np.int32)
+
+
+def _slices(order, seq_len, ref_len, budget, lib):
+    """Cut the size-sorted pairs into runs whose bh_sw_workspace stays within the budget."""
+    out, lo = [], 0
+    while lo < len(order):
+        hi, ms, mr = lo, 0, 0
+        while hi < len(order):
+            s, r = max(ms, int(seq_len[order[hi]])), max(mr, int(ref_len[order[hi]]))
+            if lib.bh_sw_workspace(hi - lo + 1, s, r) > budget:
+                break
+            hi, ms, mr = hi + 1, s, r
+        if hi == lo:
+            raise ValueError("sw_align: workspace_budget of %d bytes cannot hold one pair of lengths (%d, %d), which needs %d"
+                             % (budget, seq_len[order[lo]], ref_len[order[lo]],
+                                lib.bh_sw_workspace(1, int(seq_len[order[lo]]), int(ref_len[order[lo]]))))
+        out.append((order[lo:hi], ms, mr))
+        lo = hi
+    return out
+
+
+def sw_align(seqs, refs, match=5, mismatch=-4, gap_open=8, gap_extend=4, cigar=False, workspace_budget=DEFAULT_WORKSPACE_BUDGET,
+             device="cuda"):
+    """Smith-Waterman with affine gaps (a gap of k costs gap_open + (k - 1) * gap_extend) of seqs[i] (the query) against refs[i], for
+    lists of strings over ACGT (empty strings are legal) or code planes. The defaults are the reference's parasail arguments
+    (dnafull on A, C, G, T: +5 / -4; open 8, extend 4). Pairs are sorted by size and cut into launches whose workspace stays within
+    ``workspace_budget`` bytes; the results come back in the caller's order as a ``SwBatch``."""
+    sc, sl = _encode(seqs, "seqs")
+    rc, rl = _encode(refs, "refs")
+    n = len(sl)
+    if len(rl) != n:
+        raise ValueError("sw_align: %d seqs against %d refs" % (n, len(rl)))
+    if max([0] + sl.tolist() + rl.tolist()) > MAX_LEN:
+        raise ValueError("sw_align: sequences of up to %d bases are supported" % MAX_LEN)
+    table = np.zeros((n, len(COLUMNS)), np.int32)
+    cigars = [""] * n if cigar else None
+    if n == 0:
+        return SwBatch(table, sl, rl, cigars)
+    lib = _lib.lib()
+    passes = (sl.astype(np.int64) + 511) // 512
+    order = np.argsort(passes * (rl.astype(np.int64) + 63), kind="stable")
+    ip = C.POINTER(C.c_int32)
+    for idx, ms, mr in _slices(order, sl, rl, int(workspace_budget), lib):
+        k = len(idx)
+        sel = torch.from_numpy(np.ascontiguousarray(idx))
+        s_dev = sc[sel][:, :max(ms, 1)].contiguous().to(device)
+        r_dev = rc[sel][:, :max(mr, 1)].contiguous().to(device)
+        s_len, r_len = np.ascontiguousarray(sl[idx]), np.ascontiguousarray(rl[idx])
+        nbytes = lib.bh_sw_workspace(k, ms, mr)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        res = torch.empty((k, len(COLUMNS)), dtype=torch.int32, device=device)
+        ops = n_ops = None
+        stride = 0
+        if cigar:
+            stride = max(1, int(np.where((s_len > 0) & (r_len > 0), s_len + r_len - 1, 0).max()))
+            ops = torch.empty((k, stride), dtype=torch.int32, device=device)
+            n_ops = torch.empty(k, dtype=torch.int32, device=device)
+        _lib.check(lib.bh_sw_align(_lib.ptr(s_dev), s_dev.shape[1], s_len.ctypes.data_as(ip), _lib.ptr(r_dev), r_dev.shape[1],
+                                   r_len.ctypes.data_as(ip), k, int(match), int(mismatch), int(gap_open), int(gap_extend),
+                                   _lib.ptr(ws), nbytes, _lib.ptr(res), _lib.ptr(ops), stride, _lib.ptr(n_ops),
+                                   _lib.stream_ptr(s_dev.device)), "bh_sw_align")
+        table[idx] = res.cpu().numpy()
+        if cigar:
+            counts = n_ops.cpu().numpy()
+            width = int(counts.max()) if k else 0
+            runs = ops[:, :max(width, 1)].cpu().numpy().view(np.uint32)
+            for row, i in enumerate(idx):
+                cigars[i] = runs_to_cigar(runs[row, :counts[row]])
+    return SwBatch(table, sl, rl, cigars)
+
+
+def align(*, ref, seq, **scoring):
+    """One pair with the reference's field names (bonito/cli/evaluate.py:37-67)."""
+    return sw_align([seq], [ref], **scoring)[0]

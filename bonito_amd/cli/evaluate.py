@@ -3,11 +3,10 @@
 reference_lengths.npy) with the HIP engine -- the arguments of the reference's bonito/cli/evaluate.py:140-155.
 
 Per batch: engine forward, ``decode_batch`` (posterior decoding) and ``loss(..., reduction='none')``, i.e.
--ln P(reference | scores) / reference length per chunk from the sequence-likelihood kernel. Printed: num_chunks, mean and median
-loss, mean called / reference lengths. With ``--output_dir``: seqs.fasta, refs.fasta and summ.txt (per-chunk TSV of loss and lengths).
-
-Alignment accuracy is NOT reported: the reference computes it with parasail (sw_trace_striped_32, evaluate.py:37-67), which this
-engine neither ships nor re-implements. seqs.fasta / refs.fasta are what an external aligner needs.
+-ln P(reference | scores) / reference length per chunk from the sequence-likelihood kernel. After the calling loop every called
+sequence is aligned against its reference in ONE ``align.sw_align`` call (Smith-Waterman on the device, the reference's parasail
+arguments; evaluate.py:37-67). Printed: the reference's block (accuracy, sub / ins / del rates, lengths and clips; evaluate.py:117-129)
+plus mean and median loss. With ``--output_dir``: seqs.fasta, refs.fasta and summ.txt (per-chunk TSV: loss and the AlignResult columns).
 """
 import os
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
@@ -17,6 +16,9 @@ import numpy as np
 import torch
 
 from bonito_amd.util import init, load_model
+
+SUMM_COLUMNS = ("accuracy", "num_correct", "num_mismatches", "num_insertions", "num_deletions", "ref_len", "seq_len",
+                "align_ref_start", "align_ref_end", "align_seq_start", "align_seq_end")
 
 
 def load_numpy_datasets(limit=None, directory=None):
@@ -58,6 +60,56 @@ def decode_ref(encoded, labels):
     return "".join(labels[int(e)] for e in encoded if e)
 
 
+def report_lines(table, seq_len, ref_len, losses):
+    """The printed block from arrays: `table` int [n, 10] in align.COLUMNS order, lengths and losses per chunk. The three rates
+    divide by num_correct as the reference's do (evaluate.py:120-122), so they are averaged over the chunks with num_correct > 0
+    and the number of chunks left out is printed; accuracy and the clips average over every chunk (an unaligned chunk: accuracy 0,
+    its whole length as right clip)."""
+    table = np.asarray(table, np.int64).reshape(-1, 10)
+    seq_len, ref_len, losses = np.asarray(seq_len, np.int64), np.asarray(ref_len, np.int64), np.asarray(losses, np.float64)
+    n = len(table)
+    correct, mism, ins, dele = (table[:, c] for c in (1, 2, 3, 4))
+    ref_start, ref_end, seq_start, seq_end = (table[:, c] for c in (5, 6, 7, 8))
+    total = correct + mism + ins + dele
+    acc = np.divide(correct, total, out=np.zeros(n), where=total > 0)
+    ok = correct > 0
+
+    def mean(x):
+        return float(np.mean(x)) if len(x) else 0.0
+
+    def rate(x):
+        return mean(x[ok] / correct[ok])
+
+    return [
+        "* num_chunks      %d" % n,
+        "* loss mean       %.4f" % (losses.mean() if len(losses) else float("nan")),
+        "* loss median     %.4f" % (np.median(losses) if len(losses) else float("nan")),
+        "* accuracy        %.2f%%" % (100 * mean(acc)),
+        "* sub-rate        %.2f%%" % (100 * rate(mism)),
+        "* ins-rate        %.2f%%" % (100 * rate(ins)),
+        "* del-rate        %.2f%%" % (100 * rate(dele)),
+        "* rates left out  %d chunks with num_correct = 0" % int(n - ok.sum()),
+        "* seq_len         %.1f" % mean(seq_len),
+        "* seq_lclip       %.1f" % mean(seq_start),
+        "* seq_rclip       %.1f" % mean(seq_len - seq_end - 1),
+        "* ref_len         %.1f" % mean(ref_len),
+        "* ref_lclip       %.1f" % mean(ref_start),
+        "* ref_rclip       %.1f" % mean(ref_len - ref_end - 1),
+    ]
+
+
+def summ_lines(table, seq_len, ref_len, losses):
+    """summ.txt: a header and one tab-separated row per chunk, `loss` and then the AlignResult columns of the reference's table."""
+    table = np.asarray(table, np.int64).reshape(-1, 10)
+    lines = ["\tloss\t" + "\t".join(SUMM_COLUMNS) + "\n"]
+    for i, (row, s, r, l) in enumerate(zip(table, seq_len, ref_len, losses)):
+        total = int(row[1:5].sum())
+        acc = row[1] / total if total else 0.0
+        lines.append("%d\t%.6f\t%.6f\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n"
+                     % (i, l, acc, row[1], row[2], row[3], row[4], r, s, row[5], row[6], row[7], row[8]))
+    return lines
+
+
 def main(args):
     init(args.seed, args.device)
     if args.directory is None:
@@ -83,18 +135,10 @@ def main(args):
         losses.append(model.loss(scores, t, n, reduction="none").cpu().numpy())
     losses = np.concatenate(losses) if losses else np.zeros(0, np.float32)
     refs = [decode_ref(t[:n], model.alphabet) for t, n in zip(targets, lengths)]
-    seq_len = np.array([len(s) for s in seqs])
-    ref_len = np.array([len(r) for r in refs])
-    print("\n".join([
-        "",
-        "* num_chunks      %d" % len(refs),
-        "* loss mean       %.4f" % (losses.mean() if len(losses) else float("nan")),
-        "* loss median     %.4f" % (np.median(losses) if len(losses) else float("nan")),
-        "* seq_len         %.1f" % (seq_len.mean() if len(seq_len) else 0.0),
-        "* ref_len         %.1f" % (ref_len.mean() if len(ref_len) else 0.0),
-        "* accuracy        not computed (no aligner in this engine; align seqs.fasta against refs.fasta)",
-        "",
-    ]))
+    print("* aligning")
+    from bonito_amd.align import sw_align
+    aligned = sw_align(seqs, refs)
+    print("\n".join([""] + report_lines(aligned.table, aligned.seq_len, aligned.ref_len, losses) + [""]))
     if args.output_dir:
         args.output_dir.mkdir(exist_ok=True, parents=True)
         with (args.output_dir / "seqs.fasta").open("w") as fh:
@@ -102,8 +146,7 @@ def main(args):
         with (args.output_dir / "refs.fasta").open("w") as fh:
             fh.write("".join(">chunk_%d\n%s\n" % (i, s) for i, s in enumerate(refs)))
         with (args.output_dir / "summ.txt").open("w") as fh:
-            fh.write("\tloss\tref_len\tseq_len\n")
-            fh.write("".join("%d\t%.6f\t%d\t%d\n" % (i, l, r, s) for i, (l, r, s) in enumerate(zip(losses, ref_len, seq_len))))
+            fh.write("".join(summ_lines(aligned.table, aligned.seq_len, aligned.ref_len, losses)))
     return 0
 
 
@@ -111,8 +154,8 @@ def argparser():
     parser = ArgumentParser(
         formatter_class=ArgumentDefaultsHelpFormatter,
         add_help=False,
-        description="Loss and called sequences of labelled chunks on the HIP engine. Alignment accuracy is not computed "
-                    "(the reference uses parasail); seqs.fasta / refs.fasta in --output_dir feed an external aligner.",
+        description="Loss and alignment accuracy of labelled chunks on the HIP engine (Smith-Waterman on the device with the "
+                    "reference's parasail arguments); --output_dir receives seqs.fasta, refs.fasta and summ.txt.",
     )
     parser.add_argument("model_directory")
     parser.add_argument("--output_dir", type=Path)

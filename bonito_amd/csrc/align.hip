@@ -1,0 +1,253 @@
+// Batched Smith-Waterman local alignment with affine gaps and a traceback ("Read accuracy"): the engine's
+// counterpart of parasail.sw_trace_striped_32(seq, ref, open, extend, matrix) behind the reference's accuracy figures
+// (bonito/cli/evaluate.py:37-67, bonito/util.py:346-368). Exact 32-bit integer scores.
+//
+//   E(i,j) = max(H(i,j-1) - open, E(i,j-1) - extend)        deletion  (consumes a ref base, CIGAR D)
+//   F(i,j) = max(H(i-1,j) - open, F(i-1,j) - extend)        insertion (consumes a seq base, CIGAR I)
+//   H(i,j) = max(0, H(i-1,j-1) + s(seq_i, ref_j), E(i,j), F(i,j))
+//
+// Forward kernel: one wave per pair. A pass covers 512 query rows: lane l owns the 8 consecutive rows [8l, 8l+8) of the pass
+// and the reference streams through the lanes one column per step (lane l works on column t - l at step t). The bottom H and
+// F of a strip and the reference base move to the next lane with one DPP wave shift each; lane 0 is fed from a register chunk
+// (64 columns per coalesced load: the reference bases and, from the second pass on, the boundary row the previous pass left
+// in the workspace). Each cell leaves 4 traceback bits (2: source of H, 1: E extended, 1: F extended); the 8 cells of a lane
+// and a step make one dword, stored as [pass][step][lane], so a wave's store is one contiguous 256 bytes.
+// Traceback kernel: one pair per thread walks the bits back from the end cell, counts the ops and writes the run-length ops.
+#include "common.h"
+#include "kernels.h"
+#include <vector>
+
+namespace bh {
+
+constexpr int SW_R = 8;                     // query rows per lane
+constexpr int SW_ROWS = WAVE * SW_R;        // query rows per pass
+constexpr int SW_MAX_LEN = 4096;
+constexpr int SW_MAX_PARAM = 32767;         // |score parameter| bound: 4096 * 32767 < 2^31
+constexpr int SW_NEG = -(1 << 30);          // E / F "minus infinity": NEG - extend cannot wrap, and no H - open reaches it
+
+struct SwArgs {
+    const int8_t* seq; long seq_stride;
+    const int8_t* ref; long ref_stride;
+    const int* seq_len; const int* ref_len;   // device copies at the head of the workspace
+    int match, mismatch, open, ext;
+    unsigned* trace; size_t trace_stride;     // dwords per pair
+    int2* bound; size_t bound_stride;         // [pair][2][bound_stride] (H, F) of the last row of a pass, ping-pong by pass parity
+    int* endcell;                             // [pair][4]: score, end_i, end_j
+    int* result; unsigned* ops; long ops_stride; int* n_ops;
+};
+
+// value of the lane below (lane - 1); lane 0, which has no source, keeps `first`
+__device__ __forceinline__ int wave_shr1(int first, int v) {
+    return __builtin_amdgcn_update_dpp(first, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+}
+
+__global__ __launch_bounds__(WAVE) void sw_forward_kernel(SwArgs a) {
+    const int pair = blockIdx.x, lane = threadIdx.x;
+    const int m = a.seq_len[pair], n = a.ref_len[pair];
+    int best = 0, besti = -1, bestj = -1;
+    if (m > 0 && n > 0) {
+        const int8_t* seq = a.seq + (long)pair * a.seq_stride;
+        const int8_t* ref = a.ref + (long)pair * a.ref_stride;
+        const int S = n + WAVE - 1;                                          // steps of one pass
+        const int passes = (m + SW_ROWS - 1) / SW_ROWS;
+        const int match = a.match, mismatch = a.mismatch, open = a.open, ext = a.ext;
+        for (int p = 0; p < passes; ++p) {
+            const int row0 = p * SW_ROWS + lane * SW_R;
+            int q[SW_R], H[SW_R], E[SW_R], bH[SW_R], bJ[SW_R];
+#pragma unroll
+            for (int r = 0; r < SW_R; ++r) {
+                q[r] = row0 + r < m ? (int)seq[row0 + r] : 0;
+                H[r] = 0; E[r] = SW_NEG; bH[r] = 0; bJ[r] = 0;
+            }
+            int hdiag = 0, h_out = 0, f_out = SW_NEG, c_out = 0;
+            const int2* bin = a.bound + ((size_t)pair * 2 + (p & 1)) * a.bound_stride;
+            int2* bout = a.bound + ((size_t)pair * 2 + ((p + 1) & 1)) * a.bound_stride;
+            const bool keep = p + 1 < passes;                                // the next pass needs this pass's last row
+            unsigned* tr = a.trace + (size_t)pair * a.trace_stride + (size_t)p * S * WAVE + lane;
+            int oh = 0, of = 0;
+            for (int t0 = 0; t0 < S; t0 += WAVE) {
+                const int cj = t0 + lane;
+                const int cchunk = cj < n ? (int)ref[cj] : 0;
+                int hchunk = 0, fchunk = SW_NEG;
+                if (p > 0 && cj < n) { const int2 v = bin[cj]; hchunk = v.x; fchunk = v.y; }
+                const int kend = min(WAVE, S - t0);
+                for (int k = 0; k < kend; ++k) {
+                    const int t = t0 + k;
+                    const int hup = wave_shr1(__builtin_amdgcn_readlane(hchunk, k), h_out);
+                    const int fup = wave_shr1(__builtin_amdgcn_readlane(fchunk, k), f_out);
+                    const int refc = wave_shr1(__builtin_amdgcn_readlane(cchunk, k), c_out);
+                    c_out = refc;
+                    const int j = t - lane;
+                    if (j >= 0 && j < n) {
+                        int hd = hdiag, hu = hup, fu = fup;
+                        hdiag = hup;
+                        unsigned bits = 0;
+#pragma unroll
+                        for (int r = 0; r < SW_R; ++r) {
+                            const int s = q[r] == refc ? match : mismatch;
+                            const int eo = H[r] - open, ee = E[r] - ext;
+                            const int fo = hu - open, fe = fu - ext;
+                            const int e = max(eo, ee), f = max(fo, fe);
+                            const int d = hd + s;
+                            const int h = max(max(max(d, e), f), 0);
+                            // stop at H = 0, then the diagonal, then E, then F; E / F: the open wins a tie
+                            const unsigned src = h == 0 ? 0u : h == d ? 1u : h == e ? 2u : 3u;
+                            bits |= (src | (ee > eo ? 4u : 0u) | (fe > fo ? 8u : 0u)) << (4 * r);
+                            if (h > bH[r]) { bH[r] = h; bJ[r] = j; }         // strict: the smallest j of a row
+                            hd = H[r]; H[r] = h; E[r] = e; hu = h; fu = f;
+                        }
+                        h_out = hu; f_out = fu;
+                        tr[(size_t)t * WAVE] = bits;
+                    }
+                    if (keep) {                                              // lane 63 has just finished column t - 63
+                        const int c = t - (WAVE - 1);
+                        if (c >= 0) {
+                            if (lane == (c & (WAVE - 1))) {
+                                oh = __builtin_amdgcn_readlane(h_out, WAVE - 1);
+                                of = __builtin_amdgcn_readlane(f_out, WAVE - 1);
+                            }
+                            if ((c & (WAVE - 1)) == WAVE - 1 || c == n - 1) {
+                                const int col = (c & ~(WAVE - 1)) + lane;
+                                if (col <= c) bout[col] = make_int2(oh, of);
+                            }
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < SW_R; ++r)                                   // ascending rows, strict: the smallest i of a lane
+                if (row0 + r < m && bH[r] > best) { best = bH[r]; besti = row0 + r; bestj = bJ[r]; }
+        }
+    }
+    // end cell: the largest H, among equals the smallest i, then the smallest j
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int ob = __shfl_xor(best, off), oi = __shfl_xor(besti, off), oj = __shfl_xor(bestj, off);
+        if (ob > best || (ob == best && (oi < besti || (oi == besti && oj < bestj)))) { best = ob; besti = oi; bestj = oj; }
+    }
+    if (lane == 0) {
+        a.endcell[pair * 4 + 0] = best;
+        a.endcell[pair * 4 + 1] = besti;
+        a.endcell[pair * 4 + 2] = bestj;
+    }
+}
+
+// ops: 0 '=', 1 'X', 2 'I', 3 'D'; a run is (length << 2) | op
+__global__ __launch_bounds__(WAVE) void sw_traceback_kernel(SwArgs a, int npairs) {
+    const int pair = blockIdx.x * WAVE + threadIdx.x;
+    if (pair >= npairs) return;
+    const int m = a.seq_len[pair], n = a.ref_len[pair];
+    const int score = a.endcell[pair * 4 + 0], ei = a.endcell[pair * 4 + 1], ej = a.endcell[pair * 4 + 2];
+    int* res = a.result + (long)pair * 10;
+    if (score <= 0 || ei < 0 || ej < 0 || ei >= m || ej >= n) {
+        res[0] = 0; res[1] = 0; res[2] = 0; res[3] = 0; res[4] = 0; res[5] = 0; res[6] = -1; res[7] = 0; res[8] = -1; res[9] = 0;
+        if (a.n_ops) a.n_ops[pair] = 0;
+        return;
+    }
+    const int8_t* seq = a.seq + (long)pair * a.seq_stride;
+    const int8_t* ref = a.ref + (long)pair * a.ref_stride;
+    const unsigned* trace = a.trace + (size_t)pair * a.trace_stride;
+    unsigned* ops = a.ops ? a.ops + (long)pair * a.ops_stride : nullptr;
+    const int S = n + WAVE - 1;
+    int cnt[4] = {0, 0, 0, 0};
+    int i = ei, j = ej, state = 0, run_op = -1, run_len = 0, nruns = 0;
+    auto emit = [&](int op) {
+        cnt[0] += op == 0; cnt[1] += op == 1; cnt[2] += op == 2; cnt[3] += op == 3;
+        if (op == run_op) { ++run_len; return; }
+        if (run_len) {
+            if (ops && nruns < a.ops_stride) ops[nruns] = ((unsigned)run_len << 2) | (unsigned)run_op;
+            ++nruns;
+        }
+        run_op = op; run_len = 1;
+    };
+    for (int it = 0; it < m + n && i >= 0 && j >= 0; ++it) {                // every turn consumes a base: at most m + n turns
+        const int ln = (i & (SW_ROWS - 1)) >> 3;
+        const unsigned bits = trace[((size_t)(i / SW_ROWS) * S + j + ln) * WAVE + ln] >> (4 * (i & 7));
+        if (state == 0) {
+            const unsigned src = bits & 3u;
+            if (src == 0) break;
+            if (src == 1) { emit(seq[i] == ref[j] ? 0 : 1); --i; --j; continue; }
+            state = src == 2 ? 1 : 2;
+        }
+        if (state == 1) { emit(3); state = (bits & 4u) ? 1 : 0; --j; }
+        else { emit(2); state = (bits & 8u) ? 2 : 0; --i; }
+    }
+    if (run_len) {
+        if (ops && nruns < a.ops_stride) ops[nruns] = ((unsigned)run_len << 2) | (unsigned)run_op;
+        ++nruns;
+    }
+    if (ops) {                                                               // the walk wrote the runs last to first
+        const int w = nruns < a.ops_stride ? nruns : (int)a.ops_stride;
+        for (int x = 0, y = w - 1; x < y; ++x, --y) { const unsigned v = ops[x]; ops[x] = ops[y]; ops[y] = v; }
+    }
+    res[0] = score; res[1] = cnt[0]; res[2] = cnt[1]; res[3] = cnt[2]; res[4] = cnt[3];
+    res[5] = j + 1; res[6] = ej; res[7] = i + 1; res[8] = ei; res[9] = nruns;
+    if (a.n_ops) a.n_ops[pair] = nruns;
+}
+
+struct SwLayout { size_t endcell, bound, bound_stride, trace, trace_stride, total; };
+
+static bool sw_layout(int n, int max_seq, int max_ref, SwLayout* L) {
+    if (n <= 0 || max_seq < 0 || max_ref < 0 || max_seq > SW_MAX_LEN || max_ref > SW_MAX_LEN) return false;
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t passes = ((size_t)max_seq + SW_ROWS - 1) / SW_ROWS;
+    L->endcell = up((size_t)2 * n * sizeof(int));
+    L->bound = L->endcell + up((size_t)4 * n * sizeof(int));
+    L->bound_stride = passes > 1 ? ((size_t)max_ref + WAVE - 1) / WAVE * WAVE : 0;
+    L->trace = L->bound + up((size_t)n * 2 * L->bound_stride * sizeof(int2));
+    L->trace_stride = max_ref ? passes * ((size_t)max_ref + WAVE - 1) * WAVE : 0;
+    L->total = L->trace + (size_t)n * L->trace_stride * sizeof(unsigned);
+    return true;
+}
+
+}  // namespace bh
+
+size_t bh_k_sw_workspace(int n, int max_seq, int max_ref) {
+    bh::SwLayout L;
+    return bh::sw_layout(n, max_seq, max_ref, &L) ? L.total : 0;
+}
+
+int bh_k_sw_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,
+                  int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace, size_t workspace_bytes,
+                  int* result, unsigned* ops, long ops_stride, int* n_ops, hipStream_t stream) {
+    using namespace bh;
+    BH_REQUIRE(n > 0, "sw_align: n must be positive (got %d)", n);
+    BH_REQUIRE(seqs && refs && seq_lens && ref_lens && workspace && result, "sw_align: null pointer");
+    BH_REQUIRE(match >= 1 && match <= SW_MAX_PARAM, "sw_align: match must be in 1..%d (got %d)", SW_MAX_PARAM, match);
+    BH_REQUIRE(mismatch < match && mismatch >= -SW_MAX_PARAM, "sw_align: mismatch must be in %d..match-1 (got %d)", -SW_MAX_PARAM,
+               mismatch);
+    BH_REQUIRE(gap_extend >= 1, "sw_align: gap_extend must be at least 1 (got %d)", gap_extend);
+    BH_REQUIRE(gap_open >= gap_extend && gap_open <= SW_MAX_PARAM, "sw_align: gap_open must be in gap_extend..%d (got open %d, extend %d)",
+               SW_MAX_PARAM, gap_open, gap_extend);
+    BH_REQUIRE(seq_stride >= 0 && ref_stride >= 0 && ops_stride >= 0, "sw_align: negative stride");
+    BH_REQUIRE(!n_ops || ops, "sw_align: n_ops without an ops buffer");
+    int max_seq = 0, max_ref = 0;
+    for (int i = 0; i < n; ++i) {
+        const int m = seq_lens[i], r = ref_lens[i];
+        BH_REQUIRE(m >= 0 && r >= 0, "sw_align: pair %d has a negative length (%d, %d)", i, m, r);
+        BH_REQUIRE(m <= seq_stride && r <= ref_stride, "sw_align: pair %d: lengths (%d, %d) exceed the row strides (%ld, %ld)", i, m, r,
+                   seq_stride, ref_stride);
+        BH_REQUIRE(m <= SW_MAX_LEN && r <= SW_MAX_LEN, "sw_align: pair %d: lengths (%d, %d) exceed the supported %d", i, m, r, SW_MAX_LEN);
+        const long need = m && r ? (long)m + r - 1 : 0;                     // every op consumes a base, the first one two
+        BH_REQUIRE(!ops || need <= ops_stride, "sw_align: pair %d may need %ld CIGAR runs, the ops rows hold %ld", i, need, ops_stride);
+        max_seq = m > max_seq ? m : max_seq;
+        max_ref = r > max_ref ? r : max_ref;
+    }
+    SwLayout L;
+    BH_REQUIRE(sw_layout(n, max_seq, max_ref, &L), "sw_align: unsupported shape");
+    BH_REQUIRE(workspace_bytes >= L.total, "sw_align: workspace of %zu bytes, %zu needed (bh_sw_workspace(%d, %d, %d))", workspace_bytes,
+               L.total, n, max_seq, max_ref);
+    char* ws = (char*)workspace;
+    // the lengths are host arrays (they were just validated): one blocking copy to the head of the workspace, ordered on the stream
+    std::vector<int> lens(seq_lens, seq_lens + n);
+    lens.insert(lens.end(), ref_lens, ref_lens + n);
+    BH_CHECK_HIP(hipMemcpyWithStream(ws, lens.data(), lens.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    SwArgs a{(const int8_t*)seqs, seq_stride, (const int8_t*)refs, ref_stride, (const int*)ws, (const int*)ws + n,
+             match, mismatch, gap_open, gap_extend, (unsigned*)(ws + L.trace), L.trace_stride, (int2*)(ws + L.bound), L.bound_stride,
+             (int*)(ws + L.endcell), result, ops, ops_stride, n_ops};
+    hipLaunchKernelGGL(sw_forward_kernel, dim3(n), dim3(WAVE), 0, stream, a);
+    BH_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(sw_traceback_kernel, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), 0, stream, a, n);
+    BH_CHECK_HIP(hipGetLastError());
+    return 0;
+}

@@ -59,6 +59,12 @@ int bh_k_crf_seq(const void* scores, int N, int T, int state_len, int layout_5s,
 int bh_k_crf_logz_dense(const void* scores, int N, int T, int state_len, int layout_5s, float blank, long s_n, long s_t,
                         float* out, hipStream_t stream);
 
+// align.hip (Smith-Waterman, affine gaps, traceback; the lengths are host arrays)
+size_t bh_k_sw_workspace(int n, int max_seq, int max_ref);
+int bh_k_sw_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,
+                  int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace, size_t workspace_bytes,
+                  int* result, unsigned* ops, long ops_stride, int* n_ops, hipStream_t stream);
+
 // beam.hip
 size_t bh_k_beam_workspace(int N, int T, int state_len);
 int bh_k_crf_logz(const void* scores, int N, int T, int state_len, float blank, void* workspace, double* logz_out,

@@ -288,3 +288,49 @@ def _load_model(model_file, config, device, half=True, use_koi=True):
     model.eval()
     model.to(device)
     return model
+
+
+_CIGAR_RUN = re.compile(r"(\d+)([=XIDS])")
+
+
+def cigar_to_sam(result, seq):
+    """(reference start, SAM CIGAR with S clips) of an alignment with a CIGAR: what the reference's ``parasail_to_sam`` returns
+    (bonito/util.py:313-343). ``result``: an ``align.AlignResult`` computed with ``cigar=True``. A leading insertion joins the left
+    clip and a leading deletion moves the start instead of being written; with this engine's tie-breaks an alignment starts on a
+    match or mismatch, so neither occurs. Nothing aligned -> (0, the whole of seq clipped)."""
+    if result.cigar is None:
+        raise ValueError("cigar_to_sam: the alignment carries no CIGAR (sw_align(..., cigar=True))")
+    if not result.cigar:
+        return 0, ("%dS" % len(seq) if len(seq) else "")
+    runs = _CIGAR_RUN.findall(result.cigar)
+    rstart, clip = result.align_ref_start, result.align_seq_start
+    count, op = int(runs[0][0]), runs[0][1]
+    if op == "I":
+        pre = "%dS" % (count + clip)
+    elif op == "D":
+        pre, rstart = ("%dS" % clip if clip else ""), rstart + count
+    else:
+        pre = ("%dS" % clip if clip else "") + "%d%s" % (count, op)
+    end_clip = len(seq) - result.align_seq_end - 1
+    return rstart, pre + "".join(c + o for c, o in runs[1:]) + ("%dS" % end_clip if end_clip > 0 else "")
+
+
+def accuracy(ref, seq, balanced=False, min_coverage=0.0, result=None):
+    """Accuracy of `seq` against `ref` in percent (reference bonito/util.py:346-368): one Smith-Waterman alignment on the device
+    (align.sw_align, the reference's parasail arguments), then = / (= + X + I + D), or (= - I) / (= + X + D) when `balanced`.
+    0.0 when the alignment, counted in alignment columns as the reference counts it, covers less than `min_coverage` of `ref`,
+    and when nothing aligns. `result`: an ``AlignResult`` of this pair computed earlier with ``cigar=True`` (a training loop
+    aligns a whole validation batch in one ``sw_align`` call); the device is not touched then."""
+    if result is None:
+        from bonito_amd.align import sw_align
+        result = sw_align([seq], [ref], cigar=True)[0]
+    columns = result.num_correct + result.num_mismatches + result.num_insertions + result.num_deletions
+    if columns == 0 or len(ref) == 0 or columns / len(ref) < min_coverage:
+        return 0.0
+    _, cigar = cigar_to_sam(result, seq)
+    counts = {"=": 0, "X": 0, "I": 0, "D": 0, "S": 0}
+    for count, op in _CIGAR_RUN.findall(cigar):
+        counts[op] += int(count)
+    if balanced:
+        return (counts["="] - counts["I"]) / (counts["="] + counts["X"] + counts["D"]) * 100
+    return counts["="] / (counts["="] + counts["I"] + counts["X"] + counts["D"]) * 100

@@ -18,6 +18,9 @@
  *   bh_crf_seq_logz / bh_crf_seq_viterbi (+ bh_crf_seq_logz_free, bh_crf_logz_dense)
  *        koi.ctc.{logZ_cu, viterbi_alignments} behind CTC_CRF.ctc_loss / ctc_viterbi_alignments, SeqdistModel.loss
  *                                                                              bonito/crf/model.py:126-143,204-207
+ *   bh_sw_align
+ *        parasail.sw_trace_striped_32(seq, ref, 8, 4, parasail.dnafull) behind evaluate's align() and util.accuracy
+ *                                                                              bonito/cli/evaluate.py:37-67, bonito/util.py:346-368
  *   bh_ctc_greedy_decode / bh_ctc_beam_search
  *        fast_ctc_decode.viterbi_search / beam_search                          bonito/ctc/model.py:39-46
  *   bh_linear, bh_conv1d_*, bh_lstm_layer, ...  (operator level, used by the parity tests)
@@ -218,6 +221,31 @@ int bh_crf_seq_logz_free(const void* scores, int N, int T, int state_len, float 
                          float* logz_out, void* stream);
 int bh_crf_logz_dense(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
                       long stride_t, float* logz_out, void* stream);
+
+/* ---- Smith-Waterman local alignment with affine gaps and a traceback (csrc/align.hip) ----------------------------------
+ * n pairs of a called sequence `seq` (the query, index i) and a known sequence `ref` (index j). seqs / refs: DEVICE int8 planes
+ * [n][stride] of the codes 1..4 (decode.encode_sequences), 0 = padding. seq_lengths / ref_lengths: HOST int32 [n] (they are
+ * validated before anything is launched, then copied into the workspace). Exact int32 scores, a gap of length k costs
+ * gap_open + (k - 1) * gap_extend:
+ *     E(i,j) = max(H(i,j-1) - open, E(i,j-1) - extend)     deletion, CIGAR D        F(i,j) = max(H(i-1,j) - open, F(i-1,j) - extend)
+ *     H(i,j) = max(0, H(i-1,j-1) + (seq_i == ref_j ? match : mismatch), E(i,j), F(i,j))                         insertion, CIGAR I
+ * End cell: the largest H, among equals the smallest i, then the smallest j. Traceback in H: stop at H = 0, else prefer the
+ * diagonal, then E, then F; in E / F the open wins a tie with the extension.
+ * result: DEVICE int32 [n][10] = score, num_correct (=), num_mismatches (X), num_insertions (I), num_deletions (D),
+ *   align_ref_start, align_ref_end, align_seq_start, align_seq_end (0-based, ends inclusive), number of CIGAR runs.
+ *   A pair with score 0 (an empty sequence among them): counts 0, starts 0, ends -1, no runs.
+ * ops (optional, DEVICE uint32 [n][ops_stride]) with n_ops (optional, DEVICE int32 [n]): the run-length CIGAR in alignment order,
+ *   one run = (length << 2) | op, op 0 '=', 1 'X', 2 'I', 3 'D'. ops_stride must hold the longest CIGAR any pair could have
+ *   (seq_len + ref_len - 1 runs; 0 for an empty pair): a shorter buffer is an error, never a truncated CIGAR.
+ * workspace: DEVICE, bh_sw_workspace(n, max seq length, max ref length) bytes (0 = unsupported shape: n < 1 or a length outside
+ *   0..4096); 4 traceback bits per cell: n * ceil(max_seq / 512) * (max_ref + 63) * 256 bytes plus a small head.
+ * Errors (non-zero, bh_last_error() set, nothing launched): negative lengths, a length beyond its stride or beyond 4096,
+ *   match < 1, mismatch >= match, gap_extend < 1, gap_open < gap_extend, a parameter beyond 32767 in magnitude, a workspace or
+ *   ops buffer that is too small. */
+size_t bh_sw_workspace(int n, int max_seq, int max_ref);
+int bh_sw_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, const void* refs, long ref_stride,
+                const int32_t* ref_lengths, int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace,
+                size_t workspace_bytes, int32_t* result, uint32_t* ops, long ops_stride, int32_t* n_ops, void* stream);
 
 /* Signal ingest on the device: replaces Read.__init__'s numpy work (bonito/reader.py:122-166 normalisation + trim, the pA
  * scaling of bonito/pod5.py:52-67) and util.chunk + the fp16 cast (bonito/util.py:142-161, crf/basecall.py:31) for raw
