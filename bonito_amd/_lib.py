@@ -76,6 +76,9 @@ SIGNATURES = {
     "bh_beam_search_workspace": (_sz, [_i, _i, _i]),
     "bh_beam_search": (_i, [_vp, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bh_linear": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _i, _l, _l, _i, _vp]),
+    "bh_linear_residual": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _i, _l, _l, _i, _vp, _i, _f, _vp]),
+    "bh_linear_qkv_rotary": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _f, _vp]),
+    "bh_linear_last_kernel": (_i, []),
     "bh_conv1d_first": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _l, _l, _vp]),
     "bh_conv1d_packed_halves": (_sz, [_i, _i, _i]),
     "bh_conv1d_pack": (_i, [_vp, _i, _i, _i, _vp]),

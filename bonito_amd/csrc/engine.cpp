@@ -1291,6 +1291,20 @@ extern "C" int bh_linear(const void* X, const void* W, const float* bias, void* 
     return bh_k_linear(X, W, bias, out, M, N, K, ldx, ldw, ldo, act, scale, clamp_lo, clamp_hi, gated, row_div,
                        row_s_hi, row_s_lo, row_lim, (hipStream_t)stream);
 }
+extern "C" int bh_linear_residual(const void* X, const void* W, const float* bias, void* out, int M, int N, int K, int ldx,
+                                  int ldw, int ldo, int act, float scale, float clamp_lo, float clamp_hi, int gated,
+                                  int row_div, long row_s_hi, long row_s_lo, int row_lim, const void* residual, int ldres,
+                                  float res_scale, void* stream) {
+    BH_REQUIRE(X && W && out && residual, "linear_residual: null pointer");
+    return bh_k_linear(X, W, bias, out, M, N, K, ldx, ldw, ldo, act, scale, clamp_lo, clamp_hi, gated, row_div,
+                       row_s_hi, row_s_lo, row_lim, (hipStream_t)stream, residual, ldres, res_scale);
+}
+extern "C" int bh_linear_qkv_rotary(const void* X, const void* W, const float* bias, void* out, int M, int D, int K,
+                                    const float* cos_sin, int T, float qscale, void* stream) {
+    BH_REQUIRE(X && W && out && cos_sin, "linear_qkv_rotary: null pointer");
+    return bh_k_linear_qkv_rotary(X, W, bias, out, M, D, K, cos_sin, T, qscale, (hipStream_t)stream);
+}
+extern "C" int bh_linear_last_kernel(void) { return bh_k_linear_last_kernel(); }
 extern "C" int bh_conv1d_first(const void* signal, const float* w, const float* bias, void* out, int N, int Lin,
                                int Cout, int K, int stride, int pad, int act, float clamp_lo, float clamp_hi,
                                long os_n, long os_t, void* stream) {

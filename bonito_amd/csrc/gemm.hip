@@ -152,6 +152,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, float4_t (&acc)
                 y[i] = v0[2 * i] * swishf_(v0[2 * i + 1]);
                 y[4 + i] = v1[2 * i] * swishf_(v1[2 * i + 1]);
             }
+            if (!plain) {           // (launch-uniform; the four-wave kernel sends gated calls with scale / clamp here)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) y[i] = fminf(fmaxf(y[i] * p.scale, p.clamp_lo), p.clamp_hi);
+            }
             const half8_t o = __builtin_convertvector(y, half8_t);
             const int fo = fbase >> 1;
             if (ALIGNED || fo + 8 <= (p.N >> 1)) *(half8_t*)(p.out + orow * p.ldo + fo) = o;
@@ -1313,6 +1317,7 @@ static int g_stagger = 0;    // bh_k_linear_stagger
 // bh_k_linear_tile16 ("gemm_tile16"): gemm_w4_kernel's K-tile stream on 16x16x32 MFMAs (1, default since round 6: 5-9 % faster on every
 // shape of tools/gemm_bench.py, sup 60.4 -> 59.2 ms per batch - profiles/r06_gemm_tile16.txt) or on 32x32x16 (0: rounds 4-5)
 static int g_w4_t16 = 1;
+static int g_last_kernel = 0; // bh_k_linear_last_kernel (test hook, not thread-safe): 1 = v1, 2 = v2, 3 = v3, 5 / 6 = v5 on 32x32x16 / 16x16x32
 static int g_force_v1 = 0;   // test / A-B hook (bh_k_linear_force_v1): 1 = v1 only, 2 = never v3 / v5, 3 = never v5 (v3 where it applies), 5 = v5 whenever the shape is legal (tests: small problems)
 
 template <int ACT, bool GATED>
@@ -1367,7 +1372,7 @@ static int launch(const GemmArgs& a, hipStream_t s) {
             }
 #undef W4_LAUNCH
 #undef W4_LAUNCH_T
-            if (done) return 0;
+            if (done) { g_last_kernel = g_w4_t16 ? 6 : 5; return 0; }
         }
         if (false) {
             return 0;
@@ -1381,13 +1386,17 @@ static int launch(const GemmArgs& a, hipStream_t s) {
             const int tiles = nf3 * nt3;
             BH_CHECK_HIP(bh_max_lds((const void*)gemm_big_kernel<ACT, GATED>, 4 * TILE3));
             hipLaunchKernelGGL((gemm_big_kernel<ACT, GATED>), dim3(tiles < cus ? tiles : cus), dim3(512), 4 * TILE3, s, b);
+            g_last_kernel = 3;
             return 0;
         }
     }
-    if (a.K % BK2 == 0 && g_force_v1 != 1)
+    if (a.K % BK2 == 0 && g_force_v1 != 1) {
         hipLaunchKernelGGL((gemm_glds_kernel<ACT, GATED>), dim3(grid), dim3(256), 4 * TILE2, s, a);
-    else
+        g_last_kernel = 2;
+    } else {
         hipLaunchKernelGGL((gemm_kernel<ACT, GATED>), dim3(grid), dim3(256), 4 * TILE_BYTES, s, a);
+        g_last_kernel = 1;
+    }
     return 0;
 }
 
@@ -1398,6 +1407,7 @@ void bh_k_linear_stagger(int units) { bh::g_stagger = units; }
 void bh_k_linear_tile16(int on) { bh::g_w4_t16 = on ? 1 : 0; }
 void bh_k_linear_order(int order) { bh::g_w4_order = order ? 1 : 0; }
 void bh_k_linear_gf(int gf) { bh::g_w4_gf = gf; }
+int bh_k_linear_last_kernel() { return bh::g_last_kernel; }
 
 int bh_k_linear(const void* X, const void* W, const float* bias, void* out, int M, int N, int K,
                 int ldx, int ldw, int ldo, int act, float scale, float clamp_lo, float clamp_hi,
@@ -1408,6 +1418,8 @@ int bh_k_linear(const void* X, const void* W, const float* bias, void* out, int 
     BH_REQUIRE(K % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0, "linear: K/ldx/ldw must be multiples of 8 halves");
     BH_REQUIRE(ldo % 8 == 0, "linear: ldo must be a multiple of 8 halves");
     BH_REQUIRE(!gated || (N % 16 == 0), "linear: gated epilogue needs N %% 16 == 0");
+    // the epilogues read the residual as 16-byte vectors (v5: buffer loads of whole 128-byte lines)
+    BH_REQUIRE(residual == nullptr || ldres % 8 == 0, "linear: ldres must be a multiple of 8 halves");
     GemmArgs a;
     a.X = (const half_t*)X; a.W = (const half_t*)W; a.bias = bias; a.out = (half_t*)out;
     a.res = (const half_t*)residual; a.ldres = ldres; a.res_scale = res_scale;

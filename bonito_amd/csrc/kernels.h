@@ -17,6 +17,7 @@ void bh_k_linear_stagger(int units);
 void bh_k_linear_order(int order);  // gemm_w4_kernel's work order inside an XCD: 0 token blocks fastest, 1 feature groups fastest
 void bh_k_linear_gf(int gf);        // ... feature tiles per block (0 = automatic)
 void bh_k_linear_tile16(int on);   // gemm_w4_kernel on 16x16x32 MFMAs (1) or 32x32x16 (0)
+int bh_k_linear_last_kernel();     // test hook: the kernel the last launch took (1 = v1, 2 = v2, 3 = v3, 5 / 6 = v5 on 32x32x16 / 16x16x32); not thread-safe
 
 // conv.hip
 int bh_k_conv_first(const void* signal, const float* w, const float* bias, void* out, int N, int Lin,

@@ -332,6 +332,26 @@ int bh_beam_search(const void* scores, int N, int T, int state_len, int beam_wid
 int bh_linear(const void* X, const void* W, const float* bias, void* out, int M, int N, int K, int ldx,
               int ldw, int ldo, int act, float scale, float clamp_lo, float clamp_hi, int gated,
               int row_div, long row_s_hi, long row_s_lo, int row_lim, void* stream);
+/* bh_linear with the fused residual the transformer's out_proj / fc2 and the residual convolution branches use. Order of the epilogue,
+ * all in fp32 with ONE rounding to fp16 at the end:  z = X[m] . W[n] + bias[n];  z += res_scale * residual[m][n]  (the residual is indexed
+ * by the INPUT row m, not by the remapped output row; fp16 [M][ldres]);  activation;  * scale;  clamp.  With gated=1 the residual
+ * (N columns) is added to the interleaved (y, gate) pairs BEFORE gating, and scale / clamp apply to y * swish(gate).
+ * ldres must be a multiple of 8 halves like ldx / ldw / ldo (the kernels read the residual in 16-byte vectors): anything else is an
+ * error (nonzero return, nothing launched). */
+int bh_linear_residual(const void* X, const void* W, const float* bias, void* out, int M, int N, int K, int ldx,
+                       int ldw, int ldo, int act, float scale, float clamp_lo, float clamp_hi, int gated,
+                       int row_div, long row_s_hi, long row_s_lo, int row_lim, const void* residual, int ldres,
+                       float res_scale, void* stream);
+/* Packed Wqkv projection with the rotary embedding fused into its epilogue (what the engine's transformer layers run):
+ * X fp16 [M][K], W fp16 [3D][K], bias fp32 [3D] or null, out fp16 [M][3D]; D % 64 == 0 (heads of 64), K % 8 == 0. Row m has position
+ * m % T; cos_sin = device copy of bh_rotary_table(>= T, 64). Per head of 64 (x1 = dims 0..31, x2 = dims 32..63, non-interleaved):
+ * out[0:D) = (x1 cos - x2 sin, x1 sin + x2 cos) of q, times qscale; out[D:2D) = the same rotation of k; out[2D:3D) = v unchanged. */
+int bh_linear_qkv_rotary(const void* X, const void* W, const float* bias, void* out, int M, int D, int K,
+                         const float* cos_sin, int T, float qscale, void* stream);
+/* TEST HOOK: the kernel the last bh_linear* call (or linear layer of an encoder) of this process launched: 1 = register-staged 128-tile
+ * kernel, 2 = LDS-DMA 128-tile kernel, 3 = eight-wave 256-tile kernel, 5 / 6 = four-wave 256-tile kernel on its 32x32x16 / 16x16x32
+ * stream; 0 = none yet. A host-side static written by the launcher: process-wide, not thread-safe. */
+int bh_linear_last_kernel(void);
 /* first convolution, Cin = 1: signal fp16 [N][Lin] -> out (n*os_n + t*os_t + c), w fp32 [Cout][K] on device */
 int bh_conv1d_first(const void* signal, const float* w, const float* bias, void* out, int N, int Lin,
                     int Cout, int K, int stride, int pad, int act, float clamp_lo, float clamp_hi,

@@ -198,7 +198,7 @@ def test_transformer_layers_on_the_four_wave_gemm_match_oracle(tile16):
     residual, the SwiGLU fc1, the CRF head with scale) forced onto gemm_w4_kernel ("gemm_path" 5: any legal shape; small calls take the
     eight-wave kernels otherwise) - on its 32x32x16 K-tile stream and on the 16x16x32 one ("gemm_tile16") - against the fp32 oracle of
     the reference modules; 2 x 300 tokens: ragged token tiles, one rotary wrap inside a tile."""
-    from bonito_amd import decode, synthetic
+    from bonito_amd import _lib, decode, synthetic
     from bonito_amd.transformer import Model
     torch.manual_seed(12)
     cfg = synthetic.transformer_model_config(d_model=512, nhead=8, dim_ff=2048, depth=2, window=(127, 128), state_len=3,
@@ -217,10 +217,13 @@ def test_transformer_layers_on_the_four_wave_gemm_match_oracle(tile16):
             enc.set_option("norm_fuse", fuse)
             outs[fuse] = enc(x.cuda()).cpu().float()
             enc.check()
+            # the last linear layer of the encoder is the CRF head (600 x 256 x 512, tanh, scale 5): it ran on the four-wave kernel
+            assert _lib.lib().bh_linear_last_kernel() == (6 if tile16 else 5)
         decode.set_option("gemm_path", 2)
         enc = HipEncoder(model.encoder, batchsize=2, chunksize=1800)
         outs["small"] = enc(x.cuda()).cpu().float()
         enc.check()
+        assert _lib.lib().bh_linear_last_kernel() == 2
     finally:
         decode.set_option("gemm_path", 0)
         decode.set_option("gemm_tile16", 1)              # the library's default

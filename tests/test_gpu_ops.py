@@ -30,6 +30,11 @@ def _linear(x, w, bias=None, act=0, scale=1.0, lo=-INF, hi=INF, gated=0, row=(0,
     return out
 
 
+def _last_kernel():
+    """bh_linear_last_kernel(): 1 = v1, 2 = v2, 3 = v3 (eight waves), 5 / 6 = v5 (four waves) on its 32x32x16 / 16x16x32 stream."""
+    return _lib.lib().bh_linear_last_kernel()
+
+
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (300, 384, 96), (1000, 1024, 384), (77, 80, 32), (4096, 1536, 384)])
 def test_linear_plain(M, N, K):
     g = torch.Generator().manual_seed(M + N + K)
@@ -91,6 +96,17 @@ def test_linear_rejects_bad_shapes():
     rc = _lib.lib().bh_linear(_lib.ptr(x), _lib.ptr(w), None, _lib.ptr(out), 4, 4, 12, 12, 12, 8, 0, 1.0, -INF, INF,
                               0, 0, 0, 0, 0, _lib.stream_ptr())
     assert rc != 0 and "multiples of 8" in _lib.last_error()
+
+
+def test_linear_residual_rejects_unaligned_ldres():
+    """ldres is held to the rule of ldx / ldw / ldo (the epilogues read the residual in 16-byte vectors)."""
+    x = torch.zeros(4, 16, dtype=torch.float16, device=dev())
+    w = torch.zeros(16, 16, dtype=torch.float16, device=dev())
+    res = torch.zeros(4, 18, dtype=torch.float16, device=dev())
+    out = torch.zeros(4, 16, dtype=torch.float16, device=dev())
+    rc = _lib.lib().bh_linear_residual(_lib.ptr(x), _lib.ptr(w), None, _lib.ptr(out), 4, 16, 16, 16, 16, 16, 0, 1.0, -INF, INF,
+                                       0, 0, 0, 0, 0, _lib.ptr(res), 18, 1.0, _lib.stream_ptr())
+    assert rc != 0 and "ldres" in _lib.last_error()
 
 
 @pytest.mark.parametrize("Cout,K,stride,act", [(16, 5, 1, 1), (64, 5, 1, 1), (344, 9, 3, 0), (8, 19, 6, 2), (4, 5, 1, 1), (6, 3, 2, 0)])
@@ -380,11 +396,14 @@ def test_linear_persistent_big_tile_kernel(M, N, K, gated):
     try:
         decode.set_option("gemm_path", 3)            # (0 = automatic would pick the four-wave kernel where it applies: its own test below)
         big = _linear(x, w, b, act=0 if gated else 1, gated=gated)
+        assert _last_kernel() == 3
         decode.set_option("gemm_path", 2)
         small = _linear(x, w, b, act=0 if gated else 1, gated=gated)
+        assert _last_kernel() == 2
         decode.set_option("gemm_path", 3)
         decode.set_option("gemm_stagger", 3)
         again = _linear(x, w, b, act=0 if gated else 1, gated=gated)
+        assert _last_kernel() == 3
     finally:
         decode.set_option("gemm_path", 0)
         decode.set_option("gemm_stagger", 0)
@@ -429,9 +448,12 @@ def test_linear_four_wave_kernel(M, N, K, gated, act, tile16):
         decode.set_option("gemm_tile16", tile16)
         decode.set_option("gemm_path", 5)
         got = _linear(x, w, b, act=act, gated=gated)
+        assert _last_kernel() == (6 if tile16 else 5)
         again = _linear(x, w, b, act=act, gated=gated)
+        assert _last_kernel() == (6 if tile16 else 5)
         decode.set_option("gemm_path", 2)
         small = _linear(x, w, b, act=act, gated=gated)
+        assert _last_kernel() == 2
     finally:
         decode.set_option("gemm_path", 0)
         decode.set_option("gemm_tile16", TILE16_DEFAULT)
@@ -460,6 +482,7 @@ def test_linear_four_wave_kernel_work_order_does_not_change_bytes():
             decode.set_option("gemm_order", order)
             decode.set_option("gemm_gf", gf)
             outs.append(_linear(x, w))
+            assert _last_kernel() == 6
     finally:
         decode.set_option("gemm_path", 0)
         decode.set_option("gemm_order", 1)
@@ -484,6 +507,7 @@ def test_linear_four_wave_kernel_layouts_exactly(tile16):
         decode.set_option("gemm_tile16", tile16)
         decode.set_option("gemm_path", 5)
         got = _linear(x.half().to(dev()), w.to(dev())).cpu()
+        assert _last_kernel() == (6 if tile16 else 5)
     finally:
         decode.set_option("gemm_path", 0)
         decode.set_option("gemm_tile16", TILE16_DEFAULT)
@@ -492,8 +516,9 @@ def test_linear_four_wave_kernel_layouts_exactly(tile16):
 
 @pytest.mark.parametrize("tile16", [0, 1])
 def test_linear_four_wave_kernel_row_remap_scale_clamp(tile16):
-    """The CRF head's call shape on the four-wave kernel: (t, n)-major rows -> [N][T][C] with the padded batch rows dropped, tanh,
-    scale 5, clamp."""
+    """The CRF head's call shape under "gemm_path" 5: (t, n)-major rows -> [N][T][C] with the padded batch rows dropped, tanh,
+    scale 5, clamp. (A batch of 32 is no multiple of 256, so the four-wave launcher passes this call on to the 128-tile LDS-DMA kernel:
+    bh_linear_last_kernel() says so. The remap ON the four-wave kernel is the test below and tests/test_gpu_linear.py::test_row_remap.)"""
     from bonito_amd import decode
     T, Np, Nv, K, Cc = 70, 32, 27, 384, 1024
     g = torch.Generator().manual_seed(8)
@@ -505,6 +530,28 @@ def test_linear_four_wave_kernel_row_remap_scale_clamp(tile16):
         decode.set_option("gemm_tile16", tile16)
         decode.set_option("gemm_path", 5)
         got = _linear(x.to(dev()), w.to(dev()), act=2, scale=5.0, lo=-4.5, hi=4.5, row=(Np, 1, T, Nv), out_rows=Nv * T).cpu().float()
+        assert _last_kernel() == 2
+    finally:
+        decode.set_option("gemm_path", 0)
+        decode.set_option("gemm_tile16", TILE16_DEFAULT)
+    assert (got - want).abs().max().item() < 2e-2
+
+
+@pytest.mark.parametrize("tile16", [0, 1])
+def test_linear_four_wave_kernel_row_remap_scale_clamp_batch_of_256(tile16):
+    """The same call with a padded batch of 256 (251 valid): the remap the four-wave kernel itself serves (group size % 256 == 0)."""
+    from bonito_amd import decode
+    T, Np, Nv, K, Cc = 9, 256, 251, 384, 1024
+    g = torch.Generator().manual_seed(9)
+    x = torch.randn(T * Np, K, generator=g).half()
+    w = (torch.randn(Cc, K, generator=g) * 0.1).half()
+    z = torch.tanh(x.float() @ w.float().T) * 5.0
+    want = z.clamp(-4.5, 4.5).view(T, Np, Cc)[:, :Nv].permute(1, 0, 2).reshape(Nv * T, Cc)
+    try:
+        decode.set_option("gemm_tile16", tile16)
+        decode.set_option("gemm_path", 5)
+        got = _linear(x.to(dev()), w.to(dev()), act=2, scale=5.0, lo=-4.5, hi=4.5, row=(Np, 1, T, Nv), out_rows=Nv * T).cpu().float()
+        assert _last_kernel() == (6 if tile16 else 5)
     finally:
         decode.set_option("gemm_path", 0)
         decode.set_option("gemm_tile16", TILE16_DEFAULT)
