@@ -1,0 +1,311 @@
+// The operator-level extern "C" shells declared in include/bonito_hip.h: argument checks in front of the launchers of kernels.h,
+// host-side weight packing, and the process-wide option switch. The encoder (bh_encoder_*) lives in engine.cpp.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "../../include/bonito_hip.h"
+#include "common.h"
+#include "devbuf.h"
+#include "kernels.h"
+
+namespace bh { extern int g_q8_variant; }     // engine.cpp ("lstm_q8_variant")
+
+extern "C" size_t bh_conv1d_packed_halves(int Cin, int Cout, int K) {
+    size_t kp = ((size_t)K * Cin + 31) / 32 * 32;
+    size_t c16 = ((size_t)Cout + 15) / 16 * 16;
+    return kp * c16;
+}
+// torch conv weight [Cout][Cin][K] -> [Cout16][Kp], column index = k*Cin + c (channel-minor taps)
+extern "C" int bh_conv1d_pack(const float* w, int Cin, int Cout, int K, uint16_t* packed) {
+    BH_REQUIRE(w && packed && Cin > 0 && Cout > 0 && K > 0, "conv1d_pack: bad arguments");
+    size_t kp = ((size_t)K * Cin + 31) / 32 * 32;
+    size_t c16 = ((size_t)Cout + 15) / 16 * 16;
+    memset(packed, 0, kp * c16 * 2);
+    for (int f = 0; f < Cout; ++f)
+        for (int c = 0; c < Cin; ++c)
+            for (int k = 0; k < K; ++k)
+                packed[(size_t)f * kp + (size_t)k * Cin + c] = f2h(w[((size_t)f * Cin + c) * K + k]);
+    return 0;
+}
+// W_hh [4H][H] (torch gate order i,f,g,o) -> [slice][gate][kstep][lane][8]: the A fragment of
+// mfma 16x16x32 for rows gate*H + slice*16 + (lane&15), k = kstep*32 + (lane>>4)*8 + j.
+extern "C" int bh_lstm_pack_whh(const float* whh, int H, uint16_t* packed) {
+    BH_REQUIRE(whh && packed && H % 32 == 0 && H > 0, "lstm_pack_whh: H must be a positive multiple of 32");
+    const int nks = H / 32, nsl = H / 16;
+    for (int s = 0; s < nsl; ++s)
+        for (int g = 0; g < 4; ++g)
+            for (int ks = 0; ks < nks; ++ks)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int j = 0; j < 8; ++j) {
+                        int row = g * H + s * 16 + (lane & 15);
+                        int col = ks * 32 + (lane >> 4) * 8 + j;
+                        packed[((((size_t)s * 4 + g) * nks + ks) * 64 + lane) * 8 + j] =
+                            f2h(whh[(size_t)row * H + col]);
+                    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// operator-level shells
+extern "C" int bh_linear(const void* X, const void* W, const float* bias, void* out, int M, int N, int K, int ldx,
+                         int ldw, int ldo, int act, float scale, float clamp_lo, float clamp_hi, int gated,
+                         int row_div, long row_s_hi, long row_s_lo, int row_lim, void* stream) {
+    BH_REQUIRE(X && W && out, "linear: null pointer");
+    return bh_k_linear(X, W, bias, out, M, N, K, ldx, ldw, ldo, act, scale, clamp_lo, clamp_hi, gated, row_div,
+                       row_s_hi, row_s_lo, row_lim, (hipStream_t)stream);
+}
+extern "C" int bh_linear_residual(const void* X, const void* W, const float* bias, void* out, int M, int N, int K, int ldx,
+                                  int ldw, int ldo, int act, float scale, float clamp_lo, float clamp_hi, int gated,
+                                  int row_div, long row_s_hi, long row_s_lo, int row_lim, const void* residual, int ldres,
+                                  float res_scale, void* stream) {
+    BH_REQUIRE(X && W && out && residual, "linear_residual: null pointer");
+    return bh_k_linear(X, W, bias, out, M, N, K, ldx, ldw, ldo, act, scale, clamp_lo, clamp_hi, gated, row_div,
+                       row_s_hi, row_s_lo, row_lim, (hipStream_t)stream, residual, ldres, res_scale);
+}
+extern "C" int bh_linear_qkv_rotary(const void* X, const void* W, const float* bias, void* out, int M, int D, int K,
+                                    const float* cos_sin, int T, float qscale, void* stream) {
+    BH_REQUIRE(X && W && out && cos_sin, "linear_qkv_rotary: null pointer");
+    return bh_k_linear_qkv_rotary(X, W, bias, out, M, D, K, cos_sin, T, qscale, (hipStream_t)stream);
+}
+extern "C" int bh_linear_last_kernel(void) { return bh_k_linear_last_kernel(); }
+extern "C" int bh_conv1d_first(const void* signal, const float* w, const float* bias, void* out, int N, int Lin,
+                               int Cout, int K, int stride, int pad, int act, float clamp_lo, float clamp_hi,
+                               long os_n, long os_t, void* stream) {
+    BH_REQUIRE(signal && w && out && stride > 0, "conv1d_first: bad arguments");
+    const int lout = conv_out_len(Lin, K, stride, pad);
+    BH_REQUIRE(lout > 0, "conv1d_first: input too short");
+    return bh_k_conv_first(signal, w, bias, out, N, Lin, lout, Cout, K, stride, pad, act, clamp_lo, clamp_hi, os_n,
+                           os_t, (hipStream_t)stream);
+}
+extern "C" int bh_conv1d(const void* in, const void* wpacked, const float* bias, void* out, int N, int Lin, int Cin,
+                         int Cout, int K, int stride, int pad, int act, float clamp_lo, float clamp_hi, long os_n,
+                         long os_t, void* stream) {
+    BH_REQUIRE(in && wpacked && out && stride > 0, "conv1d: bad arguments");
+    const int lout = conv_out_len(Lin, K, stride, pad);
+    BH_REQUIRE(lout > 0, "conv1d: input too short");
+    return bh_k_conv_igemm(in, wpacked, bias, out, N, Lin, lout, Cin, Cout, K, stride, pad, act, clamp_lo, clamp_hi,
+                           os_n, os_t, (hipStream_t)stream);
+}
+// cos/sin of position * 10000^(-2i/dim), interleaved [T][dim/2][2], fp32 products like flash_attn's rotary
+extern "C" int bh_rotary_table(int T, int dim, float* out) {
+    BH_REQUIRE(out && T > 0 && dim > 0 && dim % 2 == 0, "rotary_table: bad arguments");
+    const int half = dim / 2;
+    for (int t = 0; t < T; ++t)
+        for (int i = 0; i < half; ++i) {
+            const float inv = 1.0f / powf(10000.0f, (float)(2 * i) / (float)dim);
+            const float ang = (float)t * inv;
+            out[((size_t)t * half + i) * 2] = cosf(ang);
+            out[((size_t)t * half + i) * 2 + 1] = sinf(ang);
+        }
+    return 0;
+}
+extern "C" int bh_attention(const void* qkv, void* out, const float* cos_sin, int N, int T, int nhead, int head_dim,
+                            int win_left, int win_right, void* stream) {
+    BH_REQUIRE(qkv && out && cos_sin, "attention: null pointer");
+    return bh_k_attention(qkv, out, cos_sin, N, T, nhead, head_dim, win_left, win_right, (hipStream_t)stream);
+}
+extern "C" int bh_attention_prerotated(const void* qkv, void* out, int N, int T, int nhead, int head_dim, int win_left, int win_right,
+                                       void* stream) {
+    BH_REQUIRE(qkv && out, "attention_prerotated: null pointer");
+    return bh_k_attention_prerotated(qkv, out, N, T, nhead, head_dim, win_left, win_right, (hipStream_t)stream);
+}
+extern "C" int bh_rmsnorm_residual(const void* a, const void* x, const float* w, void* out, long M, int D, float alpha,
+                                   float eps, void* stream) {
+    BH_REQUIRE(a && x && w && out && M > 0, "rmsnorm_residual: bad arguments");
+    return bh_k_rmsnorm_residual(a, x, w, out, M, D, alpha, eps, (hipStream_t)stream);
+}
+extern "C" int bh_ctc_greedy_decode(const float* logp, const long* offsets, int R, int classes, float qscale, float qbias,
+                                    int8_t* labels, int8_t* qual, int* path, int* count, void* stream) {
+    BH_REQUIRE(logp && offsets && labels && qual && path && count, "ctc_greedy_decode: null pointer");
+    return bh_k_ctc_greedy(logp, offsets, R, classes, qscale, qbias, labels, qual, path, count, (hipStream_t)stream);
+}
+extern "C" size_t bh_ctc_beam_search_workspace(long total_steps, int R, int classes, int beam_size) {
+    return bh_k_ctc_beam_workspace(total_steps, R, classes, beam_size);
+}
+extern "C" int bh_ctc_beam_search(const float* logp, const long* offsets, int R, int classes, int beam_size, float threshold,
+                                  void* workspace, int8_t* labels, int* path, int* count, void* stream) {
+    BH_REQUIRE(logp && offsets && workspace && labels && path && count, "ctc_beam_search: null pointer");
+    return bh_k_ctc_prefix_beam(logp, offsets, R, classes, beam_size, threshold, workspace, labels, path, count,
+                                (hipStream_t)stream);
+}
+extern "C" int bh_dwconv1d(const void* in, const float* w, void* out, int N, int Lin, int C, int K, int stride, int pad,
+                           void* stream) {
+    BH_REQUIRE(in && w && out && stride > 0, "dwconv1d: bad arguments");
+    const int lout = conv_out_len(Lin, K, stride, pad);
+    BH_REQUIRE(lout > 0, "dwconv1d: input too short");
+    return bh_k_dwconv(in, w, out, N, Lin, lout, C, K, stride, pad, (hipStream_t)stream);
+}
+extern "C" size_t bh_lstm_workspace(int N, int H) { return bh_k_lstm_ws_bytes(N, H); }
+extern "C" int bh_lstm_layer(const void* gates_in, const void* whh_packed, void* h_out, int T, int N, int H,
+                             int reverse, void* workspace, int* err_flag, int flags, void* stream) {
+    BH_REQUIRE(gates_in && whh_packed && h_out && err_flag && workspace, "lstm_layer: null pointer");
+    BH_REQUIRE(T > 0, "lstm_layer: T must be positive");
+    int rc = bh_k_fill_u16(h_out, 0xFFFFu, (size_t)T * N * H, (hipStream_t)stream);
+    if (rc) return rc;
+    if (H > 512 || (flags & 2)) {     // flags bit 1: force the weight-streaming kernel
+        const int per = std::max(8, bh_k_lstm_geometry(BH_LSTM_STREAM, H).rings_per_launch(bh_cu_count()));
+        for (int r0 = 0; r0 < N / 16; r0 += per) {
+            const int nr = std::min(per, N / 16 - r0);
+            rc = bh_k_lstm_layer_stream((const char*)gates_in + (size_t)r0 * 16 * 4 * H * 2, whh_packed,
+                                        (char*)h_out + (size_t)r0 * 16 * H * 2, T, N, H, reverse, err_flag,
+                                        (hipStream_t)stream, nr, (int*)workspace, flags & 1);
+            if (rc) return rc;
+        }
+        return 0;
+    }
+    return bh_k_lstm_layer(gates_in, whh_packed, h_out, T, N, H, reverse, err_flag, (hipStream_t)stream, N / 16,
+                           (int*)workspace, flags & 1);
+}
+// Operator level (parity tests): one Q8-1 recurrent layer straight from fp32 host weights. Packs, uploads, quantises x with
+// the static scale 127 / bound, runs the 8-bit kernel and synchronises. `sums` (optional) receives the exact int32 partial sums
+// [T][N][4H][2] (input part, recurrent part) the gate arithmetic started from; `hq_frag` (optional) the int8 output in
+// fragment order [T][N/16][ceil(H/64)][64][16].
+extern "C" int bh_lstm_q8_layer(const void* x, float bound, const float* w_ih, const float* w_hh, const float* bias, int T, int N,
+                                int H, int reverse, int variant, void* h16_out, int8_t* hq_frag, int32_t* sums, void* stream_) {
+    BH_REQUIRE(x && w_ih && w_hh && h16_out && T > 0 && N > 0 && N % 16 == 0, "lstm_q8_layer: bad arguments");
+    const int U = bh_k_lstm_q8_units(H, variant);
+    BH_REQUIRE(U != 0, "lstm_q8_layer: hidden size %d is not covered by the 8-bit kernel", H);
+    hipStream_t st = (hipStream_t)stream_;
+    const int R = N / 16;
+    const size_t tile = bh_k_lstm_q8_tile_bytes(H), wbytes = (size_t)4 * H * ((H + 63) / 64 * 64);
+    std::vector<int8_t> pk(wbytes);
+    std::vector<float> s_ih((size_t)4 * H), s_hh((size_t)4 * H), b((size_t)4 * H, 0.0f);
+    DevBuf q_wih, q_whh, q_sx, q_sh, q_b, xq, ex, ws, err;
+    if (bh_k_lstm_q8_pack(w_ih, H, U, pk.data(), s_ih.data()) || upload(q_wih, pk.data(), pk.size())) return -1;
+    if (bh_k_lstm_q8_pack(w_hh, H, U, pk.data(), s_hh.data()) || upload(q_whh, pk.data(), pk.size())) return -1;
+    const float xs = (float)((double)bound / 127.0);
+    for (int j = 0; j < 4 * H; ++j) { s_ih[j] *= xs; s_hh[j] /= 127.0f; if (bias) b[j] = bias[j]; }
+    if (upload_f32(q_sx, s_ih.data(), s_ih.size()) || upload_f32(q_sh, s_hh.data(), s_hh.size()) || upload_f32(q_b, b.data(), b.size())) return -1;
+    if (xq.alloc((size_t)T * R * tile) || ex.alloc(4 * (size_t)R * tile) || ws.alloc(bh_k_lstm_ws_bytes(N, 1024)) || err.alloc(sizeof(int))) return -1;
+    BH_CHECK_HIP(hipMemsetAsync(err.p, 0, sizeof(int), st));
+    int rc = bh_k_quantise_rows(x, xq.p, T, N, H, R, bound, st);
+    if (!rc) rc = bh_k_lstm_q8_arm(ex.p, R, H, st);
+    if (rc) return rc;
+    const int per = bh_k_lstm_q8_geometry(H, variant).rings_per_launch(bh_cu_count());
+    BH_REQUIRE(per >= 1, "lstm_q8_layer: device has too few CUs for hidden size %d", H);
+    for (int r0 = 0; r0 < R; r0 += per) {
+        const int nr = std::min(per, R - r0);
+        rc = bh_k_lstm_layer_q8((const char*)xq.p + (size_t)r0 * tile, q_wih.p, q_whh.p, (const float*)q_sx.p, (const float*)q_sh.p,
+                                (const float*)q_b.p, hq_frag ? (char*)hq_frag + (size_t)r0 * tile : nullptr,
+                                (char*)h16_out + (size_t)r0 * 16 * H * 2, (char*)ex.p + (size_t)r0 * tile, T, N, H, R, nr, reverse,
+                                (int*)err.p, st, (int*)ws.p, 0, variant, sums ? sums + (size_t)r0 * 16 * 4 * H * 2 : nullptr,
+                                bh_k_lstm_max_spins());
+        if (rc) return rc;
+    }
+    int flag = 0;
+    BH_CHECK_HIP(hipMemcpyAsync(&flag, err.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    BH_CHECK_HIP(hipStreamSynchronize(st));
+    BH_REQUIRE(flag == 0, "lstm_q8_layer: exchange timeout in the recurrent kernel");
+    return 0;
+}
+extern "C" size_t bh_beam_search_workspace(int N, int T, int state_len) { return bh_k_beam_workspace(N, T, state_len); }
+extern "C" int bh_beam_search(const void* scores, int N, int T, int state_len, int beam_width, float beam_cut,
+                              float blank_score, float q_scale, float q_offset, void* workspace, int8_t* sequence,
+                              int8_t* qstring, int8_t* moves, float* qfloat, void* stream) {
+    BH_REQUIRE(scores && workspace && sequence && qstring && moves, "beam_search: null pointer");
+    return bh_k_beam_search(scores, N, T, state_len, beam_width, beam_cut, blank_score, q_scale, q_offset, workspace,
+                            sequence, qstring, moves, qfloat, (hipStream_t)stream);
+}
+extern "C" int bh_crf_reverse_complement(const void* in, void* out, int N, int T, int state_len, int layout_5s,
+                                         long stride_n, long stride_t, void* stream) {
+    BH_REQUIRE(in && out, "crf_reverse_complement: null pointer");
+    return bh_k_crf_revcomp(in, out, N, T, state_len, layout_5s, stride_n, stride_t, (hipStream_t)stream);
+}
+extern "C" int bh_crf_logz(const void* scores, int N, int T, int state_len, float blank_score, void* workspace,
+                           double* logz, void* stream) {
+    BH_REQUIRE(scores && workspace && logz, "crf_logz: null pointer");
+    return bh_k_crf_logz(scores, N, T, state_len, blank_score, workspace, logz, (hipStream_t)stream);
+}
+extern "C" size_t bh_crf_seq_workspace(int N, int T, int Lmax, int state_len) {
+    return bh_k_crf_seq_workspace(N, T, Lmax, state_len);
+}
+extern "C" int bh_crf_seq_logz(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
+                               long stride_t, const void* targets, int Lmax, int target_bytes, const int32_t* target_lengths,
+                               void* workspace, float* logz_out, void* stream) {
+    BH_REQUIRE(scores && targets && target_lengths && workspace && logz_out, "crf_seq_logz: null pointer");
+    return bh_k_crf_seq(scores, N, T, state_len, layout_5s, blank_score, stride_n, stride_t, targets, target_bytes, Lmax,
+                        target_lengths, workspace, logz_out, nullptr, 0, (hipStream_t)stream);
+}
+extern "C" int bh_crf_seq_logz_free(const void* scores, int N, int T, int state_len, float blank_score, long stride_n, long stride_t,
+                                    const void* targets, int Lmax, int target_bytes, const int32_t* target_lengths, void* workspace,
+                                    float* logz_out, void* stream) {
+    BH_REQUIRE(scores && targets && target_lengths && workspace && logz_out, "crf_seq_logz_free: null pointer");
+    return bh_k_crf_seq(scores, N, T, state_len, 0, blank_score, stride_n, stride_t, targets, target_bytes, Lmax, target_lengths,
+                        workspace, logz_out, nullptr, 2, (hipStream_t)stream);
+}
+extern "C" int bh_crf_seq_viterbi(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
+                                  long stride_t, const void* targets, int Lmax, int target_bytes, const int32_t* target_lengths,
+                                  void* workspace, int32_t* align_out, float* best_out, void* stream) {
+    BH_REQUIRE(scores && targets && target_lengths && workspace && align_out && best_out, "crf_seq_viterbi: null pointer");
+    return bh_k_crf_seq(scores, N, T, state_len, layout_5s, blank_score, stride_n, stride_t, targets, target_bytes, Lmax,
+                        target_lengths, workspace, best_out, align_out, 1, (hipStream_t)stream);
+}
+extern "C" int bh_crf_logz_dense(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
+                                 long stride_t, float* logz_out, void* stream) {
+    BH_REQUIRE(scores && logz_out, "crf_logz_dense: null pointer");
+    return bh_k_crf_logz_dense(scores, N, T, state_len, layout_5s, blank_score, stride_n, stride_t, logz_out, (hipStream_t)stream);
+}
+extern "C" size_t bh_sw_workspace(int n, int max_seq, int max_ref) { return bh_k_sw_workspace(n, max_seq, max_ref); }
+extern "C" int bh_sw_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, const void* refs, long ref_stride,
+                           const int32_t* ref_lengths, int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace,
+                           size_t workspace_bytes, int32_t* result, uint32_t* ops, long ops_stride, int32_t* n_ops, void* stream) {
+    return bh_k_sw_align(seqs, seq_stride, seq_lengths, refs, ref_stride, ref_lengths, n, match, mismatch, gap_open, gap_extend,
+                         workspace, workspace_bytes, result, ops, ops_stride, n_ops, (hipStream_t)stream);
+}
+extern "C" int bh_signal_normalise(const int16_t* raw, const long* offsets, const float* cal_scale, const float* cal_offset, int n_reads,
+                                   int strategy, double quantile_a, double quantile_b, double shift_mult, double scale_mult,
+                                   double fixed_shift, double fixed_scale, int do_trim, double* shift, double* scale, int* weak,
+                                   int* trim, void* stream) {
+    return bh_k_signal_normalise(raw, offsets, cal_scale, cal_offset, n_reads, strategy, quantile_a, quantile_b, shift_mult,
+                                 scale_mult, fixed_shift, fixed_scale, do_trim, shift, scale, weak, trim, (hipStream_t)stream);
+}
+extern "C" int bh_signal_chunks(const int16_t* raw, const long* offsets, const float* cal_scale, const float* cal_offset,
+                                const double* shift, const double* scale, const int* weak, const int* chunk_read,
+                                const long* chunk_start, const long* chunk_len, int n_chunks, int chunk_samples, void* out,
+                                void* stream) {
+    BH_REQUIRE(raw && offsets && cal_scale && cal_offset && shift && scale && weak && chunk_read && chunk_start && chunk_len && out,
+               "signal_chunks: null pointer");
+    return bh_k_signal_chunks(raw, offsets, cal_scale, cal_offset, shift, scale, weak, chunk_read, chunk_start, chunk_len,
+                              n_chunks, chunk_samples, out, (hipStream_t)stream);
+}
+extern "C" int bh_set_option(const char* name, int value) {
+    BH_REQUIRE(name != nullptr, "set_option: null name");
+    if (bh_k_decode_set_option(name, value) == 0) return 0;
+    if (bh_k_conv_set_option(name, value) == 0) return 0;
+    if (bh_k_lstm_set_option(name, value) == 0) return 0;
+    if (!strcmp(name, "gemm_path")) { bh_k_linear_force_v1(value); return 0; }
+    if (!strcmp(name, "attn_waves")) { extern int g_attn_waves; g_attn_waves = value; return 0; }
+    if (!strcmp(name, "attn_version")) { extern int g_attn_version; g_attn_version = value == 1 ? 1 : 2; return 0; }
+    if (!strcmp(name, "attn_expt")) { extern int g_attn_expt; g_attn_expt = value; return 0; }
+    if (!strcmp(name, "gemm_stagger")) { bh_k_linear_stagger(value); return 0; }
+    if (!strcmp(name, "gemm_order")) { bh_k_linear_order(value); return 0; }
+    if (!strcmp(name, "gemm_gf")) { bh_k_linear_gf(value); return 0; }
+    if (!strcmp(name, "gemm_tile16")) { bh_k_linear_tile16(value); return 0; }     // process-wide A/B switch: the four-wave GEMM's MFMA shape
+    if (!strcmp(name, "lstm_q8_variant")) { bh::g_q8_variant = value; return 0; }      // read by bh_encoder_create
+    BH_REQUIRE(false, "set_option: unknown option '%s'", name);
+    return -1;
+}
+extern "C" size_t bh_crf_posterior_viterbi_workspace(int N, int T, int state_len) {
+    return bh_k_posterior_viterbi_workspace(N, T, state_len);
+}
+extern "C" int bh_crf_posterior_viterbi(const void* scores, int N, int T, int state_len, float blank_score, void* workspace,
+                                        int8_t* moves, int8_t* path, void* stream) {
+    BH_REQUIRE(scores && workspace && moves && path, "crf_posterior_viterbi: null pointer");
+    return bh_k_posterior_viterbi(scores, N, T, state_len, blank_score, workspace, moves, path, (hipStream_t)stream);
+}
+extern "C" size_t bh_crf_viterbi_workspace(int N, int T, int state_len) {
+    size_t S = 1;
+    for (int i = 0; i < state_len; ++i) S *= 4;
+    return (size_t)N * T * S + 256;
+}
+extern "C" int bh_crf_viterbi(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score,
+                              long stride_n, long stride_t, void* workspace, int8_t* moves, int8_t* path,
+                              float* best, void* stream) {
+    BH_REQUIRE(scores && workspace && moves && path, "crf_viterbi: null pointer");
+    return bh_k_crf_viterbi(scores, N, T, state_len, layout_5s, blank_score, stride_n, stride_t, workspace, nullptr,
+                            moves, path, best, (hipStream_t)stream);
+}

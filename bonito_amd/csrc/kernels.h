@@ -1,5 +1,6 @@
 // Internal launcher prototypes (one per HIP translation unit). The public C ABI in
-// include/bonito_hip.h is a thin shell over these (bonito_amd/csrc/abi.cpp, engine.cpp).
+// include/bonito_hip.h is a thin shell over these (bonito_amd/csrc/abi.cpp for the operators,
+// engine.cpp for the encoder).
 // All pointers are device pointers; all launchers are asynchronous on `stream` and return
 // 0 on success (error text via bh_last_error()).
 #pragma once
@@ -28,6 +29,29 @@ int bh_k_conv_igemm(const void* in, const void* wpk, const float* bias, void* ou
                     float clamp_hi, long os_n, long os_t, hipStream_t stream);
 
 // lstm.hip
+// Launch geometry of a recurrent kernel family: the ONE statement of how many workgroups a launch of n rings takes and, inverted,
+// how many rings fit one launch. The workgroups of a launch spin on each other, so all of them must be resident at once; rings are
+// dealt to the 8 XCDs, hence the groups of 8. The launcher's grid and co-residency guard and every caller that splits a batch
+// (engine.cpp, abi.cpp) read it from here.
+enum bh_lstm_family { BH_LSTM_WAVE, BH_LSTM_FUSED, BH_LSTM_STREAM, BH_LSTM_WGX, BH_LSTM_WGX2, BH_LSTM_CTA, BH_LSTM_WIDE, BH_LSTM_Q8 };
+struct bh_lstm_geometry {
+    int ring_chunks = 16;        // chunks per ring
+    int wgs_per_group = 0;       // workgroups that serve 8 workgroup slots, one per XCD (0: the kernel does not cover H)
+    int rings_per_slot = 1;      // rings a workgroup slot carries
+    int wgs_per_cu = 1;          // workgroups resident on one CU
+    bool unlimited = false;      // one workgroup per ring and no spin across workgroups: any number of rings per launch
+    int grid(int n_rings) const {
+        if (unlimited) return n_rings;
+        const int per_group = 8 * rings_per_slot;
+        return 8 * ((n_rings + per_group - 1) / per_group) * wgs_per_group;
+    }
+    int resident(int cus) const { return cus * wgs_per_cu; }       // workgroups the device holds at once
+    int rings_per_launch(int cus) const {                          // 0: the device is too small for one group of rings
+        if (unlimited) return INT32_MAX;
+        return wgs_per_group > 0 ? resident(cus) / (8 * wgs_per_group) * 8 * rings_per_slot : 0;
+    }
+};
+bh_lstm_geometry bh_k_lstm_geometry(bh_lstm_family family, int H);       // the fp16 families (BH_LSTM_Q8: bh_k_lstm_q8_geometry)
 int bh_k_lstm_layer(const void* gates_in, const void* whh_packed, void* h_out, int T, int N, int H,
                     int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow);
 size_t bh_k_lstm_ws_bytes(int N, int H);
@@ -127,6 +151,7 @@ size_t bh_k_lstm_wide_ex_bytes(int N, int H);
 
 // lstm_q8.hip: 8-bit recurrent path Q8-1
 int bh_k_lstm_q8_units(int H, int variant);
+bh_lstm_geometry bh_k_lstm_q8_geometry(int H, int variant);
 size_t bh_k_lstm_q8_tile_bytes(int H);
 int bh_k_lstm_q8_pack(const float* w, int H, int U, int8_t* packed, float* scale);
 int bh_k_quantise_rows(const void* x, void* out, int T, int N, int H, int R, float bound, hipStream_t stream);

@@ -1679,25 +1679,49 @@ int bh_k_fill_u16(void* dst, uint16_t value, size_t count, hipStream_t stream) {
     return 0;
 }
 
-// One launch serves at most (CUs / (8 * H/16)) * 4 * 8 rings co-resident; the caller (engine.cpp)
+// Launch geometry per kernel family (kernels.h: bh_lstm_geometry). A workgroup is four waves; a wave owns one slice of a ring's
+// hidden units (16 units in the per-wave and streaming kernels, U in the workgroup-shared ones, 8 in the wide one).
+bh_lstm_geometry bh_k_lstm_geometry(bh_lstm_family family, int H) {
+    bh_lstm_geometry g;
+    const int U = bh_k_lstm_wg_units(H);
+    switch (family) {
+        case BH_LSTM_WAVE:
+        case BH_LSTM_FUSED: g.wgs_per_group = H / 16; g.rings_per_slot = 4; break;     // a workgroup: one slice of four rings
+        case BH_LSTM_STREAM: g.wgs_per_group = H / 64; break;
+        case BH_LSTM_WGX2: g.rings_per_slot = 2; [[fallthrough]];
+        case BH_LSTM_WGX: g.wgs_per_group = U ? H / (4 * U) : 0; break;
+        case BH_LSTM_CTA: g.unlimited = true; break;
+        case BH_LSTM_WIDE: g.ring_chunks = 32; g.wgs_per_group = H / 32; break;
+        case BH_LSTM_Q8: break;                                                         // lstm_q8.hip
+    }
+    return g;
+}
+
+// The shared front of the launchers: batch padding, ring range (R: rings of the whole batch), co-residency guard, and the XCD
+// agreement slots (`slots` per ring) armed with 0xFF. Returns the grid.
+static int lstm_launch_prologue(const bh_lstm_geometry& g, int N, int R, int n_rings, int slots, int* xcc_ws, hipStream_t stream,
+                                int* grid_out) {
+    if (g.ring_chunks == 32) BH_REQUIRE(N % 32 == 0, "lstm: wide kernel needs the batch padded to a multiple of 32 (N=%d)", N);
+    else BH_REQUIRE(N % 16 == 0, "lstm: batch must be padded to a multiple of 16 (N=%d)", N);
+    BH_REQUIRE(n_rings > 0 && n_rings <= R, "lstm: n_rings=%d outside 1..%d", n_rings, R);
+    const int grid = *grid_out = g.grid(n_rings);
+    if (g.unlimited) return 0;
+    const int cus = bh_cu_count();
+    BH_REQUIRE(g.wgs_per_group > 0 && grid <= g.resident(cus), "lstm: %d workgroups must be co-resident but the device has %d CUs; split the batch", grid, cus);
+    BH_REQUIRE(xcc_ws != nullptr, "lstm: missing XCD agreement workspace");
+    BH_CHECK_HIP(hipMemsetAsync(xcc_ws, 0xFF, (size_t)n_rings * slots * sizeof(int), stream));
+    return 0;
+}
+
+// One launch serves at most bh_k_lstm_geometry(..).rings_per_launch(CUs) rings; the caller (engine.cpp: forward_lstm, abi.cpp)
 // splits larger batches by offsetting the base pointers by 16*ring0 columns: N stays the row stride of
 // G / h and n_rings is the number of 16-chunk rings this launch runs. N %% 16 == 0 (engine pads).
 int bh_k_lstm_layer(const void* gates_in, const void* whh_packed, void* h_out, int T, int N, int H,
                     int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow) {
     using namespace bh;
-    BH_REQUIRE(N % 16 == 0, "lstm: batch must be padded to a multiple of 16 (N=%d)", N);
     BH_REQUIRE(H % 32 == 0 && H >= 32 && H <= 512, "lstm: register-resident kernel needs H%%32==0, 32<=H<=512 (H=%d)", H);
-    int dev = 0, cus = 0;
-    BH_CHECK_HIP(hipGetDevice(&dev));
-    BH_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const int nsl = H / 16;
-    BH_REQUIRE(n_rings > 0 && n_rings <= N / 16, "lstm: n_rings=%d outside 1..%d", n_rings, N / 16);
-    const int rl = (n_rings + 7) / 8;          // rings per XCD
-    const int groups = (rl + 3) / 4;           // 4 rings (waves) per workgroup
-    const int grid = 8 * groups * nsl;
-    BH_REQUIRE(grid <= cus, "lstm: %d workgroups must be co-resident but the device has %d CUs; split the batch", grid, cus);
-    BH_REQUIRE(xcc_ws != nullptr, "lstm: missing XCD agreement workspace");
-    BH_CHECK_HIP(hipMemsetAsync(xcc_ws, 0xFF, (size_t)n_rings * nsl * sizeof(int), stream));
+    int grid = 0;
+    if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_WAVE, H), N, N / 16, n_rings, H / 16, xcc_ws, stream, &grid)) return rc;
     LstmArgs a{(const half_t*)gates_in, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings,
                reverse, err_flag, g_max_spins, xcc_ws, force_slow & 1, force_slow >> 8};
 #define BH_LSTM_CASE(NKS) \
@@ -1716,18 +1740,9 @@ int bh_k_lstm_layer(const void* gates_in, const void* whh_packed, void* h_out, i
 int bh_k_lstm_layer_stream(const void* gates_in, const void* whh_packed, void* h_out, int T, int N, int H,
                            int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow) {
     using namespace bh;
-    BH_REQUIRE(N % 16 == 0, "lstm: batch must be padded to a multiple of 16 (N=%d)", N);
     BH_REQUIRE(H % 64 == 0 && H >= 64 && H <= 1024, "lstm: streaming kernel needs H%%64==0, 64<=H<=1024 (H=%d)", H);
-    int dev = 0, cus = 0;
-    BH_CHECK_HIP(hipGetDevice(&dev));
-    BH_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const int nsl = H / 16, wpr = nsl / 4;
-    BH_REQUIRE(n_rings > 0 && n_rings <= N / 16, "lstm: n_rings=%d outside 1..%d", n_rings, N / 16);
-    const int rl = (n_rings + 7) / 8;
-    const int grid = 8 * rl * wpr;
-    BH_REQUIRE(grid <= cus, "lstm: %d workgroups must be co-resident but the device has %d CUs; split the batch", grid, cus);
-    BH_REQUIRE(xcc_ws != nullptr, "lstm: missing XCD agreement workspace");
-    BH_CHECK_HIP(hipMemsetAsync(xcc_ws, 0xFF, (size_t)n_rings * nsl * sizeof(int), stream));
+    int grid = 0;
+    if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_STREAM, H), N, N / 16, n_rings, H / 16, xcc_ws, stream, &grid)) return rc;
     LstmArgs a{(const half_t*)gates_in, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings,
                reverse, err_flag, g_max_spins, xcc_ws, force_slow & 1, force_slow >> 8};
     switch (H / 32) {
@@ -1750,20 +1765,10 @@ int bh_k_lstm_layer_fused(const void* x, const void* wih_packed, const float* bi
                           int T, int N, int H, int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws,
                           int force_slow) {
     using namespace bh;
-    BH_REQUIRE(N % 16 == 0, "lstm: batch must be padded to a multiple of 16 (N=%d)", N);
     BH_REQUIRE(H % 32 == 0 && H >= 32 && H <= 512, "lstm: register-resident kernel needs H%%32==0, 32<=H<=512 (H=%d)", H);
     BH_REQUIRE(x != h_out, "lstm: fused layer cannot run in place");
-    int dev = 0, cus = 0;
-    BH_CHECK_HIP(hipGetDevice(&dev));
-    BH_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const int nsl = H / 16;
-    BH_REQUIRE(n_rings > 0 && n_rings <= N / 16, "lstm: n_rings=%d outside 1..%d", n_rings, N / 16);
-    const int rl = (n_rings + 7) / 8;
-    const int groups = (rl + 3) / 4;
-    const int grid = 8 * groups * nsl;
-    BH_REQUIRE(grid <= cus, "lstm: %d workgroups must be co-resident but the device has %d CUs; split the batch", grid, cus);
-    BH_REQUIRE(xcc_ws != nullptr, "lstm: missing XCD agreement workspace");
-    BH_CHECK_HIP(hipMemsetAsync(xcc_ws, 0xFF, (size_t)n_rings * nsl * sizeof(int), stream));
+    int grid = 0;
+    if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_FUSED, H), N, N / 16, n_rings, H / 16, xcc_ws, stream, &grid)) return rc;
     LstmFusedArgs a{(const half_t*)x, (const half_t*)wih_packed, bias,
                     LstmArgs{nullptr, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings, reverse, err_flag, g_max_spins,
                              xcc_ws, force_slow & 1, force_slow >> 8}};
@@ -1802,20 +1807,11 @@ int bh_k_lstm_layer_wgx(const void* x, const void* wih_packed, const float* bias
                         int T, int N, int H, int R, int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws,
                         int force_slow, int arm) {
     using namespace bh;
-    BH_REQUIRE(N % 16 == 0, "lstm: batch must be padded to a multiple of 16 (N=%d)", N);
     const int U = bh_k_lstm_wg_units(H);
     BH_REQUIRE(U != 0, "lstm: workgroup-shared kernel does not cover H=%d", H);
     BH_REQUIRE(x != h_out && ex != nullptr, "lstm: fused layer cannot run in place / missing exchange buffer");
-    int dev = 0, cus = 0;
-    BH_CHECK_HIP(hipGetDevice(&dev));
-    BH_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const int nsl = H / U, wpr = nsl / 4;
-    BH_REQUIRE(n_rings > 0 && n_rings <= R, "lstm: n_rings=%d outside 1..%d", n_rings, R);
-    const int rl = (n_rings + 7) / 8;
-    const int grid = 8 * rl * wpr;
-    BH_REQUIRE(grid <= cus, "lstm: %d workgroups must be co-resident but the device has %d CUs; split the batch", grid, cus);
-    BH_REQUIRE(xcc_ws != nullptr, "lstm: missing XCD agreement workspace");
-    BH_CHECK_HIP(hipMemsetAsync(xcc_ws, 0xFF, (size_t)n_rings * nsl * sizeof(int), stream));
+    int grid = 0;
+    if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_WGX, H), N, R, n_rings, H / U, xcc_ws, stream, &grid)) return rc;
     const int nks = H / 32;
     if (arm) BH_CHECK_HIP(hipMemsetAsync(ex, 0xFF, (size_t)4 * R * nks * 1024, stream));
     LstmWgxArgs a{LstmFusedArgs{(const half_t*)x, (const half_t*)wih_packed, bias,
@@ -1837,26 +1833,16 @@ int bh_k_lstm_layer_wgx(const void* x, const void* wih_packed, const float* bias
     return 0;
 }
 
-// Two rings per workgroup (lstm_layer_wgx2_kernel): n_rings may be up to twice what one ring per 8 * H/(4U) workgroups allows.
+// Two rings per workgroup (lstm_layer_wgx2_kernel): n_rings may be up to twice what bh_k_lstm_layer_wgx takes.
 int bh_k_lstm_layer_wgx2(const void* x, const void* wih_packed, const float* bias, const void* whh_packed, void* h_out, void* ex,
                          int T, int N, int H, int R, int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws,
                          int force_slow, int arm) {
     using namespace bh;
-    BH_REQUIRE(N % 16 == 0, "lstm: batch must be padded to a multiple of 16 (N=%d)", N);
     const int U = bh_k_lstm_wg_units(H);
     BH_REQUIRE(U != 0, "lstm: workgroup-shared kernel does not cover H=%d", H);
     BH_REQUIRE(x != h_out && ex != nullptr, "lstm: fused layer cannot run in place / missing exchange buffer");
-    int dev = 0, cus = 0;
-    BH_CHECK_HIP(hipGetDevice(&dev));
-    BH_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const int nsl = H / U, wpr = nsl / 4;
-    BH_REQUIRE(n_rings > 0 && n_rings <= R, "lstm: n_rings=%d outside 1..%d", n_rings, R);
-    const int n_pairs = (n_rings + 1) / 2;
-    const int rl = (n_pairs + 7) / 8;
-    const int grid = 8 * rl * wpr;
-    BH_REQUIRE(grid <= cus, "lstm: %d workgroups must be co-resident but the device has %d CUs; split the batch", grid, cus);
-    BH_REQUIRE(xcc_ws != nullptr, "lstm: missing XCD agreement workspace");
-    BH_CHECK_HIP(hipMemsetAsync(xcc_ws, 0xFF, (size_t)n_rings * nsl * sizeof(int), stream));
+    int grid = 0;
+    if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_WGX2, H), N, R, n_rings, H / U, xcc_ws, stream, &grid)) return rc;
     const int nks = H / 32;
     if (arm) BH_CHECK_HIP(hipMemsetAsync(ex, 0xFF, (size_t)4 * R * nks * 1024, stream));
     LstmWgxArgs a{LstmFusedArgs{(const half_t*)x, (const half_t*)wih_packed, bias,
@@ -1894,18 +1880,18 @@ int bh_k_lstm_cta_units(int H) {
 int bh_k_lstm_layer_cta(const void* x, const void* wih_tiles, const float* bias, const void* whh_tiles, void* h_out, int T, int N,
                         int H, int reverse, hipStream_t stream, int n_rings) {
     using namespace bh;
-    BH_REQUIRE(N % 16 == 0, "lstm: batch must be padded to a multiple of 16 (N=%d)", N);
     const int U = bh_k_lstm_cta_units(H);
     BH_REQUIRE(U != 0, "lstm: ring-in-a-workgroup kernel does not cover H=%d", H);
     BH_REQUIRE(x != h_out, "lstm: fused layer cannot run in place");
-    BH_REQUIRE(n_rings > 0 && n_rings <= N / 16, "lstm: n_rings=%d outside 1..%d", n_rings, N / 16);
+    int grid = 0;
+    if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_CTA, H), N, N / 16, n_rings, 0, nullptr, stream, &grid)) return rc;
     LstmFusedArgs a{(const half_t*)x, (const half_t*)wih_tiles, bias,
                     LstmArgs{nullptr, (const half_t*)whh_tiles, (half_t*)h_out, T, N, H, n_rings, reverse, nullptr, 0u, nullptr, 0, 0}};
     const int nks = H / 32, nsl = H / U;
     const size_t lds = (size_t)4 * nks * 1024;
-    if (H == 96) hipLaunchKernelGGL((lstm_layer_cta_kernel<3, 3>), dim3(n_rings), dim3(64 * nsl), lds, stream, a);
-    else if (H == 64) hipLaunchKernelGGL((lstm_layer_cta_kernel<2, 4>), dim3(n_rings), dim3(64 * nsl), lds, stream, a);
-    else hipLaunchKernelGGL((lstm_layer_cta_kernel<4, 4>), dim3(n_rings), dim3(64 * nsl), lds, stream, a);
+    if (H == 96) hipLaunchKernelGGL((lstm_layer_cta_kernel<3, 3>), dim3(grid), dim3(64 * nsl), lds, stream, a);
+    else if (H == 64) hipLaunchKernelGGL((lstm_layer_cta_kernel<2, 4>), dim3(grid), dim3(64 * nsl), lds, stream, a);
+    else hipLaunchKernelGGL((lstm_layer_cta_kernel<4, 4>), dim3(grid), dim3(64 * nsl), lds, stream, a);
     BH_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -1920,17 +1906,8 @@ int bh_k_lstm_layer_wide(const void* gates_perm, const void* whh_tiles, void* h_
                          int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow, void* ex, int R, int arm) {
     using namespace bh;
     BH_REQUIRE(bh_k_lstm_wide_ok(H), "lstm: wide kernel does not cover H=%d", H);
-    BH_REQUIRE(N % 32 == 0, "lstm: wide kernel needs the batch padded to a multiple of 32 (N=%d)", N);
-    int dev = 0, cus = 0;
-    BH_CHECK_HIP(hipGetDevice(&dev));
-    BH_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const int nsl = H / 8, wpr = nsl / 4;
-    BH_REQUIRE(n_rings > 0 && n_rings <= N / 32, "lstm: n_rings=%d outside 1..%d", n_rings, N / 32);
-    const int rl = (n_rings + 7) / 8;
-    const int grid = 8 * rl * wpr;
-    BH_REQUIRE(grid <= cus, "lstm: %d workgroups must be co-resident but the device has %d CUs; split the batch", grid, cus);
-    BH_REQUIRE(xcc_ws != nullptr, "lstm: missing XCD agreement workspace");
-    BH_CHECK_HIP(hipMemsetAsync(xcc_ws, 0xFF, (size_t)n_rings * nsl * sizeof(int), stream));
+    int grid = 0;
+    if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_WIDE, H), N, N / 32, n_rings, H / 8, xcc_ws, stream, &grid)) return rc;
     LstmWideArgs a{(const half_t*)gates_perm,
                    LstmArgs{nullptr, (const half_t*)whh_tiles, (half_t*)h_out, T, N, H, n_rings, reverse, err_flag, g_max_spins, xcc_ws,
                             force_slow & 1, force_slow >> 8},

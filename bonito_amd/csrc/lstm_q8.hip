@@ -471,6 +471,15 @@ int bh_k_lstm_q8_arm(void* ex, int R, int H, hipStream_t stream) {
     return 0;
 }
 
+// Launch geometry (kernels.h: bh_lstm_geometry): H/(4U) workgroups per ring; the small-tile variants fit several workgroups on a CU.
+bh_lstm_geometry bh_k_lstm_q8_geometry(int H, int variant) {
+    bh_lstm_geometry g;
+    const int U = bh_k_lstm_q8_units(H, variant);
+    g.wgs_per_group = U ? H / (4 * U) : 0;
+    g.wgs_per_cu = U == 4 ? 3 : (variant == 2 && H == 384) ? 2 : 1;
+    return g;
+}
+
 // One launch serves the rings whose workgroups fit the device together (co-residency, as the fp16 wg kernel). `ex` must hold
 // 4 * R * tile bytes and be armed (bh_k_lstm_q8_arm). R = ring stride of the tensors (N / 16 of the whole batch), n_rings = rings of this launch.
 int bh_k_lstm_layer_q8(const void* xq, const void* wih, const void* whh, const float* sx, const float* sh, const float* bias,
@@ -480,14 +489,10 @@ int bh_k_lstm_layer_q8(const void* xq, const void* wih, const void* whh, const f
     const int U = bh_k_lstm_q8_units(H, variant);
     BH_REQUIRE(U != 0, "lstm_q8: hidden size %d is not covered by the 8-bit kernel", H);
     BH_REQUIRE(N % 16 == 0 && n_rings > 0 && n_rings <= R, "lstm_q8: bad batch geometry (N=%d, rings=%d of %d)", N, n_rings, R);
-    int dev = 0, cus = 0;
-    BH_CHECK_HIP(hipGetDevice(&dev));
-    BH_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const int nsl = H / U, wpr = nsl / 4, nk8 = (H + 63) / 64;
-    const int per_cu = U == 4 ? 3 : (variant == 2 && H == 384) ? 2 : 1;
-    const int rl = (n_rings + 7) / 8;
-    const int grid = 8 * rl * wpr;
-    BH_REQUIRE(grid <= cus * per_cu, "lstm_q8: %d workgroups must be co-resident but the device holds %d; split the batch", grid, cus * per_cu);
+    const bh_lstm_geometry geo = bh_k_lstm_q8_geometry(H, variant);
+    const int nsl = H / U, nk8 = (H + 63) / 64, per_cu = geo.wgs_per_cu;
+    const int grid = geo.grid(n_rings), room = geo.resident(bh_cu_count());
+    BH_REQUIRE(grid <= room, "lstm_q8: %d workgroups must be co-resident but the device holds %d; split the batch", grid, room);
     BH_REQUIRE(xcc_ws != nullptr && ex != nullptr, "lstm_q8: missing workspace");
     BH_CHECK_HIP(hipMemsetAsync(xcc_ws, 0xFF, (size_t)n_rings * nsl * sizeof(int), stream));
     const size_t tile = (size_t)nk8 * 1024;

@@ -351,6 +351,28 @@ def test_full_size_hac_encoder_kernel_variants_bit_identical():
     assert torch.equal(outs[0], outs[4])
 
 
+@pytest.mark.parametrize("N", [576, 1024])
+def test_lstm_pair_option_picks_the_kernel_and_keeps_the_bytes(N):
+    """A batch of more rings than one launch of the ring-buffer kernel holds (H = 384: 32 rings = 512 chunks; 36 rings leave a
+    second launch of 4, 64 rings fill two): "lstm_pair" 0 serves it with `lstm_layer_wgx_kernel` launched twice, 1 (the default)
+    with `lstm_layer_wgx2_kernel` once. describe() must name the kernel the forward takes, and the bytes must not depend on it."""
+    from bonito_amd import synthetic
+    model = synthetic.make_model("hac", batchsize=N, chunksize=1200)
+    x = torch.randn(N, 1, 1200, generator=torch.Generator().manual_seed(N + 1)).half().cuda()
+    outs, layouts = {}, {}
+    for pair in (0, 1):
+        enc = HipEncoder(model.encoder, batchsize=N, chunksize=1200)
+        enc.set_option("lstm_pair", pair)
+        outs[pair] = enc(x).clone()
+        layouts[pair] = enc.describe()
+        enc.check()
+        enc.close()
+    assert "lstm_layer_wgx_kernel<12,3>" in layouts[0] and "wgx2" not in layouts[0]
+    assert "lstm_layer_wgx2_kernel<12,3>" in layouts[1] and "lstm_layer_wgx_kernel" not in layouts[1]
+    assert torch.isfinite(outs[0].float()).all()
+    assert torch.equal(outs[0], outs[1])
+
+
 @pytest.mark.parametrize("quantize", [False, True])
 def test_ring_exchange_across_xcds_gives_the_same_bytes(quantize):
     """The hand-off of the recurrent kernels must not depend on workgroup -> XCD placement. "lstm_tune" bit 5 spreads the
