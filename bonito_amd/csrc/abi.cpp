@@ -11,8 +11,7 @@
 #include "common.h"
 #include "devbuf.h"
 #include "kernels.h"
-
-namespace bh { extern int g_q8_variant; }     // engine.cpp ("lstm_q8_variant")
+#include "options.h"
 
 extern "C" size_t bh_conv1d_packed_halves(int Cin, int Cout, int K) {
     size_t kp = ((size_t)K * Cin + 31) / 32 * 32;
@@ -193,7 +192,7 @@ extern "C" int bh_lstm_q8_layer(const void* x, float bound, const float* w_ih, c
                                 (const float*)q_b.p, hq_frag ? (char*)hq_frag + (size_t)r0 * tile : nullptr,
                                 (char*)h16_out + (size_t)r0 * 16 * H * 2, (char*)ex.p + (size_t)r0 * tile, T, N, H, R, nr, reverse,
                                 (int*)err.p, st, (int*)ws.p, 0, variant, sums ? sums + (size_t)r0 * 16 * 4 * H * 2 : nullptr,
-                                bh_k_lstm_max_spins());
+                                (unsigned)bh::g_opt.lstm_max_spins);
         if (rc) return rc;
     }
     int flag = 0;
@@ -274,20 +273,10 @@ extern "C" int bh_signal_chunks(const int16_t* raw, const long* offsets, const f
 }
 extern "C" int bh_set_option(const char* name, int value) {
     BH_REQUIRE(name != nullptr, "set_option: null name");
-    if (bh_k_decode_set_option(name, value) == 0) return 0;
-    if (bh_k_conv_set_option(name, value) == 0) return 0;
-    if (bh_k_lstm_set_option(name, value) == 0) return 0;
-    if (!strcmp(name, "gemm_path")) { bh_k_linear_force_v1(value); return 0; }
-    if (!strcmp(name, "attn_waves")) { extern int g_attn_waves; g_attn_waves = value; return 0; }
-    if (!strcmp(name, "attn_version")) { extern int g_attn_version; g_attn_version = value == 1 ? 1 : 2; return 0; }
-    if (!strcmp(name, "attn_expt")) { extern int g_attn_expt; g_attn_expt = value; return 0; }
-    if (!strcmp(name, "gemm_stagger")) { bh_k_linear_stagger(value); return 0; }
-    if (!strcmp(name, "gemm_order")) { bh_k_linear_order(value); return 0; }
-    if (!strcmp(name, "gemm_gf")) { bh_k_linear_gf(value); return 0; }
-    if (!strcmp(name, "gemm_tile16")) { bh_k_linear_tile16(value); return 0; }     // process-wide A/B switch: the four-wave GEMM's MFMA shape
-    if (!strcmp(name, "lstm_q8_variant")) { bh::g_q8_variant = value; return 0; }      // read by bh_encoder_create
-    BH_REQUIRE(false, "set_option: unknown option '%s'", name);
-    return -1;
+    const bh::OptionRow* row = bh::find_option(name);      // options.cpp: the one table of process-wide knobs
+    BH_REQUIRE(row != nullptr, "set_option: unknown option '%s'", name);
+    bh::g_opt.*row->member = row->normalise(value);
+    return 0;
 }
 extern "C" size_t bh_crf_posterior_viterbi_workspace(int N, int T, int state_len) {
     return bh_k_posterior_viterbi_workspace(N, T, state_len);

@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "options.h"
 
 namespace bh {
 
@@ -730,9 +731,8 @@ int bh_k_attention(const void* qkv, void* out, const float* cos_sin, int N, int 
 }
 
 // q (already rotated and scaled) | k (already rotated) | v  ->  attention output; see attention_ring_kernel.
-int g_attn_waves = 0;      // bh_set_option("attn_waves", 0 | 8 | 12): 0 = automatic
-int g_attn_version = 2;    // bh_set_option("attn_version", 1 | 2): 1 = the ring kernel of rounds 2-5, 2 = its round-6 rebuild (default)
-int g_attn_expt = 0;       // bh_set_option("attn_expt", bits): timing experiments of the round-6 kernel (wrong results on purpose; 0 in the product)
+// bh::g_opt (options.h): attn_waves 0 | 8 | 12 (0 = automatic); attn_version 1 = the ring kernel of rounds 2-5, 2 = its round-6 rebuild (default);
+// attn_expt: timing experiments of the round-6 kernel (wrong results on purpose; 0 in the product)
 
 int bh_k_attention_prerotated(const void* qkv, void* out, int N, int T, int nhead, int head_dim, int win_left, int win_right,
                               hipStream_t stream) {
@@ -743,8 +743,8 @@ int bh_k_attention_prerotated(const void* qkv, void* out, int N, int T, int nhea
     BH_REQUIRE(N > 0 && T > 0 && nhead > 0, "attention: empty problem");
     AttnRingArgs a{(const half_t*)qkv, (half_t*)out, N, T, nhead, win_left, win_right, 1};
     // twelve waves (blocks of 192 queries) where the chunk is long enough to fill them; "attn_waves" 8 / 12 forces a geometry
-    const int waves = g_attn_waves == 8 || g_attn_waves == 12 ? g_attn_waves : (T >= 384 ? 12 : 8);
-    if (g_attn_version == 1) {
+    const int waves = bh::g_opt.attn_waves == 8 || bh::g_opt.attn_waves == 12 ? bh::g_opt.attn_waves : (T >= 384 ? 12 : 8);
+    if (bh::g_opt.attn_version == 1) {
         const size_t lds = (size_t)RING * 128 + (size_t)64 * RVS * 2;
         if (waves == 12) {
             BH_CHECK_HIP(bh_max_lds((const void*)attention_ring_kernel<12>, (int)lds));
@@ -768,20 +768,20 @@ int bh_k_attention_prerotated(const void* qkv, void* out, int N, int T, int nhea
         hipLaunchKernelGGL((attention_ring2_kernel<W, E>), dim3(nhead, groups), dim3(64 * W), lds, stream, a);   \
     } while (0)
     if (waves == 8) BH_RING2(8, 0);
-    else if (g_attn_expt == 0) BH_RING2(12, 0);
+    else if (bh::g_opt.attn_expt == 0) BH_RING2(12, 0);
 #ifdef BH_ATTN_EXPT
-    else if (g_attn_expt == 1) BH_RING2(12, 1);
-    else if (g_attn_expt == 2) BH_RING2(12, 2);
-    else if (g_attn_expt == 4) BH_RING2(12, 4);
-    else if (g_attn_expt == 7) BH_RING2(12, 7);
-    else if (g_attn_expt == 8) BH_RING2(12, 8);
-    else if (g_attn_expt == 16) BH_RING2(12, 16);
-    else if (g_attn_expt == 24) BH_RING2(12, 24);
-    else if (g_attn_expt == 31) BH_RING2(12, 31);
-    else if (g_attn_expt == 32) BH_RING2(12, 32);
+    else if (bh::g_opt.attn_expt == 1) BH_RING2(12, 1);
+    else if (bh::g_opt.attn_expt == 2) BH_RING2(12, 2);
+    else if (bh::g_opt.attn_expt == 4) BH_RING2(12, 4);
+    else if (bh::g_opt.attn_expt == 7) BH_RING2(12, 7);
+    else if (bh::g_opt.attn_expt == 8) BH_RING2(12, 8);
+    else if (bh::g_opt.attn_expt == 16) BH_RING2(12, 16);
+    else if (bh::g_opt.attn_expt == 24) BH_RING2(12, 24);
+    else if (bh::g_opt.attn_expt == 31) BH_RING2(12, 31);
+    else if (bh::g_opt.attn_expt == 32) BH_RING2(12, 32);
 
 #endif
-    else BH_REQUIRE(false, "attention: timing experiment %d is not compiled into this library (BH_ATTN_EXPT)", g_attn_expt);
+    else BH_REQUIRE(false, "attention: timing experiment %d is not compiled into this library (BH_ATTN_EXPT)", bh::g_opt.attn_expt);
 #undef BH_RING2
     BH_CHECK_HIP(hipGetLastError());
     return 0;

@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "options.h"
 #include <cstring>
 #include "../../include/bh_lse_table.h"
 
@@ -328,7 +329,7 @@ struct BeamArgs {
 
 // Steps per staged block of the beam kernel; two blocks are resident (the next one streams in under the current one). Round 2 went from four
 // to two (12 KiB less LDS per chunk at 256 states, decode 4.35 -> 3.65 ms per hac batch); round 5: ONE at 256 states and above - a step of
-// a chunk is ~5 k cycles, enough to hide the DMA of the next row, and at 14.1 KiB per chunk eight chunks share a CU (g_beam_cpw): 12.97 ->
+// a chunk is ~5 k cycles, enough to hide the DMA of the next row, and at 14.1 KiB per chunk eight chunks share a CU ("beam_cpw"): 12.97 ->
 // 8.72 ms per 2048-chunk call. Below 256 states it stays two: there the four beam waves of a workgroup and their shared scan wave meet at
 // one barrier per block, and a barrier per step costs the fast-sized models' pipeline 12 % (2.35 -> 2.65 ms per batch, measured).
 // -DBH_BTB=n forces a depth (experiments).
@@ -1417,8 +1418,6 @@ __global__ __launch_bounds__(64) void beam_finalize_kernel(FinArgs p) {
 
 }  // namespace bh
 
-static int g_decode_nt = 0;     // bh_set_option("decode_nt", v)
-
 size_t bh_k_beam_workspace(int N, int T, int state_len) {
     size_t S = 1;
     for (int i = 0; i < state_len; ++i) S *= 4;
@@ -1445,7 +1444,7 @@ int bh_k_crf_logz(const void* scores, int N, int T, int state_len, float blank, 
     char* w = (char*)workspace;
     float* beta = (float*)w;   w += align((size_t)N * (T + 1) * S * sizeof(float));
     double* Bcum = (double*)w;
-    ScanArgs sa{(const half_t*)scores, N, T, S, state_len, blank, beta, Bcum, logz_out, nullptr, g_decode_nt, 1};
+    ScanArgs sa{(const half_t*)scores, N, T, S, state_len, blank, beta, Bcum, logz_out, nullptr, bh::g_opt.decode_nt, 1};
     {
         int b_threads = 0;
         size_t b_lds = 0;
@@ -1476,7 +1475,7 @@ int bh_k_posterior_viterbi(const void* scores, int N, int T, int state_len, floa
     double* Bcum = (double*)w; w += align((size_t)N * (T + 1) * sizeof(double));
     double* logZ = (double*)w;
     uint8_t* bp = (uint8_t*)workspace + bh_k_beam_workspace(N, T, state_len);
-    ScanArgs sa{(const half_t*)scores, N, T, S, state_len, blank, beta, Bcum, logZ, nullptr, g_decode_nt, 1};
+    ScanArgs sa{(const half_t*)scores, N, T, S, state_len, blank, beta, Bcum, logZ, nullptr, bh::g_opt.decode_nt, 1};
     const int threads = S < 64 ? 64 : S;
     {
         int b_threads = 0;
@@ -1498,9 +1497,10 @@ namespace {
 // One helper stream + fork/join events per (device, host thread): bh_beam_search is re-entrant per thread, and a decode
 // worker thread drives one device.
 struct SideStream { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
-int g_beam_select = 0;     // 0 histogram top-W selection, 1 radix search (A/B and regression tests)
-int g_beam_fork = -1;      // -1 auto (fork for small state spaces), 0 never, 1 always; bh_set_option("beam_fork", v)
-int g_beam_cpw = 0;        // chunks per workgroup of the fused beam kernel at 256 states ("beam_cpw": 0 = automatic, 1, 2, 4). The decode
+// bh::g_opt (options.h), as this file reads it:
+// beam_select: 0 histogram top-W selection, 1 radix search (A/B and regression tests)
+// beam_fork: -1 auto (fork for small state spaces), 0 never, 1 always; bh_set_option("beam_fork", v)
+// beam_cpw: chunks per workgroup of the fused beam kernel at 256 states ("beam_cpw": 0 = automatic, 1, 2, 4). The decode
                            // kernels are chains of dependent LDS round trips, ballots and scalar branches - ~5.5 k cycles per time step
                            // of a chunk whatever else runs - so what counts is how many chunks a CU works on AT ONCE, and whether the
                            // call fits ONE round of resident workgroups. The 16 KiB lse table is shared by the chunks of a workgroup
@@ -1511,7 +1511,7 @@ int g_beam_cpw = 0;        // chunks per workgroup of the fused beam kernel at 2
                            // tried two and three per workgroup with BTB 2 (3.71 / 3.56 / 3.63 ms per batch) and read the flat result
                            // as "instruction bound": those geometries still needed two rounds. Automatic = the smallest of 1 / 2 / 4
                            // that lets the call's chunks be resident together.
-int g_beam_fuse = -1;      // forward / posterior scan as a second wave of the beam kernel's workgroups: -1 auto (<= 256 states: one
+// beam_fuse: forward / posterior scan as a second wave of the beam kernel's workgroups: -1 auto (<= 256 states: one
                            // scan wave keeps up with the beam wave; at 1024 states its 16 states per lane make the beam wave wait:
                            // sup-LSTM 256 x 3334 decode 18 -> 36 ms), 0 never (own kernel), 1 always
 SideStream* side_stream(int S) {
@@ -1521,7 +1521,7 @@ SideStream* side_stream(int S) {
     // 25.3-25.5 ms per step), so auto mode forks for S <= 64 - and for 1024 states, where the scan is not a wave of the beam
     // kernel and that kernel is one wave per chunk on an otherwise idle CU (round 4, 256-chunk batches: decode 9.9 -> 7.5 ms of
     // the transformer sup model with its step unchanged at 67.7 ms, 17.5 -> 13.5 ms of the LSTM sup model, step 112.7 -> 111.0).
-    if (g_beam_fork == 0 || (g_beam_fork < 0 && S > 64 && S < 1024)) return nullptr;
+    if (bh::g_opt.beam_fork == 0 || (bh::g_opt.beam_fork < 0 && S > 64 && S < 1024)) return nullptr;
     thread_local SideStream per_dev[16];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
@@ -1556,10 +1556,10 @@ int bh_k_beam_search(const void* scores, int N, int T, int state_len, int beam_w
     int* fin = (int*)w;         w += align((size_t)N * sizeof(int));
     long long* dbg = getenv("BH_BEAM_DEBUG") ? (long long*)w : nullptr;
 
-    const bool fuse = g_beam_fuse != 0 && S <= 256;      // (the scan wave owns four states per lane: up to 256 states)
+    const bool fuse = bh::g_opt.beam_fuse != 0 && S <= 256;      // (the scan wave owns four states per lane: up to 256 states)
     // ---- guide: linear-domain backward scan (BS-2) -------------------------------------------------------------------------------
     {
-        Bs2Args a2{(const half_t*)scores, beta, N, T, blank, g_decode_nt};
+        Bs2Args a2{(const half_t*)scores, beta, N, T, blank, bh::g_opt.decode_nt};
         auto launch_bwd = [&](auto kern, int cpb, size_t lds, int threads) -> int {
             if (lds > 64 * 1024) BH_CHECK_HIP(bh_max_lds((const void*)kern, (int)lds));
             hipLaunchKernelGGL(kern, dim3((N + cpb - 1) / cpb), dim3(threads), lds, stream, a2);
@@ -1586,7 +1586,7 @@ int bh_k_beam_search(const void* scores, int N, int T, int state_len, int beam_w
         BH_CHECK_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
     }
     if (!fuse) {
-        Bs2FwdArgs f2{(const half_t*)scores, beta, P, N, T, blank, g_decode_nt};
+        Bs2FwdArgs f2{(const half_t*)scores, beta, P, N, T, blank, bh::g_opt.decode_nt};
         hipStream_t fs = fork ? side->stream : stream;
         auto launch_fwd = [&](auto kern, int cpb, size_t chunk_lds) -> int {
             const size_t lds = (size_t)cpb * chunk_lds;
@@ -1606,7 +1606,7 @@ int bh_k_beam_search(const void* scores, int N, int T, int state_len, int beam_w
     }
     if (fork) BH_CHECK_HIP(hipEventRecord(side->join, side->stream));
     BeamArgs ba{(const half_t*)scores, beta, N, T, S, state_len, beam_width, blank, logf(beam_cut), bp, fin, dbg,
-                g_beam_select ? 0.0f : 256.0f / fmaxf(logf(beam_cut), 1e-6f), P, g_decode_nt};
+                bh::g_opt.beam_select ? 0.0f : 256.0f / fmaxf(logf(beam_cut), 1e-6f), P, bh::g_opt.decode_nt};
     // Chunks (waves) per workgroup, measured on MI355X next to the encoder of the same model: four for the narrow state
     // spaces (fast-sized models, three lanes: 1.20e9 -> 1.26e9 samples/s); one for 256 states - two waves per workgroup
     // there cost the hac pipeline 6 % (the 78 KiB workgroups find room beside the recurrent layer's workgroups later).
@@ -1618,7 +1618,7 @@ int bh_k_beam_search(const void* scores, int N, int T, int state_len, int beam_w
         return 0;
     };
     int lrc = -2;
-    int cpw4 = g_beam_cpw;           // chunks per workgroup at 256 states
+    int cpw4 = bh::g_opt.beam_cpw;           // chunks per workgroup at 256 states
     if (fuse && state_len == 4 && cpw4 <= 0) {
         const long cus = bh_cu_count();
         cpw4 = (long)N <= 5 * cus ? 1 : (long)N <= 6 * cus ? 2 : 4;
@@ -1658,14 +1658,4 @@ int bh_k_beam_search(const void* scores, int N, int T, int state_len, int beam_w
     hipLaunchKernelGGL(beam_finalize_kernel, dim3(N), dim3(64), 0, stream, fa);
     BH_CHECK_HIP(hipGetLastError());
     return 0;
-}
-
-int bh_k_decode_set_option(const char* name, int value) {
-    if (name && !strcmp(name, "beam_fork")) { g_beam_fork = value; return 0; }
-    if (name && !strcmp(name, "beam_select")) { g_beam_select = value; return 0; }
-    if (name && !strcmp(name, "beam_fuse")) { g_beam_fuse = value; return 0; }
-    if (name && !strcmp(name, "beam_cpw")) { g_beam_cpw = value; return 0; }
-    if (name && !strcmp(name, "decode_nt")) { g_decode_nt = value; return 0; }
-    if (name && !strcmp(name, "viterbi_quad")) { bh::g_viterbi_quad = value; return 0; }
-    return 1;     // not a decoder option
 }

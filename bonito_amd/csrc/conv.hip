@@ -15,6 +15,7 @@
 //    this folds nn.Permute([2,0,1]), nn.py:331-338, into the store).
 #include "common.h"
 #include "kernels.h"
+#include "options.h"
 #include <cstring>
 
 namespace bh {
@@ -540,21 +541,14 @@ int bh_k_conv_first(const void* signal, const float* w, const float* bias, void*
     return 0;
 }
 
-int g_conv_ws = 1;      // bh_set_option("conv_ws", 0): always the generic implicit-GEMM kernel (A/B, regression tests)
-int g_conv_fuse = 1;    // bh_set_option("conv_fuse", 0): the three separate kernels instead of conv_front3_kernel (A/B, regression tests)
-int g_conv_fs = 1;      // bh_set_option("conv_fs", 0): never the feature-split instance of conv_igemm_kernel (A/B, tests)
-int g_conv_lds_kb = 64; // bh_set_option("conv_lds_kb", v): LDS a workgroup of conv_igemm_kernel may take for its input span; the positions per
+// bh::g_opt (options.h), as this file reads it:
+// conv_ws 0: always the generic implicit-GEMM kernel (A/B, regression tests)
+// conv_fuse 0: the three separate kernels instead of conv_front3_kernel (A/B, regression tests)
+// conv_fs 0: never the feature-split instance of conv_igemm_kernel (A/B, tests)
+// conv_lds_kb: LDS a workgroup of conv_igemm_kernel may take for its input span; the positions per
                         // workgroup follow. Measured on the v5 sup model (256 x 12000, conv class per batch): position-split instances
                         // 3.85 ms at 64 KiB, 3.25 at 80, 3.68 at 104, 4.28 at 150 (one workgroup per CU); with four k-steps of weight
                         // fragments per trip 2.99 at 80; feature-split instances (FS) 2.4-2.6 anywhere from 24 to 64 KiB, 2.69 at 80
-int bh_k_conv_set_option(const char* name, int value) {
-    if (name && !strcmp(name, "conv_ws")) { g_conv_ws = value; return 0; }
-    if (name && !strcmp(name, "conv_fs")) { g_conv_fs = value; return 0; }
-    if (name && !strcmp(name, "conv_fuse")) { g_conv_fuse = value; return 0; }
-    if (name && !strcmp(name, "conv_lds_kb")) { g_conv_lds_kb = value > 0 ? value : 64; return 0; }
-    return 1;
-}
-
 int bh_k_conv_igemm(const void* in, const void* wpk, const float* bias, void* out, int N, int Lin,
                     int Lout, int Cin, int Cout, int K, int stride, int pad, int act, float clamp_lo,
                     float clamp_hi, long os_n, long os_t, hipStream_t stream) {
@@ -565,7 +559,7 @@ int bh_k_conv_igemm(const void* in, const void* wpk, const float* bias, void* ou
                stride, pad, act, ((K * Cin + 31) / 32) * 32, clamp_lo, clamp_hi, os_n, os_t};
     auto lds_for = [&](int pw) { return (size_t)(((4 * pw - 1) * stride + K) * Cin + 40) * 2 + 16; };
     // wide output layer with the k-step count of the bonito conv3 (19 taps x 16 channels): weight-stationary kernel
-    if (g_conv_ws && (Cout == 384 || Cout == 96) && a.Kp == 320 && lds_for(64) <= 64 * 1024) {
+    if (bh::g_opt.conv_ws && (Cout == 384 || Cout == 96) && a.Kp == 320 && lds_for(64) <= 64 * 1024) {
         const dim3 wgrid((Lout + 255) / 256, N);
         if (Cout == 384) hipLaunchKernelGGL((conv_ws_kernel<3, 10, 8>), wgrid, dim3(512), lds_for(64), stream, a);
         else hipLaunchKernelGGL((conv_ws_kernel<1, 10, 6>), wgrid, dim3(384), lds_for(64), stream, a);
@@ -573,7 +567,7 @@ int bh_k_conv_igemm(const void* in, const void* wpk, const float* bias, void* ou
         return 0;
     }
     int pw = 64;
-    while (pw > 16 && lds_for(pw) > (size_t)g_conv_lds_kb * 1024) pw >>= 1;
+    while (pw > 16 && lds_for(pw) > (size_t)bh::g_opt.conv_lds_kb * 1024) pw >>= 1;
     size_t lds = lds_for(pw);
     BH_REQUIRE(lds <= 160 * 1024, "conv_igemm: input span does not fit LDS (%zu bytes)", lds);
     dim3 grid((Lout + 4 * pw - 1) / (4 * pw), N);
@@ -582,7 +576,7 @@ int bh_k_conv_igemm(const void* in, const void* wpk, const float* bias, void* ou
                          : pw == 32 ? (const void*)conv_igemm_kernel<2> : (const void*)conv_igemm_kernel<1>;
         BH_CHECK_HIP(bh_max_lds(fn, (int)lds));
     }
-    const bool fs = g_conv_fs && Cout % 64 == 0;
+    const bool fs = bh::g_opt.conv_fs && Cout % 64 == 0;
     if (fs) {
         if (lds > 64 * 1024) {
             const void* fn = pw == 64 ? (const void*)conv_igemm_kernel<4, true>
@@ -603,14 +597,14 @@ int bh_k_conv_igemm(const void* in, const void* wpk, const float* bias, void* ou
 // Can the three convolutions at the head of an LSTM model run as conv_front3_kernel? conv1: 1 -> <= 16 channels (16 with padding),
 // stride 1, K1 <= 8; conv2: 16 -> 16 (padded), stride 1, K2 * 16 <= 96; conv3: what conv_ws_kernel serves (16 -> 384 / 96 channels, Kp = 320).
 int bh_k_conv_front3_ok(int c1_eff, int K1, int s1, int c2_in_eff, int c2_eff, int K2, int s2, int c3_in_eff, int c3_out, int K3, int s3) {
-    if (!g_conv_fuse || !g_conv_ws) return 0;
+    if (!bh::g_opt.conv_fuse || !bh::g_opt.conv_ws) return 0;
     if (c1_eff != 16 || c2_in_eff != 16 || c2_eff != 16 || c3_in_eff != 16) return 0;
     if (s1 != 1 || s2 != 1 || K1 < 1 || K1 > 8 || K2 < 1 || K2 * 16 > 96) return 0;
     if (!(c3_out == 384 || c3_out == 96) || ((K3 * 16 + 31) / 32) * 32 != 320) return 0;
     // 96 channels (the fast models): correct (tests run it with "conv_fuse" 2) but not the default - those models keep three batches in
     // flight whose recurrent kernels share the CUs with the convolutions, and the 65 KiB, 384-thread fused workgroups cost that
     // pipeline more than the 0.04 ms of convolution time they save (bench step 2.43 -> 2.55-2.65 ms)
-    if (c3_out == 96 && g_conv_fuse < 2) return 0;
+    if (c3_out == 96 && bh::g_opt.conv_fuse < 2) return 0;
     const size_t span = (size_t)255 * s3 + K3;
     const size_t lds = ((span * 16 + 40 + 7) & ~(size_t)7) * 2 + (size_t)(256 + K2 - 1 + 6) * 16 * 2 + (span + K2 + K1 + 6) * 4 + (size_t)(16 * K1 + 16) * 4;
     return lds <= 80 * 1024 ? 1 : 0;

@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "options.h"
 
 namespace bh {
 
@@ -43,7 +44,6 @@ struct VitArgs {
 };
 
 constexpr int VU = 8;  // prefetch depth (time steps)
-int g_viterbi_quad = 1;       // "viterbi_quad": 1 = four states per thread (round 5), 0 = the round-1 kernel everywhere
 
 template <bool L5S>
 __global__ void crf_viterbi_kernel(VitArgs p) {
@@ -303,7 +303,7 @@ int bh_k_crf_viterbi(const void* scores, int N, int T, int state_len, int layout
     BH_REQUIRE(layout_5s || (s_t % 4 == 0 && s_n % 4 == 0), "viterbi: 4S layout needs strides %% 4 == 0");
     VitArgs a{(const half_t*)scores, N, T, S, blank_score, s_n, s_t, (uint8_t*)bp_ws, moves, path, best_score};
     // koi layout, 64 states and more, rows 16-byte aligned: four states per thread (round 5); "viterbi_quad" 0 = the round-1 kernel
-    if (!layout_5s && state_len >= 3 && g_viterbi_quad && s_t % 8 == 0 && s_n % 8 == 0 && ((uintptr_t)scores & 15) == 0) {
+    if (!layout_5s && state_len >= 3 && bh::g_opt.viterbi_quad && s_t % 8 == 0 && s_n % 8 == 0 && ((uintptr_t)scores & 15) == 0) {
 #define BH_VIT_QUAD(SL)                                                                                                        \
     {                                                                                                                          \
         using G = VitQuadGeo<SL>;                                                                                              \

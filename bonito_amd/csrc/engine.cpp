@@ -23,6 +23,7 @@
 #include "common.h"
 #include "devbuf.h"
 #include "kernels.h"
+#include "options.h"
 
 // ------------------------------------------------------------------------------------------------
 static thread_local char g_err[1024] = "";
@@ -43,8 +44,6 @@ extern "C" int bh_device_count(void) {
     }
     return n;
 }
-
-namespace bh { int g_q8_variant = 0; }      // process-wide: geometry of the 8-bit recurrent kernel picked at engine creation ("lstm_q8_variant", abi.cpp)
 
 // Tile packing for the workgroup-shared LSTM kernel: [slice][tile m][kstep][lane][8] with U = 4*MT units per slice;
 // row r of tile m is (unit slice*U + (r>>2)*MT + m, gate r&3), so the MFMA result leaves all four gate
@@ -294,7 +293,7 @@ static bool lstm_may_share(const bh_layer_t& d) { return d.in_size == d.out_size
 static bool lstm_may_wide(const bh_layer_t& d) { return bh_k_lstm_wide_ok(d.out_size) != 0; }
 // 8-bit kernel: int8 tiles and scales in q_*
 static bool lstm_may_q8(const bh_layer_t& d) {
-    return d.quantize && d.in_size == d.out_size && bh_k_lstm_q8_units(d.out_size, bh::g_q8_variant) != 0;
+    return d.quantize && d.in_size == d.out_size && bh_k_lstm_q8_units(d.out_size, bh::g_opt.lstm_q8_variant) != 0;
 }
 
 enum Handoff {
@@ -436,7 +435,7 @@ static int create_lstm(bh_encoder* e, size_t i, const bh_layer_t& d, CreateState
         if (!rc) rc = upload(L.w4, pk.data(), pk.size() * 2);
     }
     if (!rc && lstm_may_q8(d)) {       // Q8-1 tiles and scales
-        const int U = bh_k_lstm_q8_units(H, bh::g_q8_variant);
+        const int U = bh_k_lstm_q8_units(H, bh::g_opt.lstm_q8_variant);
         const size_t tile_bytes = (size_t)4 * H * ((H + 63) / 64 * 64);
         std::vector<int8_t> pk(tile_bytes);
         std::vector<float> s_ih((size_t)4 * H), s_hh((size_t)4 * H);
@@ -449,7 +448,7 @@ static int create_lstm(bh_encoder* e, size_t i, const bh_layer_t& d, CreateState
         if (!rc) rc = upload_f32(L.q_sx, s_ih.data(), s_ih.size());
         if (!rc) rc = upload_f32(L.q_sh, s_hh.data(), s_hh.size());
         L.q8 = true;
-        L.q_variant = bh::g_q8_variant;
+        L.q_variant = bh::g_opt.lstm_q8_variant;
         L.q_bound = cs.bound;
         cs.any_q8 = true;
     }
@@ -887,7 +886,7 @@ static int forward_lstm_q8(bh_encoder* e, size_t i, Cursor& c, const LstmPlan& p
                                 hq_out ? (char*)hq_out + (size_t)r0 * tile : nullptr,
                                 h16_out ? (char*)h16_out + (size_t)r0 * 16 * H * 2 : nullptr,
                                 (char*)e->q_ex.p + (size_t)r0 * tile, len, Np, H, R, nr, d.reverse, e->cur_err, st,
-                                (int*)e->lstm_ws.p, e->lstm_force_slow, l.q_variant, nullptr, bh_k_lstm_max_spins());
+                                (int*)e->lstm_ws.p, e->lstm_force_slow, l.q_variant, nullptr, (unsigned)bh::g_opt.lstm_max_spins);
         if (rc) return rc;
     }
     if (next_q8) { c.cur_q = hq_out; c.qi ^= 1; }
@@ -1267,7 +1266,7 @@ extern "C" int bh_encoder_set_option(bh_encoder_t* e, const char* name, int valu
     if (!strcmp(name, "lstm_exchange")) { e->lstm_exchange = value; return 0; }
     if (!strcmp(name, "lstm_pair")) { e->lstm_pair = value; return 0; }
     if (!strcmp(name, "norm_fuse")) { e->norm_fuse = value; return 0; }
-    if (!strcmp(name, "gemm_v1")) { bh_k_linear_force_v1(value); return 0; }   // process-wide A/B switch
+    if (!strcmp(name, "gemm_v1")) { bh::g_opt.gemm_path = value; return 0; }   // alias of the process-wide "gemm_path"
     if (!strcmp(name, "lstm_tune")) { e->lstm_force_slow = (e->lstm_force_slow & 1) | (value << 8); return 0; }
     BH_REQUIRE(false, "encoder_set_option: unknown option '%s'", name);
 }

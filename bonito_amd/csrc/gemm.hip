@@ -19,6 +19,7 @@
 #include <type_traits>
 #include "common.h"
 #include "kernels.h"
+#include "options.h"
 
 namespace bh {
 
@@ -1306,107 +1307,190 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs p) {
 #ifdef BH_GEMM_STATS
 unsigned long long* g_gemm_dbg = nullptr;
 #endif
-int g_w4_gf = 0;             // experiments: feature tiles per block of gemm_w4_kernel's work order (0 = default)
-// bh_k_linear_order ("gemm_order"): GemmArgs::w4_order. 1 (default since round 6): an XCD finishes ALL feature groups of a block of token tiles
-// before it moves on - the block's X tiles (GT x 256 KiB at K = 512) are fetched from HBM once and re-read from L2, the W tiles (4 MiB at
-// N = 4096: Infinity-Cache resident) come round once per token block. 0 (rounds 4-5): token blocks fastest - X streamed from HBM once per
-// feature group (fc1: four times; PMC 5.25 GB against 2.62 algorithmic). Lab, tools/gemm_lab_order.sh: +4 % where there is more than one
-// feature group (Wqkv, fc1, the N = 4096 input projections), nothing elsewhere (profiles/r06_gemm_tile16.txt)
-int g_w4_order = 1;
-static int g_stagger = 0;    // bh_k_linear_stagger
-// bh_k_linear_tile16 ("gemm_tile16"): gemm_w4_kernel's K-tile stream on 16x16x32 MFMAs (1, default since round 6: 5-9 % faster on every
-// shape of tools/gemm_bench.py, sup 60.4 -> 59.2 ms per batch - profiles/r06_gemm_tile16.txt) or on 32x32x16 (0: rounds 4-5)
-static int g_w4_t16 = 1;
-static int g_last_kernel = 0; // bh_k_linear_last_kernel (test hook, not thread-safe): 1 = v1, 2 = v2, 3 = v3, 5 / 6 = v5 on 32x32x16 / 16x16x32
-static int g_force_v1 = 0;   // test / A-B hook (bh_k_linear_force_v1): 1 = v1 only, 2 = never v3 / v5, 3 = never v5 (v3 where it applies), 5 = v5 whenever the shape is legal (tests: small problems)
+static int g_last_kernel = 0; // bh_k_linear_last_kernel (test hook, not thread-safe): the GemmKernel of the last launch
+
+// ---- dispatch: which kernel serves a call, with what geometry - stated once (gemm_plan) -------------------------------------------------
+// kernel ids as bh_linear_last_kernel() reports them: v1 gemm_kernel, v2 gemm_glds_kernel, v3 gemm_big_kernel (eight waves),
+// v5 gemm_w4_kernel (four waves) on its 32x32x16 / 16x16x32 K-tile stream
+enum GemmKernel : int { GEMM_V1 = 1, GEMM_V2 = 2, GEMM_V3 = 3, GEMM_W4_T32 = 5, GEMM_W4_T16 = 6 };
+// "gemm_path" (test / A-B hook), the public values
+enum GemmPath : int {
+    PATH_AUTO = 0,
+    PATH_V1_ONLY = 1,       // v1 only
+    PATH_NO_256 = 2,        // never a 256 x 256 kernel (v3 / v5)
+    PATH_NO_W4 = 3,         // never v5 (v3 where it applies)
+    PATH_FORCE_W4 = 5       // v5 whenever the shape is legal (tests: small problems)
+};
+
+// The instances of gemm_w4_kernel, X(activation, gated, epilogue mode), each on both K-tile streams: the ONE list. Epilogue modes are
+// compile-time (w4_epilogue): the combinations the engine uses are instantiated, anything else goes to another kernel. w4_has_instance
+// and launch_w4 are both generated from it (a combination listed twice is a duplicate case label).
+#define W4_INSTANCES(X)                                                                                                  \
+    X(ACT_NONE, true, 0)                                                                                                 \
+    X(ACT_NONE, false, 0) X(ACT_NONE, false, 1) X(ACT_NONE, false, 2) X(ACT_NONE, false, 4)                              \
+    X(ACT_TANH, false, 4) X(ACT_TANH, false, 0)                                                                          \
+    X(ACT_SWISH, false, 0)
+constexpr int w4_key(int act, bool gated, int mode) { return (act << 4) | (gated ? 8 : 0) | mode; }
+// mode: 1 = residual, 2 = rotary, 4 = scale / clamp
+static int w4_mode(const GemmArgs& a) {
+    const bool plain = a.scale == 1.0f && a.clamp_lo == -INFINITY && a.clamp_hi == INFINITY;
+    return (a.res != nullptr ? 1 : 0) | (a.rot_cs != nullptr ? 2 : 0) | (plain ? 0 : 4);
+}
+static bool w4_has_instance(int act, bool gated, int mode) {
+    switch (w4_key(act, gated, mode)) {
+#define W4_CASE(A_, G_, MODE_) case w4_key(A_, G_, MODE_):
+        W4_INSTANCES(W4_CASE)
+#undef W4_CASE
+        return true;
+    }
+    return false;
+}
+
+// What the shape allows, per family.
+// Both 256 x 256 kernels are persistent: they pay off from ~2 waves of tiles over the chip.
+static bool enough_tiles_256(const GemmArgs& a) { return (long)((a.N + BF3 - 1) / BF3) * ((a.M + BT3 - 1) / BT3) >= 512; }
+// ... and address X and W with 32-bit element offsets
+static bool offsets_fit_256(const GemmArgs& a) { return (long)a.M * a.ldx < (1l << 31) && (long)a.N * a.ldw < (1l << 31); }
+static bool shape_allows_w4(const GemmArgs& a) {
+    return a.K % 128 == 0 && a.K >= 384                                          // K-tiles of 128 halves, no tail; three at least (two-tile prologue, parked rows: nk >= NST)
+           && a.N % 256 == 0                                                     // whole feature tiles: no feature guard in its epilogues
+           && ((a.row_div == 1 && a.row_s_hi == 1) || a.row_div % 256 == 0)      // the row map is affine over a token tile
+           && (a.rot_cs == nullptr || a.rot_T >= 256)                            // rotary: a token tile wraps the position at most once
+           && (long)a.ldo * 2 * (a.row_div == 1 ? 1 : a.row_s_lo) < (1l << 24)   // < 16 MiB between stored tokens: a tile's rows stay inside its buffer descriptor
+           && offsets_fit_256(a);
+}
+static bool shape_allows_v3(const GemmArgs& a) {
+    return a.K % BK3 == 0                          // no K tail
+           && a.N >= 256 && a.N % 16 == 0          // at least one feature tile; 16-byte epilogue stores
+           && offsets_fit_256(a);
+}
+static bool shape_allows_v2(const GemmArgs& a) { return a.K % BK2 == 0; }     // no K tail (v1 takes any K % 8 == 0)
+
+// What "gemm_path" permits.
+static bool path_permits(int path, GemmKernel family) {
+    switch (family) {
+        case GEMM_W4_T32: case GEMM_W4_T16: return path == PATH_AUTO || path == PATH_FORCE_W4;
+        case GEMM_V3: return path == PATH_AUTO || path == PATH_NO_W4;
+        case GEMM_V2: return path != PATH_V1_ONLY;
+        default: return true;
+    }
+}
+
+struct GemmPlan {
+    GemmKernel kernel;
+    int grid, block, lds;     // launch geometry, dynamic LDS bytes
+    int mode;                 // w4_mode (the four-wave kernel's template argument)
+    GemmArgs args;            // as the chosen kernel reads them: n_ft / n_tt in its tiles, w4_gf, w4_order, stagger in its unit
+};
+// Pure: the caller's arguments (n_ft / n_tt in 128-tiles), the options and the CU count in, the launch out.
+static GemmPlan gemm_plan(const GemmArgs& a, int act, bool gated, const Options& opt, int cus) {
+    GemmPlan p;
+    p.args = a;
+    p.mode = w4_mode(a);
+    const int path = opt.gemm_path;
+    const bool w4 = shape_allows_w4(a) && (enough_tiles_256(a) || path == PATH_FORCE_W4) && path_permits(path, GEMM_W4_T16) &&
+                    w4_has_instance(act, gated, p.mode);
+    const bool v3 = !w4 && shape_allows_v3(a) && enough_tiles_256(a) && path_permits(path, GEMM_V3);
+    if (!w4 && !v3) {
+        p.kernel = shape_allows_v2(a) && path_permits(path, GEMM_V2) ? GEMM_V2 : GEMM_V1;
+        p.grid = a.n_ft * a.n_tt; p.block = 256; p.lds = p.kernel == GEMM_V2 ? 4 * TILE2 : 4 * TILE_BYTES;
+        return p;
+    }
+    const int nf = (a.N + BF3 - 1) / BF3, nt = (a.M + BT3 - 1) / BT3;
+    p.args.n_ft = nf; p.args.n_tt = nt;
+    // "gemm_stagger" u > 0: the workgroups of an XCD start in eight phase groups. The ONE place that converts the option: gemm_big_kernel
+    // takes u itself (gemm_stagger_start: group g sleeps g * u times ~1024 cycles); gemm_w4_kernel takes CYCLES between groups, u x 256
+    // (measured: no gain for it - its epilogue is bound by the CU's store path, not by a chip-wide burst - and the last groups finish up
+    // to 7 u x 256 cycles late). Default off.
+    if (v3) {
+        p.kernel = GEMM_V3;
+        p.args.stagger = opt.gemm_stagger;
+        p.grid = nf * nt < cus ? nf * nt : cus; p.block = 512; p.lds = 4 * TILE3;
+        return p;
+    }
+    p.kernel = opt.gemm_tile16 ? GEMM_W4_T16 : GEMM_W4_T32;
+    p.args.stagger = opt.gemm_stagger > 0 ? opt.gemm_stagger * 256 : 0;
+    // "gemm_order": GemmArgs::w4_order. 1 (default since round 6): an XCD finishes ALL feature groups of a block of token tiles before it
+    // moves on - the block's X tiles (GT x 256 KiB at K = 512) are fetched from HBM once and re-read from L2, the W tiles (4 MiB at N = 4096:
+    // Infinity-Cache resident) come round once per token block. 0 (rounds 4-5): token blocks fastest - X streamed from HBM once per feature
+    // group (fc1: four times; PMC 5.25 GB against 2.62 algorithmic). Lab, tools/gemm_lab_order.sh: +4 % where there is more than one feature
+    // group (Wqkv, fc1, the N = 4096 input projections), nothing elsewhere (profiles/r06_gemm_tile16.txt)
+    p.args.w4_order = opt.gemm_order;
+    // "gemm_gf": feature tiles per block of the work order. The kernel needs a power of two that divides 32: a request is rounded down to
+    // one. Automatic (0): 4, halved until it divides n_ft (a group that does not divide n_ft leaves slots empty: 6 tiles in groups of 4
+    // wasted a quarter). Either way no more than n_ft.
+    int gf = 4;
+    if (opt.gemm_gf > 0) for (gf = 32; gf > opt.gemm_gf;) gf >>= 1;
+    while (gf > 1 && (gf > nf || (opt.gemm_gf <= 0 && nf % gf != 0))) gf >>= 1;
+    p.args.w4_gf = gf;
+    const int gt = 32 / gf, ntx = (nt >> 3) + ((nt & 7) ? 1 : 0);
+    const long slots = 8l * ((nf + gf - 1) / gf) * ((ntx + gt - 1) / gt) * 32;
+    p.grid = slots < cus ? (int)slots : cus; p.block = 256; p.lds = W4_LDS;
+    return p;
+}
+
+// four parked rows per K-tile instance on every K (K = 384, six instances: six rows per instance over four of them measured 3 %
+// slower than four rows over five - 0.879 against 0.853 ms on the hac CRF head)
+template <int ACT, bool GATED, int MODE, bool T16>
+static int launch_w4_instance(const GemmPlan& p, hipStream_t s) {
+    BH_CHECK_HIP(bh_max_lds((const void*)gemm_w4_kernel<ACT, GATED, 4, MODE, T16>, p.lds));
+    hipLaunchKernelGGL((gemm_w4_kernel<ACT, GATED, 4, MODE, T16>), dim3(p.grid), dim3(p.block), p.lds, s, p.args);
+    return 0;
+}
+template <int ACT, bool GATED>
+static int launch_w4(const GemmPlan& p, hipStream_t s) {
+    switch (w4_key(ACT, GATED, p.mode)) {
+#define W4_CASE(A_, G_, MODE_)                                                                                                   \
+    case w4_key(A_, G_, MODE_):                                                                                                  \
+        if constexpr (ACT == A_ && GATED == G_)                                                                                  \
+            return p.kernel == GEMM_W4_T16 ? launch_w4_instance<ACT, GATED, MODE_, true>(p, s) : launch_w4_instance<ACT, GATED, MODE_, false>(p, s); \
+        break;
+        W4_INSTANCES(W4_CASE)
+#undef W4_CASE
+    }
+    BH_REQUIRE(false, "linear: gemm_w4_kernel has no instance for activation %d, gated %d, mode %d", ACT, (int)GATED, p.mode);
+}
 
 template <int ACT, bool GATED>
 static int launch(const GemmArgs& a, hipStream_t s) {
-    int grid = a.n_ft * a.n_tt;
-    // v5 (gemm_w4_kernel) / v3 when the problem has at least ~2 waves of 256 x 256 tiles over the chip and no K tail
-    {
-        const int nf3 = (a.N + BF3 - 1) / BF3, nt3 = (a.M + BT3 - 1) / BT3;
-        if (a.K % 128 == 0 && a.K >= 384 && (g_force_v1 == 0 || g_force_v1 == 5) && a.N % 256 == 0 && ((long)nf3 * nt3 >= 512 || g_force_v1 == 5) &&
-            ((a.row_div == 1 && a.row_s_hi == 1) || a.row_div % 256 == 0) && (a.rot_cs == nullptr || a.rot_T >= 256) &&
-            (long)a.ldo * 2 * (a.row_div == 1 ? 1 : a.row_s_lo) < (1l << 24) &&
-            (long)a.M * a.ldx < (1l << 31) && (long)a.N * a.ldw < (1l << 31)) {
-            const int cus = bh_cu_count();
-            GemmArgs b = a;
-            b.n_ft = nf3; b.n_tt = nt3;
-            int gf = g_w4_gf > 0 ? g_w4_gf : 4;
-            while (gf > 1 && (gf > nf3 || (g_w4_gf <= 0 && nf3 % gf != 0))) gf >>= 1;      // (a group that does not divide n_ft leaves slots empty: 6 tiles in groups of 4 wasted a quarter)
-            b.w4_gf = gf;
-            b.w4_order = g_w4_order;
-            // "gemm_stagger" n > 0: phase groups n x 256 cycles apart (measured: no gain for this kernel - its epilogue is bound by the CU's
-            // store path, not by a chip-wide burst - and the last groups finish up to 7 n x 256 cycles late); default off
-            b.stagger = g_stagger > 0 ? g_stagger * 256 : 0;
-            const int gt = 32 / gf, ntx = (nt3 >> 3) + ((nt3 & 7) ? 1 : 0);
-            const long slots = 8l * ((nf3 + gf - 1) / gf) * ((ntx + gt - 1) / gt) * 32;
-            // epilogue modes are compile-time (w4_epilogue): the combinations the engine uses are instantiated, anything else falls through
-            // to the eight-wave kernel below
-            const bool plain = a.scale == 1.0f && a.clamp_lo == -INFINITY && a.clamp_hi == INFINITY;
-            const int mode = (a.res != nullptr ? 1 : 0) | (a.rot_cs != nullptr ? 2 : 0) | (plain ? 0 : 4);
-            bool done = true;
-// four parked rows per K-tile instance on every K (K = 384, six instances: six rows per instance over four of them measured 3 %
-// slower than four rows over five - 0.879 against 0.853 ms on the hac CRF head)
-#define W4_LAUNCH_T(A_, G_, MODE_, T16_)                                                                                            \
-    do {                                                                                                                          \
-        BH_CHECK_HIP(bh_max_lds((const void*)gemm_w4_kernel<A_, G_, 4, MODE_, T16_>, W4_LDS));                                    \
-        hipLaunchKernelGGL((gemm_w4_kernel<A_, G_, 4, MODE_, T16_>), dim3(slots < cus ? (int)slots : cus), dim3(256), W4_LDS, s, b); \
-    } while (0)
-#define W4_LAUNCH(A_, G_, MODE_) do { if (g_w4_t16) W4_LAUNCH_T(A_, G_, MODE_, true); else W4_LAUNCH_T(A_, G_, MODE_, false); } while (0)
-            if constexpr (GATED) {
-                if (mode == 0) W4_LAUNCH(ACT_NONE, true, 0); else done = false;
-            } else if constexpr (ACT == ACT_NONE) {
-                if (mode == 0) W4_LAUNCH(ACT_NONE, false, 0);
-                else if (mode == 1) W4_LAUNCH(ACT_NONE, false, 1);
-                else if (mode == 2) W4_LAUNCH(ACT_NONE, false, 2);
-                else if (mode == 4) W4_LAUNCH(ACT_NONE, false, 4);
-                else done = false;
-            } else if constexpr (ACT == ACT_TANH) {
-                if (mode == 4) W4_LAUNCH(ACT_TANH, false, 4); else if (mode == 0) W4_LAUNCH(ACT_TANH, false, 0); else done = false;
-            } else if constexpr (ACT == ACT_SWISH) {
-                if (mode == 0) W4_LAUNCH(ACT_SWISH, false, 0); else done = false;
-            } else {
-                done = false;
-            }
-#undef W4_LAUNCH
-#undef W4_LAUNCH_T
-            if (done) { g_last_kernel = g_w4_t16 ? 6 : 5; return 0; }
-        }
-        if (false) {
-            return 0;
-        }
-        if (a.K % BK3 == 0 && (g_force_v1 == 0 || g_force_v1 == 3) && a.N >= 256 && a.N % 16 == 0 && (long)nf3 * nt3 >= 512 &&
-            (long)a.M * a.ldx < (1l << 31) && (long)a.N * a.ldw < (1l << 31)) {
-            const int cus = bh_cu_count();
-            GemmArgs b = a;
-            b.n_ft = nf3; b.n_tt = nt3;
-            b.stagger = g_stagger;
-            const int tiles = nf3 * nt3;
-            BH_CHECK_HIP(bh_max_lds((const void*)gemm_big_kernel<ACT, GATED>, 4 * TILE3));
-            hipLaunchKernelGGL((gemm_big_kernel<ACT, GATED>), dim3(tiles < cus ? tiles : cus), dim3(512), 4 * TILE3, s, b);
-            g_last_kernel = 3;
-            return 0;
-        }
+    const GemmPlan p = gemm_plan(a, ACT, GATED, g_opt, bh_cu_count());
+    switch (p.kernel) {
+        case GEMM_W4_T32: case GEMM_W4_T16:
+            if (int rc = launch_w4<ACT, GATED>(p, s)) return rc;
+            break;
+        case GEMM_V3:
+            BH_CHECK_HIP(bh_max_lds((const void*)gemm_big_kernel<ACT, GATED>, p.lds));
+            hipLaunchKernelGGL((gemm_big_kernel<ACT, GATED>), dim3(p.grid), dim3(p.block), p.lds, s, p.args);
+            break;
+        case GEMM_V2:
+            hipLaunchKernelGGL((gemm_glds_kernel<ACT, GATED>), dim3(p.grid), dim3(p.block), p.lds, s, p.args);
+            break;
+        case GEMM_V1:
+            hipLaunchKernelGGL((gemm_kernel<ACT, GATED>), dim3(p.grid), dim3(p.block), p.lds, s, p.args);
+            break;
     }
-    if (a.K % BK2 == 0 && g_force_v1 != 1) {
-        hipLaunchKernelGGL((gemm_glds_kernel<ACT, GATED>), dim3(grid), dim3(256), 4 * TILE2, s, a);
-        g_last_kernel = 2;
-    } else {
-        hipLaunchKernelGGL((gemm_kernel<ACT, GATED>), dim3(grid), dim3(256), 4 * TILE_BYTES, s, a);
-        g_last_kernel = 1;
-    }
+    g_last_kernel = p.kernel;
     return 0;
+}
+
+// The arguments every entry point starts from: identity row map, tile counts of the 128 x 128 kernels (gemm_plan restates them for the
+// others), neutral scale / clamp, no residual, no rotary.
+static GemmArgs gemm_args(const void* X, const void* W, const float* bias, void* out, int M, int N, int K, int ldx, int ldw, int ldo) {
+    GemmArgs a;
+    a.X = (const half_t*)X; a.W = (const half_t*)W; a.bias = bias; a.out = (half_t*)out;
+    a.res = nullptr; a.ldres = 0;
+    a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = ldw; a.ldo = ldo;
+    a.scale = 1.0f; a.clamp_lo = -INFINITY; a.clamp_hi = INFINITY;
+    a.row_div = 1; a.row_s_hi = 1; a.row_s_lo = 0; a.row_lim = 0x7fffffff;
+    a.n_ft = (N + BF - 1) / BF; a.n_tt = (M + BT - 1) / BT;
+#ifdef BH_GEMM_STATS
+    a.dbg = g_gemm_dbg;
+#endif
+    return a;
 }
 
 }  // namespace bh
 
-void bh_k_linear_force_v1(int on) { bh::g_force_v1 = on; }
-void bh_k_linear_stagger(int units) { bh::g_stagger = units; }
-void bh_k_linear_tile16(int on) { bh::g_w4_t16 = on ? 1 : 0; }
-void bh_k_linear_order(int order) { bh::g_w4_order = order ? 1 : 0; }
-void bh_k_linear_gf(int gf) { bh::g_w4_gf = gf; }
 int bh_k_linear_last_kernel() { return bh::g_last_kernel; }
 
 int bh_k_linear(const void* X, const void* W, const float* bias, void* out, int M, int N, int K,
@@ -1420,19 +1504,13 @@ int bh_k_linear(const void* X, const void* W, const float* bias, void* out, int 
     BH_REQUIRE(!gated || (N % 16 == 0), "linear: gated epilogue needs N %% 16 == 0");
     // the epilogues read the residual as 16-byte vectors (v5: buffer loads of whole 128-byte lines)
     BH_REQUIRE(residual == nullptr || ldres % 8 == 0, "linear: ldres must be a multiple of 8 halves");
-    GemmArgs a;
-    a.X = (const half_t*)X; a.W = (const half_t*)W; a.bias = bias; a.out = (half_t*)out;
+    GemmArgs a = gemm_args(X, W, bias, out, M, N, K, ldx, ldw, ldo);
     a.res = (const half_t*)residual; a.ldres = ldres; a.res_scale = res_scale;
-    a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = ldw; a.ldo = ldo;
     a.scale = scale; a.clamp_lo = clamp_lo; a.clamp_hi = clamp_hi;
-    a.row_div = row_div > 0 ? row_div : 1;
-    a.row_s_hi = row_div > 0 ? row_s_hi : 1;
-    a.row_s_lo = row_div > 0 ? row_s_lo : 0;
-    a.row_lim = (row_div > 0 && row_lim > 0) ? row_lim : 0x7fffffff;
-    a.n_ft = (N + BF - 1) / BF; a.n_tt = (M + BT - 1) / BT;
-#ifdef BH_GEMM_STATS
-    a.dbg = g_gemm_dbg;
-#endif
+    if (row_div > 0) {
+        a.row_div = row_div; a.row_s_hi = row_s_hi; a.row_s_lo = row_s_lo;
+        if (row_lim > 0) a.row_lim = row_lim;
+    }
     int rc = 0;
     if (gated) { rc = launch<ACT_NONE, true>(a, stream); }
     else switch (act) {
@@ -1454,13 +1532,7 @@ int bh_k_linear_qkv_rotary(const void* X, const void* W, const float* bias, void
     using namespace bh;
     BH_REQUIRE(M > 0 && D > 0 && K > 0 && T > 0 && cos_sin != nullptr, "linear_qkv_rotary: bad arguments");
     BH_REQUIRE(D % 64 == 0 && K % 8 == 0, "linear_qkv_rotary: d_model must be a multiple of 64 (heads of 64), K of 8");
-    GemmArgs a;
-    a.X = (const half_t*)X; a.W = (const half_t*)W; a.bias = bias; a.out = (half_t*)out;
-    a.res = nullptr; a.ldres = 0;
-    a.M = M; a.N = 3 * D; a.K = K; a.ldx = K; a.ldw = K; a.ldo = 3 * D;
-    a.scale = 1.0f; a.clamp_lo = -INFINITY; a.clamp_hi = INFINITY;
-    a.row_div = 1; a.row_s_hi = 1; a.row_s_lo = 0; a.row_lim = 0x7fffffff;
-    a.n_ft = (a.N + BF - 1) / BF; a.n_tt = (M + BT - 1) / BT;
+    GemmArgs a = gemm_args(X, W, bias, out, M, 3 * D, K, K, K, 3 * D);
     a.rot_cs = cos_sin; a.rot_T = T; a.rot_nfeat = 2 * D; a.rot_qfeat = D; a.rot_qscale = qscale;
     if (int rc = launch<ACT_NONE, false>(a, stream)) return rc;
     BH_CHECK_HIP(hipGetLastError());

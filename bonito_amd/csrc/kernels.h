@@ -12,12 +12,6 @@ int bh_k_linear(const void* X, const void* W, const float* bias, void* out, int 
                 int ldx, int ldw, int ldo, int act, float scale, float clamp_lo, float clamp_hi,
                 int gated, int row_div, long row_s_hi, long row_s_lo, int row_lim, hipStream_t stream,
                 const void* residual = nullptr, int ldres = 0, float res_scale = 1.0f);
-
-void bh_k_linear_force_v1(int on);
-void bh_k_linear_stagger(int units);
-void bh_k_linear_order(int order);  // gemm_w4_kernel's work order inside an XCD: 0 token blocks fastest, 1 feature groups fastest
-void bh_k_linear_gf(int gf);        // ... feature tiles per block (0 = automatic)
-void bh_k_linear_tile16(int on);   // gemm_w4_kernel on 16x16x32 MFMAs (1) or 32x32x16 (0)
 int bh_k_linear_last_kernel();     // test hook: the kernel the last launch took (1 = v1, 2 = v2, 3 = v3, 5 / 6 = v5 on 32x32x16 / 16x16x32); not thread-safe
 
 // conv.hip
@@ -61,7 +55,6 @@ int bh_k_lstm_layer_fused(const void* x, const void* wih_packed, const float* bi
                           int T, int N, int H, int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws,
                           int force_slow);
 int bh_k_fill_u16(void* dst, uint16_t value, size_t count, hipStream_t stream);
-int bh_k_lstm_set_option(const char* name, int value);     // "lstm_max_spins"
 size_t bh_k_lstm_packed_bytes(int H);
 int bh_k_lstm_wg_units(int H);
 int bh_k_lstm_cta_units(int H);
@@ -117,9 +110,6 @@ int bh_k_ctc_prefix_beam(const float* logp, const long* offs, int R, int C, int 
 size_t bh_k_posterior_viterbi_workspace(int N, int T, int state_len);
 int bh_k_posterior_viterbi(const void* scores, int N, int T, int state_len, float blank, void* workspace, int8_t* moves,
                            int8_t* path, hipStream_t stream);
-int bh_k_decode_set_option(const char* name, int value);
-namespace bh { extern int g_viterbi_quad; }       // crf.hip ("viterbi_quad")
-int bh_k_conv_set_option(const char* name, int value);     // "conv_ws", "conv_fs", "conv_lds_kb", "conv_fuse"
 // conv1 -> conv2 -> conv3 of an LSTM model's front end in one kernel (conv_front3_kernel); _ok: does the shape qualify?
 int bh_k_conv_front3_ok(int c1_eff, int K1, int s1, int c2_in_eff, int c2_eff, int K2, int s2, int c3_in_eff, int c3_out, int K3, int s3);
 int bh_k_conv_front3(const void* signal, int N, int L0, const float* w1, const float* b1, int K1, int pad1, int act1, float lo1, float hi1,
@@ -159,7 +149,6 @@ int bh_k_lstm_q8_arm(void* ex, int R, int H, hipStream_t stream);
 int bh_k_lstm_layer_q8(const void* xq, const void* wih, const void* whh, const float* sx, const float* sh, const float* bias,
                        void* hq_out, void* h16_out, void* ex, int T, int N, int H, int R, int n_rings, int reverse, int* err_flag,
                        hipStream_t stream, int* xcc_ws, int flags, int variant, int* dbg, unsigned max_spins);
-unsigned bh_k_lstm_max_spins();
 size_t bh_k_lstm_wgx_ex_bytes(int N, int H);
 int bh_k_lstm_layer_wgx(const void* x, const void* wih_tiles, const float* bias, const void* whh_tiles, void* h_out, void* ex, int T,
                         int N, int H, int R, int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow,

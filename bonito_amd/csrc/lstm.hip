@@ -35,6 +35,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "options.h"
 
 namespace bh {
 
@@ -1650,15 +1651,8 @@ __global__ void fill_u16_kernel(uint16_t* dst, uint16_t v, size_t count) {
 
 }  // namespace bh
 
-// Bound of every exchange spin loop (poll rounds). Process-wide; lowered by tests to provoke the timeout path.
-static unsigned g_max_spins = 1000000u;
-int bh_k_lstm_set_option(const char* name, int value) {
-    if (strcmp(name, "lstm_max_spins") != 0) return -1;
-    g_max_spins = value >= 0 ? (unsigned)value : 1000000u;     // 0: the first incomplete poll round is a timeout
-    return 0;
-}
-
-unsigned bh_k_lstm_max_spins() { return g_max_spins; }
+// Bound of every exchange spin loop (poll rounds): "lstm_max_spins" (options.h), lowered by tests to provoke the timeout path.
+static unsigned max_spins() { return (unsigned)bh::g_opt.lstm_max_spins; }
 
 size_t bh_k_lstm_packed_bytes(int H) { return (size_t)4 * H * H * 2; }
 size_t bh_k_lstm_ws_bytes(int N, int H) {
@@ -1723,7 +1717,7 @@ int bh_k_lstm_layer(const void* gates_in, const void* whh_packed, void* h_out, i
     int grid = 0;
     if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_WAVE, H), N, N / 16, n_rings, H / 16, xcc_ws, stream, &grid)) return rc;
     LstmArgs a{(const half_t*)gates_in, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings,
-               reverse, err_flag, g_max_spins, xcc_ws, force_slow & 1, force_slow >> 8};
+               reverse, err_flag, max_spins(), xcc_ws, force_slow & 1, force_slow >> 8};
 #define BH_LSTM_CASE(NKS) \
     case NKS: hipLaunchKernelGGL((lstm_layer_kernel<NKS, false>), dim3(grid), dim3(256), 0, stream, a); break;
     switch (H / 32) {
@@ -1744,7 +1738,7 @@ int bh_k_lstm_layer_stream(const void* gates_in, const void* whh_packed, void* h
     int grid = 0;
     if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_STREAM, H), N, N / 16, n_rings, H / 16, xcc_ws, stream, &grid)) return rc;
     LstmArgs a{(const half_t*)gates_in, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings,
-               reverse, err_flag, g_max_spins, xcc_ws, force_slow & 1, force_slow >> 8};
+               reverse, err_flag, max_spins(), xcc_ws, force_slow & 1, force_slow >> 8};
     switch (H / 32) {
         case 2: hipLaunchKernelGGL((lstm_layer_kernel<2, true>), dim3(grid), dim3(256), 0, stream, a); break;
         case 4: hipLaunchKernelGGL((lstm_layer_kernel<4, true>), dim3(grid), dim3(256), 0, stream, a); break;
@@ -1770,7 +1764,7 @@ int bh_k_lstm_layer_fused(const void* x, const void* wih_packed, const float* bi
     int grid = 0;
     if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_FUSED, H), N, N / 16, n_rings, H / 16, xcc_ws, stream, &grid)) return rc;
     LstmFusedArgs a{(const half_t*)x, (const half_t*)wih_packed, bias,
-                    LstmArgs{nullptr, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings, reverse, err_flag, g_max_spins,
+                    LstmArgs{nullptr, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings, reverse, err_flag, max_spins(),
                              xcc_ws, force_slow & 1, force_slow >> 8}};
     const size_t lds = (size_t)(H / 32) * 4096;
 #define BH_LSTM_CASE(NKS)                                                                                        \
@@ -1816,7 +1810,7 @@ int bh_k_lstm_layer_wgx(const void* x, const void* wih_packed, const float* bias
     if (arm) BH_CHECK_HIP(hipMemsetAsync(ex, 0xFF, (size_t)4 * R * nks * 1024, stream));
     LstmWgxArgs a{LstmFusedArgs{(const half_t*)x, (const half_t*)wih_packed, bias,
                                 LstmArgs{nullptr, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings, reverse, err_flag,
-                                         g_max_spins, xcc_ws, force_slow & 1, force_slow >> 8}},
+                                         max_spins(), xcc_ws, force_slow & 1, force_slow >> 8}},
                   (char*)ex, R};
     const size_t lds = (size_t)5 * nks * 1024 + 4 * 16 * U * 2;
 #define BH_LSTM_WGX(NKS, MT)                                                                                     \
@@ -1847,7 +1841,7 @@ int bh_k_lstm_layer_wgx2(const void* x, const void* wih_packed, const float* bia
     if (arm) BH_CHECK_HIP(hipMemsetAsync(ex, 0xFF, (size_t)4 * R * nks * 1024, stream));
     LstmWgxArgs a{LstmFusedArgs{(const half_t*)x, (const half_t*)wih_packed, bias,
                                 LstmArgs{nullptr, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings, reverse, err_flag,
-                                         g_max_spins, xcc_ws, force_slow & 1, force_slow >> 8}},
+                                         max_spins(), xcc_ws, force_slow & 1, force_slow >> 8}},
                   (char*)ex, R};
     const size_t lds = (size_t)8 * nks * 1024 + 4 * 16 * U * 2;
     if (nks == 12 && U == 12 && ((force_slow >> 8) & 4)) {          // lstm_tune bit 2: the instance with section stamps (tools/lstm_stats2.py)
@@ -1909,7 +1903,7 @@ int bh_k_lstm_layer_wide(const void* gates_perm, const void* whh_tiles, void* h_
     int grid = 0;
     if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_WIDE, H), N, N / 32, n_rings, H / 8, xcc_ws, stream, &grid)) return rc;
     LstmWideArgs a{(const half_t*)gates_perm,
-                   LstmArgs{nullptr, (const half_t*)whh_tiles, (half_t*)h_out, T, N, H, n_rings, reverse, err_flag, g_max_spins, xcc_ws,
+                   LstmArgs{nullptr, (const half_t*)whh_tiles, (half_t*)h_out, T, N, H, n_rings, reverse, err_flag, max_spins(), xcc_ws,
                             force_slow & 1, force_slow >> 8},
                    (char*)ex, R};
     const int nks = H / 32;

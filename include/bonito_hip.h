@@ -272,7 +272,9 @@ int bh_signal_chunks(const int16_t* raw, const long* offsets, const float* cal_s
 int bh_lstm_q8_layer(const void* x, float bound, const float* w_ih, const float* w_hh, const float* bias, int T, int N, int H,
                      int reverse, int variant, void* h16_out, int8_t* hq_frag, int32_t* sums, void* stream);
 
-/* Process-wide knobs (measurement / tuning hooks, no reference counterpart).
+/* Process-wide knobs (measurement / tuning hooks, no reference counterpart): the rows of the option table in csrc/options.cpp, every
+ * one described here (tests/test_abi.py holds the two lists to each other). Not thread-safe: set them while nothing else calls into
+ * the library. Values are stored as given unless a row says otherwise; an unknown name is an error.
  *   "beam_fork": -1 auto (default: where the scan is a kernel of its own - up to 64 states, and 1024 states, where the beam kernel
  *                is one wave per chunk), 0 = run the posterior scan behind the beam kernel on the caller's stream,
  *                1 = run it next to the beam kernel on an internal helper stream (joined before finalize).
@@ -283,19 +285,30 @@ int bh_lstm_q8_layer(const void* x, float bound, const float* w_ih, const float*
  *                chunks of the call be resident at once (5 / 6 / 8 chunks per CU; the kernels are latency chains, so chunks in
  *                flight per CU are what counts: 2048 x 1667 steps 12.0 -> 8.7 ms on MI355X); 1, 2, 4 force a geometry. Same bytes.
  *   "attn_waves": 0 (default) = automatic, 8 / 12 = waves per workgroup of the ring attention kernel (query blocks of 128 / 192; same results).
+ *   "attn_version": 2 (default) = the current ring attention kernel, 1 = the first ring kernel (any other value is stored as 2).
+ *   "attn_expt": bit mask of timing experiments of the ring attention kernel, for builds that compile them in. RESULTS ARE WRONG ON
+ *                PURPOSE for any value but 0 (the default): each bit removes a part of the kernel to time the rest.
  *   "beam_select": 0 (default) = top-W selection by histogram + exact boundary ranking, 1 = MSB-first radix search
  *                (the same beams either way; kept for regression tests and A/B timing).
+ *   "decode_nt": 0 (default) / 1 = the decode kernels read scores and guide rows with the non-temporal cache policy (they are read
+ *                once; keeps the L2 for the recurrent kernels when the decoder runs beside the next batch's encoder). Same bytes.
+ *   "viterbi_quad": 1 (default) = bh_crf_viterbi on its four-states-per-thread kernel where the layout allows, 0 = the one-state
+ *                kernel everywhere. Same bytes.
  *   "conv_ws": 1 (default) = weight-stationary kernel for the 384-channel / 19-tap convolution, 0 = generic implicit GEMM.
  *   "conv_fuse": 1 (default) = conv1 -> conv2 -> conv3 of a 384-channel LSTM stack as one kernel (intermediates in LDS), 2 = also
  *                for the 96-channel stacks, 0 = three kernels. "conv_fs": 1 (default) = feature-split instances of the implicit-GEMM
  *                kernel for layers with a multiple of 64 output channels, 0 = position-split. "conv_lds_kb": LDS a workgroup of that
- *                kernel may take for its input span (default 64). All of them: identical bytes (tests).
+ *                kernel may take for its input span (default 64; values <= 0 restore it). All of them: identical bytes (tests).
  *   "gemm_path": 0 auto (default), 1 = register-staged 128x128x64 kernel only, 2 = never a 256x256x64 kernel, 3 = never the
  *                four-wave kernel (gemm_w4_kernel; the eight-wave one where it applies), 5 = the four-wave kernel for every legal shape.
  *   "gemm_tile16": 1 (default) = the four-wave kernel's K-tile stream on 16x16x32 MFMAs with its epilogues in the accumulator layout,
  *                0 = the 32x32x16 stream of rounds 4-5 (results agree to fp16 rounding: another accumulation order).
  *                "gemm_order": 1 (default) = an XCD sweeps all feature groups of a block of token tiles before it moves on, 0 = token
- *                blocks fastest; "gemm_gf": feature tiles per block of that order (0 = automatic). Same bytes either way.
+ *                blocks fastest; "gemm_gf": feature tiles per block of that order: 0 = automatic, any other value is rounded down to
+ *                the nearest of 1 / 2 / 4 / 8 / 16 / 32 and to the number of feature tiles. Same bytes either way. ("gemm_tile16" and
+ *                "gemm_order" are stored as 0 / 1.)
+ *   "gemm_stagger": 0 (default) = off; n > 0 = the workgroups of an XCD start the persistent 256x256 kernels in eight phase groups,
+ *                n x 256 cycles apart in the four-wave kernel, n x ~1024 in the eight-wave one (measured without effect). Same bytes.
  *   "lstm_q8_variant": geometry of the 8-bit recurrent kernel chosen at bh_encoder_create: 0 (default) = 12 / 16 units per wave,
  *                one workgroup per CU; 1 = 4 units per wave, three workgroups per CU; 2 = 12 units per wave compiled for two
  *                workgroups per CU, so that the recurrent kernels of two engines (two batches in flight) share every CU and each

@@ -234,3 +234,23 @@ def test_profile_classes_of_the_binding_match_the_header():
     assert n == len(HipEncoder.PROF_CLASSES) == len(table)
     for i, cls in enumerate(HipEncoder.PROF_CLASSES):
         assert table[cls] == i, (cls, i, table)
+
+
+def test_option_table_header_and_library_agree():
+    """The process-wide knobs exist once, as the rows of csrc/options.cpp: every row is described (quoted) in the knob comment of
+    include/bonito_hip.h, that comment quotes nothing that is not a row, and bh_set_option takes every row's name with its default
+    and refuses a name that is no row."""
+    rows = re.findall(r"^\s*\{BH_OPT\((\w+)\),\s*(-?\d+),\s*Norm::\w+,\s*\"[^\"]+\"\},?\s*$",
+                      open(os.path.join(ROOT, "bonito_amd", "csrc", "options.cpp")).read(), flags=re.M)
+    names = [n for n, _ in rows]
+    assert len(names) >= 20 and len(set(names)) == len(names)
+    header = open(os.path.join(ROOT, "include", "bonito_hip.h")).read()
+    comment = header[header.index("/* Process-wide knobs"):header.index("int bh_set_option(")]
+    quoted = set(re.findall(r"\"(\w+)\"", comment))
+    assert set(names) - quoted == set(), "not described in the header's knob comment"
+    assert quoted - set(names) == set(), "quoted in the header's knob comment, but no row of the option table"
+    handle = _lib.lib()
+    for name, default in rows:
+        assert handle.bh_set_option(name.encode(), int(default)) == 0, name
+    assert handle.bh_set_option(b"no_such_option", 0) != 0
+    assert "unknown option 'no_such_option'" in _lib.last_error()

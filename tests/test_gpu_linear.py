@@ -204,6 +204,28 @@ def test_four_wave_fall_through_pairs_by_name():
     _run(Call(3 * 256, 256, 384, row=(256, 1, 3, 251)), 5, 1, expect=6)
 
 
+@pytest.mark.parametrize("gf", [1, 2, 3, 4, 5, 6, 8])
+def test_four_wave_gemm_gf_rounds_down_to_a_power_of_two(gf):
+    """ "gemm_gf" (feature tiles per block of the four-wave kernel's work order; eight feature tiles here, so 8 is not clamped): the kernel
+    takes a power of two, the launcher rounds a request down to one. Every value passes the whole check of `_run`, writes the bytes of
+    the default, and 3 / 5 / 6 write the bytes of 2 / 4 / 4."""
+    from bonito_amd import decode
+    c = Call(1007, 2048, 384, act=2, **S5)
+    t = lr.make_inputs(c, dev(), 11)
+    default, _ = _run(c, 5, 1, expect=6, inputs=t)
+    rounded = 1 << (gf.bit_length() - 1)
+    out = {}
+    try:
+        for g in sorted({gf, rounded}):
+            decode.set_option("gemm_gf", g)
+            out[g], _ = _run(c, 5, 1, expect=6, inputs=t)
+    finally:
+        decode.set_option("gemm_gf", 0)
+    for g in out:
+        assert torch.equal(out[g], default), "gemm_gf %d wrote other bytes than the default" % g
+    assert torch.equal(out[gf], out[rounded]), "gemm_gf %d wrote other bytes than %d" % (gf, rounded)
+
+
 ROT_TS = (1, 17, 255, 256, 300, 1667)
 
 

@@ -13,6 +13,8 @@ void bh_set_error(const char* fmt, ...) {
     va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr);
 }
 
+bh::Options bh::g_opt;      // (the library's instance is in options.cpp)
+
 // (the library's helpers of engine.cpp, restated for the stand-alone binary)
 hipError_t bh_max_lds(const void* fn, int bytes) { return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
 int bh_cu_count() {
@@ -39,11 +41,11 @@ int main(int argc, char** argv) {
         for (int i = 1; i + 3 < argc + 0; i += 4) shapes.push_back({atol(argv[i]), atoi(argv[i + 1]), atoi(argv[i + 2]), atoi(argv[i + 3])});
     }
     const int path = getenv("LAB_PATH") ? atoi(getenv("LAB_PATH")) : 0;
-    bh_k_linear_force_v1(path);
-    if (getenv("LAB_GF")) bh::g_w4_gf = atoi(getenv("LAB_GF"));
-    if (getenv("LAB_STAGGER")) bh_k_linear_stagger(atoi(getenv("LAB_STAGGER")));
-    if (getenv("LAB_ORDER")) bh_k_linear_order(atoi(getenv("LAB_ORDER")));
-    if (getenv("LAB_T16")) bh_k_linear_tile16(atoi(getenv("LAB_T16")));        // gemm_w4_kernel around the 16x16x32 K-tile stream
+    bh::g_opt.gemm_path = path;
+    if (getenv("LAB_GF")) bh::g_opt.gemm_gf = atoi(getenv("LAB_GF"));
+    if (getenv("LAB_STAGGER")) bh::g_opt.gemm_stagger = atoi(getenv("LAB_STAGGER"));
+    if (getenv("LAB_ORDER")) bh::g_opt.gemm_order = atoi(getenv("LAB_ORDER")) ? 1 : 0;
+    if (getenv("LAB_T16")) bh::g_opt.gemm_tile16 = atoi(getenv("LAB_T16")) ? 1 : 0;        // gemm_w4_kernel around the 16x16x32 K-tile stream
     const int reps = getenv("LAB_REPS") ? atoi(getenv("LAB_REPS")) : 40, warm = getenv("LAB_WARM") ? atoi(getenv("LAB_WARM")) : 25;
     unsigned long long* dbg = nullptr;
     hipMalloc((void**)&dbg, 16 * 8);
