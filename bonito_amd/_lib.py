@@ -101,11 +101,16 @@ SIGNATURES = {
     "bh_lstm_workspace": (_sz, [_i, _i]),
     "bh_lstm_layer": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "bh_lstm_q8_layer": (_i, [_vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "bh_lstm_layer_family": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "bh_encoder_debug_read": (_i, [_vp, _vp, _sz, _sz]),
     "bh_encoder_set_option": (_i, [_vp, C.c_char_p, _i]),
 }
 
 _lib = None
+
+
+# enum bh_lstm_family of include/bonito_hip.h (tests/test_abi.py keeps the two together)
+LSTM_FAMILIES = {"wave": 0, "fused": 1, "stream": 2, "wgx": 3, "wgx2": 4, "cta": 5, "wide": 6, "q8": 7}
 
 
 def lib():

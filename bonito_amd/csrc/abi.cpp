@@ -11,6 +11,7 @@
 #include "common.h"
 #include "devbuf.h"
 #include "kernels.h"
+#include "lstm_pack.h"
 #include "options.h"
 
 extern "C" size_t bh_conv1d_packed_halves(int Cin, int Cout, int K) {
@@ -199,6 +200,88 @@ extern "C" int bh_lstm_q8_layer(const void* x, float bound, const float* w_ih, c
     BH_CHECK_HIP(hipMemcpyAsync(&flag, err.p, sizeof(int), hipMemcpyDeviceToHost, st));
     BH_CHECK_HIP(hipStreamSynchronize(st));
     BH_REQUIRE(flag == 0, "lstm_q8_layer: exchange timeout in the recurrent kernel");
+    return 0;
+}
+// Operator level (parity tests): one fp16 recurrent layer on a chosen kernel family from fp32 host weights, packed by the functions
+// bh_encoder_create packs with (bh_lstm_pack_whh, lstm_pack.h) and launched once the way forward_lstm launches it.
+static bool lstm_family_serves(int family, int H) {
+    switch (family) {
+        case BH_LSTM_WAVE:
+        case BH_LSTM_FUSED: return H > 0 && H % 32 == 0 && H <= 512;
+        case BH_LSTM_STREAM: return bh_lstm_stream_ok(H);
+        case BH_LSTM_WGX:
+        case BH_LSTM_WGX2: return H > 0 && bh_k_lstm_wg_units(H) != 0;
+        case BH_LSTM_CTA: return H > 0 && bh_k_lstm_cta_units(H) != 0 && bh_k_lstm_cta_units(H) == bh_k_lstm_wg_units(H);
+        case BH_LSTM_WIDE: return bh_k_lstm_wide_ok(H) != 0;
+        default: return false;
+    }
+}
+extern "C" int bh_lstm_layer_family(const void* x, const float* w_ih, const float* w_hh, const float* bias, int T, int N, int H,
+                                    int reverse, int family, int flags, void* h_out, void* stream_) {
+    BH_REQUIRE(x && w_ih && w_hh && h_out && x != h_out, "lstm_layer_family: null pointer, or x and h_out are one buffer");
+    BH_REQUIRE(T > 0 && N > 0 && H > 0, "lstm_layer_family: T, N, H must be positive");
+    BH_REQUIRE(family >= BH_LSTM_WAVE && family < BH_LSTM_Q8, "lstm_layer_family: family %d is not an fp16 family (the 8-bit path: bh_lstm_q8_layer)", family);
+    BH_REQUIRE(lstm_family_serves(family, H), "lstm_layer_family: family %d has no instance for hidden size %d", family, H);
+    BH_REQUIRE((flags & ~(family == BH_LSTM_WIDE ? 3 : 1)) == 0, "lstm_layer_family: flags %d not understood by family %d", flags, family);
+    BH_REQUIRE(((uintptr_t)h_out & 15) == 0 && ((uintptr_t)x & 15) == 0, "lstm_layer_family: x and h_out must be 16-byte aligned");
+    const bh_lstm_family fam = (bh_lstm_family)family;
+    const bh_lstm_geometry geo = bh_k_lstm_geometry(fam, H);
+    BH_REQUIRE(N % geo.ring_chunks == 0, "lstm_layer_family: batch %d is no multiple of the family's ring of %d chunks", N, geo.ring_chunks);
+    const int R = N / geo.ring_chunks, per = geo.rings_per_launch(bh_cu_count());
+    BH_REQUIRE(R <= per, "lstm_layer_family: %d rings, one launch of family %d holds %d at hidden size %d", R, family, per, H);
+    hipStream_t st = (hipStream_t)stream_;
+    const bool gemm = fam == BH_LSTM_WAVE || fam == BH_LSTM_STREAM || fam == BH_LSTM_WIDE;
+    const bool tiles = fam == BH_LSTM_WGX || fam == BH_LSTM_WGX2 || fam == BH_LSTM_CTA;
+    const bool ring = fam == BH_LSTM_WGX || fam == BH_LSTM_WGX2 || (fam == BH_LSTM_WIDE && !(flags & 2));
+    const int slow = flags & 1;
+    const size_t nw = (size_t)4 * H * H;
+    DevBuf d_wih, d_whh, d_b, gates, ex, ws, err;
+    std::vector<uint16_t> pk(nw);
+    std::vector<float> b((size_t)4 * H, 0.0f);
+    if (bias) memcpy(b.data(), bias, sizeof(float) * 4 * H);
+    if (fam == BH_LSTM_WIDE) {
+        std::vector<float> wp(nw), bp((size_t)4 * H);
+        lstm_wide_permute(w_ih, bias, nullptr, H, H, wp.data(), bp.data());
+        if (upload_f16(d_wih, wp.data(), nw) || upload_f32(d_b, bp.data(), bp.size())) return -1;
+        if (lstm_pack_tiles(w_hh, H, LSTM_WIDE_MT, pk.data()) || upload(d_whh, pk.data(), nw * 2)) return -1;
+    } else {
+        if (upload_f32(d_b, b.data(), b.size())) return -1;
+        if (tiles) {
+            const int MT = bh_k_lstm_wg_units(H) / 4;
+            if (lstm_pack_tiles(w_ih, H, MT, pk.data()) || upload(d_wih, pk.data(), nw * 2)) return -1;
+            if (lstm_pack_tiles(w_hh, H, MT, pk.data()) || upload(d_whh, pk.data(), nw * 2)) return -1;
+        } else {
+            if (gemm) { if (upload_f16(d_wih, w_ih, nw)) return -1; }
+            else if (bh_lstm_pack_whh(w_ih, H, pk.data()) || upload(d_wih, pk.data(), nw * 2)) return -1;
+            if (bh_lstm_pack_whh(w_hh, H, pk.data()) || upload(d_whh, pk.data(), nw * 2)) return -1;
+        }
+    }
+    if (ws.alloc(bh_k_lstm_ws_bytes(N, 1024)) || err.alloc(sizeof(int))) return -1;
+    if (gemm && gates.alloc((size_t)T * N * 4 * H * 2 + 256)) return -1;
+    if (ring && ex.alloc((fam == BH_LSTM_WIDE ? bh_k_lstm_wide_ex_bytes(N, H) : bh_k_lstm_wgx_ex_bytes(N, H)) + 256)) return -1;
+    BH_CHECK_HIP(hipMemsetAsync(err.p, 0, sizeof(int), st));
+    int rc = 0;
+    if (gemm) rc = bh_k_linear(x, d_wih.p, (const float*)d_b.p, gates.p, T * N, 4 * H, H, H, H, 4 * H, bh::ACT_NONE, 1.0f, -INFINITY, INFINITY,
+                               0, 0, 0, 0, 0, st);
+    if (!rc && !ring && fam != BH_LSTM_CTA) rc = bh_k_fill_u16(h_out, 0xFFFFu, (size_t)T * N * H, st);      // hand-off through the output tensor
+    if (rc) return rc;
+    const float* bp = (const float*)d_b.p;
+    int* e = (int*)err.p;
+    int* w = (int*)ws.p;
+    switch (fam) {
+        case BH_LSTM_WAVE: rc = bh_k_lstm_layer(gates.p, d_whh.p, h_out, T, N, H, reverse, e, st, R, w, slow); break;
+        case BH_LSTM_STREAM: rc = bh_k_lstm_layer_stream(gates.p, d_whh.p, h_out, T, N, H, reverse, e, st, R, w, slow); break;
+        case BH_LSTM_FUSED: rc = bh_k_lstm_layer_fused(x, d_wih.p, bp, d_whh.p, h_out, T, N, H, reverse, e, st, R, w, slow); break;
+        case BH_LSTM_WGX: rc = bh_k_lstm_layer_wgx(x, d_wih.p, bp, d_whh.p, h_out, ex.p, T, N, H, R, reverse, e, st, R, w, slow, 1); break;
+        case BH_LSTM_WGX2: rc = bh_k_lstm_layer_wgx2(x, d_wih.p, bp, d_whh.p, h_out, ex.p, T, N, H, R, reverse, e, st, R, w, slow, 1); break;
+        case BH_LSTM_CTA: rc = bh_k_lstm_layer_cta(x, d_wih.p, bp, d_whh.p, h_out, T, N, H, reverse, st, R); break;
+        default: rc = bh_k_lstm_layer_wide(gates.p, d_whh.p, h_out, T, N, H, reverse, e, st, R, w, slow, ring ? ex.p : nullptr, R, 1);
+    }
+    if (rc) return rc;
+    int flag = 0;
+    BH_CHECK_HIP(hipMemcpyAsync(&flag, err.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    BH_CHECK_HIP(hipStreamSynchronize(st));
+    BH_REQUIRE(flag == 0, "lstm_layer_family: exchange timeout in the recurrent kernel");
     return 0;
 }
 extern "C" size_t bh_beam_search_workspace(int N, int T, int state_len) { return bh_k_beam_workspace(N, T, state_len); }

@@ -23,6 +23,7 @@
 #include "common.h"
 #include "devbuf.h"
 #include "kernels.h"
+#include "lstm_pack.h"
 #include "options.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -43,25 +44,6 @@ extern "C" int bh_device_count(void) {
         return -1;
     }
     return n;
-}
-
-// Tile packing for the workgroup-shared LSTM kernel: [slice][tile m][kstep][lane][8] with U = 4*MT units per slice;
-// row r of tile m is (unit slice*U + (r>>2)*MT + m, gate r&3), so the MFMA result leaves all four gate
-// pre-activations of MT consecutive units in one lane. w is [4H][H] in torch gate order (W_hh, or W_ih when
-// insize == H).
-static int lstm_pack_tiles(const float* w, int H, int MT, uint16_t* packed) {
-    const int U = 4 * MT, nks = H / 32, nsl = H / U;
-    for (int s = 0; s < nsl; ++s)
-        for (int m = 0; m < MT; ++m)
-            for (int ks = 0; ks < nks; ++ks)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int r = lane & 15;
-                        const int row = (r & 3) * H + s * U + (r >> 2) * MT + m;
-                        const int col = ks * 32 + (lane >> 4) * 8 + j;
-                        packed[((((size_t)s * MT + m) * nks + ks) * 64 + lane) * 8 + j] = f2h(w[(size_t)row * H + col]);
-                    }
-    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -388,7 +370,7 @@ static int create_lstm(bh_encoder* e, size_t i, const bh_layer_t& d, CreateState
     Layer& L = e->layers[i];
     const int H = d.out_size, I = d.in_size;
     BH_REQUIRE(d.w0 && d.w1 && H > 0 && I > 0, "encoder_create: layer %zu: malformed lstm", i);
-    const bool stream_ok = H % 64 == 0 && H <= 1024;
+    const bool stream_ok = bh_lstm_stream_ok(H);        // (kernels.h: read off the streaming kernel's instance list)
     BH_REQUIRE((lstm_regs_ok(H) || stream_ok) && I % 8 == 0,
                "encoder_create: layer %zu: lstm needs hidden %% 32 == 0 (<= 512) or %% 64 == 0 (<= 1024), insize %% 8 == 0 (got %d, %d)", i, H, I);
     int rc = upload_f16(L.w0, d.w0, (size_t)4 * H * I);
@@ -407,21 +389,12 @@ static int create_lstm(bh_encoder* e, size_t i, const bh_layer_t& d, CreateState
         rc = bh_lstm_pack_whh(d.w0, H, pk.data());
         if (!rc) rc = upload(L.w2, pk.data(), pk.size() * 2);
     }
-    if (!rc && lstm_may_wide(d)) {       // wide layer: W_hh tiles of 8 units + W_ih / bias with permuted rows, so that
-        const int MT = 2;                  // the GEMM writes G[t][n][(slice*4 + q)*8 + gate*2 + m]
+    if (!rc && lstm_may_wide(d)) {       // wide layer: W_hh tiles of 8 units + W_ih / bias with permuted rows (lstm_pack.h)
         std::vector<uint16_t> pk((size_t)4 * H * H);
-        rc = lstm_pack_tiles(d.w1, H, MT, pk.data());
+        rc = lstm_pack_tiles(d.w1, H, LSTM_WIDE_MT, pk.data());
         if (!rc) rc = upload(L.w3, pk.data(), pk.size() * 2);
         std::vector<float> wp((size_t)4 * H * I), bp((size_t)4 * H);
-        for (int s8 = 0; s8 < H / 8; ++s8)
-            for (int q = 0; q < 4; ++q)
-                for (int g = 0; g < 4; ++g)
-                    for (int m = 0; m < MT; ++m) {
-                        const size_t dst = (((size_t)s8 * 4 + q) * 4 + g) * MT + m;
-                        const size_t src = (size_t)g * H + s8 * 8 + q * MT + m;
-                        memcpy(&wp[dst * I], d.w0 + src * I, sizeof(float) * I);
-                        bp[dst] = (d.b0 ? d.b0[src] : 0.0f) + (d.b1 ? d.b1[src] : 0.0f);
-                    }
+        lstm_wide_permute(d.w0, d.b0, d.b1, H, I, wp.data(), bp.data());
         if (!rc) rc = upload_f16(L.w4, wp.data(), wp.size());
         if (!rc) rc = upload_f32(L.b1, bp.data(), bp.size());
         e->batch_pad = 32;

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/bonito_hip.h"      // enum bh_lstm_family
+
 // gemm.hip
 int bh_k_linear(const void* X, const void* W, const float* bias, void* out, int M, int N, int K,
                 int ldx, int ldw, int ldo, int act, float scale, float clamp_lo, float clamp_hi,
@@ -27,7 +29,7 @@ int bh_k_conv_igemm(const void* in, const void* wpk, const float* bias, void* ou
 // how many rings fit one launch. The workgroups of a launch spin on each other, so all of them must be resident at once; rings are
 // dealt to the 8 XCDs, hence the groups of 8. The launcher's grid and co-residency guard and every caller that splits a batch
 // (engine.cpp, abi.cpp) read it from here.
-enum bh_lstm_family { BH_LSTM_WAVE, BH_LSTM_FUSED, BH_LSTM_STREAM, BH_LSTM_WGX, BH_LSTM_WGX2, BH_LSTM_CTA, BH_LSTM_WIDE, BH_LSTM_Q8 };
+// (enum bh_lstm_family: include/bonito_hip.h)
 struct bh_lstm_geometry {
     int ring_chunks = 16;        // chunks per ring
     int wgs_per_group = 0;       // workgroups that serve 8 workgroup slots, one per XCD (0: the kernel does not cover H)
@@ -49,6 +51,16 @@ bh_lstm_geometry bh_k_lstm_geometry(bh_lstm_family family, int H);       // the 
 int bh_k_lstm_layer(const void* gates_in, const void* whh_packed, void* h_out, int T, int N, int H,
                     int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow);
 size_t bh_k_lstm_ws_bytes(int N, int H);
+// The streaming kernel's instances (H / 32; a workgroup serves four slices of 16 units, hence H % 64 == 0): the launcher's dispatch and
+// the predicate bh_encoder_create accepts widths by are both read off this list.
+#define BH_LSTM_STREAM_INSTANCES(X) X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18) X(20) X(22) X(24) X(26) X(28) X(30) X(32)
+static inline bool bh_lstm_stream_ok(int H) {
+    if (H <= 0 || H % 32 != 0) return false;
+#define BH_LSTM_STREAM_HAS(NKS) if (H / 32 == NKS) return true;
+    BH_LSTM_STREAM_INSTANCES(BH_LSTM_STREAM_HAS)
+#undef BH_LSTM_STREAM_HAS
+    return false;
+}
 int bh_k_lstm_layer_stream(const void* gates_in, const void* whh_packed, void* h_out, int T, int N, int H,
                            int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow);
 int bh_k_lstm_layer_fused(const void* x, const void* wih_packed, const float* bias, const void* whh_packed, void* h_out,

@@ -250,8 +250,14 @@ struct LstmFusedArgs {
 // VGPRs and serialise every LDS read behind its consumer. The compiler does not track MFMA hazards through
 // inline asm: callers keep >= 19 wait states between the last mfma16_a() and the first VALU read of `c`
 // (mfma_settle()) and never issue one directly after a VALU write of its operands.
+// GUARD: where the fragments and the accumulators do not all fit the 256 registers of that half (16 NKS + 16 >= 256: H = 480, 512)
+// the compiler parks fragments in VGPRs and copies them over (v_accvgpr_write) directly in front of the MFMA that reads them; a VALU
+// write needs two wait states before an MFMA reads the register and nothing inserts them around inline asm, so the MFMA brings its
+// own. (Without them H = 480 gave different bytes from run to run: tests/test_gpu_lstm.py, fused-480.)
+template <bool GUARD = false>
 __device__ __forceinline__ void mfma16_a(const half8_t& a_agpr, const half8_t& b, float4_t& c) {
-    asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "a"(a_agpr), "v"(b));
+    if constexpr (GUARD) asm("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "a"(a_agpr), "v"(b));
+    else asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "a"(a_agpr), "v"(b));
 }
 __device__ __forceinline__ void mfma_settle(float4_t& c0, float4_t& c1, float4_t& c2, float4_t& c3) {
     asm volatile("s_nop 15\n\ts_nop 7" : "+a"(c0), "+a"(c1), "+a"(c2), "+a"(c3));
@@ -406,7 +412,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_fused_kernel(LstmFusedArgs 
             for (int ks = 0; ks < NKS; ++ks) {
                 half8_t b = __builtin_bit_cast(half8_t, hf[ks]);
 #pragma unroll
-                for (int g = 0; g < 4; ++g) mfma16_a(w[g][ks], b, acc[g]);
+                for (int g = 0; g < 4; ++g) mfma16_a<(16 * NKS + 16 >= 256)>(w[g][ks], b, acc[g]);
             }
             mfma_settle(acc[0], acc[1], acc[2], acc[3]);
         }
@@ -1734,23 +1740,18 @@ int bh_k_lstm_layer(const void* gates_in, const void* whh_packed, void* h_out, i
 int bh_k_lstm_layer_stream(const void* gates_in, const void* whh_packed, void* h_out, int T, int N, int H,
                            int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow) {
     using namespace bh;
-    BH_REQUIRE(H % 64 == 0 && H >= 64 && H <= 1024, "lstm: streaming kernel needs H%%64==0, 64<=H<=1024 (H=%d)", H);
+    BH_REQUIRE(bh_lstm_stream_ok(H), "lstm: streaming kernel needs H%%64==0, 64<=H<=1024 (H=%d)", H);
     int grid = 0;
     if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_STREAM, H), N, N / 16, n_rings, H / 16, xcc_ws, stream, &grid)) return rc;
     LstmArgs a{(const half_t*)gates_in, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings,
                reverse, err_flag, max_spins(), xcc_ws, force_slow & 1, force_slow >> 8};
+#define BH_LSTM_CASE(NKS) \
+    case NKS: hipLaunchKernelGGL((lstm_layer_kernel<NKS, true>), dim3(grid), dim3(256), 0, stream, a); break;
     switch (H / 32) {
-        case 2: hipLaunchKernelGGL((lstm_layer_kernel<2, true>), dim3(grid), dim3(256), 0, stream, a); break;
-        case 4: hipLaunchKernelGGL((lstm_layer_kernel<4, true>), dim3(grid), dim3(256), 0, stream, a); break;
-        case 8: hipLaunchKernelGGL((lstm_layer_kernel<8, true>), dim3(grid), dim3(256), 0, stream, a); break;
-        case 12: hipLaunchKernelGGL((lstm_layer_kernel<12, true>), dim3(grid), dim3(256), 0, stream, a); break;
-        case 16: hipLaunchKernelGGL((lstm_layer_kernel<16, true>), dim3(grid), dim3(256), 0, stream, a); break;
-        case 20: hipLaunchKernelGGL((lstm_layer_kernel<20, true>), dim3(grid), dim3(256), 0, stream, a); break;
-        case 24: hipLaunchKernelGGL((lstm_layer_kernel<24, true>), dim3(grid), dim3(256), 0, stream, a); break;
-        case 28: hipLaunchKernelGGL((lstm_layer_kernel<28, true>), dim3(grid), dim3(256), 0, stream, a); break;
-        case 32: hipLaunchKernelGGL((lstm_layer_kernel<32, true>), dim3(grid), dim3(256), 0, stream, a); break;
+        BH_LSTM_STREAM_INSTANCES(BH_LSTM_CASE)
         default: BH_REQUIRE(false, "lstm: unsupported H=%d for the streaming kernel", H);
     }
+#undef BH_LSTM_CASE
     BH_CHECK_HIP(hipGetLastError());
     return 0;
 }

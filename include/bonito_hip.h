@@ -272,6 +272,27 @@ int bh_signal_chunks(const int16_t* raw, const long* offsets, const float* cal_s
 int bh_lstm_q8_layer(const void* x, float bound, const float* w_ih, const float* w_hh, const float* bias, int T, int N, int H,
                      int reverse, int variant, void* h16_out, int8_t* hq_frag, int32_t* sums, void* stream);
 
+/* The recurrent kernel families of csrc/lstm.hip (BH_LSTM_Q8: csrc/lstm_q8.hip). */
+enum bh_lstm_family {
+    BH_LSTM_WAVE = 0,    /* gate GEMM + one wave per 16 units, W_hh in registers: H % 32 == 0, H <= 512 */
+    BH_LSTM_FUSED = 1,   /* the same with the input projection inside the recurrence */
+    BH_LSTM_STREAM = 2,  /* gate GEMM + W_hh re-read every step: H % 64 == 0, H <= 1024 */
+    BH_LSTM_WGX = 3,     /* workgroup-shared, hand-off through a ring buffer: H = 64, 96, 128, 192, 256, 288, 384 */
+    BH_LSTM_WGX2 = 4,    /* the same, two rings per workgroup */
+    BH_LSTM_CTA = 5,     /* a ring in one workgroup: H = 64, 96, 128 */
+    BH_LSTM_WIDE = 6,    /* gate GEMM + stationary W_hh, rings of 32 chunks: H = 640, 768, 896, 1024 */
+    BH_LSTM_Q8 = 7       /* the 8-bit path (bh_lstm_q8_layer) */
+};
+/* Operator level (parity tests): one fp16 recurrent layer on a CHOSEN kernel family, straight from fp32 HOST weights W_ih, W_hh
+ * [4H][H] and bias [4H] (b_ih + b_hh, or NULL), packed as bh_encoder_create packs them. x: device fp16 [T][N][H]; h_out: device
+ * fp16 [T][N][H], 16-byte aligned. Allocates what the family needs (XCD workspace, the armed ring buffer, the sentinel fill of
+ * h_out, the gate tensor of the families that take a GEMM first), launches the family ONCE, synchronises and reads the timeout
+ * flag. flags bit 0: the placement-independent write-through exchange; bit 1 (BH_LSTM_WIDE only): the older hand-off through the
+ * output tensor, as "lstm_exchange" 0. Errors, never a substitute kernel: a family that has no instance for H, BH_LSTM_Q8, N that
+ * is no multiple of the family's ring (16 chunks; 32 for BH_LSTM_WIDE), more rings than one launch holds, an exchange timeout. */
+int bh_lstm_layer_family(const void* x, const float* w_ih, const float* w_hh, const float* bias, int T, int N, int H, int reverse,
+                         int family, int flags, void* h_out, void* stream);
+
 /* Process-wide knobs (measurement / tuning hooks, no reference counterpart): the rows of the option table in csrc/options.cpp, every
  * one described here (tests/test_abi.py holds the two lists to each other). Not thread-safe: set them while nothing else calls into
  * the library. Values are stored as given unless a row says otherwise; an unknown name is an error.

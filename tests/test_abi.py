@@ -254,3 +254,54 @@ def test_option_table_header_and_library_agree():
         assert handle.bh_set_option(name.encode(), int(default)) == 0, name
     assert handle.bh_set_option(b"no_such_option", 0) != 0
     assert "unknown option 'no_such_option'" in _lib.last_error()
+
+
+def test_lstm_family_enum_of_the_binding_matches_the_header():
+    text = open(os.path.join(ROOT, "include", "bonito_hip.h")).read()
+    enum = text[text.index("enum bh_lstm_family {"):]
+    enum = re.sub(r"/\*.*?\*/", "", enum[:enum.index("};")], flags=re.S)
+    table = {name.lower(): int(v) for name, v in re.findall(r"BH_LSTM_(\w+)\s*=\s*(\d+)", enum)}
+    assert table == _lib.LSTM_FAMILIES and sorted(table.values()) == list(range(8))
+    # the internal launchers use the same enumerators: there is no second definition
+    assert "enum bh_lstm_family {" not in open(os.path.join(ROOT, "bonito_amd", "csrc", "kernels.h")).read()
+
+
+def _family_call(family, H, T=3, N=32, flags=0, x=4096, w=True, h_out=8192):
+    import ctypes as C
+    import numpy as np
+    wt = np.zeros(4, np.float32)            # never read: every case below is refused by the argument checks in front of any device call
+    wp = wt.ctypes.data_as(C.c_void_p) if w else None
+    fam = _lib.LSTM_FAMILIES[family] if isinstance(family, str) else family
+    rc = _lib.lib().bh_lstm_layer_family(C.c_void_p(x), wp, wp, None, T, N, H, 0, fam, flags, C.c_void_p(h_out), None)
+    return rc, _lib.last_error()
+
+
+@pytest.mark.parametrize("family,H", [("wave", 544), ("wave", 48), ("fused", 1024), ("stream", 96), ("stream", 1088), ("wgx", 320), ("wgx", 32),
+                                      ("wgx2", 512), ("wgx2", 160), ("cta", 192), ("cta", 256), ("wide", 512), ("wide", 704), ("wide", 960),
+                                      ("wide", 1152)])
+def test_lstm_layer_family_refuses_a_width_without_an_instance(family, H):
+    rc, msg = _family_call(family, H)
+    assert rc != 0 and "has no instance for hidden size %d" % H in msg
+
+
+def test_lstm_layer_family_argument_checks():
+    for kw in (dict(x=0), dict(w=False), dict(h_out=0), dict(x=8192)):
+        rc, msg = _family_call("fused", 96, **kw)
+        assert rc != 0 and "null pointer, or x and h_out are one buffer" in msg, kw
+    for kw in (dict(T=0), dict(N=0), dict(N=-16)):
+        rc, msg = _family_call("fused", 96, **kw)
+        assert rc != 0 and "must be positive" in msg, kw
+    for fam in ("q8", -1, 8):
+        rc, msg = _family_call(fam, 96)
+        assert rc != 0 and "not an fp16 family" in msg, fam
+    for fam, N in (("fused", 24), ("wgx", 40), ("cta", 8), ("wide", 16), ("wide", 48)):      # rings of 16 chunks, 32 for the wide kernel
+        rc, msg = _family_call(fam, 1024 if fam == "wide" else 96, N=N)
+        assert rc != 0 and "no multiple of the family's ring" in msg, (fam, N)
+    for fam, flags in (("fused", 2), ("wgx", 3), ("wide", 4), ("cta", 8)):                    # bit 1 means something to the wide kernel only
+        rc, msg = _family_call(fam, 1024 if fam == "wide" else 96, flags=flags)
+        assert rc != 0 and "flags %d not understood" % flags in msg, (fam, flags)
+    rc, msg = _family_call("fused", 96, x=4100)
+    assert rc != 0 and "16-byte aligned" in msg
+    # more rings than one launch holds (32 at H = 512 on 256 CUs; 16 x 4096 chunks are too many for any device)
+    rc, msg = _family_call("wave", 512, N=16 * 4096)
+    assert rc != 0 and "one launch of family 0 holds" in msg
