@@ -75,6 +75,7 @@ SIGNATURES = {
     "bh_crf_posterior_viterbi": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "bh_beam_search_workspace": (_sz, [_i, _i, _i]),
     "bh_beam_search": (_i, [_vp, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bh_beam_search_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i]),
     "bh_linear": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _i, _l, _l, _i, _vp]),
     "bh_linear_residual": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _i, _l, _l, _i, _vp, _i, _f, _vp]),
     "bh_linear_qkv_rotary": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _f, _vp]),

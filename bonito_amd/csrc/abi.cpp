@@ -292,6 +292,9 @@ extern "C" int bh_beam_search(const void* scores, int N, int T, int state_len, i
     return bh_k_beam_search(scores, N, T, state_len, beam_width, beam_cut, blank_score, q_scale, q_offset, workspace,
                             sequence, qstring, moves, qfloat, (hipStream_t)stream);
 }
+extern "C" int bh_beam_search_plan(int N, int T, int state_len, int cu_count, int debug, int32_t* out, int n_out) {
+    return bh_k_beam_search_plan(N, T, state_len, cu_count, debug, out, n_out);
+}
 extern "C" int bh_crf_reverse_complement(const void* in, void* out, int N, int T, int state_len, int layout_5s,
                                          long stride_n, long stride_t, void* stream) {
     BH_REQUIRE(in && out, "crf_reverse_complement: null pointer");

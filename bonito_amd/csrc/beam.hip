@@ -1418,110 +1418,177 @@ __global__ __launch_bounds__(64) void beam_finalize_kernel(FinArgs p) {
 
 }  // namespace bh
 
-size_t bh_k_beam_workspace(int N, int T, int state_len) {
-    size_t S = 1;
-    for (int i = 0; i < state_len; ++i) S *= 4;
-    size_t b = 0;
-    b += (size_t)N * (T + 1) * S * sizeof(float) + 256;   // beta~
-    b += (size_t)N * (T + 1) * sizeof(double) + 256;      // Bcum
-    b += (size_t)N * sizeof(double) + 256;                // logZ
-    b += (size_t)N * T * 4 * sizeof(float) + 256;         // P
-    b += (size_t)N * T * 32 + 256;                        // bp
-    b += (size_t)N * sizeof(int) + 256;                   // final slot
-    b += (size_t)N * 8 * sizeof(long long) + 256;         // debug counters
-    return b;
-}
-
-// Log-semiring partition function (CTC_CRF.logZ, bonito/crf/model.py:47-52) on koi-layout scores: the
-// backward scan of the beam decoder already produces it. workspace: bh_k_beam_workspace bytes.
-int bh_k_crf_logz(const void* scores, int N, int T, int state_len, float blank, void* workspace, double* logz_out,
-                  hipStream_t stream) {
-    using namespace bh;
-    BH_REQUIRE(state_len >= 1 && state_len <= 5 && N > 0 && T > 0, "crf_logz: bad shape");
-    int S = 1;
-    for (int i = 0; i < state_len; ++i) S *= 4;
-    auto align = [](size_t x) { return (x + 255) / 256 * 256; };
-    char* w = (char*)workspace;
-    float* beta = (float*)w;   w += align((size_t)N * (T + 1) * S * sizeof(float));
-    double* Bcum = (double*)w;
-    ScanArgs sa{(const half_t*)scores, N, T, S, state_len, blank, beta, Bcum, logz_out, nullptr, bh::g_opt.decode_nt, 1};
-    {
-        int b_threads = 0;
-        size_t b_lds = 0;
-        backward_geometry(S, N, sa.cpb, b_threads, b_lds);
-        if (b_lds > 64 * 1024) BH_CHECK_HIP(bh_max_lds((const void*)crf_backward_kernel, (int)b_lds));
-        hipLaunchKernelGGL(crf_backward_kernel, dim3((N + sa.cpb - 1) / sa.cpb), dim3(b_threads), b_lds, stream, sa);
-        sa.cpb = 1;
-    }
-    BH_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-size_t bh_k_posterior_viterbi_workspace(int N, int T, int state_len) {
-    size_t S = 1;
-    for (int i = 0; i < state_len; ++i) S *= 4;
-    return bh_k_beam_workspace(N, T, state_len) + (size_t)N * T * S + 256;
-}
-
-int bh_k_posterior_viterbi(const void* scores, int N, int T, int state_len, float blank, void* workspace, int8_t* moves,
-                           int8_t* path, hipStream_t stream) {
-    using namespace bh;
-    BH_REQUIRE(state_len >= 1 && state_len <= 5 && N > 0 && T > 0, "posterior_viterbi: bad shape");
-    int S = 1;
-    for (int i = 0; i < state_len; ++i) S *= 4;
-    auto align = [](size_t x) { return (x + 255) / 256 * 256; };
-    char* w = (char*)workspace;
-    float* beta = (float*)w;   w += align((size_t)N * (T + 1) * S * sizeof(float));
-    double* Bcum = (double*)w; w += align((size_t)N * (T + 1) * sizeof(double));
-    double* logZ = (double*)w;
-    uint8_t* bp = (uint8_t*)workspace + bh_k_beam_workspace(N, T, state_len);
-    ScanArgs sa{(const half_t*)scores, N, T, S, state_len, blank, beta, Bcum, logZ, nullptr, bh::g_opt.decode_nt, 1};
-    const int threads = S < 64 ? 64 : S;
-    {
-        int b_threads = 0;
-        size_t b_lds = 0;
-        backward_geometry(S, N, sa.cpb, b_threads, b_lds);
-        if (b_lds > 64 * 1024) BH_CHECK_HIP(bh_max_lds((const void*)crf_backward_kernel, (int)b_lds));
-        hipLaunchKernelGGL(crf_backward_kernel, dim3((N + sa.cpb - 1) / sa.cpb), dim3(b_threads), b_lds, stream, sa);
-        sa.cpb = 1;
-    }
-    PostVitArgs pa{sa, bp, moves, path};
-    int TB = (32 * 1024) / S; if (TB > 512) TB = 512; if (TB < 1) TB = 1;
-    const size_t lds_pv = (size_t)(BH_LSE_TABLE_SIZE + 2 + 4 * S + 4) * sizeof(float) + (size_t)TB * S + 2 * TB + 32;
-    hipLaunchKernelGGL(crf_posterior_viterbi_kernel, dim3(N), dim3(threads), lds_pv, stream, pa);
-    BH_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
+// ================================================================================================================================
+// Host side. Each of these is stated once and only read by the entry points below: where the regions of the workspace lie
+// (decode_workspace), which instance of which kernel a beam search launches with what geometry (the instance lists and beam_plan),
+// and how the Log-semiring backward scan is launched (launch_crf_backward).
 namespace {
-// One helper stream + fork/join events per (device, host thread): bh_beam_search is re-entrant per thread, and a decode
-// worker thread drives one device.
+using namespace bh;
+
+size_t n_states(int state_len) {
+    size_t S = 1;
+    for (int i = 0; i < state_len; ++i) S *= 4;
+    return S;
+}
+
+// ---- workspace ---------------------------------------------------------------------------------------------------------------------
+// One layout for bh_beam_search, bh_crf_logz and bh_crf_posterior_viterbi: a call uses the regions it needs (the beam search no longer
+// reads Bcum and logZ; the Log-semiring scans use beta~, Bcum and logZ). A region starts at the next multiple of 256 behind the one
+// before it. The totals are what callers allocate by: they count 256 bytes of slack per region, which is never less than the rounding.
+struct DecodeWorkspace {
+    size_t beta, Bcum, logZ, P, bp, fin, dbg;     // byte offsets of the regions
+    size_t pv_bp;                                 // posterior Viterbi's back-pointer plane [N][T][S]: behind the beam search's total
+    size_t beam_total, pv_total;                  // bh_k_beam_workspace, bh_k_posterior_viterbi_workspace
+};
+DecodeWorkspace decode_workspace(int N, int T, int state_len) {
+    const size_t S = n_states(state_len);
+    DecodeWorkspace w{};
+    const struct { size_t* offset; size_t bytes; } regions[] = {
+        {&w.beta, (size_t)N * (T + 1) * S * sizeof(float)},      // beta~ / the linear guide b [N][T+1][S]
+        {&w.Bcum, (size_t)N * (T + 1) * sizeof(double)},         // Bcum [N][T+1]
+        {&w.logZ, (size_t)N * sizeof(double)},                   // logZ [N]
+        {&w.P, (size_t)N * T * 4 * sizeof(float)},               // class posteriors P [N][T][4]
+        {&w.bp, (size_t)N * T * 32},                             // beam back-pointers [N][T][32]
+        {&w.fin, (size_t)N * sizeof(int)},                       // final slot [N]
+        {&w.dbg, (size_t)N * 8 * sizeof(long long)},             // BH_BEAM_DEBUG counters [N][8]
+    };
+    size_t at = 0;
+    for (const auto& r : regions) {
+        *r.offset = at;
+        at += (r.bytes + 255) / 256 * 256;
+        w.beam_total += r.bytes + 256;
+    }
+    w.pv_bp = w.beam_total;
+    w.pv_total = w.beam_total + (size_t)N * T * S + 256;
+    return w;
+}
+
+// ---- the Log-semiring backward scan (bh_crf_logz, posterior Viterbi) ---------------------------------------------------------------
+// (takes its own copy of the arguments: the chunks per workgroup that backward_geometry sets are this launch's alone)
+int launch_crf_backward(ScanArgs sa, hipStream_t stream) {
+    int threads = 0;
+    size_t lds = 0;
+    backward_geometry(sa.S, sa.N, sa.cpb, threads, lds);
+    if (lds > 64 * 1024) BH_CHECK_HIP(bh_max_lds((const void*)crf_backward_kernel, (int)lds));
+    hipLaunchKernelGGL(crf_backward_kernel, dim3((sa.N + sa.cpb - 1) / sa.cpb), dim3(threads), lds, stream, sa);
+    return 0;
+}
+
+// ---- the kernels of a beam search: instance lists ----------------------------------------------------------------------------------
+// An instance is a row: what the plan looks it up by, chunks per workgroup, threads and dynamic LDS of a workgroup - taken from the
+// constants the kernel itself is compiled with - and the kernel. The lists are in the order the kernels are instantiated in.
+template <class Args>
+struct Instance { int key, cpb, block, lds; void (*kernel)(Args); };
+struct Launch { int instance, grid, block, lds; };     // instance: index into the kernel's list, -1 = none
+
+#define BS2_BACKWARD_INSTANCES(X) X(1) X(2) X(3) X(4) X(5)      // X(STATE_LEN)
+#define BS2_FORWARD_INSTANCES(X) X(1) X(2) X(3) X(4) X(5)       // X(STATE_LEN)
+// X(STATE_LEN, CPW, DBG, FUSE): fused with the posterior scan up to 256 states - at 256 states one, two or four chunks per workgroup,
+// the latter two without the debug counters - and every state length unfused.
+#define BEAM_INSTANCES(X)                                                                                                        \
+    X(4, 4, false, true) X(4, 2, false, true)                                                                                    \
+    X(1, 4, false, true) X(1, 4, true, true) X(2, 4, false, true) X(2, 4, true, true) X(3, 4, false, true) X(3, 4, true, true)   \
+    X(4, 1, false, true) X(4, 1, true, true)                                                                                     \
+    X(1, 4, false, false) X(1, 4, true, false) X(2, 4, false, false) X(2, 4, true, false) X(3, 4, false, false)                  \
+    X(3, 4, true, false) X(4, 1, false, false) X(4, 1, true, false) X(5, 1, false, false) X(5, 1, true, false)
+constexpr int beam_key(int state_len, int cpw, bool dbg, bool fuse) { return state_len * 100 + cpw * 10 + (dbg ? 2 : 0) + (fuse ? 1 : 0); }
+
+const Instance<Bs2Args> bs2_backward_instances[] = {
+#define BS2_ROW(SL) {SL, Bs2Geo<SL>::CPB, Bs2Geo<SL>::UPB * Bs2Geo<SL>::UT, Bs2Geo<SL>::UPB * Bs2Geo<SL>::UNIT_LDS, bs2_backward_kernel<SL>},
+    BS2_BACKWARD_INSTANCES(BS2_ROW)
+#undef BS2_ROW
+};
+const Instance<Bs2FwdArgs> bs2_forward_instances[] = {
+#define BS2_ROW(SL) {SL, Bs2FwdGeo<SL>::CPB, Bs2FwdGeo<SL>::CPB * Bs2FwdGeo<SL>::TPC, Bs2FwdGeo<SL>::CPB * Bs2FwdGeo<SL>::CHUNK_LDS, bs2_forward_post_kernel<SL>},
+    BS2_FORWARD_INSTANCES(BS2_ROW)
+#undef BS2_ROW
+};
+const Instance<BeamArgs> beam_instances[] = {
+#define BEAM_ROW(SL, CPW, DBG, FUSE)                                                                                             \
+    {beam_key(SL, CPW, DBG, FUSE), CPW, 64 * (CPW + beam_scan_waves<SL, CPW, FUSE>()),                                           \
+     BEAM_TAB_LDS + CPW * (beam_wave_lds<SL>() + (FUSE ? scan_wave_lds<SL>() : 0)), beam_kernel<SL, CPW, DBG, FUSE>},
+    BEAM_INSTANCES(BEAM_ROW)
+#undef BEAM_ROW
+};
+
+template <class Args, size_t n>
+Launch launch_of(const Instance<Args> (&rows)[n], int key, int N) {
+    for (size_t i = 0; i < n; ++i)
+        if (rows[i].key == key) return Launch{(int)i, (N + rows[i].cpb - 1) / rows[i].cpb, rows[i].block, rows[i].lds};
+    return Launch{-1, 0, 0, 0};
+}
+template <class Args, size_t n>
+int launch_instance(const Instance<Args> (&rows)[n], const Launch& l, hipStream_t stream, const Args& args) {
+    const auto kernel = rows[l.instance].kernel;
+    if (l.lds > 64 * 1024) BH_CHECK_HIP(bh_max_lds((const void*)kernel, l.lds));
+    hipLaunchKernelGGL(kernel, dim3(l.grid), dim3(l.block), l.lds, stream, args);
+    return 0;
+}
+
+// ---- the plan of a beam search -----------------------------------------------------------------------------------------------------
+// The backward scan (the guide), then the forward / posterior scan and the beam kernel, which both depend only on it, then finalize.
+struct BeamPlan {
+    Launch backward;                // bs2_backward_kernel<state_len>
+    bool has_forward;               // the forward / posterior scan as a kernel of its own: bs2_forward_post_kernel<state_len> ...
+    Launch forward;
+    bool forward_on_helper;         // ... ASKED to run beside the beam kernel on the helper stream (side_stream() may have none)
+    int cpw;                        // beam_kernel<state_len, cpw, debug, fuse>
+    bool debug, fuse;
+    Launch beam;
+    bool select_radix;              // BeamArgs::inv_bin = 0
+    int nt;                         // Bs2Args / Bs2FwdArgs / BeamArgs::nt
+};
+// Pure: shape, options, whether BH_BEAM_DEBUG is set and the CU count in, the launches out. The rules, as the options of bh::g_opt
+// (options.h) reach them - known behaviour, quirks included:
+//  * "beam_fuse" (-1 auto, 0 never, 1 always): the scan runs as a second wave of the beam kernel's workgroups, sharing the staged score
+//    / guide blocks, when the option is not 0 AND there are at most 256 states: the scan wave owns four states per lane, and one scan
+//    wave keeps up with the beam wave only up to there (1024 states: 16 states per lane make the beam wave wait, sup-LSTM 256 x 3334
+//    decode 18 -> 36 ms). So "always" does not fuse 1024 states either.
+//  * "beam_cpw" (0 automatic, 1, 2, 4): chunks (waves) per workgroup of the FUSED kernel at 256 states; ignored everywhere else. The
+//    decode kernels are chains of dependent LDS round trips, ballots and scalar branches - ~5.5 k cycles per time step of a chunk
+//    whatever else runs - so what counts is how many chunks a CU works on AT ONCE, and whether the call fits ONE round of resident
+//    workgroups. The 16 KiB lse table is shared by the chunks of a workgroup and a chunk's own LDS is 14.1 KiB (one-step staging
+//    blocks, BTB = 1): one chunk per workgroup = five chunks per CU, two = six, four = eight (two workgroups of 72.5 KiB). MI355X,
+//    2048 x 1667 steps at 256 states, decode stage alone: 12.97 ms (BTB 2, one per workgroup: four per CU, two rounds) -> 12.00 (BTB 1,
+//    five per CU) -> 8.72 ms (BTB 1, four per workgroup: eight per CU, one round). Automatic = the smallest of 1 / 2 / 4 that lets the
+//    call's chunks be resident together: 1 up to 5 chunks per CU, 2 up to 6, else 4. Two and four have instances only without the debug
+//    counters: any other value (3 included), and any value with BH_BEAM_DEBUG set, means 1.
+//  * Everywhere else the chunks per workgroup are fixed, measured on MI355X next to the encoder of the same model: four below 256 states
+//    (fast-sized models, three lanes: 1.20e9 -> 1.26e9 samples/s); one for unfused 256 states - two waves per workgroup there cost the
+//    hac pipeline 6 % - and for 1024 states.
+//  * "beam_fork" (-1 auto, 0 never, 1 always) applies only where the scan is a kernel of its own: it then runs BESIDE the beam kernel
+//    on a per-device helper stream, forked from and joined back into the caller's stream with events. MI355X, 512 x 1667 steps: forking
+//    shortens the decode stage 8.3 -> 6.7 ms (S = 64) / 11.3 -> 9.3 ms (S = 256). Where the decoder is the pipeline bottleneck
+//    (fast-sized models) that is a net win (10.0 -> 9.4 ms per step); next to the latency-bound LSTM of a hac-sized model the denser
+//    decode burst costs the encoder more than it saves (24.4-25.0 -> 25.3-25.5 ms per step), so auto forks up to 64 states - and at
+//    1024 states, where the beam kernel is one wave per chunk on an otherwise idle CU (256-chunk batches: decode 9.9 -> 7.5 ms of the
+//    transformer sup model with its step unchanged at 67.7 ms, 17.5 -> 13.5 ms of the LSTM sup model, step 112.7 -> 111.0).
+//  * "beam_select": 0 histogram top-W selection, 1 radix search (A/B and regression tests). "decode_nt": passed through.
+BeamPlan beam_plan(int state_len, int N, const Options& opt, bool debug, int cus) {
+    const size_t S = n_states(state_len);
+    BeamPlan p{};
+    p.fuse = opt.beam_fuse != 0 && S <= 256;
+    p.debug = debug;
+    p.cpw = state_len <= 3 ? 4 : 1;
+    if (p.fuse && state_len == 4) {
+        int cpw = opt.beam_cpw;
+        if (cpw <= 0) cpw = (long)N <= 5l * cus ? 1 : (long)N <= 6l * cus ? 2 : 4;
+        if (!debug && (cpw == 2 || cpw == 4)) p.cpw = cpw;
+    }
+    p.backward = launch_of(bs2_backward_instances, state_len, N);
+    p.has_forward = !p.fuse;
+    p.forward = p.has_forward ? launch_of(bs2_forward_instances, state_len, N) : Launch{-1, 0, 0, 0};
+    p.forward_on_helper = p.has_forward && (opt.beam_fork > 0 || (opt.beam_fork < 0 && (S <= 64 || S >= 1024)));
+    p.beam = launch_of(beam_instances, beam_key(state_len, p.cpw, debug, p.fuse), N);
+    p.select_radix = opt.beam_select != 0;
+    p.nt = opt.decode_nt;
+    return p;
+}
+
+// One helper stream + fork/join events per (device, host thread): bh_beam_search is re-entrant per thread, and a decode worker thread
+// drives one device. Null where they cannot be had: the call then runs unforked.
 struct SideStream { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
-// bh::g_opt (options.h), as this file reads it:
-// beam_select: 0 histogram top-W selection, 1 radix search (A/B and regression tests)
-// beam_fork: -1 auto (fork for small state spaces), 0 never, 1 always; bh_set_option("beam_fork", v)
-// beam_cpw: chunks per workgroup of the fused beam kernel at 256 states ("beam_cpw": 0 = automatic, 1, 2, 4). The decode
-                           // kernels are chains of dependent LDS round trips, ballots and scalar branches - ~5.5 k cycles per time step
-                           // of a chunk whatever else runs - so what counts is how many chunks a CU works on AT ONCE, and whether the
-                           // call fits ONE round of resident workgroups. The 16 KiB lse table is shared by the chunks of a workgroup
-                           // and a chunk's own LDS is 14.1 KiB (one-step staging blocks, BTB = 1): one chunk per workgroup = five
-                           // chunks per CU, two = six, four = eight (two workgroups of 72.5 KiB). Round 5, MI355X, 2048 x 1667 steps
-                           // at 256 states, decode stage alone: 12.97 ms (BTB 2, one per workgroup: four per CU, two rounds) ->
-                           // 12.00 (BTB 1, five per CU) -> 8.72 ms (BTB 1, four per workgroup: eight per CU, one round). Round 3 had
-                           // tried two and three per workgroup with BTB 2 (3.71 / 3.56 / 3.63 ms per batch) and read the flat result
-                           // as "instruction bound": those geometries still needed two rounds. Automatic = the smallest of 1 / 2 / 4
-                           // that lets the call's chunks be resident together.
-// beam_fuse: forward / posterior scan as a second wave of the beam kernel's workgroups: -1 auto (<= 256 states: one
-                           // scan wave keeps up with the beam wave; at 1024 states its 16 states per lane make the beam wave wait:
-                           // sup-LSTM 256 x 3334 decode 18 -> 36 ms), 0 never (own kernel), 1 always
-SideStream* side_stream(int S) {
-    // Measured (MI355X, 512 x 1667 steps): forking shortens the decode stage 8.3 -> 6.7 ms (S=64) / 11.3 -> 9.3 ms (S=256).
-    // Where the decoder is the pipeline bottleneck (fast-sized models) that is a net win (10.0 -> 9.4 ms per step); next to
-    // the latency-bound LSTM of a hac-sized model the denser decode burst costs the encoder more than it saves (24.4-25.0 ->
-    // 25.3-25.5 ms per step), so auto mode forks for S <= 64 - and for 1024 states, where the scan is not a wave of the beam
-    // kernel and that kernel is one wave per chunk on an otherwise idle CU (round 4, 256-chunk batches: decode 9.9 -> 7.5 ms of
-    // the transformer sup model with its step unchanged at 67.7 ms, 17.5 -> 13.5 ms of the LSTM sup model, step 112.7 -> 111.0).
-    if (bh::g_opt.beam_fork == 0 || (bh::g_opt.beam_fork < 0 && S > 64 && S < 1024)) return nullptr;
+SideStream* side_stream() {
     thread_local SideStream per_dev[16];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
@@ -1535,127 +1602,103 @@ SideStream* side_stream(int S) {
 }
 }  // namespace
 
+size_t bh_k_beam_workspace(int N, int T, int state_len) { return decode_workspace(N, T, state_len).beam_total; }
+size_t bh_k_posterior_viterbi_workspace(int N, int T, int state_len) { return decode_workspace(N, T, state_len).pv_total; }
+
+// Log-semiring partition function (CTC_CRF.logZ, bonito/crf/model.py:47-52) on koi-layout scores: the Log-semiring backward scan
+// produces it. workspace: bh_k_beam_workspace bytes.
+int bh_k_crf_logz(const void* scores, int N, int T, int state_len, float blank, void* workspace, double* logz_out,
+                  hipStream_t stream) {
+    BH_REQUIRE(state_len >= 1 && state_len <= 5 && N > 0 && T > 0, "crf_logz: bad shape");
+    const DecodeWorkspace w = decode_workspace(N, T, state_len);
+    char* ws = (char*)workspace;
+    ScanArgs sa{(const half_t*)scores, N, T, (int)n_states(state_len), state_len, blank, (float*)(ws + w.beta), (double*)(ws + w.Bcum),
+                logz_out, nullptr, bh::g_opt.decode_nt, 1};
+    if (int rc = launch_crf_backward(sa, stream)) return rc;
+    BH_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int bh_k_posterior_viterbi(const void* scores, int N, int T, int state_len, float blank, void* workspace, int8_t* moves,
+                           int8_t* path, hipStream_t stream) {
+    BH_REQUIRE(state_len >= 1 && state_len <= 5 && N > 0 && T > 0, "posterior_viterbi: bad shape");
+    const int S = (int)n_states(state_len);
+    const DecodeWorkspace w = decode_workspace(N, T, state_len);
+    char* ws = (char*)workspace;
+    ScanArgs sa{(const half_t*)scores, N, T, S, state_len, blank, (float*)(ws + w.beta), (double*)(ws + w.Bcum), (double*)(ws + w.logZ),
+                nullptr, bh::g_opt.decode_nt, 1};
+    if (int rc = launch_crf_backward(sa, stream)) return rc;
+    PostVitArgs pa{sa, (uint8_t*)(ws + w.pv_bp), moves, path};
+    pa.sc.cpb = 1;      // one chunk per workgroup here, whatever the backward scan packed
+    const int threads = S < 64 ? 64 : S;
+    int TB = (32 * 1024) / S; if (TB > 512) TB = 512; if (TB < 1) TB = 1;
+    const size_t lds_pv = (size_t)(BH_LSE_TABLE_SIZE + 2 + 4 * S + 4) * sizeof(float) + (size_t)TB * S + 2 * TB + 32;
+    hipLaunchKernelGGL(crf_posterior_viterbi_kernel, dim3(N), dim3(threads), lds_pv, stream, pa);
+    BH_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 int bh_k_beam_search(const void* scores, int N, int T, int state_len, int beam_width, float beam_cut,
                      float blank, float q_scale, float q_offset, void* workspace, int8_t* sequence,
                      int8_t* qstring, int8_t* moves, float* qfloat, hipStream_t stream) {
-    using namespace bh;
     BH_REQUIRE(state_len >= 1 && state_len <= 5, "beam_search: state_len must be in 1..5 (got %d)", state_len);
     BH_REQUIRE(N > 0 && T > 0, "beam_search: empty problem N=%d T=%d", N, T);
     BH_REQUIRE(beam_width >= 1 && beam_width <= 32, "beam_search: beam_width must be in 1..32 (got %d)", beam_width);
     BH_REQUIRE(beam_cut >= 1.0f, "beam_search: beam_cut must be >= 1");
     BH_REQUIRE(T < (1 << 17), "beam_search: at most 131071 steps per chunk (got %d)", T);
-    int S = 1;
-    for (int i = 0; i < state_len; ++i) S *= 4;
-    auto align = [](size_t x) { return (x + 255) / 256 * 256; };
-    char* w = (char*)workspace;
-    float* beta = (float*)w;   w += align((size_t)N * (T + 1) * S * sizeof(float));
-    w += align((size_t)N * (T + 1) * sizeof(double));      // (B_t and logZ of the Log-semiring scans: bh_crf_logz / posterior Viterbi share
-    w += align((size_t)N * sizeof(double));                //  this workspace layout; the beam search no longer needs them)
-    float* P = (float*)w;      w += align((size_t)N * T * 4 * sizeof(float));
-    uint8_t* bp = (uint8_t*)w; w += align((size_t)N * T * 32);
-    int* fin = (int*)w;         w += align((size_t)N * sizeof(int));
-    long long* dbg = getenv("BH_BEAM_DEBUG") ? (long long*)w : nullptr;
+    const DecodeWorkspace w = decode_workspace(N, T, state_len);
+    char* ws = (char*)workspace;
+    float* beta = (float*)(ws + w.beta);
+    float* P = (float*)(ws + w.P);
+    uint8_t* bp = (uint8_t*)(ws + w.bp);
+    int* fin = (int*)(ws + w.fin);
+    const bool debug = getenv("BH_BEAM_DEBUG") != nullptr;
+    const BeamPlan p = beam_plan(state_len, N, bh::g_opt, debug, bh_cu_count());
+    BH_REQUIRE(p.backward.instance >= 0 && (!p.has_forward || p.forward.instance >= 0) && p.beam.instance >= 0,
+               "beam_search: no kernel instance for state_len %d, %d chunks per workgroup", state_len, p.cpw);
 
-    const bool fuse = bh::g_opt.beam_fuse != 0 && S <= 256;      // (the scan wave owns four states per lane: up to 256 states)
-    // ---- guide: linear-domain backward scan (BS-2) -------------------------------------------------------------------------------
-    {
-        Bs2Args a2{(const half_t*)scores, beta, N, T, blank, bh::g_opt.decode_nt};
-        auto launch_bwd = [&](auto kern, int cpb, size_t lds, int threads) -> int {
-            if (lds > 64 * 1024) BH_CHECK_HIP(bh_max_lds((const void*)kern, (int)lds));
-            hipLaunchKernelGGL(kern, dim3((N + cpb - 1) / cpb), dim3(threads), lds, stream, a2);
-            return 0;
-        };
-        int rc = -2;
-        switch (state_len) {
-            case 1: rc = launch_bwd(bs2_backward_kernel<1>, Bs2Geo<1>::CPB, (size_t)Bs2Geo<1>::UPB * Bs2Geo<1>::UNIT_LDS, Bs2Geo<1>::UPB * Bs2Geo<1>::UT); break;
-            case 2: rc = launch_bwd(bs2_backward_kernel<2>, Bs2Geo<2>::CPB, (size_t)Bs2Geo<2>::UPB * Bs2Geo<2>::UNIT_LDS, Bs2Geo<2>::UPB * Bs2Geo<2>::UT); break;
-            case 3: rc = launch_bwd(bs2_backward_kernel<3>, Bs2Geo<3>::CPB, (size_t)Bs2Geo<3>::UPB * Bs2Geo<3>::UNIT_LDS, Bs2Geo<3>::UPB * Bs2Geo<3>::UT); break;
-            case 4: rc = launch_bwd(bs2_backward_kernel<4>, Bs2Geo<4>::CPB, (size_t)Bs2Geo<4>::UPB * Bs2Geo<4>::UNIT_LDS, Bs2Geo<4>::UPB * Bs2Geo<4>::UT); break;
-            case 5: rc = launch_bwd(bs2_backward_kernel<5>, Bs2Geo<5>::CPB, (size_t)Bs2Geo<5>::UPB * Bs2Geo<5>::UNIT_LDS, Bs2Geo<5>::UPB * Bs2Geo<5>::UT); break;
-        }
-        if (rc) return rc;
-    }
-    // The forward / posterior scan and the beam kernel both depend only on the backward scan. Default for <= 256 states: the scan runs as
-    // a second wave inside the beam kernel's workgroups (FUSE), sharing the staged score / guide blocks. Otherwise ("beam_fuse" 0, 1024
-    // states) it is a kernel of its own, and with "beam_fork" it runs BESIDE the beam kernel on a per-device helper stream, forked from
-    // and joined back into the caller's stream with events.
-    SideStream* side = fuse ? nullptr : side_stream(S);
-    const bool fork = side != nullptr;
-    if (fork) {
+    Bs2Args a2{(const half_t*)scores, beta, N, T, blank, p.nt};
+    if (int rc = launch_instance(bs2_backward_instances, p.backward, stream, a2)) return rc;
+    SideStream* side = p.forward_on_helper ? side_stream() : nullptr;
+    if (side) {
         BH_CHECK_HIP(hipEventRecord(side->fork, stream));
         BH_CHECK_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
     }
-    if (!fuse) {
-        Bs2FwdArgs f2{(const half_t*)scores, beta, P, N, T, blank, bh::g_opt.decode_nt};
-        hipStream_t fs = fork ? side->stream : stream;
-        auto launch_fwd = [&](auto kern, int cpb, size_t chunk_lds) -> int {
-            const size_t lds = (size_t)cpb * chunk_lds;
-            if (lds > 64 * 1024) BH_CHECK_HIP(bh_max_lds((const void*)kern, (int)lds));
-            hipLaunchKernelGGL(kern, dim3((N + cpb - 1) / cpb), dim3(256), lds, fs, f2);
-            return 0;
-        };
-        int rc = -2;
-        switch (state_len) {
-            case 1: rc = launch_fwd(bs2_forward_post_kernel<1>, Bs2FwdGeo<1>::CPB, Bs2FwdGeo<1>::CHUNK_LDS); break;
-            case 2: rc = launch_fwd(bs2_forward_post_kernel<2>, Bs2FwdGeo<2>::CPB, Bs2FwdGeo<2>::CHUNK_LDS); break;
-            case 3: rc = launch_fwd(bs2_forward_post_kernel<3>, Bs2FwdGeo<3>::CPB, Bs2FwdGeo<3>::CHUNK_LDS); break;
-            case 4: rc = launch_fwd(bs2_forward_post_kernel<4>, Bs2FwdGeo<4>::CPB, Bs2FwdGeo<4>::CHUNK_LDS); break;
-            case 5: rc = launch_fwd(bs2_forward_post_kernel<5>, Bs2FwdGeo<5>::CPB, Bs2FwdGeo<5>::CHUNK_LDS); break;
-        }
-        if (rc) return rc;
+    if (p.has_forward) {
+        Bs2FwdArgs f2{(const half_t*)scores, beta, P, N, T, blank, p.nt};
+        if (int rc = launch_instance(bs2_forward_instances, p.forward, side ? side->stream : stream, f2)) return rc;
     }
-    if (fork) BH_CHECK_HIP(hipEventRecord(side->join, side->stream));
-    BeamArgs ba{(const half_t*)scores, beta, N, T, S, state_len, beam_width, blank, logf(beam_cut), bp, fin, dbg,
-                bh::g_opt.beam_select ? 0.0f : 256.0f / fmaxf(logf(beam_cut), 1e-6f), P, bh::g_opt.decode_nt};
-    // Chunks (waves) per workgroup, measured on MI355X next to the encoder of the same model: four for the narrow state
-    // spaces (fast-sized models, three lanes: 1.20e9 -> 1.26e9 samples/s); one for 256 states - two waves per workgroup
-    // there cost the hac pipeline 6 % (the 78 KiB workgroups find room beside the recurrent layer's workgroups later).
-    auto launch_beam = [&](auto kern, int cpw, size_t wave_lds, size_t scan_lds = 0) -> int {
-        const size_t lds_beam = (size_t)BEAM_TAB_LDS + cpw * (wave_lds + scan_lds);
-        if (lds_beam > 64 * 1024)
-            BH_CHECK_HIP(bh_max_lds((const void*)kern, (int)lds_beam));
-        hipLaunchKernelGGL(kern, dim3((N + cpw - 1) / cpw), dim3(64 * (cpw + (!scan_lds ? 0 : S >= 256 ? cpw : 1))), lds_beam, stream, ba);
-        return 0;
-    };
-    int lrc = -2;
-    int cpw4 = bh::g_opt.beam_cpw;           // chunks per workgroup at 256 states
-    if (fuse && state_len == 4 && cpw4 <= 0) {
-        const long cus = bh_cu_count();
-        cpw4 = (long)N <= 5 * cus ? 1 : (long)N <= 6 * cus ? 2 : 4;
-    }
-    if (false) {
-    } else if (fuse && state_len == 4 && !dbg && cpw4 == 4) {
-        lrc = launch_beam(beam_kernel<4, 4, false, true>, 4, beam_wave_lds<4>(), scan_wave_lds<4>());
-    } else if (fuse && state_len == 4 && !dbg && cpw4 == 2) {
-        lrc = launch_beam(beam_kernel<4, 2, false, true>, 2, beam_wave_lds<4>(), scan_wave_lds<4>());
-    } else if (fuse) {
-        switch (state_len * 2 + (dbg ? 1 : 0)) {
-            case 2: lrc = launch_beam(beam_kernel<1, 4, false, true>, 4, beam_wave_lds<1>(), scan_wave_lds<1>()); break;
-            case 3: lrc = launch_beam(beam_kernel<1, 4, true, true>, 4, beam_wave_lds<1>(), scan_wave_lds<1>()); break;
-            case 4: lrc = launch_beam(beam_kernel<2, 4, false, true>, 4, beam_wave_lds<2>(), scan_wave_lds<2>()); break;
-            case 5: lrc = launch_beam(beam_kernel<2, 4, true, true>, 4, beam_wave_lds<2>(), scan_wave_lds<2>()); break;
-            case 6: lrc = launch_beam(beam_kernel<3, 4, false, true>, 4, beam_wave_lds<3>(), scan_wave_lds<3>()); break;
-            case 7: lrc = launch_beam(beam_kernel<3, 4, true, true>, 4, beam_wave_lds<3>(), scan_wave_lds<3>()); break;
-            case 8: lrc = launch_beam(beam_kernel<4, 1, false, true>, 1, beam_wave_lds<4>(), scan_wave_lds<4>()); break;
-            case 9: lrc = launch_beam(beam_kernel<4, 1, true, true>, 1, beam_wave_lds<4>(), scan_wave_lds<4>()); break;
-        }
-    } else
-    switch (state_len * 2 + (dbg ? 1 : 0)) {
-        case 2: lrc = launch_beam(beam_kernel<1, 4, false>, 4, beam_wave_lds<1>()); break;
-        case 3: lrc = launch_beam(beam_kernel<1, 4, true>, 4, beam_wave_lds<1>()); break;
-        case 4: lrc = launch_beam(beam_kernel<2, 4, false>, 4, beam_wave_lds<2>()); break;
-        case 5: lrc = launch_beam(beam_kernel<2, 4, true>, 4, beam_wave_lds<2>()); break;
-        case 6: lrc = launch_beam(beam_kernel<3, 4, false>, 4, beam_wave_lds<3>()); break;
-        case 7: lrc = launch_beam(beam_kernel<3, 4, true>, 4, beam_wave_lds<3>()); break;
-        case 8: lrc = launch_beam(beam_kernel<4, 1, false>, 1, beam_wave_lds<4>()); break;
-        case 9: lrc = launch_beam(beam_kernel<4, 1, true>, 1, beam_wave_lds<4>()); break;
-        case 10: lrc = launch_beam(beam_kernel<5, 1, false>, 1, beam_wave_lds<5>()); break;
-        case 11: lrc = launch_beam(beam_kernel<5, 1, true>, 1, beam_wave_lds<5>()); break;
-    }
-    if (lrc) return lrc;
-    if (fork) BH_CHECK_HIP(hipStreamWaitEvent(stream, side->join, 0));
+    if (side) BH_CHECK_HIP(hipEventRecord(side->join, side->stream));
+    BeamArgs ba{(const half_t*)scores, beta, N, T, (int)n_states(state_len), state_len, beam_width, blank, logf(beam_cut), bp, fin,
+                debug ? (long long*)(ws + w.dbg) : nullptr, p.select_radix ? 0.0f : 256.0f / fmaxf(logf(beam_cut), 1e-6f), P, p.nt};
+    if (int rc = launch_instance(beam_instances, p.beam, stream, ba)) return rc;
+    if (side) BH_CHECK_HIP(hipStreamWaitEvent(stream, side->join, 0));
     FinArgs fa{bp, fin, P, N, T, q_scale, q_offset, sequence, qstring, moves, qfloat};
     hipLaunchKernelGGL(beam_finalize_kernel, dim3(N), dim3(64), 0, stream, fa);
     BH_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// TEST HOOK (bh_beam_search_plan): what bh_k_beam_search would launch, and the three calls carve, for this shape under the current
+// options, as integers. No device call.
+int bh_k_beam_search_plan(int N, int T, int state_len, int cu_count, int debug, int32_t* out, int n_out) {
+    BH_REQUIRE(state_len >= 1 && state_len <= 5, "beam_search_plan: state_len must be in 1..5 (got %d)", state_len);
+    BH_REQUIRE(N > 0 && T > 0 && out, "beam_search_plan: empty problem N=%d T=%d, or no record", N, T);
+    const BeamPlan p = beam_plan(state_len, N, bh::g_opt, debug != 0, cu_count);
+    const DecodeWorkspace w = decode_workspace(N, T, state_len);
+    const int32_t plan[] = {bs2_backward_instances[p.backward.instance].key, p.backward.grid, p.backward.block, p.backward.lds,
+                            p.has_forward, p.has_forward ? bs2_forward_instances[p.forward.instance].key : 0, p.forward.grid,
+                            p.forward.block, p.forward.lds, p.forward_on_helper,
+                            state_len, p.cpw, p.debug, p.fuse, p.beam.grid, p.beam.block, p.beam.lds, p.select_radix, p.nt};
+    const size_t layout[] = {w.beta, w.Bcum, w.logZ, w.P, w.bp, w.fin, w.dbg, w.pv_bp, w.beam_total, w.pv_total};
+    constexpr int n_plan = sizeof(plan) / sizeof(plan[0]), n_layout = sizeof(layout) / sizeof(layout[0]);
+    static_assert(n_plan + 2 * n_layout == BH_BEAM_PLAN_RECORD, "include/bonito_hip.h states the record's length");
+    BH_REQUIRE(n_out >= BH_BEAM_PLAN_RECORD, "beam_search_plan: the record takes %d integers (room for %d)", BH_BEAM_PLAN_RECORD, n_out);
+    BH_REQUIRE(p.beam.instance >= 0, "beam_search_plan: no beam_kernel instance");
+    memcpy(out, plan, sizeof(plan));
+    for (int i = 0; i < n_layout; ++i) {
+        out[n_plan + 2 * i] = (int32_t)(uint32_t)layout[i];
+        out[n_plan + 2 * i + 1] = (int32_t)(layout[i] >> 32);
+    }
     return 0;
 }

@@ -95,8 +95,15 @@ int bh_k_sw_align(const void* seqs, long seq_stride, const int* seq_lens, const 
                   int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace, size_t workspace_bytes,
                   int* result, unsigned* ops, long ops_stride, int* n_ops, hipStream_t stream);
 
-// beam.hip
-size_t bh_k_beam_workspace(int N, int T, int state_len);
+// beam.hip: the decode stage on koi-layout scores. The three calls share ONE workspace layout (decode_workspace); a beam search's
+// launches - backward scan, forward / posterior scan (fused into the beam kernel or not, on the helper stream or not), beam kernel
+// instance, selection - are decided by ONE pure function of shape, options and CU count (beam_plan), which the entry point executes.
+size_t bh_k_beam_workspace(int N, int T, int state_len);                    // bh_k_beam_search and bh_k_crf_logz
+size_t bh_k_posterior_viterbi_workspace(int N, int T, int state_len);       // the same regions + the posterior back-pointer plane
+int bh_k_posterior_viterbi(const void* scores, int N, int T, int state_len, float blank, void* workspace, int8_t* moves,
+                           int8_t* path, hipStream_t stream);
+// test hook: beam_plan and the layout for this shape under the current options, as BH_BEAM_PLAN_RECORD integers (include/bonito_hip.h lists them); no device call
+int bh_k_beam_search_plan(int N, int T, int state_len, int cu_count, int debug, int32_t* out, int n_out);
 int bh_k_crf_logz(const void* scores, int N, int T, int state_len, float blank, void* workspace, double* logz_out,
                    hipStream_t stream);
 int bh_k_beam_search(const void* scores, int N, int T, int state_len, int beam_width, float beam_cut,
@@ -119,9 +126,6 @@ int bh_k_ctc_greedy(const float* logp, const long* offs, int R, int C, float qsc
 size_t bh_k_ctc_beam_workspace(long total_steps, int R, int C, int beam_size);
 int bh_k_ctc_prefix_beam(const float* logp, const long* offs, int R, int C, int beam_size, float threshold, void* workspace,
                          int8_t* labels, int* path, int* count, hipStream_t stream);
-size_t bh_k_posterior_viterbi_workspace(int N, int T, int state_len);
-int bh_k_posterior_viterbi(const void* scores, int N, int T, int state_len, float blank, void* workspace, int8_t* moves,
-                           int8_t* path, hipStream_t stream);
 // conv1 -> conv2 -> conv3 of an LSTM model's front end in one kernel (conv_front3_kernel); _ok: does the shape qualify?
 int bh_k_conv_front3_ok(int c1_eff, int K1, int s1, int c2_in_eff, int c2_eff, int K2, int s2, int c3_in_eff, int c3_out, int K3, int s3);
 int bh_k_conv_front3(const void* signal, int N, int L0, const float* w1, const float* b1, int K1, int pad1, int act1, float lo1, float hi1,

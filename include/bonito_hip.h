@@ -357,6 +357,19 @@ size_t bh_beam_search_workspace(int N, int T, int state_len);
 int bh_beam_search(const void* scores, int N, int T, int state_len, int beam_width, float beam_cut,
                    float blank_score, float q_scale, float q_offset, void* workspace, int8_t* sequence,
                    int8_t* qstring, int8_t* moves, float* qfloat, void* stream);
+/* TEST HOOK: what bh_beam_search would launch, and bh_beam_search / bh_crf_logz / bh_crf_posterior_viterbi carve out of their
+ * workspace, for (N, T, state_len) under the current bh_set_option values, on a device of cu_count compute units, with (debug != 0)
+ * or without the BH_BEAM_DEBUG counters. Touches no device. Writes BH_BEAM_PLAN_RECORD integers (n_out = room in out):
+ *   0..3    backward scan of the beam search: state_len of the instance, grid, block, dynamic LDS bytes
+ *   4..9    forward / posterior scan as a kernel of its own: present, state_len, grid, block, LDS bytes, asked onto the helper stream
+ *           (all 0 where the scan is a wave of the beam kernel)
+ *   10..16  beam kernel: its template arguments state_len, chunks per workgroup, debug, fused; grid, block, LDS bytes
+ *   17, 18  selection by radix search ("beam_select"), non-temporal staging ("decode_nt")
+ *   19..38  the workspace layout, each value as (low, high) 32-bit halves: byte offsets of beta~, Bcum, logZ, P, the beam back-pointers,
+ *           the final slots, the debug counters and the posterior-Viterbi back-pointer plane, then bh_beam_search_workspace and
+ *           bh_crf_posterior_viterbi_workspace. */
+enum { BH_BEAM_PLAN_RECORD = 39 };
+int bh_beam_search_plan(int N, int T, int state_len, int cu_count, int debug, int32_t* out, int n_out);
 
 /* ---- operator level (parity tests, custom pipelines) ----------------------------------------- */
 /* out[m][n] = clamp(act(X[m][:] . W[n][:] + bias[n]) * scale); fp16 X [M][ldx], W [N][ldw], out [.][ldo].

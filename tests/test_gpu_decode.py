@@ -389,3 +389,51 @@ def test_fused_and_separate_posterior_scan_agree(state_len):
             assert torch.equal(o[0], outs[3][0]) and torch.equal(o[2], outs[3][2]), (N, T)
             assert (o[3] - outs[3][3]).abs().max().item() < 1e-4
             assert (o[1] != outs[3][1]).float().mean().item() < 1e-3
+
+
+@pytest.mark.parametrize("state_len", [1, 2, 3, 4, 5])
+def test_decode_calls_stay_inside_the_workspace_they_ask_for(state_len):
+    """bh_beam_search, bh_crf_posterior_viterbi and bh_crf_logz through the C ABI on a workspace of exactly bh_beam_search_workspace /
+    bh_crf_posterior_viterbi_workspace bytes with 4 KiB of 0xA5 on either side: the guards stay as they were (the three calls carve
+    one layout, whose regions must end inside the totals callers allocate by), and the outputs are those of the Python entry points."""
+    from bonito_amd import _lib
+    lib = _lib.lib()
+    GUARD = 4096
+    rng = np.random.default_rng(700 + state_len)
+    st = _lib.stream_ptr("cuda:0")
+
+    def guarded(nbytes):
+        buf = torch.full((nbytes + 2 * GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
+        return buf, buf.data_ptr() + GUARD
+
+    def guards_intact(buf):
+        torch.cuda.synchronize()
+        return bool((buf[:GUARD] == 0xA5).all()) and bool((buf[-GUARD:] == 0xA5).all())
+
+    for N, T in ((3, 7), (5, 33)):
+        sc = torch.from_numpy(_scores(rng, N, T, 4 ** (state_len + 1), "normal")).cuda()
+        beam_bytes = lib.bh_beam_search_workspace(N, T, state_len)
+        pv_bytes = lib.bh_crf_posterior_viterbi_workspace(N, T, state_len)
+
+        buf, ws = guarded(beam_bytes)
+        out = torch.zeros((3, N, T), dtype=torch.int8, device="cuda")
+        qf = torch.zeros((N, T), dtype=torch.float32, device="cuda")
+        _lib.check(lib.bh_beam_search(_lib.ptr(sc), N, T, state_len, 32, 100.0, 2.0, 1.0, 0.0, ws, _lib.ptr(out[0]), _lib.ptr(out[1]),
+                                      _lib.ptr(out[2]), _lib.ptr(qf), st), "bh_beam_search")
+        assert guards_intact(buf), ("bh_beam_search", N, T)
+        for got, want in zip((out[0], out[1], out[2], qf), decode.beam_search(sc, return_qfloat=True)):
+            assert torch.equal(got.cpu(), want), ("bh_beam_search", N, T)
+
+        buf, ws = guarded(pv_bytes)
+        mp = torch.zeros((2, N, T), dtype=torch.int8, device="cuda")
+        _lib.check(lib.bh_crf_posterior_viterbi(_lib.ptr(sc), N, T, state_len, 2.0, ws, _lib.ptr(mp[0]), _lib.ptr(mp[1]), st),
+                   "bh_crf_posterior_viterbi")
+        assert guards_intact(buf), ("bh_crf_posterior_viterbi", N, T)
+        for got, want in zip((mp[0], mp[1]), decode.posterior_viterbi(sc)):
+            assert torch.equal(got.cpu(), want), ("bh_crf_posterior_viterbi", N, T)
+
+        buf, ws = guarded(beam_bytes)
+        lz = torch.zeros(N, dtype=torch.float64, device="cuda")
+        _lib.check(lib.bh_crf_logz(_lib.ptr(sc), N, T, state_len, 2.0, ws, _lib.ptr(lz), st), "bh_crf_logz")
+        assert guards_intact(buf), ("bh_crf_logz", N, T)
+        assert torch.equal(lz.cpu(), decode.logz(sc)), ("bh_crf_logz", N, T)
