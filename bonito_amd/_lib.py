@@ -84,6 +84,9 @@ SIGNATURES = {
     "bh_conv1d_packed_halves": (_sz, [_i, _i, _i]),
     "bh_conv1d_pack": (_i, [_vp, _i, _i, _i, _vp]),
     "bh_conv1d": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _l, _l, _vp]),
+    "bh_conv1d_front3": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _i, _i, _i, _i, _i, _f, _f,
+                              _vp, _l, _l, _vp]),
+    "bh_conv1d_last_kernel": (_i, []),
     "bh_ctc_greedy_decode": (_i, [_vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "bh_ctc_beam_search_workspace": (_sz, [_l, _i, _i, _i]),
     "bh_ctc_beam_search": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
@@ -108,6 +111,14 @@ SIGNATURES = {
 }
 
 _lib = None
+
+
+# enum bh_conv_kernel of include/bonito_hip.h (tests/test_abi.py keeps the two together); conv_igemm_kernel<NTT, FS> is igemm(NTT, FS)
+CONV_KERNELS = {"none": 0, "first": 1, "ws_384": 20, "ws_96": 21, "front3_384": 30, "front3_96": 31, "dwconv": 40, "igemm_base": 100}
+
+
+def conv_igemm_code(ntt, fs):
+    return CONV_KERNELS["igemm_base"] + 10 * ntt + int(fs)
 
 
 # enum bh_lstm_family of include/bonito_hip.h (tests/test_abi.py keeps the two together)

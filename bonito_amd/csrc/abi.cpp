@@ -90,6 +90,21 @@ extern "C" int bh_conv1d(const void* in, const void* wpacked, const float* bias,
     return bh_k_conv_igemm(in, wpacked, bias, out, N, Lin, lout, Cin, Cout, K, stride, pad, act, clamp_lo, clamp_hi,
                            os_n, os_t, (hipStream_t)stream);
 }
+extern "C" int bh_conv1d_front3(const void* signal, int N, int L0, const float* w1, const float* b1, int K1, int pad1, int act1, float lo1,
+                                float hi1, const void* w2packed, const float* b2, int K2, int pad2, int act2, float lo2, float hi2,
+                                const void* w3packed, const float* b3, int Cout3, int K3, int stride3, int pad3, int act3, float lo3,
+                                float hi3, void* out, long os_n, long os_t, void* stream) {
+    BH_REQUIRE(signal && w1 && w2packed && w3packed && out && stride3 > 0 && N > 0, "conv1d_front3: bad arguments");
+    BH_REQUIRE(bh_k_conv_front3_shape_ok(K1, K2, Cout3, K3, stride3),
+               "conv1d_front3: the fused front end has no instance for K1=%d K2=%d Cout3=%d K3=%d stride3=%d", K1, K2, Cout3, K3, stride3);
+    const int l1 = conv_out_len(L0, K1, 1, pad1);
+    const int l2 = l1 > 0 ? conv_out_len(l1, K2, 1, pad2) : 0;
+    const int l3 = l2 > 0 && l2 + 2 * pad3 >= K3 ? conv_out_len(l2, K3, stride3, pad3) : 0;
+    BH_REQUIRE(l1 > 0 && l2 > 0 && l3 > 0, "conv1d_front3: input too short");
+    return bh_k_conv_front3(signal, N, L0, w1, b1, K1, pad1, act1, lo1, hi1, w2packed, b2, K2, pad2, act2, lo2, hi2, w3packed, b3, Cout3,
+                            K3, stride3, pad3, act3, lo3, hi3, out, os_n, os_t, (hipStream_t)stream);
+}
+extern "C" int bh_conv1d_last_kernel(void) { return bh_k_conv_last_kernel(); }
 // cos/sin of position * 10000^(-2i/dim), interleaved [T][dim/2][2], fp32 products like flash_attn's rotary
 extern "C" int bh_rotary_table(int T, int dim, float* out) {
     BH_REQUIRE(out && T > 0 && dim > 0 && dim % 2 == 0, "rotary_table: bad arguments");

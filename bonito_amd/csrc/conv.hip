@@ -311,7 +311,7 @@ struct ConvFront3Args {
     const half_t* sig;     // [N][L0]
     const float* w1;       // [16][K1]
     const float* b1;       // [16]
-    const half_t* w2pk;    // [16][Kp2 = 96]
+    const half_t* w2pk;    // [16][Kp2], Kp2 = K2 * 16 rounded up to 32 (<= 96), as bh_conv1d_pack lays it out
     const float* b2;       // [16]
     int L0, L1, L2;        // lengths: signal, conv1 output, conv2 output
     int K1, pad1, act1;
@@ -340,9 +340,15 @@ __global__ __launch_bounds__(64 * WAVES) void conv_front3_kernel(ConvFront3Args 
 
     // conv2's three weight fragments and bias (conv3's 120 registers of fragments are fetched behind the front phase: held across it they
     // pushed the kernel to the register limit)
+    // (the packer pads a row to Kp2 = K2 * 16 rounded up to 32 halves: 96 for the models' K2 = 5, 32 / 64 for K2 <= 4, whose missing
+    // k-steps are zero fragments here - they add exact zeros to the accumulator, the bytes stay those of conv_igemm_kernel's one or two steps)
+    const int kp2 = ((q.K2 * 16 + 31) >> 5) << 5;
     half8_t a2[3];
 #pragma unroll
-    for (int ks = 0; ks < 3; ++ks) a2[ks] = *(const half8_t*)(q.w2pk + (long)r * 96 + kg * 8 + ks * 32);
+    for (int ks = 0; ks < 3; ++ks) {
+        a2[ks] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+        if (ks * 32 < kp2) a2[ks] = *(const half8_t*)(q.w2pk + (long)r * kp2 + kg * 8 + ks * 32);
+    }
     float b2v[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) b2v[g] = q.b2 ? q.b2[kg * 4 + g] : 0.0f;
@@ -527,6 +533,11 @@ __global__ __launch_bounds__(64 * WAVES) void conv_front3_kernel(ConvFront3Args 
 
 }  // namespace bh
 
+// bh_k_conv_last_kernel (test hook, not thread-safe): the bh_conv_kernel code of the last convolution launch of this process
+static int g_conv_last_kernel = 0;
+void bh_k_conv_note_kernel(int code) { g_conv_last_kernel = code; }
+int bh_k_conv_last_kernel() { return g_conv_last_kernel; }
+
 int bh_k_conv_first(const void* signal, const float* w, const float* bias, void* out, int N, int Lin,
                     int Lout, int Cout, int K, int stride, int pad, int act, float clamp_lo,
                     float clamp_hi, long os_n, long os_t, hipStream_t stream) {
@@ -538,6 +549,7 @@ int bh_k_conv_first(const void* signal, const float* w, const float* bias, void*
     size_t lds = (size_t)(Cout * K + Cout + 255 * stride + K) * sizeof(float);
     hipLaunchKernelGGL(conv_first_kernel, dim3((Lout + 255) / 256, N), dim3(256), lds, stream, a);
     BH_CHECK_HIP(hipGetLastError());
+    g_conv_last_kernel = BH_CONV_K_FIRST;
     return 0;
 }
 
@@ -558,12 +570,14 @@ int bh_k_conv_igemm(const void* in, const void* wpk, const float* bias, void* ou
     ConvArgs a{(const half_t*)in, (const half_t*)wpk, bias, (half_t*)out, N, Lin, Lout, Cin, Cout, K,
                stride, pad, act, ((K * Cin + 31) / 32) * 32, clamp_lo, clamp_hi, os_n, os_t};
     auto lds_for = [&](int pw) { return (size_t)(((4 * pw - 1) * stride + K) * Cin + 40) * 2 + 16; };
-    // wide output layer with the k-step count of the bonito conv3 (19 taps x 16 channels): weight-stationary kernel
-    if (bh::g_opt.conv_ws && (Cout == 384 || Cout == 96) && a.Kp == 320 && lds_for(64) <= 64 * 1024) {
+    // wide output layer with the k-step count of the bonito conv3 (19 taps x 16 channels): weight-stationary kernel. It loads four
+    // biases at a time (float4), so a bias that is not 16-byte aligned goes to the generic kernel, which reads them one by one
+    if (bh::g_opt.conv_ws && (Cout == 384 || Cout == 96) && a.Kp == 320 && lds_for(64) <= 64 * 1024 && ((uintptr_t)bias & 15) == 0) {
         const dim3 wgrid((Lout + 255) / 256, N);
         if (Cout == 384) hipLaunchKernelGGL((conv_ws_kernel<3, 10, 8>), wgrid, dim3(512), lds_for(64), stream, a);
         else hipLaunchKernelGGL((conv_ws_kernel<1, 10, 6>), wgrid, dim3(384), lds_for(64), stream, a);
         BH_CHECK_HIP(hipGetLastError());
+        g_conv_last_kernel = Cout == 384 ? BH_CONV_K_WS_384 : BH_CONV_K_WS_96;
         return 0;
     }
     int pw = 64;
@@ -590,24 +604,39 @@ int bh_k_conv_igemm(const void* in, const void* wpk, const float* bias, void* ou
     else if (pw == 32) hipLaunchKernelGGL(conv_igemm_kernel<2>, grid, dim3(256), lds, stream, a);
     else hipLaunchKernelGGL(conv_igemm_kernel<1>, grid, dim3(256), lds, stream, a);
     BH_CHECK_HIP(hipGetLastError());
+    g_conv_last_kernel = BH_CONV_K_IGEMM(pw / 16, fs ? 1 : 0);
     return 0;
 }
 
 
-// Can the three convolutions at the head of an LSTM model run as conv_front3_kernel? conv1: 1 -> <= 16 channels (16 with padding),
-// stride 1, K1 <= 8; conv2: 16 -> 16 (padded), stride 1, K2 * 16 <= 96; conv3: what conv_ws_kernel serves (16 -> 384 / 96 channels, Kp = 320).
-int bh_k_conv_front3_ok(int c1_eff, int K1, int s1, int c2_in_eff, int c2_eff, int K2, int s2, int c3_in_eff, int c3_out, int K3, int s3) {
+// Can the three convolutions at the head of an LSTM model run as conv_front3_kernel? Three questions, asked separately:
+//  * bh_k_conv_front3_shape_ok: what the KERNEL needs of the arguments its launcher takes. K1 <= 8 (conv1's taps; the signal span is sized for
+//    them), K2 * 16 <= 96 (conv2's three k-steps), conv3 what conv_ws_kernel serves (384 / 96 channels, padded K3 * 16 == 320: ten k-steps
+//    held in registers), and a workgroup's LDS within 80 KiB. The launcher requires it; nothing else protects the packed weights from
+//    being read outside.
+//  * bh_k_conv_front3_option_ok: the process-wide options ("conv_fuse", "conv_ws").
+//  * bh_k_conv_front3_ok: the engine's question - channel counts as laid out (16 everywhere between the layers), strides 1 in front of
+//    conv3, and both of the above.
+static size_t conv_front3_lds(int K1, int K2, int K3, int s3) {
+    const size_t span = (size_t)255 * s3 + K3;
+    return ((span * 16 + 40 + 7) & ~(size_t)7) * 2 + (size_t)(256 + K2 - 1 + 6) * 16 * 2 + (span + K2 + K1 + 6) * 4 + (size_t)(16 * K1 + 16) * 4;
+}
+static int conv_front3_kp(int K3) { return ((K3 * 16 + 31) / 32) * 32; }
+int bh_k_conv_front3_shape_ok(int K1, int K2, int c3_out, int K3, int s3) {
+    if (K1 < 1 || K1 > 8 || K2 < 1 || K2 * 16 > 96 || K3 < 1 || s3 < 1) return 0;
+    if (!(c3_out == 384 || c3_out == 96) || conv_front3_kp(K3) != 320) return 0;
+    return conv_front3_lds(K1, K2, K3, s3) <= 80 * 1024 ? 1 : 0;
+}
+int bh_k_conv_front3_option_ok(int c3_out) {
     if (!bh::g_opt.conv_fuse || !bh::g_opt.conv_ws) return 0;
-    if (c1_eff != 16 || c2_in_eff != 16 || c2_eff != 16 || c3_in_eff != 16) return 0;
-    if (s1 != 1 || s2 != 1 || K1 < 1 || K1 > 8 || K2 < 1 || K2 * 16 > 96) return 0;
-    if (!(c3_out == 384 || c3_out == 96) || ((K3 * 16 + 31) / 32) * 32 != 320) return 0;
     // 96 channels (the fast models): correct (tests run it with "conv_fuse" 2) but not the default - those models keep three batches in
     // flight whose recurrent kernels share the CUs with the convolutions, and the 65 KiB, 384-thread fused workgroups cost that
     // pipeline more than the 0.04 ms of convolution time they save (bench step 2.43 -> 2.55-2.65 ms)
-    if (c3_out == 96 && bh::g_opt.conv_fuse < 2) return 0;
-    const size_t span = (size_t)255 * s3 + K3;
-    const size_t lds = ((span * 16 + 40 + 7) & ~(size_t)7) * 2 + (size_t)(256 + K2 - 1 + 6) * 16 * 2 + (span + K2 + K1 + 6) * 4 + (size_t)(16 * K1 + 16) * 4;
-    return lds <= 80 * 1024 ? 1 : 0;
+    return (c3_out == 96 && bh::g_opt.conv_fuse < 2) ? 0 : 1;
+}
+int bh_k_conv_front3_ok(int c1_eff, int K1, int s1, int c2_in_eff, int c2_eff, int K2, int s2, int c3_in_eff, int c3_out, int K3, int s3) {
+    if (c1_eff != 16 || c2_in_eff != 16 || c2_eff != 16 || c3_in_eff != 16 || s1 != 1 || s2 != 1) return 0;
+    return bh_k_conv_front3_shape_ok(K1, K2, c3_out, K3, s3) && bh_k_conv_front3_option_ok(c3_out);
 }
 
 int bh_k_conv_front3(const void* signal, int N, int L0, const float* w1, const float* b1, int K1, int pad1, int act1, float lo1, float hi1,
@@ -615,14 +644,16 @@ int bh_k_conv_front3(const void* signal, int N, int L0, const float* w1, const f
                      const float* b3, int Cout3, int K3, int stride3, int pad3, int act3, float lo3, float hi3, void* out, long os_n,
                      long os_t, hipStream_t stream) {
     using namespace bh;
+    BH_REQUIRE(bh_k_conv_front3_shape_ok(K1, K2, Cout3, K3, stride3),
+               "conv_front3: no instance for K1=%d K2=%d Cout3=%d K3=%d stride3=%d (bh_k_conv_front3_shape_ok)", K1, K2, Cout3, K3, stride3);
+    BH_REQUIRE(((uintptr_t)b3 & 15) == 0, "conv_front3: conv3's bias must be 16-byte aligned (or null)");
     const int L1 = L0 + 2 * pad1 - K1 + 1, L2 = L1 + 2 * pad2 - K2 + 1, L3 = (L2 + 2 * pad3 - K3) / stride3 + 1;
     BH_REQUIRE(L1 > 0 && L2 > 0 && L3 > 0, "conv_front3: chunk of %d samples is too short", L0);
     BH_REQUIRE(os_t % 4 == 0 && os_n % 4 == 0, "conv_front3: output strides must be multiples of 4");
     ConvFront3Args a{(const half_t*)signal, w1, b1, (const half_t*)w2pk, b2, L0, L1, L2, K1, pad1, act1, K2, pad2, act2, lo1, hi1, lo2, hi2,
-                     ConvArgs{nullptr, (const half_t*)w3pk, b3, (half_t*)out, N, L2, L3, 16, Cout3, K3, stride3, pad3, act3, 320, lo3, hi3,
+                     ConvArgs{nullptr, (const half_t*)w3pk, b3, (half_t*)out, N, L2, L3, 16, Cout3, K3, stride3, pad3, act3, conv_front3_kp(K3), lo3, hi3,
                               os_n, os_t}};
-    const size_t span = (size_t)255 * stride3 + K3;
-    const size_t lds = ((span * 16 + 40 + 7) & ~(size_t)7) * 2 + (size_t)(256 + K2 - 1 + 6) * 16 * 2 + (span + K2 + K1 + 6) * 4 + (size_t)(16 * K1 + 16) * 4;
+    const size_t lds = conv_front3_lds(K1, K2, K3, stride3);
     const dim3 grid((L3 + 255) / 256, N);
     if (Cout3 == 384) {
         if (lds > 64 * 1024) BH_CHECK_HIP(bh_max_lds((const void*)conv_front3_kernel<3, 10, 8>, (int)lds));
@@ -632,5 +663,6 @@ int bh_k_conv_front3(const void* signal, int N, int L0, const float* w1, const f
         hipLaunchKernelGGL((conv_front3_kernel<1, 10, 6>), grid, dim3(384), lds, stream, a);
     }
     BH_CHECK_HIP(hipGetLastError());
+    g_conv_last_kernel = Cout3 == 384 ? BH_CONV_K_FRONT3_384 : BH_CONV_K_FRONT3_96;
     return 0;
 }

@@ -114,6 +114,7 @@ int bh_k_dwconv(const void* in, const float* w, void* out, int N, int Lin, int L
     dim3 grid((Lout + DW_T - 1) / DW_T, (C + DW_C - 1) / DW_C, N);
     hipLaunchKernelGGL(dwconv_kernel, grid, dim3(256), lds, stream, a);
     BH_CHECK_HIP(hipGetLastError());
+    bh_k_conv_note_kernel(BH_CONV_K_DWCONV);
     return 0;
 }
 

@@ -23,6 +23,10 @@ int bh_k_conv_first(const void* signal, const float* w, const float* bias, void*
 int bh_k_conv_igemm(const void* in, const void* wpk, const float* bias, void* out, int N, int Lin,
                     int Lout, int Cin, int Cout, int K, int stride, int pad, int act, float clamp_lo,
                     float clamp_hi, long os_n, long os_t, hipStream_t stream);
+// test hook: the kernel and instance the last convolution launch took, as a bh_conv_kernel code (include/bonito_hip.h); every launcher
+// of conv.hip and bh_k_dwconv note theirs. A host-side static: process-wide, not thread-safe
+int bh_k_conv_last_kernel();
+void bh_k_conv_note_kernel(int code);
 
 // lstm.hip
 // Launch geometry of a recurrent kernel family: the ONE statement of how many workgroups a launch of n rings takes and, inverted,
@@ -126,7 +130,11 @@ int bh_k_ctc_greedy(const float* logp, const long* offs, int R, int C, float qsc
 size_t bh_k_ctc_beam_workspace(long total_steps, int R, int C, int beam_size);
 int bh_k_ctc_prefix_beam(const float* logp, const long* offs, int R, int C, int beam_size, float threshold, void* workspace,
                          int8_t* labels, int* path, int* count, hipStream_t stream);
-// conv1 -> conv2 -> conv3 of an LSTM model's front end in one kernel (conv_front3_kernel); _ok: does the shape qualify?
+// conv1 -> conv2 -> conv3 of an LSTM model's front end in one kernel (conv_front3_kernel). _shape_ok: do the launcher's own arguments have
+// an instance (pure; the launcher requires it)? _option_ok: do "conv_fuse" / "conv_ws" allow it? _ok: the engine's question - the layers'
+// channel counts and strides, and both of the former
+int bh_k_conv_front3_shape_ok(int K1, int K2, int c3_out, int K3, int s3);
+int bh_k_conv_front3_option_ok(int c3_out);
 int bh_k_conv_front3_ok(int c1_eff, int K1, int s1, int c2_in_eff, int c2_eff, int K2, int s2, int c3_in_eff, int c3_out, int K3, int s3);
 int bh_k_conv_front3(const void* signal, int N, int L0, const float* w1, const float* b1, int K1, int pad1, int act1, float lo1, float hi1,
                      const void* w2pk, const float* b2, int K2, int pad2, int act2, float lo2, float hi2, const void* w3pk,

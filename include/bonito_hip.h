@@ -406,10 +406,38 @@ int bh_conv1d_first(const void* signal, const float* w, const float* bias, void*
 /* packed conv weight size in halves and host-side packer: torch [Cout][Cin][K] fp32 -> [Cout16][Kp] fp16 */
 size_t bh_conv1d_packed_halves(int Cin, int Cout, int K);
 int bh_conv1d_pack(const float* w, int Cin, int Cout, int K, uint16_t* packed);
-/* channel-minor implicit-GEMM conv: in fp16 [N][Lin][Cin] -> out (n*os_n + t*os_t + c) */
+/* channel-minor implicit-GEMM conv: in fp16 [N][Lin][Cin] -> out (n*os_n + t*os_t + c). Cin % 8 == 0, Cout % 4 == 0, os_n and os_t
+ * multiples of 4. The weight-stationary kernel (384 / 96 channels, ten k-steps) is taken only with a null or 16-byte aligned bias. */
 int bh_conv1d(const void* in, const void* wpacked, const float* bias, void* out, int N, int Lin, int Cin,
               int Cout, int K, int stride, int pad, int act, float clamp_lo, float clamp_hi, long os_n,
               long os_t, void* stream);
+/* The fused front end of an LSTM model: conv1 (1 -> 16 channels, K1 taps, stride 1) -> conv2 (16 -> 16, K2 taps, stride 1) -> conv3
+ * (16 -> Cout3 channels, K3 taps, stride3) in one kernel, the 16-channel intermediates never leaving the CU; each layer with its own
+ * padding, activation and clamp, each computed by the operations of bh_conv1d_first / bh_conv1d / bh_conv1d in their order (identical
+ * bytes). signal fp16 [N][L0]; w1 fp32 [16][K1], b1 / b2 / b3 fp32 or null (b3 16-byte aligned); w2packed = bh_conv1d_pack(16, 16, K2),
+ * w3packed = bh_conv1d_pack(16, Cout3, K3); out (n*os_n + t*os_t + c), os_n and os_t multiples of 4.
+ * Shapes with an instance: 1 <= K1 <= 8, K2 <= 6, Cout3 384 or 96, K3 19 or 20 (ten k-steps of 32), stride3 small enough for the
+ * workgroup's LDS (<= 7 at these sizes). Anything else is an error (nonzero return, nothing launched, output untouched). The process-wide
+ * options "conv_fuse" / "conv_ws" decide what the ENGINE runs; this entry point does not read them. */
+int bh_conv1d_front3(const void* signal, int N, int L0, const float* w1, const float* b1, int K1, int pad1, int act1, float lo1,
+                     float hi1, const void* w2packed, const float* b2, int K2, int pad2, int act2, float lo2, float hi2,
+                     const void* w3packed, const float* b3, int Cout3, int K3, int stride3, int pad3, int act3, float lo3,
+                     float hi3, void* out, long os_n, long os_t, void* stream);
+/* TEST HOOK: the kernel and instance the last convolution launch of this process took (bh_conv1d_first, bh_conv1d, bh_conv1d_front3,
+ * bh_dwconv1d, or a convolution layer of an encoder), as one of the codes below; 0 = none yet. A host-side static written by the
+ * launchers: process-wide, NOT thread-safe. */
+enum bh_conv_kernel {
+    BH_CONV_K_NONE = 0,
+    BH_CONV_K_FIRST = 1,          /* conv_first_kernel */
+    BH_CONV_K_WS_384 = 20,        /* conv_ws_kernel<3, 10, 8>: weight-stationary, 384 channels */
+    BH_CONV_K_WS_96 = 21,         /* conv_ws_kernel<1, 10, 6>: 96 channels */
+    BH_CONV_K_FRONT3_384 = 30,    /* conv_front3_kernel<3, 10, 8> */
+    BH_CONV_K_FRONT3_96 = 31,     /* conv_front3_kernel<1, 10, 6> */
+    BH_CONV_K_DWCONV = 40,        /* dwconv_kernel */
+    BH_CONV_K_IGEMM_BASE = 100    /* conv_igemm_kernel<NTT, FS>: 100 + 10 * NTT + FS, NTT in 1 / 2 / 4 (64 / 128 / 256 positions per workgroup) */
+};
+#define BH_CONV_K_IGEMM(ntt, fs) (BH_CONV_K_IGEMM_BASE + 10 * (ntt) + (fs))
+int bh_conv1d_last_kernel(void);
 /* Greedy CTC decode of R reads in one launch: replaces fast_ctc_decode.viterbi_search(probs, alphabet,
  * qstring=True, qscale, qbias) (bonito/ctc/model.py:39-42).  logp: device fp32 [sum T_r][classes]
  * log-probabilities, offsets: device int64 [R+1].  Outputs (device, compacted per read at offsets[r]):

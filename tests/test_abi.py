@@ -266,6 +266,45 @@ def test_lstm_family_enum_of_the_binding_matches_the_header():
     assert "enum bh_lstm_family {" not in open(os.path.join(ROOT, "bonito_amd", "csrc", "kernels.h")).read()
 
 
+def test_conv_kernel_codes_of_the_binding_match_the_header():
+    text = open(os.path.join(ROOT, "include", "bonito_hip.h")).read()
+    enum = text[text.index("enum bh_conv_kernel {"):]
+    enum = re.sub(r"/\*.*?\*/", "", enum[:enum.index("};")], flags=re.S)
+    table = {name.lower(): int(v) for name, v in re.findall(r"BH_CONV_K_(\w+)\s*=\s*(\d+)", enum)}
+    assert table == _lib.CONV_KERNELS and len(set(table.values())) == len(table)
+    assert "#define BH_CONV_K_IGEMM(ntt, fs) (BH_CONV_K_IGEMM_BASE + 10 * (ntt) + (fs))" in text
+    assert _lib.conv_igemm_code(4, True) == 141 and _lib.conv_igemm_code(1, False) == 110
+
+
+@pytest.mark.parametrize("kw", [dict(Cout3=128), dict(Cout3=0), dict(K2=7), dict(K2=0), dict(K1=9), dict(K1=0), dict(K3=21), dict(K3=18),
+                                dict(s3=8), dict(s3=64)], ids=lambda kw: "%s_%d" % next(iter(kw.items())))
+def test_conv_front3_refuses_a_shape_without_an_instance(kw):
+    """bh_conv1d_front3 checks its shape predicate in front of any device call (the pointers below are never read): the 96-channel
+    instance must not be handed any Cout3 != 384, nor packed weights of another K2 / K3 than its fragment loads assume."""
+    import ctypes as C
+    a = dict(K1=5, K2=5, K3=19, s3=6, Cout3=384)
+    a.update(kw)
+    p = C.c_void_p(4096)
+    rc = _lib.lib().bh_conv1d_front3(p, 3, 1600, p, p, a["K1"], 2, 1, -0.5, 3.5, p, p, a["K2"], 2, 1, -0.5, 3.5, p, p, a["Cout3"], a["K3"], a["s3"],
+                                     9, 1, -0.5, 3.5, p, 384, 3 * 384, None)
+    assert rc != 0 and "no instance for K1=%d K2=%d Cout3=%d K3=%d stride3=%d" % (a["K1"], a["K2"], a["Cout3"], a["K3"], a["s3"]) in _lib.last_error()
+
+
+def test_conv_front3_argument_checks():
+    import ctypes as C
+    p = C.c_void_p(4096)
+
+    def call(sig=p, w1=p, w2=p, w3=p, out=p, N=3, L0=1600, s3=6):
+        rc = _lib.lib().bh_conv1d_front3(sig, N, L0, w1, None, 5, 2, 1, -0.5, 3.5, w2, None, 5, 2, 1, -0.5, 3.5, w3, None, 384, 19, s3, 9, 1, -0.5, 3.5,
+                                         out, 384, 3 * 384, None)
+        return rc, _lib.last_error()
+    for kw in (dict(sig=None), dict(w1=None), dict(w2=None), dict(w3=None), dict(out=None), dict(N=0), dict(s3=0), dict(s3=-1)):
+        rc, msg = call(**kw)
+        assert rc != 0 and "bad arguments" in msg, kw
+    rc, msg = call(L0=0)
+    assert rc != 0 and "too short" in msg
+
+
 def _family_call(family, H, T=3, N=32, flags=0, x=4096, w=True, h_out=8192):
     import ctypes as C
     import numpy as np
