@@ -65,6 +65,10 @@ SIGNATURES = {
     "bh_crf_seq_viterbi": (_i, [_vp, _i, _i, _i, _i, _f, _l, _l, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "bh_crf_seq_logz_free": (_i, [_vp, _i, _i, _i, _f, _l, _l, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "bh_crf_logz_dense": (_i, [_vp, _i, _i, _i, _i, _f, _l, _l, _vp, _vp]),
+    "bh_crf_seq_grad_workspace": (_sz, [_i, _i, _i, _i]),
+    "bh_crf_seq_logz_grad": (_i, [_vp, _i, _i, _i, _i, _f, _l, _l, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _l, _i, _i, _vp]),
+    "bh_crf_logz_dense_grad_workspace": (_sz, [_i, _i, _i]),
+    "bh_crf_logz_dense_grad": (_i, [_vp, _i, _i, _i, _i, _f, _l, _l, _vp, _vp, _vp, _vp, _l, _l, _i, _vp]),
     "bh_sw_workspace": (_sz, [_i, _i, _i]),
     "bh_sw_align": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _l, _vp, _vp]),
     "bh_set_option": (_i, [C.c_char_p, _i]),

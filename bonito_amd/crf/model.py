@@ -32,6 +32,48 @@ def get_stride(m, stride=1):
     return stride
 
 
+class _CtcLoss(torch.autograd.Function):
+    """CTC_CRF.ctc_loss with a backward: per-chunk loss [N] of device scores. The forward takes logz and the edge posteriors of both
+    log-sums from one launch each (bh_crf_seq_logz_grad, bh_crf_logz_dense_grad) and keeps post_dense - post_chain in fp32; the
+    backward scales it by upstream * clip_mask / length. The value is computed by the expression of the no-grad path, from the
+    same numbers (contiguous koi-layout scores take logZ from bh_crf_logz there, so here too)."""
+
+    @staticmethod
+    def forward(ctx, scores, targets, target_lengths, state_len, loss_clip, normalise_scores, blank_score):
+        keep = torch.empty(scores.shape, dtype=torch.float32, device=scores.device)
+        if normalise_scores:
+            lz, _ = hip_decode.logz_grad(scores, state_len, blank_score, out=keep)
+            S = 4 ** state_len
+            half = scores.detach().to(torch.float16)
+            if scores.shape[-1] == 4 * S and (half if half.stride(2) == 1 else half.contiguous()).is_contiguous():
+                lz = hip_decode.logz_any(half, state_len, blank_score)              # (bh_crf_logz, as the no-grad path)
+            minus = torch.full((scores.shape[1 if scores.shape[-1] == 5 * S else 0],), -1.0, device=scores.device)
+            logz, _ = hip_decode.seq_logz_grad(scores, targets, target_lengths, state_len, blank_score, weight=minus, out=keep,
+                                               accumulate=True)
+            logz = logz.double() - lz.double()
+        else:
+            logz, _ = hip_decode.seq_logz_grad(scores, targets, target_lengths, state_len, blank_score, out=keep)
+            keep.neg_()
+            logz = logz.double()
+        lengths = target_lengths.to(logz.device)
+        loss = (-(logz / lengths)).float()
+        scale = torch.isfinite(loss).float() / lengths.float()                  # a target that cannot fit: +inf loss, zero gradient
+        if loss_clip:
+            scale = scale * ((loss >= 0.0) & (loss <= loss_clip)).float()       # torch.clamp's gradient: 1 inside [0, clip]
+            loss = torch.clamp(loss, 0.0, loss_clip)
+        ctx.save_for_backward(keep, scale)
+        ctx.five = scores.shape[-1] == 5 * 4 ** state_len
+        ctx.dtype = scores.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, upstream):
+        keep, scale = ctx.saved_tensors
+        w = upstream.float() * scale
+        grad = keep * (w[None, :, None] if ctx.five else w[:, None, None])
+        return grad.to(ctx.dtype), None, None, None, None, None, None
+
+
 class CTC_CRF:
     """k-mer CTC-CRF sequence distribution (reference crf/model.py:30-108).
 
@@ -75,6 +117,12 @@ class CTC_CRF:
         """Log partition function per chunk of koi-layout scores [N, T, 4S] (reference crf/model.py:47-52)."""
         return hip_decode.logz(scores.contiguous(), blank_score)
 
+    def posteriors(self, scores, blank_score=None):
+        """Edge posteriors of the Log semiring (the reference's SequenceDist.posteriors: the gradient of logZ), for the reference
+        layout [T, N, 5S] or the engine layout [N, T, 4S] with ``blank_score`` (the four move edges per state; the stay edge
+        is a scalar there). Shape and dtype of ``scores``. The Max semiring stays with ``viterbi`` / ``posterior_viterbi``."""
+        return hip_decode.logz_grad(scores, self.state_len, blank_score)[1]
+
     def normalise(self, scores):
         """scores - logZ / T on the reference layout [T, N, 5S] (reference crf/model.py:54-55). The koi layout keeps its stay
         score outside the tensor, so it cannot be normalised in place; ``ctc_loss`` never needs the normalised copy."""
@@ -101,12 +149,24 @@ class CTC_CRF:
 
     def ctc_loss(self, scores, targets, target_lengths, loss_clip=None, reduction="mean", normalise_scores=True,
                  blank_score=None):
-        """-ln P(target | scores) / target_length per chunk (reference crf/model.py:126-139), forward value only.
+        """-ln P(target | scores) / target_length per chunk (reference crf/model.py:126-139).
         scores: the reference layout [T, N, 5S], or the engine layout [N, T, 4S] with ``blank_score``; cuda fp16 (fp32 is
         rounded to fp16). With ``normalise_scores`` no normalised copy is written: normalisation subtracts logZ / T from each
-        of the T edges of every path, so the loss is -(seq_logz(raw) - logZ(raw)) / target_length."""
+        of the T edges of every path, so the loss is -(seq_logz(raw) - logZ(raw)) / target_length.
+        Device scores with ``requires_grad`` are differentiable: d loss_n / d scores = clip_mask_n / length_n * (posteriors of
+        logZ - posteriors of the target chain), from the alpha-beta kernels of csrc/seqdist_grad.hip, in the dtype and layout of
+        ``scores``; the values equal the no-grad path's bit for bit. fp32 scores are rounded to fp16 for the kernels and the
+        gradient is that of the ROUNDED scores, passed straight through. A chunk whose target cannot fit into T steps has loss
+        +inf and a zero gradient; a clipped chunk (loss outside [0, loss_clip]) has a zero gradient, as with torch.clamp.
+        Host tensors with requires_grad are refused (NoTorchCompute): there is no torch compute path."""
         if reduction not in ("mean", "none", None):
             raise ValueError("Unknown reduction type {}".format(reduction))
+        if scores.requires_grad and torch.is_grad_enabled():
+            if not scores.is_cuda:
+                raise NoTorchCompute("ctc_loss has a backward on a HIP device only: host scores with requires_grad are refused")
+            hip_decode.seq_layout(scores, self.state_len, blank_score)
+            loss = _CtcLoss.apply(scores, targets, target_lengths, self.state_len, loss_clip, bool(normalise_scores), blank_score)
+            return loss.mean() if reduction == "mean" else loss
         logz = hip_decode.seq_logz(scores, targets, target_lengths, self.state_len, blank_score).double()
         if normalise_scores:
             logz = logz - hip_decode.logz_any(scores, self.state_len, blank_score)
@@ -239,8 +299,9 @@ class SeqdistModel(Module):
         return None
 
     def loss(self, scores, targets, target_lengths, **kwargs):
-        """CTC-CRF loss of labelled chunks (reference crf/model.py:204-207), forward value only. ``scores``: this model's
-        engine output [N, T, 4S] (the head's blank score is filled in) or the reference layout [T, N, 5S]."""
+        """CTC-CRF loss of labelled chunks (reference crf/model.py:204-207); differentiable for device scores that require
+        grad (see ``CTC_CRF.ctc_loss``). ``scores``: this model's engine output [N, T, 4S] (the head's blank score is filled
+        in) or the reference layout [T, N, 5S]."""
         if self.target_projection is not None:
             targets = self.target_projection.to(targets.device)[targets.long()]
         if scores.shape[-1] != self.seqdist.n_score():

@@ -349,6 +349,28 @@ extern "C" int bh_crf_logz_dense(const void* scores, int N, int T, int state_len
     BH_REQUIRE(scores && logz_out, "crf_logz_dense: null pointer");
     return bh_k_crf_logz_dense(scores, N, T, state_len, layout_5s, blank_score, stride_n, stride_t, logz_out, (hipStream_t)stream);
 }
+extern "C" size_t bh_crf_seq_grad_workspace(int N, int T, int Lmax, int state_len) {
+    return bh_k_crf_seq_grad_workspace(N, T, Lmax, state_len);
+}
+extern "C" int bh_crf_seq_logz_grad(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
+                                    long stride_t, const void* targets, int Lmax, int target_bytes, const int32_t* target_lengths,
+                                    const float* weight, void* workspace, float* logz_out, void* grad, long g_stride_n,
+                                    long g_stride_t, int grad_fp32, int accumulate, void* stream) {
+    BH_REQUIRE(scores && targets && target_lengths && workspace && logz_out && grad, "crf_seq_logz_grad: null pointer");
+    return bh_k_crf_seq_grad(scores, N, T, state_len, layout_5s, blank_score, stride_n, stride_t, targets, target_bytes, Lmax,
+                             target_lengths, weight, workspace, logz_out, grad, g_stride_n, g_stride_t, grad_fp32, accumulate,
+                             (hipStream_t)stream);
+}
+extern "C" size_t bh_crf_logz_dense_grad_workspace(int N, int T, int state_len) {
+    return bh_k_crf_logz_dense_grad_workspace(N, T, state_len);
+}
+extern "C" int bh_crf_logz_dense_grad(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score,
+                                      long stride_n, long stride_t, const float* weight, void* workspace, float* logz_out,
+                                      void* grad, long g_stride_n, long g_stride_t, int grad_fp32, void* stream) {
+    BH_REQUIRE(scores && workspace && logz_out && grad, "crf_logz_dense_grad: null pointer");
+    return bh_k_crf_logz_dense_grad(scores, N, T, state_len, layout_5s, blank_score, stride_n, stride_t, weight, workspace,
+                                    logz_out, grad, g_stride_n, g_stride_t, grad_fp32, (hipStream_t)stream);
+}
 extern "C" size_t bh_sw_workspace(int n, int max_seq, int max_ref) { return bh_k_sw_workspace(n, max_seq, max_ref); }
 extern "C" int bh_sw_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, const void* refs, long ref_stride,
                            const int32_t* ref_lengths, int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace,

@@ -93,6 +93,16 @@ int bh_k_crf_seq(const void* scores, int N, int T, int state_len, int layout_5s,
 int bh_k_crf_logz_dense(const void* scores, int N, int T, int state_len, int layout_5s, float blank, long s_n, long s_t,
                         float* out, hipStream_t stream);
 
+// seqdist_grad.hip (alpha-beta passes: logz and its gradient, the posterior occupancy of every edge, from one launch)
+size_t bh_k_crf_seq_grad_workspace(int N, int T, int Lmax, int state_len);
+int bh_k_crf_seq_grad(const void* scores, int N, int T, int state_len, int layout_5s, float blank, long s_n, long s_t,
+                      const void* targets, int target_bytes, int Lmax, const int* lens, const float* weight, void* workspace,
+                      float* out, void* grad, long g_n, long g_t, int grad_fp32, int accumulate, hipStream_t stream);
+size_t bh_k_crf_logz_dense_grad_workspace(int N, int T, int state_len);
+int bh_k_crf_logz_dense_grad(const void* scores, int N, int T, int state_len, int layout_5s, float blank, long s_n, long s_t,
+                             const float* weight, void* workspace, float* out, void* grad, long g_n, long g_t, int grad_fp32,
+                             hipStream_t stream);
+
 // align.hip (Smith-Waterman, affine gaps, traceback; the lengths are host arrays)
 size_t bh_k_sw_workspace(int n, int max_seq, int max_ref);
 int bh_k_sw_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,

@@ -276,7 +276,8 @@ def check_targets(targets, target_lengths, state_len, free_start=False):
 def _seq_call(scores, targets, target_lengths, state_len, blank_score, mode):
     if scores.requires_grad:
         from bonito_amd.nn import NoTorchCompute
-        raise NoTorchCompute("the sequence scans are forward values only: scores with requires_grad have no backward here")
+        raise NoTorchCompute("this entry point returns a plain tensor: for scores with requires_grad use seq_logz_grad / "
+                             "CTC_CRF.ctc_loss, which carry the backward")
     N, T, five, s_n, s_t = seq_layout(scores, state_len, blank_score)
     if mode == "free" and five:
         raise ValueError("the free-start sum is defined on koi-layout scores [N, T, 4S]")
@@ -361,6 +362,112 @@ def logz_any(scores, state_len, blank_score=None):
         _lib.check(lib.bh_crf_logz_dense(_lib.ptr(scores), N, T, state_len, five, float(blank_score or 0.0), s_n, s_t,
                                          _lib.ptr(out), _lib.stream_ptr(dev)), "bh_crf_logz_dense")
         return out.double()
+
+
+def _grad_scores(scores, state_len, blank_score):
+    """Device fp16 scores with a dense score axis for the gradient entry points (fp32 is rounded to fp16, as in the forward scans;
+    the gradient is then that of the rounded scores). -> (scores fp16, grad dtype)."""
+    seq_layout(scores, state_len, blank_score)
+    if not scores.is_cuda:
+        raise _lib.HipEngineError("scores must live on a HIP device (no CPU fallback)")
+    if scores.dtype not in (torch.float16, torch.float32):
+        raise TypeError("scores must be fp16 or fp32, got %s" % scores.dtype)
+    gdtype = scores.dtype
+    scores = scores.detach()
+    if scores.dtype != torch.float16:
+        scores = scores.to(torch.float16)
+    if scores.stride(2) != 1:
+        scores = scores.contiguous()
+    return scores, gdtype
+
+
+def _grad_out(out, scores, gdtype, state_len, blank_score):
+    """The gradient tensor: a new one shaped like `scores`, or the caller's `out` (fp16 / fp32, same shape, same device, its own
+    strides with a dense score axis). -> (out, g_stride_n, g_stride_t, grad_fp32)."""
+    if out is None:
+        out = torch.empty(scores.shape, dtype=gdtype, device=scores.device)
+    else:
+        if tuple(out.shape) != tuple(scores.shape) or out.device != scores.device:
+            raise ValueError("out must have the shape %s and the device of the scores" % (tuple(scores.shape),))
+        if out.dtype not in (torch.float16, torch.float32):
+            raise TypeError("out must be fp16 or fp32, got %s" % out.dtype)
+        if out.stride(2) != 1:
+            raise ValueError("the score axis of out must be dense")
+        if out.requires_grad:
+            raise ValueError("out must not require grad")
+    _, _, _, g_n, g_t = seq_layout(out, state_len, 0.0 if blank_score is None else blank_score)
+    return out, g_n, g_t, int(out.dtype == torch.float32)
+
+
+def _weight(weight, N, dev):
+    if weight is None:
+        return None
+    weight = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if weight.shape != (N,):
+        raise ValueError("weight must be [N] = [%d]" % N)
+    return weight
+
+
+def seq_logz_grad(scores, targets, target_lengths, state_len, blank_score=None, weight=None, out=None, accumulate=False):
+    """seq_logz AND its gradient from one launch (bh_crf_seq_logz_grad): (logz float32 [N], grad), both on the device.
+    grad[n, t, c] = weight[n] * the posterior probability that the alignment takes, at step t, an edge whose score is element c
+    (positions that share an element are summed). It has the shape and dtype (fp16 / fp32) of `scores`; fp32 scores are rounded to
+    fp16 for the kernel and the gradient is that of the rounded scores. ``out``: write into this tensor instead (fp16 or fp32, own
+    strides, dense score axis); ``accumulate=True`` adds into it. A chunk whose target cannot fit into T steps has logz = -inf and a
+    ZERO gradient (this project's definition). The result is bit-identical from call to call. Koi-layout scores: the stay edge is
+    the scalar blank_score and gets no gradient."""
+    state_len = int(state_len)
+    N, T, five, s_n, s_t = seq_layout(scores, state_len, blank_score)
+    targets, lengths = check_targets(targets, target_lengths, state_len)
+    if targets.shape[0] != N:
+        raise ValueError("%d target rows for %d chunks" % (targets.shape[0], N))
+    if accumulate and out is None:
+        raise ValueError("accumulate=True needs out")
+    scores, gdtype = _grad_scores(scores, state_len, blank_score)
+    N, T, five, s_n, s_t = seq_layout(scores, state_len, blank_score)
+    out, g_n, g_t, g32 = _grad_out(out, scores, gdtype, state_len, blank_score)
+    lib = _lib.lib()
+    dev = scores.device
+    Lmax = int(targets.shape[1])
+    targets = targets.to(dev).contiguous()
+    lengths = lengths.to(dev).contiguous()
+    weight = _weight(weight, N, dev)
+    nbytes = lib.bh_crf_seq_grad_workspace(N, T, Lmax, state_len)
+    if nbytes == 0:
+        raise ValueError("unsupported shape: Lmax + 1 - state_len = %d positions (limit 4096), state_len %d (1..5)"
+                         % (Lmax + 1 - state_len, state_len))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    logz = torch.empty(N, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.bh_crf_seq_logz_grad(_lib.ptr(scores), N, T, state_len, five, float(blank_score or 0.0), s_n, s_t,
+                                            _lib.ptr(targets), Lmax, targets.element_size(), _lib.ptr(lengths), _lib.ptr(weight),
+                                            _lib.ptr(ws), _lib.ptr(logz), _lib.ptr(out), g_n, g_t, g32, int(bool(accumulate)),
+                                            _lib.stream_ptr(dev)), "bh_crf_seq_logz_grad")
+    return logz, out
+
+
+def logz_grad(scores, state_len, blank_score=None, weight=None, out=None):
+    """CTC_CRF.logZ AND its gradient from one launch (bh_crf_logz_dense_grad): (logZ float32 [N], grad), both on the device.
+    grad[n, t, :] = weight[n] * the posterior probability of every edge at step t (SequenceDist.posteriors with the Log semiring);
+    shape and dtype of `scores` (either layout; the koi layout has the four move edges per state only), or written into ``out``.
+    Every element is written; fp32 scores are rounded to fp16 for the kernel."""
+    state_len = int(state_len)
+    scores, gdtype = _grad_scores(scores, state_len, blank_score)
+    N, T, five, s_n, s_t = seq_layout(scores, state_len, blank_score)
+    out, g_n, g_t, g32 = _grad_out(out, scores, gdtype, state_len, blank_score)
+    lib = _lib.lib()
+    dev = scores.device
+    weight = _weight(weight, N, dev)
+    nbytes = lib.bh_crf_logz_dense_grad_workspace(N, T, state_len)
+    if nbytes == 0:
+        raise ValueError("unsupported shape: N %d, T %d, state_len %d (1..5)" % (N, T, state_len))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    logz = torch.empty(N, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.bh_crf_logz_dense_grad(_lib.ptr(scores), N, T, state_len, five, float(blank_score or 0.0), s_n, s_t,
+                                              _lib.ptr(weight), _lib.ptr(ws), _lib.ptr(logz), _lib.ptr(out), g_n, g_t, g32,
+                                              _lib.stream_ptr(dev)), "bh_crf_logz_dense_grad")
+    return logz, out
 
 
 def encode_sequences(sequences):

@@ -18,6 +18,9 @@
  *   bh_crf_seq_logz / bh_crf_seq_viterbi (+ bh_crf_seq_logz_free, bh_crf_logz_dense)
  *        koi.ctc.{logZ_cu, viterbi_alignments} behind CTC_CRF.ctc_loss / ctc_viterbi_alignments, SeqdistModel.loss
  *                                                                              bonito/crf/model.py:126-143,204-207
+ *   bh_crf_seq_logz_grad / bh_crf_logz_dense_grad
+ *        the backward of koi.ctc.{logZ_cu, logZ_cu_sparse} (autograd of CTC_CRF.ctc_loss) and SequenceDist.posteriors
+ *                                                                              bonito/crf/model.py:47-67,126-139
  *   bh_sw_align
  *        parasail.sw_trace_striped_32(seq, ref, 8, 4, parasail.dnafull) behind evaluate's align() and util.accuracy
  *                                                                              bonito/cli/evaluate.py:37-67, bonito/util.py:346-368
@@ -221,6 +224,37 @@ int bh_crf_seq_logz_free(const void* scores, int N, int T, int state_len, float 
                          float* logz_out, void* stream);
 int bh_crf_logz_dense(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
                       long stride_t, float* logz_out, void* stream);
+
+/* ---- Gradients of the two log-sums above (csrc/seqdist_grad.hip): logz AND its gradient from one launch ---------------
+ * The gradient of a log-sum over paths is the posterior occupancy of every edge. With alpha_t the Log scan before step t,
+ * beta_t the mirror scan from beta_T[n-1] = 0 and logz = alpha_T[n-1]:
+ *     p_stay[t][j] = exp(alpha_t[j]   + stay_t[j] + beta_{t+1}[j] - logz)
+ *     p_move[t][j] = exp(alpha_t[j-1] + move_t[j] + beta_{t+1}[j] - logz)
+ * bh_crf_seq_logz_grad: scores / targets / range exactly as bh_crf_seq_logz. grad[n][t][c] (+)= weight[n] * (sum of p over the
+ *   edges whose gathered score element is c); in the koi layout the stay edge is the scalar blank_score and gets no gradient.
+ *   grad: fp16 (grad_fp32 = 0) or fp32 (1) with its own element strides (g_stride_n, g_stride_t), the score axis dense, 4S or 5S
+ *   wide like the scores. weight: device float [N], NULL = 1. accumulate = 1 adds into grad; accumulate = 0 writes every element
+ *   of the chunk's T rows exactly once (zeros where no edge gathers). logz_out[N] is bit-identical to bh_crf_seq_logz.
+ *   Positions that gather the same element at the same step (repeated k-mers) are summed before the write, in integer fixed
+ *   point at scale 2^30 (a step's posteriors sum to 1), so the result is bit-identical from call to call.
+ *   A row whose target cannot fit (n - 1 > T) has logz = -inf and, BY THIS PROJECT'S DEFINITION, a zero gradient (nothing added,
+ *   or zeros on overwrite): koi is closed, its behaviour there is unknown, and a NaN would poison an optimiser step.
+ *   A row with len < state_len or len > Lmax yields logz = NaN and no gradient is written.
+ *   workspace: bh_crf_seq_grad_workspace(N, T, Lmax, state_len) bytes (every alpha_t in fp32; 0 = unsupported shape).
+ * bh_crf_logz_dense_grad: the posteriors of CTC_CRF.logZ for either layout with strides (SequenceDist.posteriors, Log semiring):
+ *     grad[n][t][5s'+0]   = weight[n] * exp(alpha_t[s'] + stay_t[s'] + beta_{t+1}[s'] - logZ)
+ *     grad[n][t][5s'+1+r] = weight[n] * exp(alpha_t[r S/4 + s'/4] + move_t[s'][r] + beta_{t+1}[s'] - logZ)
+ *   (the koi layout has the four move elements 4s'+r only). Every element of grad is written exactly once; logz_out[N] float is
+ *   bit-identical to bh_crf_logz_dense. workspace: bh_crf_logz_dense_grad_workspace(N, T, state_len) bytes (0 = unsupported). */
+size_t bh_crf_seq_grad_workspace(int N, int T, int Lmax, int state_len);
+int bh_crf_seq_logz_grad(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
+                         long stride_t, const void* targets, int Lmax, int target_bytes, const int32_t* target_lengths,
+                         const float* weight, void* workspace, float* logz_out, void* grad, long g_stride_n, long g_stride_t,
+                         int grad_fp32, int accumulate, void* stream);
+size_t bh_crf_logz_dense_grad_workspace(int N, int T, int state_len);
+int bh_crf_logz_dense_grad(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
+                           long stride_t, const float* weight, void* workspace, float* logz_out, void* grad, long g_stride_n,
+                           long g_stride_t, int grad_fp32, void* stream);
 
 /* ---- Smith-Waterman local alignment with affine gaps and a traceback (csrc/align.hip) ----------------------------------
  * n pairs of a called sequence `seq` (the query, index i) and a known sequence `ref` (index j). seqs / refs: DEVICE int8 planes
