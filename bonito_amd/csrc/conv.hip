@@ -531,6 +531,304 @@ __global__ __launch_bounds__(64 * WAVES) void conv_front3_kernel(ConvFront3Args 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The fused front end as a pipeline ("conv_front_pipe", 384-channel stacks): conv1 / conv2 of block k + 1 run BESIDE conv3 of block k.
+// conv_front3_kernel's one workgroup per CU (166 registers: 3 waves per SIMD, and 8 waves are one workgroup) runs its phases one after
+// another - while conv1 issues on the VALU the matrix pipe idles, while conv3's MFMAs run the wave's own VALU waits. Here a workgroup
+// is 12 waves, exactly what a CU holds at 168 registers:
+//  * waves 0-7, the CONSUMERS, are conv_front3_kernel's conv3 loop (weight fragments in registers, fetched once per workgroup, the same
+//    MFMA order and epilogue) on one of TWO span buffers;
+//  * waves 8-11, the PRODUCERS (one per SIMD), fill the other span buffer for the next block. Each is self-contained: it takes a
+//    contiguous quarter of the span's 16-row tiles and walks it in slices of 64 conv2 rows - the slice's signal into a private LDS
+//    strip, conv1 of the slice into a private [64 + K2 - 1] row buffer (the K2 - 1 halo rows are computed once per quarter and carried
+//    from slice to slice by a copy, so a slice is two WHOLE passes of 64 conv1 items - no 520-of-512 straggler), then conv2 of its
+//    four tiles into the span buffer. Producers never wait on each other; within a wave LDS operations complete in order.
+//  * ONE workgroup barrier per block. A workgroup walks a contiguous run of (chunk, block) pairs (grid: at most one workgroup per CU,
+//    runs split evenly), so the pipeline fills and drains once per run. Workgroups never wait on each other.
+// The two roles are two loops, not two branches in one loop: registers are allocated per kernel, and conv3's 132 registers of weight
+// fragments and biases, live through a shared loop body, would leave conv1 36. BOTH LOOPS RUN it = 0 .. nrun WITH EXACTLY ONE BARRIER
+// PER TRIP, nrun is computed in front of the split, and nothing inside a trip leaves it early: every wave executes 1 + (nrun + 1)
+// barriers. At trip `it` the producers write buffer it & 1 and the consumers read buffer (it - 1) & 1.
+// Arithmetic: that of conv_front3_kernel operation for operation (identical bytes: tests/test_gpu_conv_front_pipeline.py). A last
+// block with few positions produces only the span rows its position tiles read (through the zero-weight twentieth row); what the
+// other rows of the buffer hold reaches only MFMA columns of positions that are not stored.
+// The clamp as ONE instruction, v_med3_f32, where fminf(fmaxf(x, lo), hi) is three (the compiler puts a canonicalising v_max in front of
+// the pair): the same value for lo <= hi - x itself inside, the bound outside, and lo for a NaN (of three operands with a NaN the
+// instruction returns their minimum, which skips the NaN) - so the same bytes (2048 x 10000: 1.31 -> 1.22 ms over the three layers).
+static __device__ __forceinline__ float clamp_med3(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(x, lo, hi); }
+
+static __device__ __forceinline__ void wave_lds_sync() {       // orders this wave's LDS traffic across its lanes (the hardware keeps a wave's LDS operations in order)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+constexpr int PIPE_CW = 8, PIPE_PW = 4, PIPE_SL = 64;             // consumer waves, producer waves, conv2 rows per producer slice
+constexpr int PIPE_A1R = PIPE_SL + 5 + 7;                         // rows of a producer's conv1 buffer: slice + halo (K2 <= 6) + rows under conv2's zero-padded k columns
+constexpr int PIPE_NSV = (PIPE_SL + 12 + 63) / 64;                   // samples of a strip per lane
+constexpr int PIPE_SG = PIPE_SL + 5 + 7 + 4;                      // floats of a producer's signal strip: slice + K2 - 1 + K1 - 1 (K1 <= 8)
+
+template <int FPW, int NKS>
+__global__ __launch_bounds__(64 * (PIPE_CW + PIPE_PW)) void conv_front3_pipe_kernel(ConvFront3Args q, int nb, int total) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const ConvArgs& p = q.c3;
+    constexpr int PB = 256, C16 = 16, NT = 64 * (PIPE_CW + PIPE_PW);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, kg = lane >> 4;
+    const int span_pos = (PB - 1) * p.stride + p.K;                  // conv2 positions conv3 reads
+    const int span_halves = span_pos * C16 + 32 + 8;
+    const int xin_halves = (span_halves + 7) & ~7;
+    half_t* xin0 = (half_t*)smem;                                     // two span buffers [span_pos][16] (+ tail)
+    half_t* a1all = xin0 + 2 * xin_halves;                            // the producers' conv1 buffers [PIPE_PW][PIPE_A1R][16]
+    float* slall = (float*)(a1all + PIPE_PW * PIPE_A1R * C16);        // the producers' signal strips [PIPE_PW][PIPE_SG]
+    float* wl = slall + PIPE_PW * PIPE_SG;                            // conv1 weights [16][K1] and bias [16]
+    float* bl = wl + C16 * q.K1;
+    float* b3l = bl + C16;                                            // conv3's bias [16 * FPW * PIPE_CW] (zeros without one)
+
+    // this workgroup's run of (chunk, block) pairs
+    const int first = (int)((long)blockIdx.x * total / gridDim.x);
+    const int nrun = (int)((long)(blockIdx.x + 1) * total / gridDim.x) - first;
+
+    for (int i = tid; i < C16 * q.K1; i += NT) wl[i] = q.w1[i];
+    if (tid < C16) bl[tid] = q.b1 ? q.b1[tid] : 0.0f;
+    for (int i = tid; i < C16 * FPW * PIPE_CW; i += NT) b3l[i] = p.bias ? p.bias[i] : 0.0f;
+    for (int b = 0; b < 2; ++b)
+        for (int e = span_pos * C16 + tid; e < span_halves; e += NT) xin0[b * xin_halves + e] = (half_t)0.0f;   // tails read by conv3's zero-padded k columns
+    for (int e = tid; e < PIPE_PW * PIPE_A1R * C16; e += NT) a1all[e] = (half_t)0.0f;    // rows under conv2's zero-padded k columns: never anything but finite values
+    __syncthreads();
+
+    if (wave >= PIPE_CW) {
+        // ---- producers: signal -> conv1 -> conv2 -> span buffer it & 1 ------------------------------------------------------------
+        // One producer shares its SIMD with two consumers, and it is the youngest of the three: at equal priority it gets the issue slots
+        // the consumers leave, finishes its block behind them and the barrier waits for it (2048 x 10000: 1.50 ms; with the producers
+        // at priority 1 1.31, the consumers taking what is left of a SIMD they cannot fill alone)
+        __builtin_amdgcn_s_setprio(1);
+        const int pw = wave - PIPE_CW;
+        half_t* a1 = a1all + pw * PIPE_A1R * C16;
+        float* sl = slall + pw * PIPE_SG;
+        const int kp2 = ((q.K2 * 16 + 31) >> 5) << 5;
+        half8_t a2[3];
+#pragma unroll
+        for (int ks = 0; ks < 3; ++ks) {
+            a2[ks] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+            if (ks * 32 < kp2) a2[ks] = *(const half8_t*)(q.w2pk + (long)r * kp2 + kg * 8 + ks * 32);
+        }
+        float b2v[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) b2v[g] = q.b2 ? q.b2[kg * 4 + g] : 0.0f;
+        const int c0t = (lane & 1) * 8;
+        float w1r[8][5], w1b[8];
+        if (q.K1 == 5) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                w1b[c] = bl[c0t + c];
+#pragma unroll
+                for (int k = 0; k < 5; ++k) w1r[c][k] = wl[(c0t + c) * 5 + k];
+            }
+        }
+        const int halo = q.K2 - 1;
+        half_t sv[PIPE_NSV];
+        auto fetch = [&](const half_t* sg, int s0, int len) {             // samples s0 + lane, s0 + lane + 64 of the chunk, zero outside it
+#pragma unroll
+            for (int u = 0; u < PIPE_NSV; ++u) {
+                const int i = lane + 64 * u, pos = s0 + i;
+                sv[u] = (half_t)0.0f;
+                if (i < len && pos >= 0 && pos < q.L0) sv[u] = sg[pos];
+            }
+        };
+        __builtin_amdgcn_s_waitcnt(0x0F70);                               // vmcnt(0): conv2's fragments have landed; inside the loop only samples are in flight
+        for (int it = 0; it <= nrun; ++it) {
+            if (it < nrun) {
+                const int item = first + it, n = item / nb, t0 = (item - n * nb) * PB;
+                half_t* xin = xin0 + (it & 1) * xin_halves;
+                const int p3_start = t0 * p.stride - p.pad;               // conv2 position of span row 0
+                const int vt = min(PB, (p.Lout - t0 + 15) & ~15);         // positions of this block's tiles
+                const int rows = min(span_pos, (vt - 1) * p.stride + 2 * NKS);   // span rows they read
+                const int ntl = (rows + 15) >> 4;
+                const int tlo = ntl * pw / PIPE_PW, thi = ntl * (pw + 1) / PIPE_PW;   // this wave's tiles
+                const half_t* sg = q.sig + (long)n * q.L0;
+                for (int ts = tlo; ts < thi; ts += PIPE_SL / 16) {
+                    const int nt = min(PIPE_SL / 16, thi - ts);
+                    const int r0 = ts * 16;                               // span row of the slice's first conv2 row
+                    // a1 row i = conv1 position u0 + i; its first tap = signal position s0 + i = strip element i
+                    const int u0 = p3_start + r0 - q.pad2, s0 = u0 - q.pad1;
+                    const bool head = ts == tlo;
+                    wave_lds_sync();                                      // the previous slice's reads of the strip and of a1 are issued
+                    // the strip (at most PIPE_SG - 4 samples, two per lane): the head slice fetches its own, every other slice finds
+                    // its samples in registers, requested one slice earlier
+                    if (head) fetch(sg, s0, nt * 16 + halo + q.K1 - 1);
+#pragma unroll
+                    for (int u = 0; u < PIPE_NSV; ++u)
+                        if (lane + 64 * u < nt * 16 + halo + q.K1 - 1) sl[lane + 64 * u] = (float)sv[u];
+                    if (ts + PIPE_SL / 16 < thi) fetch(sg, s0 + PIPE_SL, min(PIPE_SL / 16, thi - ts - PIPE_SL / 16) * 16 + halo + q.K1 - 1);
+                    if (!head && lane < 2 * halo)                         // the halo rows: the last K2 - 1 conv1 rows of the previous (full) slice
+                        *(half8_t*)(a1 + lane * 8) = *(const half8_t*)(a1 + PIPE_SL * C16 + lane * 8);
+                    wave_lds_sync();
+                    const int i_lo = head ? 0 : halo, i_hi = nt * 16 + halo;
+                    if (q.K1 == 5) {
+                        for (int w = 2 * i_lo + lane; w < 2 * i_hi; w += 64) {       // eight channels (c0t) of one position, as conv_front3_kernel
+                            const int i = w >> 1;
+                            const int u = u0 + i;
+                            const float* x = sl + i;
+                            const float x0 = x[0], x1 = x[1], x2 = x[2], x3 = x[3], x4 = x[4];
+                            float av[8];
+#pragma unroll
+                            for (int c = 0; c < 8; ++c) {
+                                float a = w1b[c];
+                                a = fmaf(w1r[c][0], x0, a);
+                                a = fmaf(w1r[c][1], x1, a);
+                                a = fmaf(w1r[c][2], x2, a);
+                                a = fmaf(w1r[c][3], x3, a);
+                                a = fmaf(w1r[c][4], x4, a);
+                                av[c] = a;
+                            }
+                            if (q.act1 == ACT_SWISH) {
+#pragma unroll
+                                for (int c = 0; c < 8; ++c) av[c] = swishf_(av[c]);
+                            } else {
+#pragma unroll
+                                for (int c = 0; c < 8; ++c) av[c] = apply_act_rt(av[c], q.act1);
+                            }
+                            const bool inside = u >= 0 && u < q.L1;
+                            half8_t o;
+#pragma unroll
+                            for (int c = 0; c < 8; ++c) o[c] = inside ? (half_t)clamp_med3(av[c], q.lo1, q.hi1) : (half_t)0.0f;
+                            *(half8_t*)(a1 + i * C16 + c0t) = o;
+                        }
+                    } else
+                    for (int w = 2 * i_lo + lane; w < 2 * i_hi; w += 64) {           // generic tap count
+                        const int i = w >> 1;
+                        const int u = u0 + i;
+                        const float* x = sl + i;
+                        half8_t o;
+#pragma unroll
+                        for (int c = 0; c < 8; ++c) {
+                            const float* wr = wl + (c0t + c) * q.K1;
+                            float a = bl[c0t + c];
+                            for (int k = 0; k < q.K1; ++k) a = fmaf(wr[k], x[k], a);
+                            a = apply_act_rt(a, q.act1);
+                            const half_t hv = (half_t)fminf(fmaxf(a, q.lo1), q.hi1);
+                            o[c] = (u >= 0 && u < q.L1) ? hv : (half_t)0.0f;          // outside conv1's output: conv2's zero padding
+                        }
+                        *(half8_t*)(a1 + i * C16 + c0t) = o;
+                    }
+                    wave_lds_sync();
+                    // conv2 of the slice's tiles (K = K2 * 16 halves of a row run, padded to 96 with zero weights)
+#pragma unroll
+                    for (int tt = 0; tt < PIPE_SL / 16; ++tt) {
+                        if (tt < nt) {
+                            const half_t* xrow = a1 + (tt * 16 + r) * C16 + kg * 8;
+                            float4_t acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                            for (int ks = 0; ks < 3; ++ks) acc = mfma16(a2[ks], *(const half8_t*)(xrow + ks * 32), acc);
+                            const int j = r0 + tt * 16 + r;               // span row = conv2 position p3_start + j
+                            const int v = p3_start + j;
+                            float xv[4];
+#pragma unroll
+                            for (int g = 0; g < 4; ++g) xv[g] = acc[g] + b2v[g];
+                            if (q.act2 == ACT_SWISH) {
+#pragma unroll
+                                for (int g = 0; g < 4; ++g) xv[g] = swishf_(xv[g]);
+                            } else {
+#pragma unroll
+                                for (int g = 0; g < 4; ++g) xv[g] = apply_act_rt(xv[g], q.act2);
+                            }
+                            const bool inside = v >= 0 && v < q.L2;       // outside conv2's output: conv3's zero padding
+                            half4_t o;
+#pragma unroll
+                            for (int g = 0; g < 4; ++g) o[g] = inside ? (half_t)clamp_med3(xv[g], q.lo2, q.hi2) : (half_t)0.0f;
+                            if (j < span_pos) *(half4_t*)(xin + j * C16 + kg * 4) = o;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    } else {
+        // ---- consumers: conv3 (conv_ws_kernel's loop) on span buffer (it - 1) & 1 ---------------------------------------------------
+        half8_t afr[FPW][NKS];
+#pragma unroll
+        for (int f = 0; f < FPW; ++f) {
+            const half_t* wrow = p.wpk + (long)((wave * FPW + f) * 16 + r) * p.Kp + kg * 8;
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) afr[f][ks] = *(const half8_t*)(wrow + ks * 32);
+        }
+        const int RS = p.stride * C16;
+        // the fragments have landed before the loop: a wait for them inside it would also wait, block after block, for the output stores
+        // (loads and stores share one in-order counter)
+        __builtin_amdgcn_s_waitcnt(0x0F70);                                   // vmcnt(0)
+        for (int it = 0; it <= nrun; ++it) {
+            if (it >= 1) {
+                const int item = first + it - 1, n = item / nb, t0 = (item - n * nb) * PB;
+                const half_t* xin = xin0 + ((it - 1) & 1) * xin_halves;
+                // the lane's row and k-group are derived again for every block: held across the loop, the addresses made of them are
+                // spilled (the weight fragments leave no register), and a reload from scratch waits for the block's output stores
+                int ln;
+                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+                const int r = ln & 15, kg = ln >> 4;
+                for (int pt = 0; pt < PB / 16; ++pt) {
+                    const int t = t0 + pt * 16 + r;
+                    if (t0 + pt * 16 >= p.Lout) break;
+                    const half_t* xrow = xin + (pt * 16 + r) * RS + kg * 8;
+                    half8_t b[NKS];
+#pragma unroll
+                    for (int ks = 0; ks < NKS; ++ks) b[ks] = *(const half8_t*)(xrow + ks * 32);
+                    float4_t acc[FPW];
+#pragma unroll
+                    for (int f = 0; f < FPW; ++f) acc[f] = float4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+                        for (int f = 0; f < FPW; ++f) acc[f] = mfma16(afr[f][ks], b[ks], acc[f]);
+                    // the biases come from LDS tile by tile (the offset is opaque, so that the reads stay in this loop): the weight
+                    // fragments leave no twelve registers to hold them in, and spilled fragments are reloaded in this loop
+                    int bo = (wave * FPW * 16 + kg * 4) * 4;
+                    asm volatile("" : "+v"(bo));
+#pragma unroll
+                    for (int f = 0; f < FPW; ++f) {
+                        const float4_t bv = *(const float4_t*)((const char*)b3l + bo + f * 64);
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) acc[f][g] += bv[g];
+                    }
+                    switch (p.act) {
+                        case ACT_SWISH:
+#pragma unroll
+                            for (int f = 0; f < FPW; ++f)
+#pragma unroll
+                                for (int g = 0; g < 4; ++g) acc[f][g] = swishf_(acc[f][g]);
+                            break;
+                        case ACT_TANH:
+#pragma unroll
+                            for (int f = 0; f < FPW; ++f)
+#pragma unroll
+                                for (int g = 0; g < 4; ++g) acc[f][g] = tanhf_(acc[f][g]);
+                            break;
+                        case ACT_RELU:
+#pragma unroll
+                            for (int f = 0; f < FPW; ++f)
+#pragma unroll
+                                for (int g = 0; g < 4; ++g) acc[f][g] = fmaxf(acc[f][g], 0.0f);
+                            break;
+                        default: break;
+                    }
+                    if (t < p.Lout) {
+                        half_t* drow = p.out + (long)n * p.os_n + (long)t * p.os_t + kg * 4;
+#pragma unroll
+                        for (int f = 0; f < FPW; ++f) {
+                            half4_t o;
+#pragma unroll
+                            for (int g = 0; g < 4; ++g) o[g] = (half_t)clamp_med3(acc[f][g], p.clamp_lo, p.clamp_hi);
+                            *(half4_t*)(drow + (wave * FPW + f) * 16) = o;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 }  // namespace bh
 
 // bh_k_conv_last_kernel (test hook, not thread-safe): the bh_conv_kernel code of the last convolution launch of this process
@@ -556,6 +854,8 @@ int bh_k_conv_first(const void* signal, const float* w, const float* bias, void*
 // bh::g_opt (options.h), as this file reads it:
 // conv_ws 0: always the generic implicit-GEMM kernel (A/B, regression tests)
 // conv_fuse 0: the three separate kernels instead of conv_front3_kernel (A/B, regression tests)
+// conv_front_pipe 0: conv_front3_kernel<3, 10, 8> instead of conv_front3_pipe_kernel for the 384-channel stacks (A/B, byte reference)
+// conv_front_wgs: cap of conv_front3_pipe_kernel's grid (0: one workgroup per CU; tests use it to make a workgroup walk several blocks of a small shape)
 // conv_fs 0: never the feature-split instance of conv_igemm_kernel (A/B, tests)
 // conv_lds_kb: LDS a workgroup of conv_igemm_kernel may take for its input span; the positions per
                         // workgroup follow. Measured on the v5 sup model (256 x 12000, conv class per batch): position-split instances
@@ -622,6 +922,11 @@ static size_t conv_front3_lds(int K1, int K2, int K3, int s3) {
     return ((span * 16 + 40 + 7) & ~(size_t)7) * 2 + (size_t)(256 + K2 - 1 + 6) * 16 * 2 + (span + K2 + K1 + 6) * 4 + (size_t)(16 * K1 + 16) * 4;
 }
 static int conv_front3_kp(int K3) { return ((K3 * 16 + 31) / 32) * 32; }
+// conv_front3_pipe_kernel: two span buffers, the producers' conv1 buffers and signal strips, conv1's weights, conv3's bias (at most 128 KiB: stride 7, 20 taps)
+static size_t conv_front3_pipe_lds(int K1, int K3, int s3) {
+    const size_t span = (size_t)255 * s3 + K3;
+    return 2 * ((span * 16 + 40 + 7) & ~(size_t)7) * 2 + (size_t)bh::PIPE_PW * bh::PIPE_A1R * 16 * 2 + (size_t)bh::PIPE_PW * bh::PIPE_SG * 4 + (size_t)(16 * K1 + 16 + 384) * 4;
+}
 int bh_k_conv_front3_shape_ok(int K1, int K2, int c3_out, int K3, int s3) {
     if (K1 < 1 || K1 > 8 || K2 < 1 || K2 * 16 > 96 || K3 < 1 || s3 < 1) return 0;
     if (!(c3_out == 384 || c3_out == 96) || conv_front3_kp(K3) != 320) return 0;
@@ -653,6 +958,21 @@ int bh_k_conv_front3(const void* signal, int N, int L0, const float* w1, const f
     ConvFront3Args a{(const half_t*)signal, w1, b1, (const half_t*)w2pk, b2, L0, L1, L2, K1, pad1, act1, K2, pad2, act2, lo1, hi1, lo2, hi2,
                      ConvArgs{nullptr, (const half_t*)w3pk, b3, (half_t*)out, N, L2, L3, 16, Cout3, K3, stride3, pad3, act3, conv_front3_kp(K3), lo3, hi3,
                               os_n, os_t}};
+    if (Cout3 == 384 && bh::g_opt.conv_front_pipe) {
+        // the pipelined instance: a persistent grid of at most one workgroup per CU, each with a contiguous run of the N * nb blocks
+        const size_t plds = conv_front3_pipe_lds(K1, K3, stride3);
+        const int nb = (L3 + 255) / 256;
+        const long total = (long)N * nb;
+        BH_REQUIRE(total < (1l << 30), "conv_front3: %ld blocks are more than the pipelined kernel indexes", total);
+        long wgs = bh_cu_count() > 0 ? bh_cu_count() : 256;
+        if (bh::g_opt.conv_front_wgs > 0 && bh::g_opt.conv_front_wgs < wgs) wgs = bh::g_opt.conv_front_wgs;
+        if (wgs > total) wgs = total;
+        BH_CHECK_HIP(bh_max_lds((const void*)conv_front3_pipe_kernel<3, 10>, (int)plds));
+        hipLaunchKernelGGL((conv_front3_pipe_kernel<3, 10>), dim3((unsigned)wgs), dim3(64 * (PIPE_CW + PIPE_PW)), plds, stream, a, nb, (int)total);
+        BH_CHECK_HIP(hipGetLastError());
+        g_conv_last_kernel = BH_CONV_K_FRONT3_384;
+        return 0;
+    }
     const size_t lds = conv_front3_lds(K1, K2, K3, stride3);
     const dim3 grid((L3 + 255) / 256, N);
     if (Cout3 == 384) {

@@ -30,6 +30,8 @@ static constexpr OptionRow OPTION_TABLE[] = {
     {BH_OPT(conv_fs), 1, Norm::keep, "feature-split instances of the implicit-GEMM convolution: 1 on, 0 = position-split"},
     {BH_OPT(conv_fuse), 1, Norm::keep, "conv1 -> conv2 -> conv3 as one kernel: 1 = 384-channel stacks, 2 = also 96-channel, 0 = three kernels"},
     {BH_OPT(conv_lds_kb), 64, Norm::positive_or_def, "KiB of LDS a workgroup of the implicit-GEMM convolution may take for its input span"},
+    {BH_OPT(conv_front_pipe), 1, Norm::keep, "fused front end of the 384-channel stacks: 1 = conv1 / conv2 of the next block beside conv3 (12-wave pipeline), 0 = phase after phase (same bytes)"},
+    {BH_OPT(conv_front_wgs), 0, Norm::keep, "workgroups of the pipelined front end: 0 = one per CU, n > 0 caps the grid (same bytes; test hook, A/B)"},
     {BH_OPT(lstm_max_spins), 1000000, Norm::nonneg_or_def, "bound of the recurrent kernels' exchange spin loops (0: the first incomplete poll round is a timeout)"},
     {BH_OPT(lstm_q8_variant), 0, Norm::keep, "geometry of the 8-bit recurrent kernel, read at bh_encoder_create: 0, 1, 2"},
 };

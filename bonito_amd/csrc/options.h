@@ -28,6 +28,8 @@ struct Options {
     int conv_fs = 1;
     int conv_fuse = 1;
     int conv_lds_kb = 64;
+    int conv_front_pipe = 1;    // conv_front3_pipe_kernel for the 384-channel stacks
+    int conv_front_wgs = 0;     // cap of its grid (0 = one workgroup per CU)
     // lstm.hip, lstm_q8.hip, engine.cpp
     int lstm_max_spins = 1000000;     // never negative (the table's normalisation); the kernels take it as unsigned
     int lstm_q8_variant = 0;          // read by bh_encoder_create

@@ -354,6 +354,12 @@ int bh_lstm_layer_family(const void* x, const float* w_ih, const float* w_hh, co
  *                for the 96-channel stacks, 0 = three kernels. "conv_fs": 1 (default) = feature-split instances of the implicit-GEMM
  *                kernel for layers with a multiple of 64 output channels, 0 = position-split. "conv_lds_kb": LDS a workgroup of that
  *                kernel may take for its input span (default 64; values <= 0 restore it). All of them: identical bytes (tests).
+ *   "conv_front_pipe": 1 (default) = the fused front end of a 384-channel stack as a pipeline: 12-wave workgroups, one per CU, each
+ *                walking a contiguous run of 256-position blocks; four waves compute conv1 / conv2 of the next block into a second
+ *                LDS span buffer while eight waves run conv3 of the current one. 0 = the phase-after-phase kernel (one 8-wave
+ *                workgroup per block), which also serves the 96-channel stacks. Identical bytes.
+ *   "conv_front_wgs": 0 (default) = one workgroup of the pipelined front end per CU; n > 0 caps the grid at n workgroups, so that a
+ *                workgroup walks more blocks (test hook and A/B knob). Identical bytes.
  *   "gemm_path": 0 auto (default), 1 = register-staged 128x128x64 kernel only, 2 = never a 256x256x64 kernel, 3 = never the
  *                four-wave kernel (gemm_w4_kernel; the eight-wave one where it applies), 5 = the four-wave kernel for every legal shape.
  *   "gemm_tile16": 1 (default) = the four-wave kernel's K-tile stream on 16x16x32 MFMAs with its epilogues in the accumulator layout,
@@ -452,7 +458,8 @@ int bh_conv1d(const void* in, const void* wpacked, const float* bias, void* out,
  * w3packed = bh_conv1d_pack(16, Cout3, K3); out (n*os_n + t*os_t + c), os_n and os_t multiples of 4.
  * Shapes with an instance: 1 <= K1 <= 8, K2 <= 6, Cout3 384 or 96, K3 19 or 20 (ten k-steps of 32), stride3 small enough for the
  * workgroup's LDS (<= 7 at these sizes). Anything else is an error (nonzero return, nothing launched, output untouched). The process-wide
- * options "conv_fuse" / "conv_ws" decide what the ENGINE runs; this entry point does not read them. */
+ * options "conv_fuse" / "conv_ws" decide what the ENGINE runs; this entry point does not read them. It reads "conv_front_pipe" and
+ * "conv_front_wgs", which pick between the two 384-channel instances and size the pipelined one's grid (identical bytes). */
 int bh_conv1d_front3(const void* signal, int N, int L0, const float* w1, const float* b1, int K1, int pad1, int act1, float lo1,
                      float hi1, const void* w2packed, const float* b2, int K2, int pad2, int act2, float lo2, float hi2,
                      const void* w3packed, const float* b3, int Cout3, int K3, int stride3, int pad3, int act3, float lo3,
@@ -465,7 +472,7 @@ enum bh_conv_kernel {
     BH_CONV_K_FIRST = 1,          /* conv_first_kernel */
     BH_CONV_K_WS_384 = 20,        /* conv_ws_kernel<3, 10, 8>: weight-stationary, 384 channels */
     BH_CONV_K_WS_96 = 21,         /* conv_ws_kernel<1, 10, 6>: 96 channels */
-    BH_CONV_K_FRONT3_384 = 30,    /* conv_front3_kernel<3, 10, 8> */
+    BH_CONV_K_FRONT3_384 = 30,    /* conv_front3_kernel<3, 10, 8>, or conv_front3_pipe_kernel<3, 10> under "conv_front_pipe" */
     BH_CONV_K_FRONT3_96 = 31,     /* conv_front3_kernel<1, 10, 6> */
     BH_CONV_K_DWCONV = 40,        /* dwconv_kernel */
     BH_CONV_K_IGEMM_BASE = 100    /* conv_igemm_kernel<NTT, FS>: 100 + 10 * NTT + FS, NTT in 1 / 2 / 4 (64 / 128 / 256 positions per workgroup) */
