@@ -110,6 +110,7 @@ SIGNATURES = {
     "bh_lstm_layer": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "bh_lstm_q8_layer": (_i, [_vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "bh_lstm_layer_family": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "bh_lstm_launch_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i]),
     "bh_encoder_debug_read": (_i, [_vp, _vp, _sz, _sz]),
     "bh_encoder_set_option": (_i, [_vp, C.c_char_p, _i]),
 }

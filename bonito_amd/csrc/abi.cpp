@@ -161,19 +161,19 @@ extern "C" int bh_lstm_layer(const void* gates_in, const void* whh_packed, void*
     BH_REQUIRE(T > 0, "lstm_layer: T must be positive");
     int rc = bh_k_fill_u16(h_out, 0xFFFFu, (size_t)T * N * H, (hipStream_t)stream);
     if (rc) return rc;
-    if (H > 512 || (flags & 2)) {     // flags bit 1: force the weight-streaming kernel
-        const int per = std::max(8, bh_k_lstm_geometry(BH_LSTM_STREAM, H).rings_per_launch(bh_cu_count()));
-        for (int r0 = 0; r0 < N / 16; r0 += per) {
-            const int nr = std::min(per, N / 16 - r0);
-            rc = bh_k_lstm_layer_stream((const char*)gates_in + (size_t)r0 * 16 * 4 * H * 2, whh_packed,
-                                        (char*)h_out + (size_t)r0 * 16 * H * 2, T, N, H, reverse, err_flag,
-                                        (hipStream_t)stream, nr, (int*)workspace, flags & 1);
-            if (rc) return rc;
-        }
-        return 0;
-    }
-    return bh_k_lstm_layer(gates_in, whh_packed, h_out, T, N, H, reverse, err_flag, (hipStream_t)stream, N / 16,
-                           (int*)workspace, flags & 1);
+    bh_lstm_launch layer{};
+    layer.family = H > 512 || (flags & 2) ? BH_LSTM_STREAM : BH_LSTM_WAVE;     // flags bit 1: force the weight-streaming kernel
+    layer.input = gates_in; layer.w_hh = whh_packed; layer.h_out = h_out;
+    layer.T = T; layer.N = N; layer.H = H;
+    layer.R = layer.n_rings = N / 16;
+    layer.reverse = reverse;
+    layer.err_flag = err_flag; layer.xcc_ws = (int*)workspace;
+    layer.write_through = flags & 1;
+    // the streaming kernel's batch is split (at 8 rings even where the device holds fewer: the launch then says so); the
+    // register-resident kernel's is one launch
+    const bh_lstm_instance* row = bh_k_lstm_find(layer.family, H, 0);
+    const int per = layer.family == BH_LSTM_STREAM && row ? std::max(8, row->geo.rings_per_launch(bh_cu_count())) : std::max(1, layer.R);
+    return bh_k_lstm_run_layer(layer, per, false, (hipStream_t)stream);
 }
 // Operator level (parity tests): one Q8-1 recurrent layer straight from fp32 host weights. Packs, uploads, quantises x with
 // the static scale 127 / bound, runs the 8-bit kernel and synchronises. `sums` (optional) receives the exact int32 partial sums
@@ -218,80 +218,50 @@ extern "C" int bh_lstm_q8_layer(const void* x, float bound, const float* w_ih, c
     return 0;
 }
 // Operator level (parity tests): one fp16 recurrent layer on a chosen kernel family from fp32 host weights, packed by the functions
-// bh_encoder_create packs with (bh_lstm_pack_whh, lstm_pack.h) and launched once the way forward_lstm launches it.
-static bool lstm_family_serves(int family, int H) {
-    switch (family) {
-        case BH_LSTM_WAVE:
-        case BH_LSTM_FUSED: return H > 0 && H % 32 == 0 && H <= 512;
-        case BH_LSTM_STREAM: return bh_lstm_stream_ok(H);
-        case BH_LSTM_WGX:
-        case BH_LSTM_WGX2: return H > 0 && bh_k_lstm_wg_units(H) != 0;
-        case BH_LSTM_CTA: return H > 0 && bh_k_lstm_cta_units(H) != 0 && bh_k_lstm_cta_units(H) == bh_k_lstm_wg_units(H);
-        case BH_LSTM_WIDE: return bh_k_lstm_wide_ok(H) != 0;
-        default: return false;
-    }
-}
+// bh_encoder_create packs with (lstm_pack.h), in the layouts the instance wants, and launched the way forward_lstm launches it.
 extern "C" int bh_lstm_layer_family(const void* x, const float* w_ih, const float* w_hh, const float* bias, int T, int N, int H,
                                     int reverse, int family, int flags, void* h_out, void* stream_) {
     BH_REQUIRE(x && w_ih && w_hh && h_out && x != h_out, "lstm_layer_family: null pointer, or x and h_out are one buffer");
     BH_REQUIRE(T > 0 && N > 0 && H > 0, "lstm_layer_family: T, N, H must be positive");
     BH_REQUIRE(family >= BH_LSTM_WAVE && family < BH_LSTM_Q8, "lstm_layer_family: family %d is not an fp16 family (the 8-bit path: bh_lstm_q8_layer)", family);
-    BH_REQUIRE(lstm_family_serves(family, H), "lstm_layer_family: family %d has no instance for hidden size %d", family, H);
-    BH_REQUIRE((flags & ~(family == BH_LSTM_WIDE ? 3 : 1)) == 0, "lstm_layer_family: flags %d not understood by family %d", flags, family);
+    const bh_lstm_instance* row = bh_k_lstm_find(family, H, flags & BH_LSTM_V_OUTPUT);
+    BH_REQUIRE(bh_k_lstm_serves(family, H), "lstm_layer_family: family %d has no instance for hidden size %d", family, H);
+    BH_REQUIRE(row && (flags & ~(BH_LSTM_V_OUTPUT | 1)) == 0, "lstm_layer_family: flags %d not understood by family %d", flags, family);
     BH_REQUIRE(((uintptr_t)h_out & 15) == 0 && ((uintptr_t)x & 15) == 0, "lstm_layer_family: x and h_out must be 16-byte aligned");
-    const bh_lstm_family fam = (bh_lstm_family)family;
-    const bh_lstm_geometry geo = bh_k_lstm_geometry(fam, H);
+    const bh_lstm_geometry& geo = row->geo;
     BH_REQUIRE(N % geo.ring_chunks == 0, "lstm_layer_family: batch %d is no multiple of the family's ring of %d chunks", N, geo.ring_chunks);
     const int R = N / geo.ring_chunks, per = geo.rings_per_launch(bh_cu_count());
     BH_REQUIRE(R <= per, "lstm_layer_family: %d rings, one launch of family %d holds %d at hidden size %d", R, family, per, H);
     hipStream_t st = (hipStream_t)stream_;
-    const bool gemm = fam == BH_LSTM_WAVE || fam == BH_LSTM_STREAM || fam == BH_LSTM_WIDE;
-    const bool tiles = fam == BH_LSTM_WGX || fam == BH_LSTM_WGX2 || fam == BH_LSTM_CTA;
-    const bool ring = fam == BH_LSTM_WGX || fam == BH_LSTM_WGX2 || (fam == BH_LSTM_WIDE && !(flags & 2));
-    const int slow = flags & 1;
     const size_t nw = (size_t)4 * H * H;
     DevBuf d_wih, d_whh, d_b, gates, ex, ws, err;
     std::vector<uint16_t> pk(nw);
-    std::vector<float> b((size_t)4 * H, 0.0f);
-    if (bias) memcpy(b.data(), bias, sizeof(float) * 4 * H);
-    if (fam == BH_LSTM_WIDE) {
-        std::vector<float> wp(nw), bp((size_t)4 * H);
-        lstm_wide_permute(w_ih, bias, nullptr, H, H, wp.data(), bp.data());
-        if (upload_f16(d_wih, wp.data(), nw) || upload_f32(d_b, bp.data(), bp.size())) return -1;
-        if (lstm_pack_tiles(w_hh, H, LSTM_WIDE_MT, pk.data()) || upload(d_whh, pk.data(), nw * 2)) return -1;
-    } else {
-        if (upload_f32(d_b, b.data(), b.size())) return -1;
-        if (tiles) {
-            const int MT = bh_k_lstm_wg_units(H) / 4;
-            if (lstm_pack_tiles(w_ih, H, MT, pk.data()) || upload(d_wih, pk.data(), nw * 2)) return -1;
-            if (lstm_pack_tiles(w_hh, H, MT, pk.data()) || upload(d_whh, pk.data(), nw * 2)) return -1;
-        } else {
-            if (gemm) { if (upload_f16(d_wih, w_ih, nw)) return -1; }
-            else if (bh_lstm_pack_whh(w_ih, H, pk.data()) || upload(d_wih, pk.data(), nw * 2)) return -1;
-            if (bh_lstm_pack_whh(w_hh, H, pk.data()) || upload(d_whh, pk.data(), nw * 2)) return -1;
-        }
-    }
+    std::vector<float> b((size_t)4 * H);
+    lstm_pack_bias(row->w_ih, bias, nullptr, H, b.data());
+    if (upload_f32(d_b, b.data(), b.size())) return -1;
+    if (lstm_pack(row->w_ih, row->mt, w_ih, H, H, pk.data()) || upload(d_wih, pk.data(), nw * 2)) return -1;
+    if (lstm_pack(row->w_hh, row->mt, w_hh, H, H, pk.data()) || upload(d_whh, pk.data(), nw * 2)) return -1;
     if (ws.alloc(bh_k_lstm_ws_bytes(N, 1024)) || err.alloc(sizeof(int))) return -1;
-    if (gemm && gates.alloc((size_t)T * N * 4 * H * 2 + 256)) return -1;
-    if (ring && ex.alloc((fam == BH_LSTM_WIDE ? bh_k_lstm_wide_ex_bytes(N, H) : bh_k_lstm_wgx_ex_bytes(N, H)) + 256)) return -1;
+    if (!row->projects && gates.alloc((size_t)T * N * 4 * H * 2 + 256)) return -1;
+    if (row->ex_bytes && ex.alloc((size_t)4 * R * row->ex_bytes + 256)) return -1;
     BH_CHECK_HIP(hipMemsetAsync(err.p, 0, sizeof(int), st));
     int rc = 0;
-    if (gemm) rc = bh_k_linear(x, d_wih.p, (const float*)d_b.p, gates.p, T * N, 4 * H, H, H, H, 4 * H, bh::ACT_NONE, 1.0f, -INFINITY, INFINITY,
-                               0, 0, 0, 0, 0, st);
-    if (!rc && !ring && fam != BH_LSTM_CTA) rc = bh_k_fill_u16(h_out, 0xFFFFu, (size_t)T * N * H, st);      // hand-off through the output tensor
+    if (!row->projects) rc = bh_k_linear(x, d_wih.p, (const float*)d_b.p, gates.p, T * N, 4 * H, H, H, H, 4 * H, bh::ACT_NONE, 1.0f, -INFINITY,
+                                         INFINITY, 0, 0, 0, 0, 0, st);
+    if (!rc && !row->ex_bytes && !geo.unlimited) rc = bh_k_fill_u16(h_out, 0xFFFFu, (size_t)T * N * H, st);      // hand-off through the output tensor
     if (rc) return rc;
-    const float* bp = (const float*)d_b.p;
-    int* e = (int*)err.p;
-    int* w = (int*)ws.p;
-    switch (fam) {
-        case BH_LSTM_WAVE: rc = bh_k_lstm_layer(gates.p, d_whh.p, h_out, T, N, H, reverse, e, st, R, w, slow); break;
-        case BH_LSTM_STREAM: rc = bh_k_lstm_layer_stream(gates.p, d_whh.p, h_out, T, N, H, reverse, e, st, R, w, slow); break;
-        case BH_LSTM_FUSED: rc = bh_k_lstm_layer_fused(x, d_wih.p, bp, d_whh.p, h_out, T, N, H, reverse, e, st, R, w, slow); break;
-        case BH_LSTM_WGX: rc = bh_k_lstm_layer_wgx(x, d_wih.p, bp, d_whh.p, h_out, ex.p, T, N, H, R, reverse, e, st, R, w, slow, 1); break;
-        case BH_LSTM_WGX2: rc = bh_k_lstm_layer_wgx2(x, d_wih.p, bp, d_whh.p, h_out, ex.p, T, N, H, R, reverse, e, st, R, w, slow, 1); break;
-        case BH_LSTM_CTA: rc = bh_k_lstm_layer_cta(x, d_wih.p, bp, d_whh.p, h_out, T, N, H, reverse, st, R); break;
-        default: rc = bh_k_lstm_layer_wide(gates.p, d_whh.p, h_out, T, N, H, reverse, e, st, R, w, slow, ring ? ex.p : nullptr, R, 1);
-    }
+    bh_lstm_launch layer{};
+    layer.family = (bh_lstm_family)family;
+    layer.input = row->projects ? x : gates.p;
+    layer.w_ih = d_wih.p; layer.w_hh = d_whh.p; layer.bias = (const float*)d_b.p;
+    layer.h_out = h_out;
+    layer.ex = ex.p;
+    layer.T = T; layer.N = N; layer.H = H;
+    layer.R = layer.n_rings = R;
+    layer.reverse = reverse;
+    layer.err_flag = (int*)err.p; layer.xcc_ws = (int*)ws.p;
+    layer.write_through = flags & 1;
+    rc = bh_k_lstm_run_layer(layer, per, false, st);
     if (rc) return rc;
     int flag = 0;
     BH_CHECK_HIP(hipMemcpyAsync(&flag, err.p, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -306,6 +276,9 @@ extern "C" int bh_beam_search(const void* scores, int N, int T, int state_len, i
     BH_REQUIRE(scores && workspace && sequence && qstring && moves, "beam_search: null pointer");
     return bh_k_beam_search(scores, N, T, state_len, beam_width, beam_cut, blank_score, q_scale, q_offset, workspace,
                             sequence, qstring, moves, qfloat, (hipStream_t)stream);
+}
+extern "C" int bh_lstm_launch_plan(int family, int H, int flags, int n_rings, int cu_count, int32_t* out, int n_out) {
+    return bh_k_lstm_launch_plan(family, H, flags, n_rings, cu_count, out, n_out);
 }
 extern "C" int bh_beam_search_plan(int N, int T, int state_len, int cu_count, int debug, int32_t* out, int n_out) {
     return bh_k_beam_search_plan(N, T, state_len, cu_count, debug, out, n_out);

@@ -64,6 +64,10 @@ struct Layer {
     int q_variant = 0;
     float q_bound = 1.0f;
     DevBuf q_wih, q_whh, q_sx, q_sh;
+    // recurrent layer, fp16: W_ih and W_hh in every layout that a kernel family the shape admits wants (kernels.h: bh_lstm_layout;
+    // the tiles are of 4 * lstm_mt units). b0 is b_ih + b_hh in torch order, lstm_bias_wide the same for the wide kernel's gate GEMM.
+    DevBuf lstm_ih[BH_LSTM_W_LAYOUTS], lstm_hh[BH_LSTM_W_LAYOUTS], lstm_bias_wide;
+    int lstm_mt = 0;
 };
 
 enum Layout { L_SIGNAL, L_NLC, L_TNC };
@@ -150,7 +154,7 @@ struct bh_encoder {
     DevBuf t_qkv, t_mid, t_a, t_b, rot;   // transformer workspace + rotary cos/sin table [Tmax][32][2]
     int rot_len = 0;
     int out_features = 0;
-    int lstm_force_slow = 0;
+    int lstm_force_slow = 0, lstm_tune = 0;
     int batch_pad = 16;          // chunks per LSTM ring: 16, or 32 when a wide (H > 512) layer uses two column tiles per ring
     int lstm_wide = 1;           // H > 512: stationary-W_hh kernel with 32-chunk rings (0: weight-streaming kernel)
     int attn_ring = 1;           // transformer: rotary in the Wqkv epilogue + persistent ring-buffer attention kernel
@@ -263,18 +267,22 @@ static int next_kind(const bh_encoder* e, size_t i) {
     return j < e->layers.size() ? e->layers[j].d.kind : 0;
 }
 
-// ---- which recurrent kernel serves a layer (see lstm.hip) ------------------------------------------------------------------------------
-// What a layer's shape admits. bh_encoder_create packs and allocates by these, lstm_plan dispatches by them together with the
+// ---- which recurrent kernel serves a layer (the instance table of lstm.hip) -----------------------------------------------------------
+// What a layer's shape admits: the fp16 families that have an instance for its width and, where the input projection is inside the
+// kernel, whose input is as wide. bh_encoder_create packs and allocates by these rows, lstm_plan dispatches among them by the
 // engine's options: the two cannot disagree.
-static bool lstm_regs_ok(int H) { return H % 32 == 0 && H <= 512; }              // W_hh stays in registers (else: wide or streaming kernel)
-// input projection inside the recurrence: fragment-packed W_ih in w2
-static bool lstm_may_fuse(const bh_layer_t& d) { return d.in_size == d.out_size && lstm_regs_ok(d.out_size); }
-// workgroup-shared kernels (wgx, wgx2, cta): tile-packed W_hh / W_ih in w3 / w4, the ex16 ring buffer
-static bool lstm_may_share(const bh_layer_t& d) { return d.in_size == d.out_size && bh_k_lstm_wg_units(d.out_size) != 0; }
-// wide kernel: W_hh tiles in w3, row-permuted W_ih / bias in w4 / b1, rings of 32 chunks (batch_pad), the ex16 ring buffer
-static bool lstm_may_wide(const bh_layer_t& d) { return bh_k_lstm_wide_ok(d.out_size) != 0; }
+static const bh_lstm_instance* lstm_admits(const bh_layer_t& d, int family, int variant = 0) {
+    const bh_lstm_instance* row = bh_k_lstm_find(family, d.out_size, variant);
+    return row && (!row->projects || d.in_size == d.out_size) ? row : nullptr;
+}
+static std::vector<const bh_lstm_instance*> lstm_admitted(const bh_layer_t& d) {
+    std::vector<const bh_lstm_instance*> rows;
+    for (int f = BH_LSTM_WAVE; f < BH_LSTM_Q8; ++f)
+        if (const bh_lstm_instance* row = lstm_admits(d, f)) rows.push_back(row);
+    return rows;
+}
 // 8-bit kernel: int8 tiles and scales in q_*
-static bool lstm_may_q8(const bh_layer_t& d) {
+static bool lstm_admits_q8(const bh_layer_t& d) {
     return d.quantize && d.in_size == d.out_size && bh_k_lstm_q8_units(d.out_size, bh::g_opt.lstm_q8_variant) != 0;
 }
 
@@ -287,6 +295,7 @@ enum Handoff {
 // change between forwards (bh_encoder_set_option), and describe() must show what the next forward will do.
 struct LstmPlan {
     bh_lstm_family family;          // the kernel of a launch (BH_LSTM_WGX2 only through pair_launch)
+    const bh_lstm_instance* row = nullptr;      // the fp16 instance (null: BH_LSTM_Q8)
     const void* gate_w = nullptr;   // non-null: a GEMM writes the gate pre-activations first, with these weights / bias
     const float* gate_b = nullptr;
     Handoff handoff;
@@ -298,21 +307,27 @@ struct LstmPlan {
 static LstmPlan lstm_plan(const bh_encoder* e, const Layer& l, int Np) {
     const bh_layer_t& d = l.d;
     const int H = d.out_size;
-    const bool regs = lstm_regs_ok(H);
+    const bool regs = lstm_admits(d, BH_LSTM_WAVE);             // W_hh stays in registers (else: wide or streaming kernel)
     const bool q8 = l.q8 && e->lstm_q8 && d.in_size == H;       // clears everything below
-    const bool wide = !q8 && !regs && e->lstm_wide && lstm_may_wide(d);
-    const bool fused = !q8 && e->lstm_fused && lstm_may_fuse(d);
-    const bool share = fused && e->lstm_fused >= 2 && lstm_may_share(d);
-    const bool cta = share && e->lstm_fused >= 3 && bh_k_lstm_cta_units(H) != 0 && bh_k_lstm_cta_units(H) == bh_k_lstm_wg_units(H);
+    const bool wide = !q8 && !regs && e->lstm_wide && lstm_admits(d, BH_LSTM_WIDE);
+    const bool fused = !q8 && e->lstm_fused && lstm_admits(d, BH_LSTM_FUSED);
+    const bool share = fused && e->lstm_fused >= 2 && lstm_admits(d, BH_LSTM_WGX);
+    const bool cta = share && e->lstm_fused >= 3 && lstm_admits(d, BH_LSTM_CTA);
     const bool ring = e->lstm_exchange && e->ex16.p != nullptr;
     LstmPlan p;
     p.family = q8 ? BH_LSTM_Q8 : cta ? BH_LSTM_CTA : share && ring ? BH_LSTM_WGX : fused ? BH_LSTM_FUSED
                : wide ? BH_LSTM_WIDE : regs ? BH_LSTM_WAVE : BH_LSTM_STREAM;
-    if (p.family == BH_LSTM_WIDE) { p.gate_w = l.w4.p; p.gate_b = (const float*)l.b1.p; }
-    else if (p.family == BH_LSTM_WAVE || p.family == BH_LSTM_STREAM) { p.gate_w = l.w0.p; p.gate_b = (const float*)l.b0.p; }
-    p.handoff = p.family == BH_LSTM_CTA ? HANDOFF_LDS
-                : p.family == BH_LSTM_Q8 || p.family == BH_LSTM_WGX || (p.family == BH_LSTM_WIDE && ring) ? HANDOFF_RING : HANDOFF_OUTPUT;
-    p.geo = q8 ? bh_k_lstm_q8_geometry(H, l.q_variant) : bh_k_lstm_geometry(p.family, H);
+    p.handoff = HANDOFF_RING;
+    p.geo = bh_k_lstm_q8_geometry(H, l.q_variant);
+    if (!q8) {
+        p.row = lstm_admits(d, p.family, wide && !ring ? BH_LSTM_V_OUTPUT : 0);
+        p.geo = p.row->geo;
+        p.handoff = p.geo.unlimited ? HANDOFF_LDS : p.row->ex_bytes ? HANDOFF_RING : HANDOFF_OUTPUT;
+        if (!p.row->projects) {
+            p.gate_w = l.lstm_ih[p.row->w_ih].p;
+            p.gate_b = (const float*)(p.row->w_ih == BH_LSTM_W_WIDE_ROWS ? l.lstm_bias_wide : l.b0).p;
+        }
+    }
     p.n_rings = Np / p.geo.ring_chunks;
     p.rings_per_launch = p.geo.rings_per_launch(e->n_cus);
     p.pairs = p.family == BH_LSTM_WGX && e->lstm_pair;
@@ -370,44 +385,34 @@ static int create_lstm(bh_encoder* e, size_t i, const bh_layer_t& d, CreateState
     Layer& L = e->layers[i];
     const int H = d.out_size, I = d.in_size;
     BH_REQUIRE(d.w0 && d.w1 && H > 0 && I > 0, "encoder_create: layer %zu: malformed lstm", i);
-    const bool stream_ok = bh_lstm_stream_ok(H);        // (kernels.h: read off the streaming kernel's instance list)
-    BH_REQUIRE((lstm_regs_ok(H) || stream_ok) && I % 8 == 0,
+    const std::vector<const bh_lstm_instance*> rows = lstm_admitted(d);
+    BH_REQUIRE(!rows.empty() && I % 8 == 0,
                "encoder_create: layer %zu: lstm needs hidden %% 32 == 0 (<= 512) or %% 64 == 0 (<= 1024), insize %% 8 == 0 (got %d, %d)", i, H, I);
-    int rc = upload_f16(L.w0, d.w0, (size_t)4 * H * I);
-    if (!rc) {
-        std::vector<uint16_t> pk((size_t)4 * H * H);
-        rc = bh_lstm_pack_whh(d.w1, H, pk.data());
-        if (!rc) rc = upload(L.w1, pk.data(), pk.size() * 2);
+    std::vector<float> b((size_t)4 * H);
+    lstm_pack_bias(BH_LSTM_W_ROWS, d.b0, d.b1, H, b.data());
+    int rc = upload_f32(L.b0, b.data(), b.size());
+    // each layout once, however many of the admitted instances want it
+    std::vector<uint16_t> pk((size_t)4 * H * std::max(H, I));
+    for (const bh_lstm_instance* row : rows) {
+        if (row->w_ih == BH_LSTM_W_TILES || row->w_hh == BH_LSTM_W_TILES) {
+            BH_REQUIRE(L.lstm_mt == 0 || L.lstm_mt == row->mt, "encoder_create: layer %zu: two tile sizes for hidden size %d", i, H);
+            L.lstm_mt = row->mt;
+        }
+        if (!rc && !L.lstm_ih[row->w_ih].p) {
+            rc = lstm_pack(row->w_ih, row->mt, d.w0, H, I, pk.data());
+            if (!rc) rc = upload(L.lstm_ih[row->w_ih], pk.data(), (size_t)4 * H * I * 2);
+        }
+        if (!rc && !L.lstm_hh[row->w_hh].p) {
+            rc = lstm_pack(row->w_hh, row->mt, d.w1, H, H, pk.data());
+            if (!rc) rc = upload(L.lstm_hh[row->w_hh], pk.data(), (size_t)4 * H * H * 2);
+        }
+        if (!rc && row->w_ih == BH_LSTM_W_WIDE_ROWS && !L.lstm_bias_wide.p) {
+            lstm_pack_bias(row->w_ih, d.b0, d.b1, H, b.data());
+            rc = upload_f32(L.lstm_bias_wide, b.data(), b.size());
+        }
+        e->batch_pad = std::max(e->batch_pad, row->geo.ring_chunks);        // (32: rings of the wide kernel)
     }
-    if (!rc) {
-        std::vector<float> b((size_t)4 * H, 0.0f);
-        for (int j = 0; j < 4 * H; ++j) b[j] = (d.b0 ? d.b0[j] : 0.0f) + (d.b1 ? d.b1[j] : 0.0f);
-        rc = upload_f32(L.b0, b.data(), b.size());
-    }
-    if (!rc && lstm_may_fuse(d)) {      // fragment-packed W_ih for the fused kernel
-        std::vector<uint16_t> pk((size_t)4 * H * H);
-        rc = bh_lstm_pack_whh(d.w0, H, pk.data());
-        if (!rc) rc = upload(L.w2, pk.data(), pk.size() * 2);
-    }
-    if (!rc && lstm_may_wide(d)) {       // wide layer: W_hh tiles of 8 units + W_ih / bias with permuted rows (lstm_pack.h)
-        std::vector<uint16_t> pk((size_t)4 * H * H);
-        rc = lstm_pack_tiles(d.w1, H, LSTM_WIDE_MT, pk.data());
-        if (!rc) rc = upload(L.w3, pk.data(), pk.size() * 2);
-        std::vector<float> wp((size_t)4 * H * I), bp((size_t)4 * H);
-        lstm_wide_permute(d.w0, d.b0, d.b1, H, I, wp.data(), bp.data());
-        if (!rc) rc = upload_f16(L.w4, wp.data(), wp.size());
-        if (!rc) rc = upload_f32(L.b1, bp.data(), bp.size());
-        e->batch_pad = 32;
-    }
-    if (!rc && lstm_may_share(d)) {    // tile-packed pair for the workgroup-shared kernel
-        const int MT = bh_k_lstm_wg_units(H) / 4;
-        std::vector<uint16_t> pk((size_t)4 * H * H);
-        rc = lstm_pack_tiles(d.w1, H, MT, pk.data());
-        if (!rc) rc = upload(L.w3, pk.data(), pk.size() * 2);
-        if (!rc) rc = lstm_pack_tiles(d.w0, H, MT, pk.data());
-        if (!rc) rc = upload(L.w4, pk.data(), pk.size() * 2);
-    }
-    if (!rc && lstm_may_q8(d)) {       // Q8-1 tiles and scales
+    if (!rc && lstm_admits_q8(d)) {       // Q8-1 tiles and scales
         const int U = bh_k_lstm_q8_units(H, bh::g_opt.lstm_q8_variant);
         const size_t tile_bytes = (size_t)4 * H * ((H + 63) / 64 * 64);
         std::vector<int8_t> pk(tile_bytes);
@@ -556,12 +561,11 @@ static int create_workspace(bh_encoder* e, const CreateState& cs) {
         if (e->q_act[0].alloc(ab + 256) || e->q_act[1].alloc(ab + 256) || e->q_ex.alloc((size_t)4 * (Np / 16) * 16 * 1024 + 256))
             return -1;
     }
-    {   // exchange ring buffer of the fp16 workgroup-shared and wide recurrent kernels
+    {   // exchange ring buffer of the fp16 recurrent kernels that hand off through one: [4 time slots][rings]
         size_t exb = 0;
         for (const auto& l : e->layers) {
             if (l.d.kind != BH_LAYER_LSTM) continue;
-            if (lstm_may_share(l.d)) exb = std::max(exb, bh_k_lstm_wgx_ex_bytes(Np, l.d.out_size));
-            if (lstm_may_wide(l.d)) exb = std::max(exb, bh_k_lstm_wide_ex_bytes(Np, l.d.out_size));
+            for (const bh_lstm_instance* row : lstm_admitted(l.d)) exb = std::max(exb, (size_t)4 * (Np / row->geo.ring_chunks) * row->ex_bytes);
         }
         if (exb && e->ex16.alloc(exb + 256)) return -1;
     }
@@ -699,17 +703,14 @@ extern "C" int bh_encoder_describe(const bh_encoder_t* e, char* buf, size_t n) {
             case BH_LAYER_LSTM: {
                 // (at the batch the engine was created for: more rings than one launch holds are served two per workgroup)
                 const LstmPlan p = lstm_plan(e, l, (e->max_batch + e->batch_pad - 1) / e->batch_pad * e->batch_pad);
-                const int H = d.out_size, nks = H / 32, MT = bh_k_lstm_wg_units(H) / 4;
+                const int H = d.out_size;
                 char k[128];
-                switch (p.family) {
-                    case BH_LSTM_Q8: snprintf(k, sizeof(k), "lstm_layer_q8_kernel<%d,%d> (int8 W/x/h, i32 MFMA 16x16x64)", (H + 63) / 64, bh_k_lstm_q8_units(H, l.q_variant) / 4); break;
-                    case BH_LSTM_CTA: snprintf(k, sizeof(k), "lstm_layer_cta_kernel<%d,%d>", nks, MT); break;
-                    case BH_LSTM_WGX: snprintf(k, sizeof(k), "lstm_layer_%s_kernel<%d,%d>", p.pair_launch(p.n_rings) ? "wgx2" : "wgx", nks, MT); break;
-                    case BH_LSTM_FUSED: snprintf(k, sizeof(k), "lstm_layer_fused_kernel<%d>", nks); break;
-                    case BH_LSTM_WIDE: snprintf(k, sizeof(k), "gemm + lstm_layer_wide_kernel<%d,%s>", nks, p.handoff == HANDOFF_RING ? "true" : "false"); break;
-                    case BH_LSTM_WAVE: snprintf(k, sizeof(k), "gemm + lstm_layer_kernel<%d,false>", nks); break;
-                    default: snprintf(k, sizeof(k), "gemm + lstm_layer_kernel<%d,true> (weight streaming)", nks);
-                }
+                if (p.family == BH_LSTM_Q8)
+                    snprintf(k, sizeof(k), "lstm_layer_q8_kernel<%d,%d> (int8 W/x/h, i32 MFMA 16x16x64)", (H + 63) / 64, bh_k_lstm_q8_units(H, l.q_variant) / 4);
+                else
+                    snprintf(k, sizeof(k), "%s%s%s", p.row->projects ? "" : "gemm + ",
+                             (p.pair_launch(p.n_rings) ? bh_k_lstm_find(BH_LSTM_WGX2, H, 0) : p.row)->name,
+                             p.family == BH_LSTM_STREAM ? " (weight streaming)" : "");
                 snprintf(line, sizeof(line), "%d lstm %d%s: %s\n", li, H, d.reverse ? " rev" : "", k);
                 break;
             }
@@ -859,7 +860,7 @@ static int forward_lstm_q8(bh_encoder* e, size_t i, Cursor& c, const LstmPlan& p
                                 hq_out ? (char*)hq_out + (size_t)r0 * tile : nullptr,
                                 h16_out ? (char*)h16_out + (size_t)r0 * 16 * H * 2 : nullptr,
                                 (char*)e->q_ex.p + (size_t)r0 * tile, len, Np, H, R, nr, d.reverse, e->cur_err, st,
-                                (int*)e->lstm_ws.p, e->lstm_force_slow, l.q_variant, nullptr, (unsigned)bh::g_opt.lstm_max_spins);
+                                (int*)e->lstm_ws.p, e->lstm_force_slow | e->lstm_tune << 8, l.q_variant, nullptr, (unsigned)bh::g_opt.lstm_max_spins);
         if (rc) return rc;
     }
     if (next_q8) { c.cur_q = hq_out; c.qi ^= 1; }
@@ -901,37 +902,20 @@ static int forward_lstm(bh_encoder* e, size_t i, Cursor& c) {
     e->prefilled = nullptr;
     if (next_kind(e, i) == BH_LAYER_LSTM) { rc = prefill_next(e, c, i, (size_t)M); if (rc) return rc; }
     ProfSpan span(e, st, BH_PROF_LSTM_REC);
-    const int n_rings = p.n_rings, rev = d.reverse, slow = e->lstm_force_slow;
-    int* ws = (int*)e->lstm_ws.p;
-    const float* bias = (const float*)l.b0.p;
-    for (int r0 = 0; r0 < n_rings;) {
-        // more rings than one launch holds: the ring-buffer kernel carries two rings per workgroup (lstm_layer_wgx2_kernel)
-        const bool pair = p.pair_launch(n_rings - r0);
-        const int nr = std::min(pair ? 2 * p.rings_per_launch : p.rings_per_launch, n_rings - r0);
-        const size_t col = (size_t)r0 * p.geo.ring_chunks;
-        const char* x = (const char*)c.cur + col * H * 2;
-        const char* g = (const char*)e->gates.p + col * 4 * H * 2;
-        char* h = (char*)dst + col * H * 2;
-        char* ex = e->ex16.p ? (char*)e->ex16.p + (size_t)r0 * (p.geo.ring_chunks / 16) * (H / 32) * 1024 : nullptr;
-        switch (pair ? BH_LSTM_WGX2 : p.family) {
-            case BH_LSTM_WGX2:
-                rc = bh_k_lstm_layer_wgx2(x, l.w4.p, bias, l.w3.p, h, ex, len, Np, H, n_rings, rev, e->cur_err, st, nr, ws, slow, r0 == 0);
-                break;
-            case BH_LSTM_WGX:
-                rc = bh_k_lstm_layer_wgx(x, l.w4.p, bias, l.w3.p, h, ex, len, Np, H, n_rings, rev, e->cur_err, st, nr, ws, slow, r0 == 0);
-                break;
-            case BH_LSTM_WIDE:
-                rc = bh_k_lstm_layer_wide(g, l.w3.p, h, len, Np, H, rev, e->cur_err, st, nr, ws, slow,
-                                          p.handoff == HANDOFF_RING ? ex : nullptr, n_rings, r0 == 0);
-                break;
-            case BH_LSTM_CTA: rc = bh_k_lstm_layer_cta(x, l.w4.p, bias, l.w3.p, h, len, Np, H, rev, st, nr); break;
-            case BH_LSTM_FUSED: rc = bh_k_lstm_layer_fused(x, l.w2.p, bias, l.w1.p, h, len, Np, H, rev, e->cur_err, st, nr, ws, slow); break;
-            case BH_LSTM_WAVE: rc = bh_k_lstm_layer(g, l.w1.p, h, len, Np, H, rev, e->cur_err, st, nr, ws, slow); break;
-            default: rc = bh_k_lstm_layer_stream(g, l.w1.p, h, len, Np, H, rev, e->cur_err, st, nr, ws, slow);
-        }
-        if (rc) return rc;
-        r0 += nr;
-    }
+    bh_lstm_launch layer{};
+    layer.family = p.family;
+    layer.input = p.gate_w ? e->gates.p : c.cur;
+    layer.w_ih = l.lstm_ih[p.row->w_ih].p; layer.w_hh = l.lstm_hh[p.row->w_hh].p; layer.bias = (const float*)l.b0.p;
+    layer.h_out = dst;
+    layer.ex = p.handoff == HANDOFF_RING ? e->ex16.p : nullptr;
+    layer.T = len; layer.N = Np; layer.H = H;
+    layer.R = layer.n_rings = p.n_rings;
+    layer.reverse = d.reverse;
+    layer.err_flag = e->cur_err; layer.xcc_ws = (int*)e->lstm_ws.p;
+    layer.write_through = e->lstm_force_slow; layer.tune = e->lstm_tune;
+    // (more rings than one launch holds: the ring-buffer kernel carries two rings per workgroup where the plan pairs)
+    rc = bh_k_lstm_run_layer(layer, p.rings_per_launch, p.pairs, st);
+    if (rc) return rc;
     c.advance(dst); c.C = H;
     return 0;
 }
@@ -1230,7 +1214,7 @@ extern "C" int bh_encoder_debug_read(bh_encoder_t* e, void* host, size_t bytes, 
 }
 extern "C" int bh_encoder_set_option(bh_encoder_t* e, const char* name, int value) {
     BH_REQUIRE(e && name, "encoder_set_option: null argument");
-    if (!strcmp(name, "lstm_force_slow")) { e->lstm_force_slow = (e->lstm_force_slow & ~1) | (value & 1); return 0; }
+    if (!strcmp(name, "lstm_force_slow")) { e->lstm_force_slow = value & 1; return 0; }
     if (!strcmp(name, "lstm_fused")) { e->lstm_fused = value; return 0; }
     if (!strcmp(name, "attn_ring")) { e->attn_ring = value; return 0; }
     if (!strcmp(name, "lstm_wide")) { e->lstm_wide = value; return 0; }
@@ -1240,6 +1224,6 @@ extern "C" int bh_encoder_set_option(bh_encoder_t* e, const char* name, int valu
     if (!strcmp(name, "lstm_pair")) { e->lstm_pair = value; return 0; }
     if (!strcmp(name, "norm_fuse")) { e->norm_fuse = value; return 0; }
     if (!strcmp(name, "gemm_v1")) { bh::g_opt.gemm_path = value; return 0; }   // alias of the process-wide "gemm_path"
-    if (!strcmp(name, "lstm_tune")) { e->lstm_force_slow = (e->lstm_force_slow & 1) | (value << 8); return 0; }
+    if (!strcmp(name, "lstm_tune")) { e->lstm_tune = value; return 0; }
     BH_REQUIRE(false, "encoder_set_option: unknown option '%s'", name);
 }

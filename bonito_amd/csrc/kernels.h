@@ -32,7 +32,7 @@ void bh_k_conv_note_kernel(int code);
 // Launch geometry of a recurrent kernel family: the ONE statement of how many workgroups a launch of n rings takes and, inverted,
 // how many rings fit one launch. The workgroups of a launch spin on each other, so all of them must be resident at once; rings are
 // dealt to the 8 XCDs, hence the groups of 8. The launcher's grid and co-residency guard and every caller that splits a batch
-// (engine.cpp, abi.cpp) read it from here.
+// (bh_k_lstm_run_layer) read it from here.
 // (enum bh_lstm_family: include/bonito_hip.h)
 struct bh_lstm_geometry {
     int ring_chunks = 16;        // chunks per ring
@@ -51,31 +51,68 @@ struct bh_lstm_geometry {
         return wgs_per_group > 0 ? resident(cus) / (8 * wgs_per_group) * 8 * rings_per_slot : 0;
     }
 };
-bh_lstm_geometry bh_k_lstm_geometry(bh_lstm_family family, int H);       // the fp16 families (BH_LSTM_Q8: bh_k_lstm_q8_geometry)
-int bh_k_lstm_layer(const void* gates_in, const void* whh_packed, void* h_out, int T, int N, int H,
-                    int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow);
+// How a recurrent kernel wants a weight matrix laid out (lstm_pack.h packs them).
+enum bh_lstm_layout {
+    BH_LSTM_W_ROWS = 0,        // fp16 rows in torch order: the operand of the gate GEMM
+    BH_LSTM_W_FRAGS,           // per-wave MFMA fragments of 16 units (bh_lstm_pack_whh)
+    BH_LSTM_W_TILES,           // tiles of 4 * MT units per slice (MT: the instance's)
+    BH_LSTM_W_WIDE_ROWS,       // fp16 rows, and the bias, in the wide kernel's gate order: the operand of ITS gate GEMM
+    BH_LSTM_W_LAYOUTS
+};
+constexpr int BH_LSTM_WIDE_MT = 2;      // the wide kernel's tiles: 8 units
+// Variants of an instance (bh_k_lstm_find). BH_LSTM_V_OUTPUT is bit 1 of bh_lstm_layer_family's and bh_lstm_launch_plan's flags.
+enum { BH_LSTM_V_OUTPUT = 2,            // hand-off through the output tensor where the family's default is the ring buffer (wide: RX = false)
+       BH_LSTM_V_STATS = 4 };           // the instance with section stamps, taken under "lstm_tune" bit 2 where it exists
+// One row of the instance table of lstm.hip: a (family, H, variant) that is compiled, with what the kernel was compiled with and what
+// a launch of it needs. The ONE statement of which widths a family serves; every caller reads it from here.
+struct bh_lstm_instance {
+    bh_lstm_family family;
+    int H, variant;
+    int nks, mt, key_flags;     // template key: H / 32, M tiles per wave (0: none), bit 0 = the kernel's STREAM / RX parameter, bit 1 = STATS
+    const void* kernel;
+    const char* name;           // as bh_encoder_describe prints it
+    int args;                   // which argument struct the kernel takes (lstm.hip)
+    int block;
+    int lds_bytes;              // dynamic LDS
+    bool raise_lds;             // the max-dynamic-LDS attribute must be raised first
+    bh_lstm_geometry geo;
+    int slots_per_ring;         // XCD agreement slots (0: no agreement)
+    size_t ex_bytes;            // exchange ring buffer: bytes per ring and time slot (the buffer is [4][R] of them), 0: none
+    bool projects;              // the input projection is inside: reads x [T][N][H] (in_size == H), W_ih and the bias go to the kernel.
+                                // false: reads the gate pre-activations [T][N][4H] of a GEMM with W_ih and the bias
+    bh_lstm_layout w_ih, w_hh;
+};
+const bh_lstm_instance* bh_k_lstm_find(int family, int H, int variant);      // null: no such instance
+inline bool bh_k_lstm_serves(int family, int H) { return bh_k_lstm_find(family, H, 0) != nullptr; }
+// One launch of an fp16 recurrent kernel. The tensors keep the row stride of the whole batch (N chunks = R rings); a launch runs
+// n_rings of them from the pointers it is given.
+struct bh_lstm_launch {
+    bh_lstm_family family;
+    const void* input;          // x or the gate pre-activations (bh_lstm_instance::projects)
+    const void* w_ih;           // in the instance's layouts; w_ih and bias are read by the projecting kernels only
+    const void* w_hh;
+    const float* bias;
+    void* h_out;
+    void* ex;                   // exchange ring buffer, or null: hand-off through the output tensor (which the caller has filled with 0xFFFF)
+    int T, N, H;
+    int R, n_rings;             // ring stride of `ex` = rings of the whole batch; rings of this launch
+    int reverse;
+    int* err_flag;
+    int* xcc_ws;                // bh_k_lstm_ws_bytes
+    int write_through;          // "lstm_force_slow"
+    int tune;                   // "lstm_tune"
+    int arm;                    // fill `ex` with the sentinel first: once per layer
+};
+// The only function that launches an fp16 recurrent kernel.
+int bh_k_lstm_launch(const bh_lstm_launch& l, hipStream_t stream);
+// All rings of a layer (layer.n_rings == layer.R, pointers at ring 0), at most rings_per_launch per launch; `pair`: BH_LSTM_WGX serves
+// more rings than that two per workgroup (BH_LSTM_WGX2, twice as many per launch) instead of in two launches.
+int bh_k_lstm_run_layer(const bh_lstm_launch& layer, int rings_per_launch, bool pair, hipStream_t stream);
+// test hook: the launch bh_k_lstm_launch (BH_LSTM_Q8: bh_k_lstm_layer_q8) would make of n_rings = R rings with `arm` set on a device of
+// `cus` CUs, as BH_LSTM_PLAN_RECORD integers (include/bonito_hip.h lists them); no device call
+int bh_k_lstm_launch_plan(int family, int H, int flags, int n_rings, int cus, int32_t* out, int n_out);
 size_t bh_k_lstm_ws_bytes(int N, int H);
-// The streaming kernel's instances (H / 32; a workgroup serves four slices of 16 units, hence H % 64 == 0): the launcher's dispatch and
-// the predicate bh_encoder_create accepts widths by are both read off this list.
-#define BH_LSTM_STREAM_INSTANCES(X) X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18) X(20) X(22) X(24) X(26) X(28) X(30) X(32)
-static inline bool bh_lstm_stream_ok(int H) {
-    if (H <= 0 || H % 32 != 0) return false;
-#define BH_LSTM_STREAM_HAS(NKS) if (H / 32 == NKS) return true;
-    BH_LSTM_STREAM_INSTANCES(BH_LSTM_STREAM_HAS)
-#undef BH_LSTM_STREAM_HAS
-    return false;
-}
-int bh_k_lstm_layer_stream(const void* gates_in, const void* whh_packed, void* h_out, int T, int N, int H,
-                           int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow);
-int bh_k_lstm_layer_fused(const void* x, const void* wih_packed, const float* bias, const void* whh_packed, void* h_out,
-                          int T, int N, int H, int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws,
-                          int force_slow);
 int bh_k_fill_u16(void* dst, uint16_t value, size_t count, hipStream_t stream);
-size_t bh_k_lstm_packed_bytes(int H);
-int bh_k_lstm_wg_units(int H);
-int bh_k_lstm_cta_units(int H);
-int bh_k_lstm_layer_cta(const void* x, const void* wih_tiles, const float* bias, const void* whh_tiles, void* h_out, int T, int N,
-                        int H, int reverse, hipStream_t stream, int n_rings);
 
 // crf.hip
 int bh_k_crf_viterbi(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score,
@@ -167,11 +204,6 @@ int bh_k_signal_normalise(const int16_t* raw, const long* offs, const float* cal
 int bh_k_signal_chunks(const int16_t* raw, const long* offs, const float* cal_scale, const float* cal_offset, const double* shift,
                        const double* scale, const int* weak, const int* chunk_read, const long* chunk_start, const long* chunk_len,
                        int n_chunks, int L, void* out, hipStream_t stream);
-int bh_k_lstm_wide_ok(int H);
-int bh_k_lstm_layer_wide(const void* gates_perm, const void* whh_tiles, void* h_out, int T, int N, int H, int reverse,
-                         int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow, void* ex = nullptr, int R = 0,
-                         int arm = 0);
-size_t bh_k_lstm_wide_ex_bytes(int N, int H);
 
 // lstm_q8.hip: 8-bit recurrent path Q8-1
 int bh_k_lstm_q8_units(int H, int variant);
@@ -183,10 +215,4 @@ int bh_k_lstm_q8_arm(void* ex, int R, int H, hipStream_t stream);
 int bh_k_lstm_layer_q8(const void* xq, const void* wih, const void* whh, const float* sx, const float* sh, const float* bias,
                        void* hq_out, void* h16_out, void* ex, int T, int N, int H, int R, int n_rings, int reverse, int* err_flag,
                        hipStream_t stream, int* xcc_ws, int flags, int variant, int* dbg, unsigned max_spins);
-size_t bh_k_lstm_wgx_ex_bytes(int N, int H);
-int bh_k_lstm_layer_wgx(const void* x, const void* wih_tiles, const float* bias, const void* whh_tiles, void* h_out, void* ex, int T,
-                        int N, int H, int R, int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow,
-                        int arm);
-int bh_k_lstm_layer_wgx2(const void* x, const void* wih_tiles, const float* bias, const void* whh_tiles, void* h_out, void* ex, int T,
-                        int N, int H, int R, int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow,
-                        int arm);      // two rings per workgroup: n_rings up to twice as many
+int bh_k_lstm_q8_launch_plan(int H, int variant, int n_rings, int cus, int32_t* out);      // bh_k_lstm_launch_plan for BH_LSTM_Q8

@@ -1657,10 +1657,11 @@ __global__ void fill_u16_kernel(uint16_t* dst, uint16_t v, size_t count) {
 
 }  // namespace bh
 
+#include <algorithm>
+
 // Bound of every exchange spin loop (poll rounds): "lstm_max_spins" (options.h), lowered by tests to provoke the timeout path.
 static unsigned max_spins() { return (unsigned)bh::g_opt.lstm_max_spins; }
 
-size_t bh_k_lstm_packed_bytes(int H) { return (size_t)4 * H * H * 2; }
 size_t bh_k_lstm_ws_bytes(int N, int H) {
     // XCD agreement slots + (tune bit 4) per-wave statistics: up to 16 x int64 per (ring, slice)
     const size_t waves = (size_t)((N + 15) / 16) * ((H + 7) / 8);        // up to H/8 slices per ring (wide variant)
@@ -1679,252 +1680,209 @@ int bh_k_fill_u16(void* dst, uint16_t value, size_t count, hipStream_t stream) {
     return 0;
 }
 
-// Launch geometry per kernel family (kernels.h: bh_lstm_geometry). A workgroup is four waves; a wave owns one slice of a ring's
-// hidden units (16 units in the per-wave and streaming kernels, U in the workgroup-shared ones, 8 in the wide one).
-bh_lstm_geometry bh_k_lstm_geometry(bh_lstm_family family, int H) {
-    bh_lstm_geometry g;
-    const int U = bh_k_lstm_wg_units(H);
+// ---- the instances --------------------------------------------------------------------------------------------------------------------
+// One list per kernel template: what is compiled is what is listed, and the table below has one row per entry. NKS = H / 32; a
+// wave of the workgroup-shared kernels (wgx, wgx2, cta) owns U = 4 * MT units. The order is the order the code object's kernels come in.
+#define BH_LSTM_REGISTER_NKS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
+#define BH_LSTM_WAVE_INSTANCES(X) BH_LSTM_REGISTER_NKS(X)           // lstm_layer_kernel<NKS, false>: W_hh in registers, H <= 512
+// lstm_layer_kernel<NKS, true>: a workgroup serves four slices of 16 units, hence H % 64 == 0
+#define BH_LSTM_STREAM_INSTANCES(X) X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18) X(20) X(22) X(24) X(26) X(28) X(30) X(32)
+#define BH_LSTM_FUSED_INSTANCES(X) BH_LSTM_REGISTER_NKS(X)          // lstm_layer_fused_kernel<NKS>
+// lstm_layer_wgx_kernel<NKS, MT>: 4 * U | H and both weight sets fit the register file
+#define BH_LSTM_WGX_INSTANCES(X) X(3, 3) X(6, 3) X(9, 3) X(12, 3) X(2, 4) X(4, 4) X(8, 4)
+// lstm_layer_wgx2_kernel<NKS, MT, STATS>; STATS: section stamps for tools/lstm_stats2.py
+#define BH_LSTM_WGX2_INSTANCES(X) X(12, 3, true) X(3, 3, false) X(6, 3, false) X(9, 3, false) X(12, 3, false) X(2, 4, false) X(4, 4, false) X(8, 4, false)
+#define BH_LSTM_CTA_INSTANCES(X) X(3, 3) X(2, 4) X(4, 4)            // lstm_layer_cta_kernel<NKS, MT>: the ring's H / U <= 16 waves are one workgroup
+// lstm_layer_wide_kernel<NKS, RX, STATS>; RX: hand-off through the ring buffer
+#define BH_LSTM_WIDE_INSTANCES(X) \
+    X(32, true, true) X(20, true, false) X(20, false, false) X(24, true, false) X(24, false, false) X(28, true, false) X(28, false, false) \
+    X(32, true, false) X(32, false, false)
+
+enum LstmArgsKind { ARGS_LSTM, ARGS_FUSED, ARGS_WGX, ARGS_WIDE };      // LstmArgs, LstmFusedArgs, LstmWgxArgs, LstmWideArgs
+
+// What a family's kernels need, as a function of their template key: the per-family arithmetic, stated here and nowhere else. A
+// workgroup is four waves (cta: one wave per slice); a wave owns one slice of a ring's hidden units - 16 in the per-wave and
+// streaming kernels, 4 * MT in the workgroup-shared ones, 8 in the wide one.
+static bh_lstm_instance lstm_instance(bh_lstm_family family, int nks, int mt, bool flag, bool stats, const void* kernel, const char* name) {
+    bh_lstm_instance r{};
+    const int H = 32 * nks, U = 4 * mt;
+    r.family = family; r.H = H; r.nks = nks; r.mt = mt; r.key_flags = (flag ? 1 : 0) | (stats ? 2 : 0);
+    r.variant = stats ? BH_LSTM_V_STATS : 0;
+    r.kernel = kernel; r.name = name;
+    r.block = 256;
+    r.w_ih = BH_LSTM_W_ROWS; r.w_hh = BH_LSTM_W_FRAGS;
     switch (family) {
-        case BH_LSTM_WAVE:
-        case BH_LSTM_FUSED: g.wgs_per_group = H / 16; g.rings_per_slot = 4; break;     // a workgroup: one slice of four rings
-        case BH_LSTM_STREAM: g.wgs_per_group = H / 64; break;
-        case BH_LSTM_WGX2: g.rings_per_slot = 2; [[fallthrough]];
-        case BH_LSTM_WGX: g.wgs_per_group = U ? H / (4 * U) : 0; break;
-        case BH_LSTM_CTA: g.unlimited = true; break;
-        case BH_LSTM_WIDE: g.ring_chunks = 32; g.wgs_per_group = H / 32; break;
-        case BH_LSTM_Q8: break;                                                         // lstm_q8.hip
+        case BH_LSTM_FUSED:
+            r.args = ARGS_FUSED; r.projects = true; r.w_ih = BH_LSTM_W_FRAGS;
+            r.lds_bytes = nks * 4096;
+            [[fallthrough]];
+        case BH_LSTM_WAVE:       // a workgroup: one slice of four rings
+            r.geo.wgs_per_group = H / 16; r.geo.rings_per_slot = 4; r.slots_per_ring = H / 16;
+            break;
+        case BH_LSTM_STREAM:
+            r.geo.wgs_per_group = H / 64; r.slots_per_ring = H / 16;
+            break;
+        case BH_LSTM_WGX2:       // two rings per workgroup on one copy of the weights
+            r.geo.rings_per_slot = 2;
+            [[fallthrough]];
+        case BH_LSTM_WGX:
+            r.args = ARGS_WGX; r.projects = true; r.w_ih = r.w_hh = BH_LSTM_W_TILES;
+            r.geo.wgs_per_group = H / (4 * U); r.slots_per_ring = H / U;
+            r.lds_bytes = (family == BH_LSTM_WGX2 ? 8 : 5) * nks * 1024 + 4 * 16 * U * 2;
+            r.ex_bytes = (size_t)nks * 1024;
+            break;
+        case BH_LSTM_CTA:
+            r.args = ARGS_FUSED; r.projects = true; r.w_ih = r.w_hh = BH_LSTM_W_TILES;
+            r.geo.unlimited = true;
+            r.block = 64 * (H / U);
+            r.lds_bytes = 4 * nks * 1024;
+            break;
+        case BH_LSTM_WIDE:       // rings of 32 chunks: two column tiles; flag = RX
+            r.args = ARGS_WIDE; r.w_ih = BH_LSTM_W_WIDE_ROWS; r.w_hh = BH_LSTM_W_TILES;
+            r.geo.ring_chunks = 32; r.geo.wgs_per_group = H / 32; r.slots_per_ring = H / 8;
+            r.lds_bytes = 2 * 2 * nks * 1024 + 4 * 16 * 8 * 2;
+            r.ex_bytes = flag ? (size_t)2 * nks * 1024 : 0;
+            if (!flag) r.variant |= BH_LSTM_V_OUTPUT;
+            break;
+        case BH_LSTM_Q8: break;      // lstm_q8.hip
     }
-    return g;
+    r.raise_lds = family == BH_LSTM_WIDE || r.lds_bytes > 64 * 1024;
+    return r;
 }
 
-// The shared front of the launchers: batch padding, ring range (R: rings of the whole batch), co-residency guard, and the XCD
-// agreement slots (`slots` per ring) armed with 0xFF. Returns the grid.
-static int lstm_launch_prologue(const bh_lstm_geometry& g, int N, int R, int n_rings, int slots, int* xcc_ws, hipStream_t stream,
-                                int* grid_out) {
+static const bh_lstm_instance LSTM_INSTANCES[] = {
+#define BH_ROW(NKS) lstm_instance(BH_LSTM_WAVE, NKS, 0, false, false, (const void*)bh::lstm_layer_kernel<NKS, false>, "lstm_layer_kernel<" #NKS ",false>"),
+    BH_LSTM_WAVE_INSTANCES(BH_ROW)
+#undef BH_ROW
+#define BH_ROW(NKS) lstm_instance(BH_LSTM_STREAM, NKS, 0, true, false, (const void*)bh::lstm_layer_kernel<NKS, true>, "lstm_layer_kernel<" #NKS ",true>"),
+    BH_LSTM_STREAM_INSTANCES(BH_ROW)
+#undef BH_ROW
+#define BH_ROW(NKS) lstm_instance(BH_LSTM_FUSED, NKS, 0, false, false, (const void*)bh::lstm_layer_fused_kernel<NKS>, "lstm_layer_fused_kernel<" #NKS ">"),
+    BH_LSTM_FUSED_INSTANCES(BH_ROW)
+#undef BH_ROW
+#define BH_ROW(NKS, MT) lstm_instance(BH_LSTM_WGX, NKS, MT, false, false, (const void*)bh::lstm_layer_wgx_kernel<NKS, MT>, "lstm_layer_wgx_kernel<" #NKS "," #MT ">"),
+    BH_LSTM_WGX_INSTANCES(BH_ROW)
+#undef BH_ROW
+#define BH_ROW(NKS, MT, STATS) lstm_instance(BH_LSTM_WGX2, NKS, MT, false, STATS, (const void*)bh::lstm_layer_wgx2_kernel<NKS, MT, STATS>, "lstm_layer_wgx2_kernel<" #NKS "," #MT ">"),
+    BH_LSTM_WGX2_INSTANCES(BH_ROW)
+#undef BH_ROW
+#define BH_ROW(NKS, MT) lstm_instance(BH_LSTM_CTA, NKS, MT, false, false, (const void*)bh::lstm_layer_cta_kernel<NKS, MT>, "lstm_layer_cta_kernel<" #NKS "," #MT ">"),
+    BH_LSTM_CTA_INSTANCES(BH_ROW)
+#undef BH_ROW
+#define BH_ROW(NKS, RX, STATS) lstm_instance(BH_LSTM_WIDE, NKS, BH_LSTM_WIDE_MT, RX, STATS, (const void*)bh::lstm_layer_wide_kernel<NKS, RX, STATS>, "lstm_layer_wide_kernel<" #NKS "," #RX ">"),
+    BH_LSTM_WIDE_INSTANCES(BH_ROW)
+#undef BH_ROW
+};
+
+const bh_lstm_instance* bh_k_lstm_find(int family, int H, int variant) {
+    for (const bh_lstm_instance& r : LSTM_INSTANCES)
+        if (r.family == family && r.H == H && r.variant == variant) return &r;
+    return nullptr;
+}
+
+// ---- one launch -----------------------------------------------------------------------------------------------------------------------
+// Everything about a launch that needs no pointer: the instance, the grid, and what is armed in front of it. bh_k_lstm_launch executes
+// it, bh_k_lstm_launch_plan reports it.
+struct LstmLaunchPlan {
+    const bh_lstm_instance* row;
+    int grid;
+    size_t xcc_bytes;       // XCD agreement slots, armed with 0xFF
+    size_t arm_bytes;       // the whole exchange ring buffer, armed with 0xFF (0: not by this launch)
+};
+// N: batch padded to whole rings, R: rings of the whole batch, n_rings: rings of this launch. The workgroups of a launch must be
+// co-resident; a caller with more rings splits the batch (bh_k_lstm_run_layer).
+static int lstm_launch_plan(int family, int H, bool has_ex, int tune, int N, int R, int n_rings, bool arm, int cus, LstmLaunchPlan* p) {
+    const bh_lstm_instance* row = bh_k_lstm_find(family, H, 0);
+    BH_REQUIRE(row, "lstm: family %d has no instance for H=%d", family, H);
+    if (row->ex_bytes && !has_ex) {
+        row = bh_k_lstm_find(family, H, BH_LSTM_V_OUTPUT);
+        BH_REQUIRE(row, "lstm: fused layer cannot run in place / missing exchange buffer");
+    }
+    if (tune & 4)           // lstm_tune bit 2: the instance with section stamps (tools/lstm_stats2.py, tools/lstm_wide_stats.py)
+        if (const bh_lstm_instance* stats = bh_k_lstm_find(family, H, row->variant | BH_LSTM_V_STATS)) row = stats;
+    const bh_lstm_geometry& g = row->geo;
     if (g.ring_chunks == 32) BH_REQUIRE(N % 32 == 0, "lstm: wide kernel needs the batch padded to a multiple of 32 (N=%d)", N);
     else BH_REQUIRE(N % 16 == 0, "lstm: batch must be padded to a multiple of 16 (N=%d)", N);
     BH_REQUIRE(n_rings > 0 && n_rings <= R, "lstm: n_rings=%d outside 1..%d", n_rings, R);
-    const int grid = *grid_out = g.grid(n_rings);
+    p->row = row;
+    p->grid = g.grid(n_rings);
+    p->xcc_bytes = 0;
+    p->arm_bytes = arm ? (size_t)4 * R * row->ex_bytes : 0;
     if (g.unlimited) return 0;
-    const int cus = bh_cu_count();
-    BH_REQUIRE(g.wgs_per_group > 0 && grid <= g.resident(cus), "lstm: %d workgroups must be co-resident but the device has %d CUs; split the batch", grid, cus);
-    BH_REQUIRE(xcc_ws != nullptr, "lstm: missing XCD agreement workspace");
-    BH_CHECK_HIP(hipMemsetAsync(xcc_ws, 0xFF, (size_t)n_rings * slots * sizeof(int), stream));
+    BH_REQUIRE(g.wgs_per_group > 0 && p->grid <= g.resident(cus), "lstm: %d workgroups must be co-resident but the device has %d CUs; split the batch", p->grid, cus);
+    p->xcc_bytes = (size_t)n_rings * row->slots_per_ring * sizeof(int);
     return 0;
 }
 
-// One launch serves at most bh_k_lstm_geometry(..).rings_per_launch(CUs) rings; the caller (engine.cpp: forward_lstm, abi.cpp)
-// splits larger batches by offsetting the base pointers by 16*ring0 columns: N stays the row stride of
-// G / h and n_rings is the number of 16-chunk rings this launch runs. N %% 16 == 0 (engine pads).
-int bh_k_lstm_layer(const void* gates_in, const void* whh_packed, void* h_out, int T, int N, int H,
-                    int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow) {
+int bh_k_lstm_launch(const bh_lstm_launch& l, hipStream_t stream) {
     using namespace bh;
-    BH_REQUIRE(H % 32 == 0 && H >= 32 && H <= 512, "lstm: register-resident kernel needs H%%32==0, 32<=H<=512 (H=%d)", H);
-    int grid = 0;
-    if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_WAVE, H), N, N / 16, n_rings, H / 16, xcc_ws, stream, &grid)) return rc;
-    LstmArgs a{(const half_t*)gates_in, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings,
-               reverse, err_flag, max_spins(), xcc_ws, force_slow & 1, force_slow >> 8};
-#define BH_LSTM_CASE(NKS) \
-    case NKS: hipLaunchKernelGGL((lstm_layer_kernel<NKS, false>), dim3(grid), dim3(256), 0, stream, a); break;
-    switch (H / 32) {
-        BH_LSTM_CASE(1) BH_LSTM_CASE(2) BH_LSTM_CASE(3) BH_LSTM_CASE(4) BH_LSTM_CASE(5) BH_LSTM_CASE(6)
-        BH_LSTM_CASE(7) BH_LSTM_CASE(8) BH_LSTM_CASE(9) BH_LSTM_CASE(10) BH_LSTM_CASE(11) BH_LSTM_CASE(12)
-        BH_LSTM_CASE(13) BH_LSTM_CASE(14) BH_LSTM_CASE(15) BH_LSTM_CASE(16)
-        default: BH_REQUIRE(false, "lstm: unsupported H=%d", H);
+    LstmLaunchPlan p;
+    if (int rc = lstm_launch_plan(l.family, l.H, l.ex != nullptr, l.tune, l.N, l.R, l.n_rings, l.arm != 0, bh_cu_count(), &p)) return rc;
+    const bh_lstm_instance& row = *p.row;
+    BH_REQUIRE(!row.projects || l.input != l.h_out, "lstm: fused layer cannot run in place");
+    if (!row.geo.unlimited) {
+        BH_REQUIRE(l.xcc_ws != nullptr, "lstm: missing XCD agreement workspace");
+        BH_CHECK_HIP(hipMemsetAsync(l.xcc_ws, 0xFF, p.xcc_bytes, stream));
     }
-#undef BH_LSTM_CASE
-    BH_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-int bh_k_lstm_layer_stream(const void* gates_in, const void* whh_packed, void* h_out, int T, int N, int H,
-                           int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow) {
-    using namespace bh;
-    BH_REQUIRE(bh_lstm_stream_ok(H), "lstm: streaming kernel needs H%%64==0, 64<=H<=1024 (H=%d)", H);
-    int grid = 0;
-    if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_STREAM, H), N, N / 16, n_rings, H / 16, xcc_ws, stream, &grid)) return rc;
-    LstmArgs a{(const half_t*)gates_in, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings,
-               reverse, err_flag, max_spins(), xcc_ws, force_slow & 1, force_slow >> 8};
-#define BH_LSTM_CASE(NKS) \
-    case NKS: hipLaunchKernelGGL((lstm_layer_kernel<NKS, true>), dim3(grid), dim3(256), 0, stream, a); break;
-    switch (H / 32) {
-        BH_LSTM_STREAM_INSTANCES(BH_LSTM_CASE)
-        default: BH_REQUIRE(false, "lstm: unsupported H=%d for the streaming kernel", H);
+    if (p.arm_bytes) BH_CHECK_HIP(hipMemsetAsync(l.ex, 0xFF, p.arm_bytes, stream));
+    const LstmArgs a{row.projects || row.args == ARGS_WIDE ? nullptr : (const half_t*)l.input, (const half_t*)l.w_hh, (half_t*)l.h_out,
+                     l.T, l.N, l.H, l.n_rings, l.reverse, l.err_flag, max_spins(), l.xcc_ws, l.write_through, l.tune};
+    const LstmFusedArgs fa{(const half_t*)l.input, (const half_t*)l.w_ih, l.bias, a};
+    if (row.raise_lds) BH_CHECK_HIP(bh_max_lds(row.kernel, row.lds_bytes));
+    const dim3 grid(p.grid), block(row.block);
+    switch (row.args) {
+        case ARGS_LSTM: hipLaunchKernelGGL(((void (*)(LstmArgs))row.kernel), grid, block, row.lds_bytes, stream, a); break;
+        case ARGS_FUSED: hipLaunchKernelGGL(((void (*)(LstmFusedArgs))row.kernel), grid, block, row.lds_bytes, stream, fa); break;
+        case ARGS_WGX:
+            hipLaunchKernelGGL(((void (*)(LstmWgxArgs))row.kernel), grid, block, row.lds_bytes, stream, LstmWgxArgs{fa, (char*)l.ex, l.R});
+            break;
+        case ARGS_WIDE:
+            hipLaunchKernelGGL(((void (*)(LstmWideArgs))row.kernel), grid, block, row.lds_bytes, stream,
+                               LstmWideArgs{(const half_t*)l.input, a, (char*)l.ex, l.R});
+            break;
     }
-#undef BH_LSTM_CASE
     BH_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-int bh_k_lstm_layer_fused(const void* x, const void* wih_packed, const float* bias, const void* whh_packed, void* h_out,
-                          int T, int N, int H, int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws,
-                          int force_slow) {
-    using namespace bh;
-    BH_REQUIRE(H % 32 == 0 && H >= 32 && H <= 512, "lstm: register-resident kernel needs H%%32==0, 32<=H<=512 (H=%d)", H);
-    BH_REQUIRE(x != h_out, "lstm: fused layer cannot run in place");
-    int grid = 0;
-    if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_FUSED, H), N, N / 16, n_rings, H / 16, xcc_ws, stream, &grid)) return rc;
-    LstmFusedArgs a{(const half_t*)x, (const half_t*)wih_packed, bias,
-                    LstmArgs{nullptr, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings, reverse, err_flag, max_spins(),
-                             xcc_ws, force_slow & 1, force_slow >> 8}};
-    const size_t lds = (size_t)(H / 32) * 4096;
-#define BH_LSTM_CASE(NKS)                                                                                        \
-    case NKS:                                                                                                    \
-        if (lds > 64 * 1024)                                                                                     \
-            BH_CHECK_HIP(bh_max_lds((const void*)lstm_layer_fused_kernel<NKS>, (int)lds));            \
-        hipLaunchKernelGGL(lstm_layer_fused_kernel<NKS>, dim3(grid), dim3(256), lds, stream, a);                 \
-        break;
-    switch (H / 32) {
-        BH_LSTM_CASE(1) BH_LSTM_CASE(2) BH_LSTM_CASE(3) BH_LSTM_CASE(4) BH_LSTM_CASE(5) BH_LSTM_CASE(6)
-        BH_LSTM_CASE(7) BH_LSTM_CASE(8) BH_LSTM_CASE(9) BH_LSTM_CASE(10) BH_LSTM_CASE(11) BH_LSTM_CASE(12)
-        BH_LSTM_CASE(13) BH_LSTM_CASE(14) BH_LSTM_CASE(15) BH_LSTM_CASE(16)
-        default: BH_REQUIRE(false, "lstm: unsupported H=%d", H);
+int bh_k_lstm_run_layer(const bh_lstm_launch& layer, int rings_per_launch, bool pair, hipStream_t stream) {
+    const bh_lstm_instance* row = bh_k_lstm_find(layer.family, layer.H, 0);
+    BH_REQUIRE(row, "lstm: family %d has no instance for H=%d", layer.family, layer.H);
+    BH_REQUIRE(rings_per_launch >= 1, "lstm: the device has too few CUs for hidden size %d", layer.H);
+    for (int r0 = 0; r0 < layer.R;) {
+        bh_lstm_launch l = layer;
+        const bool pair_now = pair && layer.family == BH_LSTM_WGX && layer.R - r0 > rings_per_launch;
+        if (pair_now) l.family = BH_LSTM_WGX2;
+        l.n_rings = std::min(pair_now ? 2 * rings_per_launch : rings_per_launch, layer.R - r0);
+        const size_t col = (size_t)r0 * row->geo.ring_chunks;
+        l.input = (const char*)layer.input + col * (row->projects ? 1 : 4) * layer.H * 2;
+        l.h_out = (char*)layer.h_out + col * layer.H * 2;
+        if (layer.ex) l.ex = (char*)layer.ex + (size_t)r0 * row->ex_bytes;
+        l.arm = r0 == 0;
+        if (int rc = bh_k_lstm_launch(l, stream)) return rc;
+        r0 += l.n_rings;
     }
-#undef BH_LSTM_CASE
-    BH_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-// Workgroup-shared variant: usable when 4*U | H (U = 12 or 16 units per wave) and both weight sets fit the
-// register file. Returns the units-per-wave it would use, 0 if the shape is not covered.
-int bh_k_lstm_wg_units(int H) {
-    if (H % 32 != 0) return 0;
-    const int nks = H / 32;
-    if (H % 48 == 0 && nks <= 12) return 12;
-    if (H % 64 == 0 && nks <= 8) return 16;
-    return 0;
-}
-
-// Ring-buffer exchange variant of the workgroup-shared kernel (lstm_layer_wgx_kernel). `ex`: 4 * R * (H/32) KiB, armed here
-// with 0xFF when `arm` is set (once per layer: launches of one layer share it, each with its ring offset applied by the caller).
-size_t bh_k_lstm_wgx_ex_bytes(int N, int H) { return (size_t)4 * (N / 16) * (H / 32) * 1024; }
-int bh_k_lstm_layer_wgx(const void* x, const void* wih_packed, const float* bias, const void* whh_packed, void* h_out, void* ex,
-                        int T, int N, int H, int R, int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws,
-                        int force_slow, int arm) {
-    using namespace bh;
-    const int U = bh_k_lstm_wg_units(H);
-    BH_REQUIRE(U != 0, "lstm: workgroup-shared kernel does not cover H=%d", H);
-    BH_REQUIRE(x != h_out && ex != nullptr, "lstm: fused layer cannot run in place / missing exchange buffer");
-    int grid = 0;
-    if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_WGX, H), N, R, n_rings, H / U, xcc_ws, stream, &grid)) return rc;
-    const int nks = H / 32;
-    if (arm) BH_CHECK_HIP(hipMemsetAsync(ex, 0xFF, (size_t)4 * R * nks * 1024, stream));
-    LstmWgxArgs a{LstmFusedArgs{(const half_t*)x, (const half_t*)wih_packed, bias,
-                                LstmArgs{nullptr, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings, reverse, err_flag,
-                                         max_spins(), xcc_ws, force_slow & 1, force_slow >> 8}},
-                  (char*)ex, R};
-    const size_t lds = (size_t)5 * nks * 1024 + 4 * 16 * U * 2;
-#define BH_LSTM_WGX(NKS, MT)                                                                                     \
-    if (nks == NKS && U == 4 * MT) {                                                                             \
-        if (lds > 64 * 1024)                                                                                     \
-            BH_CHECK_HIP(bh_max_lds((const void*)lstm_layer_wgx_kernel<NKS, MT>, (int)lds));            \
-        hipLaunchKernelGGL((lstm_layer_wgx_kernel<NKS, MT>), dim3(grid), dim3(256), lds, stream, a);              \
-    } else
-    BH_LSTM_WGX(3, 3) BH_LSTM_WGX(6, 3) BH_LSTM_WGX(9, 3) BH_LSTM_WGX(12, 3)
-    BH_LSTM_WGX(2, 4) BH_LSTM_WGX(4, 4) BH_LSTM_WGX(8, 4)
-    { BH_REQUIRE(false, "lstm: workgroup-shared kernel has no instance for H=%d", H); }
-#undef BH_LSTM_WGX
-    BH_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-// Two rings per workgroup (lstm_layer_wgx2_kernel): n_rings may be up to twice what bh_k_lstm_layer_wgx takes.
-int bh_k_lstm_layer_wgx2(const void* x, const void* wih_packed, const float* bias, const void* whh_packed, void* h_out, void* ex,
-                         int T, int N, int H, int R, int reverse, int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws,
-                         int force_slow, int arm) {
-    using namespace bh;
-    const int U = bh_k_lstm_wg_units(H);
-    BH_REQUIRE(U != 0, "lstm: workgroup-shared kernel does not cover H=%d", H);
-    BH_REQUIRE(x != h_out && ex != nullptr, "lstm: fused layer cannot run in place / missing exchange buffer");
-    int grid = 0;
-    if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_WGX2, H), N, R, n_rings, H / U, xcc_ws, stream, &grid)) return rc;
-    const int nks = H / 32;
-    if (arm) BH_CHECK_HIP(hipMemsetAsync(ex, 0xFF, (size_t)4 * R * nks * 1024, stream));
-    LstmWgxArgs a{LstmFusedArgs{(const half_t*)x, (const half_t*)wih_packed, bias,
-                                LstmArgs{nullptr, (const half_t*)whh_packed, (half_t*)h_out, T, N, H, n_rings, reverse, err_flag,
-                                         max_spins(), xcc_ws, force_slow & 1, force_slow >> 8}},
-                  (char*)ex, R};
-    const size_t lds = (size_t)8 * nks * 1024 + 4 * 16 * U * 2;
-    if (nks == 12 && U == 12 && ((force_slow >> 8) & 4)) {          // lstm_tune bit 2: the instance with section stamps (tools/lstm_stats2.py)
-        BH_CHECK_HIP(bh_max_lds((const void*)lstm_layer_wgx2_kernel<12, 3, true>, (int)lds));
-        hipLaunchKernelGGL((lstm_layer_wgx2_kernel<12, 3, true>), dim3(grid), dim3(256), lds, stream, a);
-        BH_CHECK_HIP(hipGetLastError());
-        return 0;
+int bh_k_lstm_launch_plan(int family, int H, int flags, int n_rings, int cus, int32_t* out, int n_out) {
+    BH_REQUIRE(out && n_out >= BH_LSTM_PLAN_RECORD, "lstm_launch_plan: out must hold %d integers", (int)BH_LSTM_PLAN_RECORD);
+    BH_REQUIRE(family >= BH_LSTM_WAVE && family <= BH_LSTM_Q8 && cus > 0, "lstm_launch_plan: family %d, %d CUs", family, cus);
+    memset(out, 0, sizeof(int32_t) * BH_LSTM_PLAN_RECORD);
+    if (family == BH_LSTM_Q8) return bh_k_lstm_q8_launch_plan(H, flags & 0xff, n_rings, cus, out);
+    LstmLaunchPlan p{};
+    const bh_lstm_instance* any = bh_k_lstm_find(family, H, 0);
+    if (any) {
+        const bh_lstm_geometry& g = any->geo;
+        const int per = g.rings_per_launch(cus);
+        const int32_t head[7] = {1, g.ring_chunks, g.wgs_per_group, g.rings_per_slot, g.wgs_per_cu, g.unlimited, per};
+        memcpy(out, head, sizeof(head));
     }
-#define BH_LSTM_WGX2(NKS, MT)                                                                                    \
-    if (nks == NKS && U == 4 * MT) {                                                                             \
-        if (lds > 64 * 1024)                                                                                     \
-            BH_CHECK_HIP(bh_max_lds((const void*)lstm_layer_wgx2_kernel<NKS, MT>, (int)lds));            \
-        hipLaunchKernelGGL((lstm_layer_wgx2_kernel<NKS, MT>), dim3(grid), dim3(256), lds, stream, a);             \
-    } else
-    BH_LSTM_WGX2(3, 3) BH_LSTM_WGX2(6, 3) BH_LSTM_WGX2(9, 3) BH_LSTM_WGX2(12, 3)
-    BH_LSTM_WGX2(2, 4) BH_LSTM_WGX2(4, 4) BH_LSTM_WGX2(8, 4)
-    { BH_REQUIRE(false, "lstm: workgroup-shared kernel has no instance for H=%d", H); }
-#undef BH_LSTM_WGX2
-    BH_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-// Ring-in-a-workgroup kernel: covers the narrow layers whose two weight sets fit the registers of H/U <= 16 waves.
-int bh_k_lstm_cta_units(int H) {
-    if (H == 96) return 12;
-    if (H == 64 || H == 128) return 16;
-    return 0;
-}
-
-int bh_k_lstm_layer_cta(const void* x, const void* wih_tiles, const float* bias, const void* whh_tiles, void* h_out, int T, int N,
-                        int H, int reverse, hipStream_t stream, int n_rings) {
-    using namespace bh;
-    const int U = bh_k_lstm_cta_units(H);
-    BH_REQUIRE(U != 0, "lstm: ring-in-a-workgroup kernel does not cover H=%d", H);
-    BH_REQUIRE(x != h_out, "lstm: fused layer cannot run in place");
-    int grid = 0;
-    if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_CTA, H), N, N / 16, n_rings, 0, nullptr, stream, &grid)) return rc;
-    LstmFusedArgs a{(const half_t*)x, (const half_t*)wih_tiles, bias,
-                    LstmArgs{nullptr, (const half_t*)whh_tiles, (half_t*)h_out, T, N, H, n_rings, reverse, nullptr, 0u, nullptr, 0, 0}};
-    const int nks = H / 32, nsl = H / U;
-    const size_t lds = (size_t)4 * nks * 1024;
-    if (H == 96) hipLaunchKernelGGL((lstm_layer_cta_kernel<3, 3>), dim3(grid), dim3(64 * nsl), lds, stream, a);
-    else if (H == 64) hipLaunchKernelGGL((lstm_layer_cta_kernel<2, 4>), dim3(grid), dim3(64 * nsl), lds, stream, a);
-    else hipLaunchKernelGGL((lstm_layer_cta_kernel<4, 4>), dim3(grid), dim3(64 * nsl), lds, stream, a);
-    BH_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-// Wide layers: stationary W_hh, rings of 32 chunks; the caller provides G with permuted columns (bh_k_lstm_wide_permute).
-int bh_k_lstm_wide_ok(int H) { return H > 512 && H <= 1024 && H % 128 == 0; }
-
-size_t bh_k_lstm_wide_ex_bytes(int N, int H) { return (size_t)4 * (N / 32) * 2 * (H / 32) * 1024; }
-
-// ex != nullptr: ring-buffer exchange (R = rings of the whole batch, `arm` = fill it with the sentinel first: once per layer)
-int bh_k_lstm_layer_wide(const void* gates_perm, const void* whh_tiles, void* h_out, int T, int N, int H, int reverse,
-                         int* err_flag, hipStream_t stream, int n_rings, int* xcc_ws, int force_slow, void* ex, int R, int arm) {
-    using namespace bh;
-    BH_REQUIRE(bh_k_lstm_wide_ok(H), "lstm: wide kernel does not cover H=%d", H);
-    int grid = 0;
-    if (int rc = lstm_launch_prologue(bh_k_lstm_geometry(BH_LSTM_WIDE, H), N, N / 32, n_rings, H / 8, xcc_ws, stream, &grid)) return rc;
-    LstmWideArgs a{(const half_t*)gates_perm,
-                   LstmArgs{nullptr, (const half_t*)whh_tiles, (half_t*)h_out, T, N, H, n_rings, reverse, err_flag, max_spins(), xcc_ws,
-                            force_slow & 1, force_slow >> 8},
-                   (char*)ex, R};
-    const int nks = H / 32;
-    if (ex && arm) BH_CHECK_HIP(hipMemsetAsync(ex, 0xFF, (size_t)4 * R * 2 * nks * 1024, stream));
-    const size_t lds = (size_t)2 * 2 * nks * 1024 + 4 * 16 * 8 * 2;
-#define BH_LSTM_WIDE(NKS)                                                                                               \
-    if (nks == NKS && ex) {                                                                                             \
-        BH_CHECK_HIP(bh_max_lds((const void*)lstm_layer_wide_kernel<NKS, true>, (int)lds));                                                                    \
-        hipLaunchKernelGGL((lstm_layer_wide_kernel<NKS, true>), dim3(grid), dim3(256), lds, stream, a);                  \
-    } else if (nks == NKS) {                                                                                            \
-        BH_CHECK_HIP(bh_max_lds((const void*)lstm_layer_wide_kernel<NKS, false>, (int)lds));                                                                    \
-        hipLaunchKernelGGL((lstm_layer_wide_kernel<NKS, false>), dim3(grid), dim3(256), lds, stream, a);                 \
-    } else
-    if (nks == 32 && ex && ((force_slow >> 8) & 4)) {
-        BH_CHECK_HIP(bh_max_lds((const void*)lstm_layer_wide_kernel<32, true, true>, (int)lds));
-        hipLaunchKernelGGL((lstm_layer_wide_kernel<32, true, true>), dim3(grid), dim3(256), lds, stream, a);
-    } else
-    BH_LSTM_WIDE(20) BH_LSTM_WIDE(24) BH_LSTM_WIDE(28) BH_LSTM_WIDE(32)
-    { BH_REQUIRE(false, "lstm: wide kernel has no instance for H=%d", H); }
-#undef BH_LSTM_WIDE
-    BH_CHECK_HIP(hipGetLastError());
+    const int ring_chunks = any ? any->geo.ring_chunks : 16;
+    if (int rc = lstm_launch_plan(family, H, !(flags & BH_LSTM_V_OUTPUT), flags >> 8, n_rings * ring_chunks, n_rings, n_rings, true, cus, &p)) return rc;
+    const bh_lstm_instance& r = *p.row;
+    const int32_t tail[10] = {p.grid, r.block, r.lds_bytes, r.raise_lds, (int32_t)p.xcc_bytes, (int32_t)p.arm_bytes, (int32_t)r.ex_bytes,
+                              r.nks, r.mt, r.key_flags};
+    memcpy(out + 7, tail, sizeof(tail));
     return 0;
 }

@@ -1,10 +1,11 @@
-// Host-side weight layouts of the recurrent kernels that take tiles (lstm.hip: wgx, wgx2, cta, wide), stated once for
-// engine.cpp (create_lstm) and abi.cpp (bh_lstm_layer_family). The per-wave fragment order is bh_lstm_pack_whh (abi.cpp).
+// Host-side weight layouts of the recurrent kernels (kernels.h: bh_lstm_layout), stated once for engine.cpp (create_lstm) and
+// abi.cpp (bh_lstm_layer_family): lstm_pack / lstm_pack_bias. The per-wave fragment order is bh_lstm_pack_whh (abi.cpp).
 #pragma once
 #include <stdint.h>
 #include <string.h>
 
 #include "devbuf.h"
+#include "kernels.h"
 
 namespace {      // (internal to each translation unit that includes this)
 
@@ -27,21 +28,33 @@ static inline int lstm_pack_tiles(const float* w, int H, int MT, uint16_t* packe
     return 0;
 }
 
-// Wide layer: tiles of 8 units (MT = 2), and W_ih / bias with permuted rows, so that the gate GEMM writes
-// G[t][n][(slice*4 + q)*8 + gate*2 + m] for unit slice*8 + q*2 + m. w_ih is [4H][I]; wp receives [4H][I], bp [4H] = b0 + b1
-// (either may be null).
-constexpr int LSTM_WIDE_MT = 2;
-static inline void lstm_wide_permute(const float* w_ih, const float* b0, const float* b1, int H, int I, float* wp, float* bp) {
-    const int MT = LSTM_WIDE_MT;
-    for (int s8 = 0; s8 < H / 8; ++s8)
-        for (int q = 0; q < 4; ++q)
-            for (int g = 0; g < 4; ++g)
-                for (int m = 0; m < MT; ++m) {
-                    const size_t dst = (((size_t)s8 * 4 + q) * 4 + g) * MT + m;
-                    const size_t src = (size_t)g * H + s8 * 8 + q * MT + m;
-                    memcpy(&wp[dst * I], w_ih + src * I, sizeof(float) * I);
-                    bp[dst] = (b0 ? b0[src] : 0.0f) + (b1 ? b1[src] : 0.0f);
-                }
+// Wide layer: its gate GEMM writes G[t][n][(slice*4 + q)*8 + gate*2 + m] for unit slice*8 + q*2 + m (slices of 8 units, tiles of
+// BH_LSTM_WIDE_MT = 2). The torch row (gate*H + unit) that row `dst` of the permuted W_ih / bias holds:
+static inline size_t lstm_wide_row(int H, size_t dst) {
+    const int MT = BH_LSTM_WIDE_MT;
+    const size_t m = dst % MT, g = dst / MT % 4, q = dst / (4 * MT) % 4, s8 = dst / (16 * MT);
+    return g * H + s8 * 8 + q * MT + m;
+}
+
+// fp32 weights w [4H][I] in torch gate order -> fp16 in layout L, 4 * H * I halves. FRAGS and TILES (of 4 * MT units) take I == H.
+static inline int lstm_pack(bh_lstm_layout L, int MT, const float* w, int H, int I, uint16_t* packed) {
+    switch (L) {
+        case BH_LSTM_W_FRAGS: return I == H ? bh_lstm_pack_whh(w, H, packed) : -2;
+        case BH_LSTM_W_TILES: return I == H && MT > 0 ? lstm_pack_tiles(w, H, MT, packed) : -2;
+        default:
+            for (size_t r = 0; r < (size_t)4 * H; ++r) {
+                const float* src = w + (L == BH_LSTM_W_WIDE_ROWS ? lstm_wide_row(H, r) : r) * I;
+                for (int c = 0; c < I; ++c) packed[r * I + c] = f2h(src[c]);
+            }
+            return 0;
+    }
+}
+// b0 + b1 [4H] (either may be null) in the row order of W_ih layout L
+static inline void lstm_pack_bias(bh_lstm_layout L, const float* b0, const float* b1, int H, float* bias) {
+    for (size_t r = 0; r < (size_t)4 * H; ++r) {
+        const size_t src = L == BH_LSTM_W_WIDE_ROWS ? lstm_wide_row(H, r) : r;
+        bias[r] = (b0 ? b0[src] : 0.0f) + (b1 ? b1[src] : 0.0f);
+    }
 }
 
 }  // namespace

@@ -402,18 +402,27 @@ __global__ void quantise_rows_kernel(const half_t* x, int8_t* out, long pieces, 
 
 }  // namespace bh
 
-// Units per wave of the 8-bit kernel for hidden size H (0: not covered). `variant` 1 asks for the single-tile geometry
-// (U = 4, three workgroups per CU) where it is instantiated.
-// Hidden units per wave of the 8-bit kernel, 0 = this width has no instance (the layer then keeps the fp16 kernels). Must name
-// exactly the (k-steps, M tiles) pairs instantiated in bh_k_lstm_layer_q8 below: a width this accepted without an instance
-// (48, 240, 320, 432, 448, 480) made every forward of a quantised model fail instead of falling back (advisor finding, round 2).
+// The instances of lstm_layer_q8_kernel<NK8, MT, WPS, ..>: k-steps of 64 (ceil(H / 64)), M tiles per wave (U = 4 * MT hidden units),
+// workgroups per CU. What is compiled is what is listed; the widths the 8-bit path accepts (bh_k_lstm_q8_units), its geometry and its
+// launcher's dispatch are all read off this list. A width without an instance keeps the fp16 kernels.
+#define BH_LSTM_Q8_INSTANCES(X) X(6, 3, 1) X(6, 3, 2) X(6, 1, 3) X(2, 3, 1) X(3, 3, 1) X(5, 3, 1) X(1, 4, 1) X(2, 4, 1) X(4, 4, 1) X(8, 4, 1)
+struct Q8Key { int nk8, mt, wps; };
+// The instance that serves (H, "lstm_q8_variant"): 12 units per wave where 48 | H, else 16 where 64 | H, one workgroup per CU. At
+// H = 384, variant 1 asks for the single-tile geometry (U = 4, three workgroups per CU), variant 2 for two workgroups per CU.
+static bool q8_key(int H, int variant, Q8Key* key) {
+    if (H <= 0 || H % 16 != 0) return false;
+    Q8Key want{(H + 63) / 64, H % 48 == 0 ? 3 : H % 64 == 0 ? 4 : 0, 1};
+    if (H == 384 && variant == 1) { want.mt = 1; want.wps = 3; }
+    if (H == 384 && variant == 2) want.wps = 2;
+#define BH_Q8_HAS(NK8, MT, WPS) if (want.nk8 == NK8 && want.mt == MT && want.wps == WPS) { *key = want; return true; }
+    BH_LSTM_Q8_INSTANCES(BH_Q8_HAS)
+#undef BH_Q8_HAS
+    return false;
+}
+// Hidden units per wave, 0 = this width has no instance
 int bh_k_lstm_q8_units(int H, int variant) {
-    if (H % 16 != 0 || H > 512 || H <= 0) return 0;
-    if (variant == 1 && H == 384) return 4;
-    const int nk8 = (H + 63) / 64;
-    if (H % 48 == 0) return (nk8 == 2 || nk8 == 3 || nk8 == 5 || nk8 == 6) ? 12 : 0;      // 96, 144, 192, 288, 336, 384
-    if (H % 64 == 0) return (nk8 == 1 || nk8 == 2 || nk8 == 4 || nk8 == 8) ? 16 : 0;      // 64, 128, 256, 512
-    return 0;
+    Q8Key k;
+    return q8_key(H, variant, &k) ? 4 * k.mt : 0;
 }
 size_t bh_k_lstm_q8_tile_bytes(int H) { return (size_t)((H + 63) / 64) * 1024; }
 
@@ -474,10 +483,30 @@ int bh_k_lstm_q8_arm(void* ex, int R, int H, hipStream_t stream) {
 // Launch geometry (kernels.h: bh_lstm_geometry): H/(4U) workgroups per ring; the small-tile variants fit several workgroups on a CU.
 bh_lstm_geometry bh_k_lstm_q8_geometry(int H, int variant) {
     bh_lstm_geometry g;
-    const int U = bh_k_lstm_q8_units(H, variant);
-    g.wgs_per_group = U ? H / (4 * U) : 0;
-    g.wgs_per_cu = U == 4 ? 3 : (variant == 2 && H == 384) ? 2 : 1;
+    Q8Key k;
+    if (!q8_key(H, variant, &k)) return g;
+    g.wgs_per_group = H / (16 * k.mt);
+    g.wgs_per_cu = k.wps;
     return g;
+}
+
+// Everything about a launch that needs no pointer; bh_k_lstm_layer_q8 executes it, bh_k_lstm_q8_launch_plan reports it.
+struct Q8LaunchPlan {
+    Q8Key key;
+    bh_lstm_geometry geo;
+    int grid;
+    size_t lds, xcc_bytes;
+};
+static int q8_launch_plan(int H, int variant, int N, int R, int n_rings, int cus, Q8LaunchPlan* p) {
+    BH_REQUIRE(q8_key(H, variant, &p->key), "lstm_q8: hidden size %d is not covered by the 8-bit kernel", H);
+    BH_REQUIRE(N % 16 == 0 && n_rings > 0 && n_rings <= R, "lstm_q8: bad batch geometry (N=%d, rings=%d of %d)", N, n_rings, R);
+    p->geo = bh_k_lstm_q8_geometry(H, variant);
+    const int U = 4 * p->key.mt, room = p->geo.resident(cus);
+    p->grid = p->geo.grid(n_rings);
+    BH_REQUIRE(p->grid <= room, "lstm_q8: %d workgroups must be co-resident but the device holds %d; split the batch", p->grid, room);
+    p->xcc_bytes = (size_t)n_rings * (H / U) * sizeof(int);
+    p->lds = 5 * bh_k_lstm_q8_tile_bytes(H) + 4 * (size_t)(16 * U * 3);
+    return 0;
 }
 
 // One launch serves the rings whose workgroups fit the device together (co-residency, as the fp16 wg kernel). `ex` must hold
@@ -486,19 +515,14 @@ int bh_k_lstm_layer_q8(const void* xq, const void* wih, const void* whh, const f
                        void* hq_out, void* h16_out, void* ex, int T, int N, int H, int R, int n_rings, int reverse, int* err_flag,
                        hipStream_t stream, int* xcc_ws, int flags, int variant, int* dbg, unsigned max_spins) {
     using namespace bh;
-    const int U = bh_k_lstm_q8_units(H, variant);
-    BH_REQUIRE(U != 0, "lstm_q8: hidden size %d is not covered by the 8-bit kernel", H);
-    BH_REQUIRE(N % 16 == 0 && n_rings > 0 && n_rings <= R, "lstm_q8: bad batch geometry (N=%d, rings=%d of %d)", N, n_rings, R);
-    const bh_lstm_geometry geo = bh_k_lstm_q8_geometry(H, variant);
-    const int nsl = H / U, nk8 = (H + 63) / 64, per_cu = geo.wgs_per_cu;
-    const int grid = geo.grid(n_rings), room = geo.resident(bh_cu_count());
-    BH_REQUIRE(grid <= room, "lstm_q8: %d workgroups must be co-resident but the device holds %d; split the batch", grid, room);
+    Q8LaunchPlan p;
+    if (int rc = q8_launch_plan(H, variant, N, R, n_rings, bh_cu_count(), &p)) return rc;
     BH_REQUIRE(xcc_ws != nullptr && ex != nullptr, "lstm_q8: missing workspace");
-    BH_CHECK_HIP(hipMemsetAsync(xcc_ws, 0xFF, (size_t)n_rings * nsl * sizeof(int), stream));
-    const size_t tile = (size_t)nk8 * 1024;
+    BH_CHECK_HIP(hipMemsetAsync(xcc_ws, 0xFF, p.xcc_bytes, stream));
     LstmQ8Args a{(const int8_t*)xq, (int8_t*)hq_out, (half_t*)h16_out, (int8_t*)ex, (const int8_t*)wih, (const int8_t*)whh, sx, sh, bias,
                  T, N, H, R, n_rings, reverse, err_flag, max_spins, xcc_ws, flags & 1, flags >> 8, dbg};
-    const size_t lds = 5 * tile + 4 * (size_t)(16 * U * 3);
+    const size_t lds = p.lds;
+    const int grid = p.grid;
     const bool last = h16_out != nullptr;
     BH_REQUIRE(last || hq_out != nullptr, "lstm_q8: no output buffer");
 #define BH_Q8_LAUNCH(NK8, MT, WPS, LAST, DBG)                                                                            \
@@ -508,15 +532,29 @@ int bh_k_lstm_layer_q8(const void* xq, const void* wih, const void* whh, const f
         hipLaunchKernelGGL((lstm_layer_q8_kernel<NK8, MT, WPS, LAST, DBG>), dim3(grid), dim3(256), lds, stream, a);       \
     } while (0)
 #define BH_Q8(NK8, MT, WPS)                                                                                              \
-    if (nk8 == NK8 && U == 4 * MT && per_cu == WPS) {                                                                                  \
+    if (p.key.nk8 == NK8 && p.key.mt == MT && p.key.wps == WPS) {                                                        \
         if (dbg) BH_Q8_LAUNCH(NK8, MT, WPS, true, true);                                                                 \
         else if (last) BH_Q8_LAUNCH(NK8, MT, WPS, true, false);                                                          \
         else BH_Q8_LAUNCH(NK8, MT, WPS, false, false);                                                                   \
-    } else
-    BH_Q8(6, 3, 1) BH_Q8(6, 3, 2) BH_Q8(6, 1, 3) BH_Q8(2, 3, 1) BH_Q8(3, 3, 1) BH_Q8(5, 3, 1) BH_Q8(1, 4, 1) BH_Q8(2, 4, 1) BH_Q8(4, 4, 1) BH_Q8(8, 4, 1)
-    { BH_REQUIRE(false, "lstm_q8: no kernel instance for H=%d", H); }
+    }
+    BH_LSTM_Q8_INSTANCES(BH_Q8)
 #undef BH_Q8_LAUNCH
 #undef BH_Q8
     BH_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int bh_k_lstm_q8_launch_plan(int H, int variant, int n_rings, int cus, int32_t* out) {
+    Q8LaunchPlan p;
+    if (q8_key(H, variant, &p.key)) {
+        const bh_lstm_geometry g = bh_k_lstm_q8_geometry(H, variant);
+        const int32_t head[7] = {1, g.ring_chunks, g.wgs_per_group, g.rings_per_slot, g.wgs_per_cu, g.unlimited, g.rings_per_launch(cus)};
+        memcpy(out, head, sizeof(head));
+    }
+    if (int rc = q8_launch_plan(H, variant, 16 * n_rings, n_rings, n_rings, cus, &p)) return rc;
+    const int32_t tile = (int32_t)bh_k_lstm_q8_tile_bytes(H);        // the ring buffer is [4][R][tile], armed by bh_k_lstm_q8_arm
+    const int32_t tail[10] = {p.grid, 256, (int32_t)p.lds, p.lds > 64 * 1024, (int32_t)p.xcc_bytes, 4 * n_rings * tile, tile,
+                              p.key.nk8, p.key.mt, p.key.wps};
+    memcpy(out + 7, tail, sizeof(tail));
     return 0;
 }

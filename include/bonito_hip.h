@@ -306,7 +306,8 @@ int bh_signal_chunks(const int16_t* raw, const long* offsets, const float* cal_s
 int bh_lstm_q8_layer(const void* x, float bound, const float* w_ih, const float* w_hh, const float* bias, int T, int N, int H,
                      int reverse, int variant, void* h16_out, int8_t* hq_frag, int32_t* sums, void* stream);
 
-/* The recurrent kernel families of csrc/lstm.hip (BH_LSTM_Q8: csrc/lstm_q8.hip). */
+/* The recurrent kernel families of csrc/lstm.hip (BH_LSTM_Q8: csrc/lstm_q8.hip). The widths named below are read off the instance
+ * table of lstm.hip (bh_lstm_launch_plan reports it); tests/test_gpu_lstm.py keeps an independent list. */
 enum bh_lstm_family {
     BH_LSTM_WAVE = 0,    /* gate GEMM + one wave per 16 units, W_hh in registers: H % 32 == 0, H <= 512 */
     BH_LSTM_FUSED = 1,   /* the same with the input projection inside the recurrence */
@@ -326,6 +327,19 @@ enum bh_lstm_family {
  * is no multiple of the family's ring (16 chunks; 32 for BH_LSTM_WIDE), more rings than one launch holds, an exchange timeout. */
 int bh_lstm_layer_family(const void* x, const float* w_ih, const float* w_hh, const float* bias, int T, int N, int H, int reverse,
                          int family, int flags, void* h_out, void* stream);
+/* Test hook: the launch the library would make of `n_rings` rings (the whole batch, exchange buffer armed) of family `family` at
+ * hidden size H on a device of `cu_count` CUs. Touches no device. flags bits 0-7: the variant - fp16 families: bit 1 as in
+ * bh_lstm_layer_family; BH_LSTM_Q8: "lstm_q8_variant" - bits 8 and up: "lstm_tune". Writes BH_LSTM_PLAN_RECORD integers (n_out = room
+ * in out):
+ *   0 the family has an instance for H, 1 chunks per ring, 2 workgroups per group of 8 slots, 3 rings per slot, 4 workgroups per CU,
+ *   5 one workgroup per ring and any number of rings per launch, 6 rings one launch holds on cu_count CUs
+ *   7 grid, 8 block, 9 dynamic LDS bytes, 10 the max-dynamic-LDS attribute is raised first
+ *   11 bytes of XCD agreement slots armed, 12 bytes of exchange ring buffer armed, 13 exchange-buffer bytes per ring and time slot
+ *   (the stride of a split batch), 14-16 the kernel's template key: k-steps, M tiles per wave, flags (fp16: bit 0 = STREAM / RX,
+ *   bit 1 = STATS; BH_LSTM_Q8: workgroups per CU)
+ * A launch the library refuses is a non-zero return with its message; 0-6 are still written where the family has an instance. */
+enum { BH_LSTM_PLAN_RECORD = 17 };
+int bh_lstm_launch_plan(int family, int H, int flags, int n_rings, int cu_count, int32_t* out, int n_out);
 
 /* Process-wide knobs (measurement / tuning hooks, no reference counterpart): the rows of the option table in csrc/options.cpp, every
  * one described here (tests/test_abi.py holds the two lists to each other). Not thread-safe: set them while nothing else calls into
