@@ -1,17 +1,25 @@
-// Signal ingest on the device: raw int16 ADC samples -> pA -> quantile normalisation -> adapter trim ->
-// fp16 chunk rows of the encoder's input batch. Replaces the per-read numpy work of /root/reference bonito/reader.py:
-// 122-166 (`normalisation`, `trim`) and bonito/pod5.py:52-67 plus `util.chunk` + the fp32->fp16 cast for the product path:
-// the host ships 2 bytes per sample once and a table of chunk origins.
+// Signal ingest on the device: raw int16 ADC samples -> pA -> normalisation -> adapter trim -> fp16 chunk rows of
+// the encoder's input batch. Replaces the per-read numpy work of the reference's bonito/pod5.py:57-67 with bonito/reader.py:
+// 122-166 (`normalisation`, `trim`) under it, plus `util.chunk` + the fp16 cast of crf/basecall.py:33 for the product path: the
+// host ships 2 bytes per sample once and a table of chunk origins.
 //
-// Everything here reproduces the reference's arithmetic bit for bit (tests compare with bonito_amd/reader.py, which is
-// pinned on fixtures generated by the reference):
+// Everything here reproduces the reference's arithmetic bit for bit. tests/test_gpu_signal.py holds shift / scale (fp64 bits),
+// trim and every fp16 chunk sample to tests/signal_ref.py, a line-by-line restatement that tests/golden/signal_cases.npz pins to
+// the reference itself; the cases include every int16 value under both strategies.
 //   scaled  = f32(scaling) * (f32(raw) + f32(offset))                       two fp32 roundings, no fma
-//   qa, qb  = np.quantile(scaled, [a, b])      order statistics are taken on the raw int16 values (the map to pA is
-//             monotone for scaling > 0), interpolation as numpy's _lerp: diff in fp32, the rest in fp64
-//   shift   = max(10, m_shift * (qa + qb)), scale = max(1.0, m_scale * (qb - qa))      fp64; Python's max() returns the
-//             int 10 / the float 1.0 themselves when they win, and NumPy's promotion rules then keep the subtraction
-//             (and a division by 1.0) in fp32 -- reproduced through the two `weak` flags
-//   norm    = f32((scaled - shift) / scale), chunk rows = f16(norm)          round-to-nearest-even twice
+//   quantile strategy:
+//     qa, qb  = np.quantile(scaled, [a, b])    order statistics are taken on the raw int16 values (the map to pA is
+//               monotone for scaling > 0), interpolation as numpy's _lerp: diff in fp32, the rest in fp64
+//     shift   = max(10, m_shift * (qa + qb)), scale = max(1.0, m_scale * (qb - qa))    fp64; Python's max() returns the
+//               int 10 / the float 1.0 themselves when they win: Python scalars, where the others are np.float64
+//   fixed pA strategy: shift, scale = the config's mean, stdev (or 0.0, 1.0): Python scalars both
+//   NumPy's promotion rules (NEP 50) decide the rest. A Python scalar is rounded to the array's fp32 and the operation stays
+//   in fp32; a np.float64 takes it to fp64. The per-read `weak` word records which is which:
+//     bit 0  shift is Python's 10          bit 1  scale is Python's 1.0          bit 2  fixed pA: both are Python floats
+//   thresh  = scale * 2.4 + shift              fp64, two roundings; a Python float only when shift and scale both are
+//   trim    : `scaled > thresh` on the pA signal, in fp32 against f32(thresh) for a Python float, in fp64 otherwise
+//   norm    = (scaled - shift) / scale          fp32 subtract / divide with the constants rounded to fp32, or fp64
+//   chunk rows = f16(f32(norm))                 round-to-nearest-even twice, as torch casts fp64 to fp16 on the CPU
 #include "common.h"
 #include "kernels.h"
 
@@ -29,32 +37,32 @@ struct SigStatsArgs {
     const float* cal_offset; // [R]
     int R;
     double qa, qb, shift_mult, scale_mult;
-    int strategy;            // 0 quantile, 1 fixed (shift/scale given), see bh_signal_normalise
+    int strategy;            // 0 quantile, 1 fixed pA (shift/scale given), see bh_signal_normalise
     double fixed_shift, fixed_scale;
     double* shift;           // [R]
     double* scale;           // [R]
-    int* weak;               // [R] bit0: shift is Python's int 10, bit1: scale is Python's float 1.0
+    int* weak;               // [R] WEAK_SHIFT | WEAK_SCALE | WEAK_FIXED
     int* trim;               // [R]
     int do_trim, window, min_trim, min_elements, max_samples;
-    double threshold, max_trim;
+    double threshold, max_trim;     // threshold: in units of scale above shift (2.4)
 };
 
 __device__ __forceinline__ float to_pa(int16_t raw, float cs, float co) { return __fmul_rn(cs, __fadd_rn((float)raw, co)); }
 
-// norm = (scaled - shift) / scale under NumPy's promotion rules: fp32 throughout when both constants are Python's own
-// (weak) scalars, fp64 as soon as one of them is a np.float64
-__device__ __forceinline__ double normalise_wide(float scaled, double shift, double scale, int weak) {
-    if (weak & 1) return (double)__fsub_rn(scaled, 10.0f) / scale;
-    return ((double)scaled - shift) / scale;                    // a weak 1.0 divides exactly
-}
+enum { WEAK_SHIFT = 1, WEAK_SCALE = 2, WEAK_FIXED = 4 };      // bits of the per-read `weak` word, see the head of the file
+
+// norm = (scaled - shift) / scale under NumPy's promotion rules, rounded to fp32
 __device__ __forceinline__ float normalise(float scaled, double shift, double scale, int weak) {
-    if ((weak & 3) == 3) return __fsub_rn(scaled, 10.0f);      // / 1.0f is exact
-    return (float)normalise_wide(scaled, shift, scale, weak);
+    if (weak & WEAK_FIXED) return __fdiv_rn(__fsub_rn(scaled, (float)shift), (float)scale);
+    if ((weak & 3) == 3) return __fsub_rn(scaled, 10.0f);                                  // / 1.0f is exact
+    if (weak & WEAK_SHIFT) return (float)((double)__fsub_rn(scaled, 10.0f) / scale);
+    return (float)(((double)scaled - shift) / scale);                                      // a weak 1.0 divides exactly
 }
-// `norm > threshold` as reader.trim sees it: norm is an fp32 array (threshold rounds to fp32) or an fp64 one
-__device__ __forceinline__ bool above_threshold(float scaled, double shift, double scale, int weak, double thr) {
-    if ((weak & 3) == 3) return __fsub_rn(scaled, 10.0f) > (float)thr;
-    return normalise_wide(scaled, shift, scale, weak) > thr;
+// the trim threshold on the pA signal and whether it is a Python float (bonito/pod5.py:62)
+__device__ __forceinline__ double trim_threshold(double shift, double scale, double mult) { return scale * mult + shift; }
+__device__ __forceinline__ bool threshold_is_weak(int weak) { return (weak & WEAK_FIXED) || (weak & 3) == 3; }
+__device__ __forceinline__ bool above_threshold(float scaled, double thr, bool thr_weak) {
+    return thr_weak ? scaled > (float)thr : (double)scaled > thr;
 }
 
 // k-th smallest (0-based) of the read's int16 values: 256-bin histogram of the high byte, then of the low byte inside the
@@ -100,8 +108,9 @@ __global__ __launch_bounds__(256) void signal_stats_kernel(SigStatsArgs p) {
     const int16_t* x = p.raw + o0;
     const float cs = p.cal_scale[r], co = p.cal_offset[r];
     double shift = p.fixed_shift, scale = p.fixed_scale;
-    int weak = 0;
+    int weak = WEAK_FIXED;
     if (p.strategy == 0) {
+        weak = 0;
         double q[2];
         for (int which = 0; which < 2; ++which) {
             const double vi = (double)(n - 1) * (which == 0 ? p.qa : p.qb);
@@ -114,8 +123,8 @@ __global__ __launch_bounds__(256) void signal_stats_kernel(SigStatsArgs p) {
 
         }
         const double sh = p.shift_mult * (q[0] + q[1]), sc = p.scale_mult * (q[1] - q[0]);
-        if (sh > 10.0) shift = sh; else { shift = 10.0; weak |= 1; }        // max(10, x): the first argument wins ties
-        if (sc > 1.0) scale = sc; else { scale = 1.0; weak |= 2; }
+        if (sh > 10.0) shift = sh; else { shift = 10.0; weak |= WEAK_SHIFT; }        // max(10, x): the first argument wins ties
+        if (sc > 1.0) scale = sc; else { scale = 1.0; weak |= WEAK_SCALE; }
     }
     if (threadIdx.x == 0) { p.shift[r] = shift; p.scale[r] = scale; p.weak[r] = weak; s_trim = 0; }
     __syncthreads();
@@ -123,7 +132,8 @@ __global__ __launch_bounds__(256) void signal_stats_kernel(SigStatsArgs p) {
     if (p.do_trim && threadIdx.x < 64) {
         const int lane = threadIdx.x;
         const long limit = n < p.max_samples ? n : p.max_samples;
-        const double thr = p.threshold;
+        const double thr = trim_threshold(shift, scale, p.threshold);
+        const bool thr_weak = threshold_is_weak(weak);
         bool seen = false;
         int result = p.min_trim;
         const int nwin = (int)(limit / p.window);
@@ -134,7 +144,7 @@ __global__ __launch_bounds__(256) void signal_stats_kernel(SigStatsArgs p) {
             for (int base = 0; base < p.window; base += 64) {
                 const long i = start + base + lane;
                 bool above = false;
-                if (base + lane < p.window && i < n) above = above_threshold(to_pa(x[i], cs, co), shift, scale, weak, thr);
+                if (base + lane < p.window && i < n) above = above_threshold(to_pa(x[i], cs, co), thr, thr_weak);
                 cnt += __popcll(__ballot(above));
                 // window[-1]: the last element that exists (numpy slicing clips at the end of the signal)
                 const long last = (end < n ? end : n) - 1;

@@ -41,6 +41,9 @@ class Pod5FormatError(ValueError):
     pass
 
 
+MAX_ROW_SAMPLES = 1 << 26          # a signal row of MinKNOW's holds 102 400 samples; `samples` is a uint32 and sizes buffers
+
+
 # ---- FlatBuffers, read side: just enough for the footer -------------------------------------------------------------------------------
 def _fb_table(buf, pos):
     """-> (table position, list of field offsets relative to it; 0 = absent / default)"""
@@ -95,8 +98,15 @@ def vbz_decode(block, count, out=None):
 
     from bonito_amd import _lib
     count = int(count)
+    if not 0 <= count <= MAX_ROW_SAMPLES:
+        raise Pod5FormatError("a signal row of %d samples" % count)
     if out is None:
         out = np.empty(count, np.int16)
+    # the library writes `count` samples through a bare pointer: the array has to be what it takes it for
+    if not isinstance(out, np.ndarray) or out.dtype != np.int16 or out.ndim != 1 or not out.flags.c_contiguous or not out.flags.writeable:
+        raise ValueError("vbz_decode: `out` must be a writable C-contiguous 1-D int16 array")
+    if out.size < count:
+        raise Pod5FormatError("VBZ block of %d samples, room for %d" % (count, out.size))
     if count == 0:
         return out
     # an svb16 block of `count` values is at most ceil(count / 8) + 2 count bytes (+ 16 so that the decoder's wide path may over-read).
@@ -270,23 +280,38 @@ class Reader:
     def _signal_of(self, rows, total):
         import pyarrow as pa
         batches, starts = self._signal_rows()
-        out = np.empty(int(total), np.int16)
-        pos = 0
+        total = int(total)
+        # the counts first, so that an inconsistent file sizes no buffer and decodes nothing
+        where, held = [], 0
         for r in rows:
             b = int(np.searchsorted(starts, r, side="right") - 1)
+            if r < 0 or b < 0 or b >= len(batches) or r - starts[b] >= batches[b].num_rows:
+                raise Pod5FormatError("%s: a read names signal row %d, the table has %d" % (self.path, r, starts[-1]))
             batch = batches[b]
             k = int(r - starts[b])
             n = int(batch.column(batch.schema.get_field_index("samples"))[k].as_py())
+            if n > MAX_ROW_SAMPLES:
+                raise Pod5FormatError("%s: signal row %d claims %d samples" % (self.path, r, n))
+            where.append((batch, k, n))
+            held += n
+        if held != total:
+            raise Pod5FormatError("%s: a read's signal rows hold %d samples, its record says %d" % (self.path, held, total))
+        out = np.empty(total, np.int16)
+        pos = 0
+        for batch, k, n in where:
+            if pos + n > total:                                 # (implied by the sum above; the slice below must never be short)
+                raise Pod5FormatError("%s: signal row of %d samples at %d of %d" % (self.path, n, pos, total))
             col = batch.column(batch.schema.get_field_index("signal"))
             if isinstance(col, pa.ExtensionArray):
                 col = col.storage
             if pa.types.is_large_binary(col.type) or pa.types.is_binary(col.type):
                 vbz_decode(col[k].as_buffer(), n, out=out[pos:pos + n])
             else:                                               # uncompressed: list<int16>
-                out[pos:pos + n] = np.asarray(col[k].values.to_numpy(zero_copy_only=False), np.int16)[:n]
+                values = np.asarray(col[k].values.to_numpy(zero_copy_only=False), np.int16)
+                if len(values) < n:
+                    raise Pod5FormatError("%s: signal row holds %d samples, claims %d" % (self.path, len(values), n))
+                out[pos:pos + n] = values[:n]
             pos += n
-        if pos != total:
-            raise Pod5FormatError("%s: a read's signal rows hold %d samples, its record says %d" % (self.path, pos, total))
         return out
 
     def reads(self, selection=None, missing_ok=True, preload=None):

@@ -19,6 +19,18 @@ import numpy as np
 __default_norm_params__ = {"quantile_a": 0.2, "quantile_b": 0.9, "shift_multiplier": 0.51, "scale_multiplier": 0.53}
 
 
+def trim_threshold(shift, scale):
+    """The trim threshold on the pA signal (bonito/pod5.py:62). A np.float64 unless shift and scale are both Python's own scalars,
+    and `signal > threshold` then compares in the signal's fp32 or in fp64 accordingly, as it does in the reference."""
+    return scale * 2.4 + shift
+
+
+def above_threshold(scaled, shift, scale):
+    """Which pA samples count towards the adapter peak: the reference's form, not `(scaled - shift) / scale > 2.4`, which rounds
+    differently next to the threshold (tests/test_signal_ref_cpu.py walks every int16 value)."""
+    return scaled > trim_threshold(shift, scale)
+
+
 def trim(signal, window_size=40, threshold=2.4, min_trim=10, min_elements=3, max_samples=8000, max_trim=0.3):
     """Index at which the read proper starts: scan windows for the first stretch above `threshold` (the
     open-pore / adapter peak) and cut where the signal drops back; fall back to `min_trim`."""
@@ -67,8 +79,8 @@ class Read:
         scaled = raw.astype(np.float32) if raw.dtype.kind == "f" else np.array(scaling * (raw.astype(np.float32) + offset),
                                                                                 dtype=np.float32)
         self.shift, self.scale = normalisation(scaled, scaling_strategy, norm_params)
+        self.trimmed_samples = trim(scaled, threshold=trim_threshold(self.shift, self.scale)) if do_trim else 0
         norm = (scaled - self.shift) / self.scale
-        self.trimmed_samples = trim(norm) if do_trim else 0
         self.template_start = self.start + self.trimmed_samples / sample_rate
         self.template_duration = self.duration - self.trimmed_samples / sample_rate
         self.signal = np.ascontiguousarray(norm[self.trimmed_samples:], dtype=np.float32)

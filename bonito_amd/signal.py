@@ -4,7 +4,8 @@ encoder's fp16 input batches (libbonito_hip.so: bh_signal_normalise / bh_signal_
 
 Device counterpart of `bonito_amd.reader.Read.__init__` (itself a mirror of /root/reference bonito/reader.py:122-166 and
 bonito/pod5.py:52-67) followed by `util.chunk` + `batchify` + the fp16 cast: same shift / scale / trim per read and the
-same fp16 chunk rows, bit for bit (tests/test_gpu_signal.py), with 2 bytes per sample crossing PCIe once.
+same fp16 chunk rows, bit for bit (tests/test_gpu_signal.py against tests/signal_ref.py, the reference restated and pinned to
+it by tests/golden/signal_cases.npz), with 2 bytes per sample crossing PCIe once.
 """
 import ctypes as C
 
@@ -87,12 +88,14 @@ class RawBatch:
         trims = self.trim.cpu().numpy() if trims is None else np.asarray(trims)
         return chunk_table(self.lengths, trims, chunksize, overlap)
 
-    def chunks(self, table, chunksize, lo=0, hi=None):
-        """fp16 [n, 1, chunksize] device tensor of table rows lo:hi (call `normalise` first)."""
+    def chunks(self, table, chunksize, lo=0, hi=None, out=None):
+        """fp16 [n, 1, chunksize] device tensor of table rows lo:hi (call `normalise` first); written into `out` when given."""
         reads, starts, avail = (t[lo:hi] for t in table)
         n = len(reads)
         dev = self.device
-        out = torch.empty((n, 1, chunksize), dtype=torch.float16, device=dev)
+        if out is None:
+            out = torch.empty((n, 1, chunksize), dtype=torch.float16, device=dev)
+        assert out.dtype == torch.float16 and out.is_contiguous() and out.numel() == n * chunksize and out.device == self.raw.device
         if n == 0:
             return out
         d_reads = torch.from_numpy(np.ascontiguousarray(reads)).to(dev)

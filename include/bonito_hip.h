@@ -282,12 +282,13 @@ int bh_sw_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, c
                 size_t workspace_bytes, int32_t* result, uint32_t* ops, long ops_stride, int32_t* n_ops, void* stream);
 
 /* Signal ingest on the device: replaces Read.__init__'s numpy work (bonito/reader.py:122-166 normalisation + trim, the pA
- * scaling of bonito/pod5.py:52-67) and util.chunk + the fp16 cast (bonito/util.py:142-161, crf/basecall.py:31) for raw
+ * scaling and the trim threshold of bonito/pod5.py:52-67) and util.chunk + the fp16 cast (bonito/util.py:142-161, crf/basecall.py:31) for raw
  * int16 reads, with the reference's arithmetic reproduced bit for bit. All pointers are device pointers.
  *   raw: concatenated int16 samples of n_reads reads, offsets[n_reads + 1]; cal_scale / cal_offset: per-read calibration
  *   (pA = cal_scale * (raw + cal_offset)); strategy 0 = quantile scaling with (quantile_a, quantile_b, shift_mult,
- *   scale_mult), 1 = fixed (fixed_shift, fixed_scale). Outputs per read: shift, scale (fp64), weak (bit0: shift is the
- *   literal 10, bit1: scale is the literal 1.0 -- NumPy's promotion then differs), trim (first sample of the read proper).
+ *   scale_mult), 1 = fixed pA (fixed_shift, fixed_scale). Outputs per read: shift, scale (fp64), weak (bit0: shift is the
+ *   literal 10, bit1: scale is the literal 1.0, bit2: fixed pA, both are config floats -- NumPy's promotion then keeps the
+ *   arithmetic in fp32 with the constants rounded to fp32), trim (first sample of the read proper).
  * bh_signal_chunks writes normalised fp16 rows [n_chunks][chunk_samples]: row i = read chunk_read[i], samples
  *   chunk_start[i] .. (chunk_len[i] >= chunk_samples) or the chunk_len[i] available samples tiled (short reads). */
 int bh_signal_normalise(const int16_t* raw, const long* offsets, const float* cal_scale, const float* cal_offset, int n_reads,

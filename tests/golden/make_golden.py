@@ -12,6 +12,9 @@ What is produced (all seeded, fp32 CPU):
   crf_decode.npz     reference CTC_CRF.logZ / viterbi / path_to_str and SeqdistModel.decode_batch, executed with a torch
                      restatement of the four koi.ctc names they call (koi is closed source)                (make_crf_decode_fixture)
   reader_cases.npz   reference bonito/reader.py normalisation + trim in the order of bonito/pod5.py:61-62 (make_reader_fixture)
+  signal_cases.npz   reference bonito/pod5.py Read.__init__ (int16 samples + calibration -> shift / scale / trim / signal), then
+                     bonito/util.py chunk and the fp16 cast of crf/basecall.py:33, on the cases of tests/signal_ref.py: scalars and
+                     digests only                                                                        (make_signal_fixture)
   tf_<name>.npz / ctc_<name>.npz   reference transformer / QuartzNet forward
 Every fixture is also checked here against the oracle restatements (oracle/nn_ref.py), so a committed
 fixture certifies "oracle == reference" at generation time; tests/ re-check the oracle against the files.
@@ -356,6 +359,71 @@ def make_reader_fixture(n_cases=8):
     print("reader_cases.npz: %d cases, trims %s" % (len(meta), [m["trim"] for m in meta]))
 
 
+def ref_pod5():
+    """The reference's bonito/pod5.py with bonito/reader.py under it: the REAL files; the `pod5` wheel it imports at module level
+    (only `Reader`, for opening files) is an inert stub, since the records come from FakePod5Record below."""
+    pkg = types.ModuleType("bonito")
+    pkg.__path__ = [os.path.join(REF, "bonito")]
+    sys.modules["bonito"] = pkg
+    stub = types.ModuleType("pod5")
+    stub.Reader = None
+    sys.modules["pod5"] = stub
+    for name in ("bonito.reader", "bonito.pod5"):
+        sys.modules.pop(name, None)
+    import importlib
+    return importlib.import_module("bonito.pod5")
+
+
+class FakePod5Record:
+    """What bonito/pod5.py:18-56 reads from a pod5 record; `signal` int16, the calibration Python floats as the wheel hands them out."""
+
+    def __init__(self, raw, scaling, offset):
+        import datetime
+        from pathlib import Path
+        self.read_id = "00000000-0000-0000-0000-000000000000"
+        self.run_info = types.SimpleNamespace(
+            sample_id="s", acquisition_id="a", acquisition_start_time=datetime.datetime(2024, 1, 1, tzinfo=datetime.timezone.utc),
+            flow_cell_id="f", sequencer_position="p", context_tags={"sample_frequency": "5000"})
+        self.pore = types.SimpleNamespace(well=1, channel=1)
+        self.read_number, self.sample_count, self.start_sample = 0, len(raw), 0
+        self.signal = raw
+        self.calibration = types.SimpleNamespace(scale=float(scaling), offset=float(offset))
+        self.path = Path("fixture.pod5")
+
+
+def make_signal_fixture():
+    """signal_cases.npz: per case of tests/signal_ref.py::cases() the recipe of its int16 samples, calibration and parameters, and
+    what the REFERENCE computes from them: shift / scale (fp64 bit patterns + whether each is a Python scalar), trim, length and
+    digest of the signal cast to fp16, and a digest of `chunk(...)` cast to fp16 per chunk geometry."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import signal_ref
+    rp = ref_pod5()
+    util = ref_util()
+    meta = []
+    for c in signal_ref.cases():
+        raw = signal_ref.make_raw(c["recipe"])
+        rec = FakePod5Record(raw, c["scaling"], c["offset"])
+        rd = rp.Read(rec, rec.path, do_trim=c["do_trim"], scaling_strategy=c["strategy"], norm_params=c["params"])
+        sig = rd.signal
+        half = torch.from_numpy(sig).to(torch.float16)
+        entry = dict(c, n=int(len(raw)), raw_digest=signal_ref.digest(raw),
+                     shift_bits=signal_ref.f64_bits(rd.shift), scale_bits=signal_ref.f64_bits(rd.scale),
+                     shift_python=signal_ref.is_python_scalar(rd.shift), scale_python=signal_ref.is_python_scalar(rd.scale),
+                     trim=int(rd.trimmed_samples), signal_dtype=str(sig.dtype), signal_len=int(len(sig)),
+                     signal_digest=signal_ref.digest(half.numpy()), chunks={})
+        if len(sig):                                  # (the reference's chunk divides by zero on an empty signal)
+            for L, ov in signal_ref.geometries_of(len(raw)):
+                rows = util.chunk(torch.from_numpy(sig), L, ov).to(torch.float16)
+                entry["chunks"]["%d,%d" % (L, ov)] = [int(rows.shape[0]), signal_ref.digest(rows.numpy())]
+        meta.append(entry)
+    path = os.path.join(HERE, "signal_cases.npz")
+    np.savez_compressed(path, meta=np.array(json.dumps(meta)))
+    weak = [(m["shift_python"], m["scale_python"]) for m in meta if m["strategy"] is None]
+    print("signal_cases.npz: %d cases (%d KiB); quantile cases by (shift, scale) Python scalar: %s; trims %s" %
+          (len(meta), os.path.getsize(path) // 1024, {k: weak.count(k) for k in sorted(set(weak))},
+           sorted({m["trim"] for m in meta})))
+
+
 def koi_ctc_stub():
     """A torch restatement of the four names of `koi.ctc` that bonito/crf/model.py:9-10 needs for CTC_CRF.logZ / posteriors /
     viterbi, so that the REFERENCE's own class body runs here. koi (ont-koi 0.5.4, requirements.txt:19) is closed binary +
@@ -480,6 +548,9 @@ def main():
     if "--ctc-only" in sys.argv:
         make_ctc_fixture("quartz_small", CTC_BLOCKS_SMALL, N=3, L=600)
         return
+    if "--signal-only" in sys.argv:
+        make_signal_fixture()
+        return
     if "--crf-only" in sys.argv:
         make_crf_rc_fixture()
         make_crf_decode_fixture()
@@ -509,6 +580,7 @@ def main():
     make_crf_rc_fixture()
     make_crf_decode_fixture()
     make_reader_fixture()
+    make_signal_fixture()
 
 
 if __name__ == "__main__":

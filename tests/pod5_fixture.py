@@ -3,7 +3,8 @@ to read - there is no ``.pod5`` under /root/reference and no pod5 wheel here. Th
 
     write_pod5(path, reads, compress=True, rows=..., sample_rate=5000)
 
-`reads`: list of dicts {read_id (uuid str), signal (int16 array), offset, scale, channel, well, start, read_number}. The signal of a read
+`reads`: list of dicts {read_id (uuid str), signal (int16 array), offset, scale, channel, well, start, read_number}; for files that
+contradict themselves, `num_samples` overrides the record's sample count and `row_samples` {row of the read: count} a row's. The signal of a read
 is split into rows of `rows` samples (MinKNOW uses 102 400); with `compress` every row is VBZ: zig-zag first differences ->
 streamvbyte-16 -> zstd. The footer is a hand-built FlatBuffers table of the schema the format publishes.
 """
@@ -99,7 +100,7 @@ def write_pod5(path, reads, compress=True, rows=4096, sample_rate=5000, acquisit
             idx.append(len(sig_blocks))
             sig_ids.append(uuid.UUID(r["read_id"]).bytes)
             sig_blocks.append(vbz_encode(part) if compress else part)
-            sig_samples.append(len(part))
+            sig_samples.append(r.get("row_samples", {}).get(len(idx) - 1, len(part)))
         read_rows.append(idx)
     if compress:
         sig_col = pa.array(sig_blocks, pa.large_binary())
@@ -122,7 +123,7 @@ def write_pod5(path, reads, compress=True, rows=4096, sample_rate=5000, acquisit
         "end_reason": pa.array(["signal_positive"] * n).dictionary_encode(),
         "end_reason_forced": pa.array([False] * n),
         "run_info": pa.array([acquisition_id] * n).dictionary_encode(),
-        "num_samples": pa.array([len(r["signal"]) for r in reads], pa.uint64()),
+        "num_samples": pa.array([r.get("num_samples", len(r["signal"])) for r in reads], pa.uint64()),
     })
     if batch_reads:                                              # several record batches in the reads table
         reads_table = pa.Table.from_batches(reads_table.to_batches(max_chunksize=batch_reads))

@@ -1,15 +1,122 @@
-"""Device signal ingest (csrc/signal.hip) vs the host reader (bonito_amd/reader.py, pinned on reference fixtures): same
-shift / scale / trim per read and the same fp16 chunk rows, bit for bit (-m gpu)."""
+"""Device signal ingest (csrc/signal.hip), bit for bit (-m gpu).
+
+The sweep holds the two kernels to tests/signal_ref.py, the reference's raw-to-chunk-rows path restated line by line, which
+tests/test_signal_ref_cpu.py pins to the reference itself (tests/golden/signal_cases.npz) and to bonito_amd/reader.py. Every
+comparison is equality of bits: shift and scale as fp64 patterns, the `weak` word they imply, trim, every fp16 chunk sample, and the
+guard bytes around the output rows. The reads: signal_ref.cases(); the chunk lengths: signal_ref.GEOMETRIES.
+
+The tests further down compare with the host reader on reads shaped like real ones, and end to end through the basecaller."""
+import json
+
 import numpy as np
 import pytest
 import torch
 
+import signal_ref
 from bonito_amd import reader, signal
 from bonito_amd.util import chunk
 
 pytestmark = pytest.mark.gpu
 
 
+# ---- the sweep against the restatement ------------------------------------------------------------------------------------------------------
+GUARD = 4096          # bytes of 0xA5 on either side of the output rows
+
+
+class Group:
+    """The cases that share normalisation parameters: one RawBatch, one bh_signal_normalise launch."""
+
+    def __init__(self, cases):
+        self.cases = cases
+        self.raws = [signal_ref.make_raw(c["recipe"]) for c in cases]
+        self.want = [signal_ref.ingest(raw, c["scaling"], c["offset"], c["strategy"], c["params"], c["do_trim"])
+                     for raw, c in zip(self.raws, cases)]
+        self.batch = signal.RawBatch(self.raws, [c["scaling"] for c in cases], [c["offset"] for c in cases])
+        self.shift, self.scale, self.trim = self.batch.normalise(cases[0]["strategy"], cases[0]["params"], do_trim=cases[0]["do_trim"])
+        self.weak = self.batch.weak.cpu().numpy()
+        self.rows = {}
+
+    def want_rows(self, L, ov, keep):
+        """Rows of the restatement for the reads in `keep`, read by read (computed once per geometry)."""
+        key = (L, ov, tuple(keep))
+        if key not in self.rows:
+            self.rows[key] = np.concatenate([np.zeros((0, 1, L), np.float16)] + [
+                signal_ref.chunk_rows(w["signal"], L, ov) for w, k in zip(self.want, keep) if k])
+        return self.rows[key]
+
+    def table(self, L, ov, keep):
+        reads, starts, avail = self.batch.chunk_table(L, ov)
+        sel = np.asarray(keep)[reads] if len(reads) else np.zeros(0, bool)
+        return reads[sel], starts[sel], avail[sel]
+
+
+@pytest.fixture(scope="module")
+def sweep():
+    groups = {}
+    for c in signal_ref.cases():
+        groups.setdefault(json.dumps([c["strategy"], c["params"], c["do_trim"]], sort_keys=True), []).append(c)
+    return [Group(cs) for cs in groups.values()]
+
+
+def guarded_chunks(batch, table, L, lo=0, hi=None):
+    """batch.chunks into a buffer with GUARD bytes of 0xA5 before and behind; -> the rows as uint16 bits on the host."""
+    n = len(table[0][lo:hi])
+    buf = torch.full((2 * GUARD + 2 * n * L,), 0xA5, dtype=torch.uint8, device="cuda")
+    out = buf[GUARD:GUARD + 2 * n * L].view(torch.float16).view(n, 1, L)
+    batch.chunks(table, L, lo, hi, out=out)
+    host = buf.cpu().numpy()
+    assert (host[:GUARD] == 0xA5).all() and (host[GUARD + 2 * n * L:] == 0xA5).all(), "wrote outside the rows"
+    return host[GUARD:GUARD + 2 * n * L].view(np.uint16).reshape(n, 1, L)
+
+
+def test_sweep_shift_scale_weak_trim_equal_restatement(sweep):
+    seen = set()
+    for g in sweep:
+        for i, (c, w) in enumerate(zip(g.cases, g.want)):
+            name = c["name"]
+            assert int(g.shift[i].view(np.uint64)) == signal_ref.f64_bits(w["shift"]), (name, g.shift[i], w["shift"])
+            assert int(g.scale[i].view(np.uint64)) == signal_ref.f64_bits(w["scale"]), (name, g.scale[i], w["scale"])
+            fixed = bool(c["strategy"]) and c["strategy"]["strategy"] == "pa"
+            weak = 4 if fixed else int(signal_ref.is_python_scalar(w["shift"])) | int(signal_ref.is_python_scalar(w["scale"])) << 1
+            assert g.weak[i] == weak, (name, g.weak[i], weak)
+            assert g.trim[i] == w["trim"], (name, g.trim[i], w["trim"])
+            seen.add(weak)
+    assert seen == {0, 1, 2, 3, 4}
+
+
+@pytest.mark.parametrize("L,ov,longest", signal_ref.GEOMETRIES)
+def test_sweep_chunk_rows_equal_restatement(sweep, L, ov, longest):
+    """Every fp16 sample of every chunk row: both store paths of the kernel (L % 4), one and two blocks per row, stub chunks, exact
+    fits, short reads tiled (T = 1, 7, L - 1 among them), overlap 0 and L - 1."""
+    rows = 0
+    for g in sweep:
+        keep = [longest is None or len(raw) <= longest for raw in g.raws]
+        want = g.want_rows(L, ov, keep).view(np.uint16)
+        got = guarded_chunks(g.batch, g.table(L, ov, keep), L)
+        assert got.shape == want.shape, (g.cases[0]["name"], got.shape, want.shape)
+        bad = np.argwhere(got != want)
+        assert len(bad) == 0, (g.cases[0]["name"], len(bad), bad[:4].tolist())
+        rows += len(want)
+    assert rows > 0
+
+
+@pytest.mark.parametrize("L,ov", [(67, 5), (1024, 0)])
+def test_sweep_table_slice_starts_inside_a_read(sweep, L, ov):
+    for g in sweep:
+        keep = [True] * len(g.raws)
+        table = g.table(L, ov, keep)
+        want = g.want_rows(L, ov, keep).view(np.uint16)
+        reads = table[0]
+        inside = [k for k in range(1, len(reads)) if reads[k] == reads[k - 1]]       # rows that are not the first of their read
+        if not inside:
+            continue
+        lo = inside[len(inside) // 2]
+        hi = min(len(reads), lo + 37)
+        assert np.array_equal(guarded_chunks(g.batch, table, L, lo, hi), want[lo:hi]), (g.cases[0]["name"], lo, hi)
+        assert guarded_chunks(g.batch, table, L, lo, lo).shape == (0, 1, L)
+
+
+# ---- against the host reader, on reads shaped like real ones ---------------------------------------------------------------------------------
 def _raw_read(rng, n, peak):
     """int16 ADC samples shaped like a nanopore read: an open-pore / adapter stretch, then the read proper."""
     x = rng.normal(480, 60, n)

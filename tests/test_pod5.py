@@ -119,3 +119,134 @@ def test_reader_yields_the_same_reads_from_pod5_and_from_npy(tmp_path):
     b = list(reader.Reader(str(d_pod)).get_reads(raw=True))
     for x, y in zip(a, b):                                       # device ingest: the int16 samples and the calibration travel as they are
         assert np.array_equal(x.raw, y.raw) and y.raw.dtype == np.int16 and abs(x.scaling - y.scaling) < 1e-7 and x.offset == y.offset
+
+
+# ---- files that contradict themselves ------------------------------------------------------------------------------------------------------
+def _hostile(tmp_path, monkeypatch, compress, **override):
+    """A two-row read whose counts disagree as `override` says -> the exception of reading its signal; nothing may be decoded."""
+    rng = np.random.default_rng(11)
+    good = {"read_id": str(uuid.UUID(int=1)), "signal": _signals(rng, 1, 900, 901)[0]}
+    bad = dict({"read_id": str(uuid.UUID(int=2)), "signal": _signals(rng, 1, 1000, 1001)[0]}, **override)
+    path = write_pod5(str(tmp_path / "h.pod5"), [good, bad], compress=compress, rows=600)
+    decoded = []
+    real = pod5.vbz_decode
+    monkeypatch.setattr(pod5, "vbz_decode", lambda *a, **k: decoded.append(a[1]) or real(*a, **k))
+    with pod5.Reader(path) as fh:
+        first, second = list(fh.reads())
+        assert np.array_equal(first.signal, good["signal"])          # the sound read beside it still decodes
+        del decoded[:]
+        with pytest.raises(pod5.Pod5FormatError):
+            second.signal
+    assert decoded == []
+
+
+@pytest.mark.parametrize("compress", [True, False])
+@pytest.mark.parametrize("override", [{"num_samples": 700}, {"num_samples": 1300}, {"row_samples": {1: 401}}, {"row_samples": {0: 1000}},
+                                      {"row_samples": {1: 0xFFFFFFF0}}],
+                         ids=["record_smaller", "record_larger", "row_exceeds_remainder", "first_row_claims_all", "row_huge"])
+def test_inconsistent_sample_counts_are_refused_before_decoding(tmp_path, monkeypatch, compress, override):
+    _hostile(tmp_path, monkeypatch, compress, **override)
+
+
+@pytest.mark.parametrize("compress", [True, False])
+def test_row_that_claims_more_than_it_holds_is_refused(tmp_path, compress):
+    """The counts add up (700 + 300 = 1000) but the first row holds 600 samples: the decoder runs out of input, or the list is short."""
+    sig = _signals(np.random.default_rng(12), 1, 1000, 1001)[0]
+    rec = {"read_id": str(uuid.UUID(int=3)), "signal": sig, "row_samples": {0: 700, 1: 300}}
+    path = write_pod5(str(tmp_path / "s.pod5"), [rec], compress=compress, rows=600)
+    with pod5.Reader(path) as fh:
+        with pytest.raises(pod5.Pod5FormatError):
+            next(iter(fh.reads())).signal
+
+
+def test_vbz_decode_refuses_an_output_it_cannot_fill():
+    x = np.arange(100, dtype=np.int16)
+    block = vbz_encode(x)
+    guard = np.full(120, 0x5A5A, np.int16)
+    with pytest.raises(pod5.Pod5FormatError):
+        pod5.vbz_decode(block, 100, out=guard[:99])                  # one short: NumPy would have cut the slice silently
+    with pytest.raises(pod5.Pod5FormatError):
+        pod5.vbz_decode(block, 100, out=guard[110:300])              # a slice that runs off the end of its array
+    with pytest.raises(ValueError):
+        pod5.vbz_decode(block, 100, out=guard[::1].view(np.uint16)[:100].astype(np.int32))
+    with pytest.raises(ValueError):
+        pod5.vbz_decode(block, 100, out=np.full(240, 0x5A5A, np.int16)[::2])
+    with pytest.raises(pod5.Pod5FormatError):
+        pod5.vbz_decode(block, pod5.MAX_ROW_SAMPLES + 1)
+    with pytest.raises(pod5.Pod5FormatError):
+        pod5.vbz_decode(block, -1)
+    assert (guard == 0x5A5A).all()
+    assert np.array_equal(pod5.vbz_decode(block, 100, out=guard[5:105]), x) and (guard[:5] == 0x5A5A).all() and (guard[105:] == 0x5A5A).all()
+
+
+# ---- bh_host_svb16_decode against a second decoder ----------------------------------------------------------------------------------------------
+def svb16_decode_scalar(data, count):
+    """The codec once more, one value at a time, from the format description alone: ceil(count / 8) key bytes, bit (i % 8) of key byte
+    i // 8 set when value i has two data bytes (little-endian), else one; value -> zig-zag -> delta; samples are the running sum
+    modulo 2^16. -> (samples as Python ints in int16 range, bytes consumed) or None when `data` ends early."""
+    nkeys = (count + 7) // 8
+    if len(data) < nkeys:
+        return None
+    pos, prev, out = nkeys, 0, []
+    for i in range(count):
+        width = 2 if (data[i // 8] >> (i % 8)) & 1 else 1
+        if pos + width > len(data):
+            return None
+        v = data[pos] if width == 1 else data[pos] + 256 * data[pos + 1]
+        pos += width
+        delta = v // 2 if v % 2 == 0 else -(v + 1) // 2
+        prev = (prev + delta) % 65536
+        out.append(prev - 65536 if prev >= 32768 else prev)
+    return out, pos
+
+
+def _from_widths(widths, rng):
+    """Samples whose successive differences take the given number of data bytes each (1: |zig-zag| < 256, 2: above), kept in range by
+    letting the 16-bit sum wrap."""
+    deltas = [int(rng.integers(-128, 128)) if w == 1 else int(rng.choice([-1, 1])) * int(rng.integers(129, 32768)) for w in widths]
+    return (np.cumsum(deltas) % 65536).astype(np.uint16).view(np.int16)
+
+
+def _svb16_blocks():
+    rng = np.random.default_rng(21)
+    blocks = {}
+    for count in (0, 1, 7, 8, 9, 15, 16, 17, 64, 65):
+        blocks["mixed%d" % count] = _from_widths(rng.integers(1, 3, count), rng)
+        blocks["one%d" % count] = _from_widths([1] * count, rng)
+        blocks["two%d" % count] = _from_widths([2] * count, rng)
+    # after the first group of eight, exactly 15 / 16 / 17 data bytes are left: the wide path (taken while 16 remain) hands over
+    # to the byte-wise tail before, at and after that point
+    blocks["left15"] = _from_widths([2] * 8 + [1] * 15, rng)
+    blocks["left16"] = _from_widths([1, 2] * 4 + [1] * 16, rng)
+    blocks["left17"] = _from_widths([1] * 8 + [1] * 7 + [2] + [1] * 8, rng)
+    blocks["left16_two_byte_end"] = _from_widths([1] * 8 + [2] * 8, rng)
+    blocks["wrap"] = np.array([32767, -32768, 32767, -1, 0, -32768, -32768, 32767, 1, -32767, 255, 256, -128, -129, 128, 127, -256, -255,
+                               32767, 0, -32768, 0], np.int16)
+    return blocks
+
+
+@pytest.mark.parametrize("name", list(_svb16_blocks()))
+def test_host_svb16_decode_equals_scalar_decoder(name):
+    import ctypes as C
+    from bonito_amd import _lib
+    x = _svb16_blocks()[name]
+    enc = svb16_encode(x)
+    count = len(x)
+    want = svb16_decode_scalar(enc, count)
+    assert want is not None and want[0] == x.tolist() and want[1] == len(enc)          # the second decoder undoes the writer
+    decode = _lib.lib().bh_host_svb16_decode
+
+    def run(n_in):
+        src = np.frombuffer(enc + b"\xff" * 32, np.uint8)                              # what lies behind a short input is readable here
+        out = np.full(count + 16, 0x5A5A, np.int16)
+        used = decode(src.ctypes.data_as(C.c_void_p), n_in, count, out.ctypes.data_as(C.c_void_p))
+        assert (out[count:] == 0x5A5A).all(), "wrote behind out"
+        return used, out[:count]
+
+    used, got = run(len(enc))
+    assert used == len(enc) and got.tolist() == want[0]
+    used, got = run(len(enc) + 32)                                                     # bytes behind the block are left alone
+    assert used == len(enc) and got.tolist() == want[0]
+    for cut in range(1, min(17, len(enc)) + 1):                                        # every truncation is refused, never read past
+        assert svb16_decode_scalar(enc[:len(enc) - cut], count) is None
+        assert run(len(enc) - cut)[0] == -1, cut
