@@ -3,9 +3,9 @@ import sys
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
 from bonito_amd import __version__
-from bonito_amd.cli import basecaller, evaluate
+from bonito_amd.cli import basecaller, duplex, evaluate
 
-modules = ["basecaller", "evaluate"]
+modules = ["basecaller", "duplex", "evaluate"]
 
 
 def main(argv=None):

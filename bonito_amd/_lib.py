@@ -71,6 +71,9 @@ SIGNATURES = {
     "bh_crf_logz_dense_grad": (_i, [_vp, _i, _i, _i, _i, _f, _l, _l, _vp, _vp, _vp, _vp, _l, _l, _i, _vp]),
     "bh_sw_workspace": (_sz, [_i, _i, _i]),
     "bh_sw_align": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _l, _vp, _vp]),
+    "bh_sg_align": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _l, _vp, _vp]),
+    "bh_nw_workspace": (_sz, [_i, _i, _i, _l]),
+    "bh_nw_align": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _vp, _sz, _vp, _vp, _l, _vp, _vp]),
     "bh_set_option": (_i, [C.c_char_p, _i]),
     "bh_signal_normalise": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                             _i, _vp, _vp, _vp, _vp, _vp]),

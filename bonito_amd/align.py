@@ -4,6 +4,10 @@ call behind the reference's read accuracy (bonito/cli/evaluate.py:37-67 ``align`
 
 ``sw_align`` is the batched entry (kernel: csrc/align.hip through ``bh_sw_align``); ``align`` / ``AlignResult`` carry the reference's
 names. The definition, with its tie-breaks, is in DESIGN.md section 6. There is no host fallback.
+
+The duplex caller's two alignments live here too: ``sg_align`` (the semi-global mode of the same kernels, ``bh_sg_align``; parasail's
+``sg_trace_scan_32``) and ``nw_align`` (banded global alignment under unit costs for reads of up to 65536 bases, csrc/nw.hip through
+``bh_nw_align``; edlib's ``align(..., task="path")``), bonito/cli/duplex.py:224-269.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -128,18 +132,34 @@ def sw_align(seqs, refs, match=5, mismatch=-4, gap_open=8, gap_extend=4, cigar=F
     lists of strings over ACGT (empty strings are legal) or code planes. The defaults are the reference's parasail arguments
     (dnafull on A, C, G, T: +5 / -4; open 8, extend 4). Pairs are sorted by size and cut into launches whose workspace stays within
     ``workspace_budget`` bytes; the results come back in the caller's order as a ``SwBatch``."""
+    return _affine("sw_align", seqs, refs, match, mismatch, gap_open, gap_extend, cigar, workspace_budget, device)
+
+
+def sg_align(seqs, refs, match=5, mismatch=-4, gap_open=10, gap_extend=2, cigar=True, workspace_budget=DEFAULT_WORKSPACE_BUDGET,
+             device="cuda"):
+    """The semi-global mode of the same aligner (kernel: ``bh_sg_align``): end gaps are free on both sequences at both ends, and the
+    CIGAR covers both sequences completely - the unaligned head and tail come out as one I or D run each. The defaults are the
+    reference's ``parasail.sg_trace_scan_32(query, ref, 10, 2, dnafull)`` (bonito/cli/duplex.py:240-243). The definition, with its
+    tie-breaks, is in DESIGN.md section 6. Same limits, slicing and ``SwBatch`` as ``sw_align``; the counts include the overhang
+    runs, the start / end columns describe the aligned part."""
+    return _affine("sg_align", seqs, refs, match, mismatch, gap_open, gap_extend, cigar, workspace_budget, device)
+
+
+def _affine(name, seqs, refs, match, mismatch, gap_open, gap_extend, cigar, workspace_budget, device):
+    sg = name == "sg_align"
     sc, sl = _encode(seqs, "seqs")
     rc, rl = _encode(refs, "refs")
     n = len(sl)
     if len(rl) != n:
-        raise ValueError("sw_align: %d seqs against %d refs" % (n, len(rl)))
+        raise ValueError("%s: %d seqs against %d refs" % (name, n, len(rl)))
     if max([0] + sl.tolist() + rl.tolist()) > MAX_LEN:
-        raise ValueError("sw_align: sequences of up to %d bases are supported" % MAX_LEN)
+        raise ValueError("%s: sequences of up to %d bases are supported" % (name, MAX_LEN))
     table = np.zeros((n, len(COLUMNS)), np.int32)
     cigars = [""] * n if cigar else None
     if n == 0:
         return SwBatch(table, sl, rl, cigars)
     lib = _lib.lib()
+    entry = lib.bh_sg_align if sg else lib.bh_sw_align
     passes = (sl.astype(np.int64) + 511) // 512
     order = np.argsort(passes * (rl.astype(np.int64) + 63), kind="stable")
     ip = C.POINTER(C.c_int32)
@@ -155,13 +175,13 @@ def sw_align(seqs, refs, match=5, mismatch=-4, gap_open=8, gap_extend=4, cigar=F
         ops = n_ops = None
         stride = 0
         if cigar:
-            stride = max(1, int(np.where((s_len > 0) & (r_len > 0), s_len + r_len - 1, 0).max()))
+            stride = max(1, int((s_len + r_len).max() if sg else np.where((s_len > 0) & (r_len > 0), s_len + r_len - 1, 0).max()))
             ops = torch.empty((k, stride), dtype=torch.int32, device=device)
             n_ops = torch.empty(k, dtype=torch.int32, device=device)
-        _lib.check(lib.bh_sw_align(_lib.ptr(s_dev), s_dev.shape[1], s_len.ctypes.data_as(ip), _lib.ptr(r_dev), r_dev.shape[1],
-                                   r_len.ctypes.data_as(ip), k, int(match), int(mismatch), int(gap_open), int(gap_extend),
-                                   _lib.ptr(ws), nbytes, _lib.ptr(res), _lib.ptr(ops), stride, _lib.ptr(n_ops),
-                                   _lib.stream_ptr(s_dev.device)), "bh_sw_align")
+        _lib.check(entry(_lib.ptr(s_dev), s_dev.shape[1], s_len.ctypes.data_as(ip), _lib.ptr(r_dev), r_dev.shape[1],
+                         r_len.ctypes.data_as(ip), k, int(match), int(mismatch), int(gap_open), int(gap_extend),
+                         _lib.ptr(ws), nbytes, _lib.ptr(res), _lib.ptr(ops), stride, _lib.ptr(n_ops),
+                         _lib.stream_ptr(s_dev.device)), "bh_sg_align" if sg else "bh_sw_align")
         table[idx] = res.cpu().numpy()
         if cigar:
             counts = n_ops.cpu().numpy()
@@ -170,6 +190,140 @@ def sw_align(seqs, refs, match=5, mismatch=-4, gap_open=8, gap_extend=4, cigar=F
             for row, i in enumerate(idx):
                 cigars[i] = runs_to_cigar(runs[row, :counts[row]])
     return SwBatch(table, sl, rl, cigars)
+
+
+NW_COLUMNS = ("distance", "num_correct", "num_mismatches", "num_insertions", "num_deletions", "num_runs", "band", "status")
+NW_MAX_LEN = 65536
+NW_FIRST_BAND = 64                               # the first half-width k; a rejected pair runs again with k doubled ...
+NW_MAX_BAND = 65536                              # ... up to the half-width at which the band holds every cell of the longest pair
+# Traceback bits cost ceil(seq / 512) * (min(ref, 511 + band width) + 63) * 128 bytes per pair, band width = |ref - seq| + 2 k + 1:
+# 4.3 MiB for 10 000 bases at k = 512, 60 MiB for 50 000 at k = 2048, 2 GiB for the full matrix of the longest pair. 8 GiB keeps a
+# batch of 512 reads or 64 long ones in one launch, one wave per pair.
+NW_WORKSPACE_BUDGET = 8 << 30
+NW_OK, NW_NO_FIT = 0, 2                          # status: accepted / the band the pair needs does not fit the workspace budget
+
+
+class NwBatch:
+    """Results of one ``nw_align`` call in the caller's order: ``table`` int32 [n, 8] (``NW_COLUMNS``), ``seq_len`` / ``ref_len``,
+    ``runs`` (per pair the uint32 runs of bh_nw_align, or None; no runs where status is not 0), ``cigar`` (the same as strings, made
+    on first use: long reads have thousands of runs each) and ``ops(i)`` (the same as [(length, op character)]); every column is an
+    attribute."""
+
+    def __init__(self, table, seq_len, ref_len, runs=None):
+        self.table = np.asarray(table, np.int32).reshape(-1, len(NW_COLUMNS))
+        self.seq_len = np.asarray(seq_len, np.int32)
+        self.ref_len = np.asarray(ref_len, np.int32)
+        self.runs = runs
+        self._cigar = None
+
+    @property
+    def cigar(self):
+        if self._cigar is None and self.runs is not None:
+            self._cigar = [runs_to_cigar(r) for r in self.runs]
+        return self._cigar
+
+    def ops(self, i):
+        r = self.runs[i]
+        return list(zip((r >> 2).tolist(), [OPS[c] for c in (r & 3).tolist()]))
+
+    def __len__(self):
+        return self.table.shape[0]
+
+    def __getattr__(self, name):
+        if name in NW_COLUMNS:
+            return self.table[:, NW_COLUMNS.index(name)]
+        raise AttributeError(name)
+
+
+def _nw_slices(order, seq_len, ref_len, k, budget, lib):
+    """Cut the size-sorted pairs into runs whose bh_nw_workspace at half-width k stays within the budget -> (runs of (indices, max
+    seq, max ref, max band), indices of the pairs that do not fit alone)."""
+    out, unfit, lo = [], [], 0
+    band = np.abs(ref_len.astype(np.int64) - seq_len) + 2 * k + 1
+    while lo < len(order):
+        hi, ms, mr, mb = lo, 0, 0, 1
+        while hi < len(order):
+            i = order[hi]
+            s, r, b = max(ms, int(seq_len[i])), max(mr, int(ref_len[i])), max(mb, int(band[i]))
+            if lib.bh_nw_workspace(hi - lo + 1, s, r, b) > budget:
+                break
+            hi, ms, mr, mb = hi + 1, s, r, b
+        if hi == lo:
+            unfit.append(order[lo])
+            lo += 1
+            continue
+        out.append((order[lo:hi], ms, mr, mb))
+        lo = hi
+    return out, unfit
+
+
+def nw_align(seqs, refs, cigar=True, band=NW_FIRST_BAND, workspace_budget=NW_WORKSPACE_BUDGET, device="cuda"):
+    """Global alignment under unit costs (edit distance with a path) of seqs[i] (the query) against refs[i], for lists of strings
+    over ACGT (empty strings are legal) or code planes of up to 65536 bases: the engine's counterpart of
+    ``edlib.align(query, ref, task="path")`` (kernel: csrc/nw.hip through ``bh_nw_align``; the definition, its tie-breaks and the
+    band argument are in DESIGN.md section 6). ``band`` is the first half-width k of the diagonal band; a pair whose banded distance
+    d does not satisfy floor((d - |len difference|) / 2) <= k is run again with k doubled, so the results do not depend on it
+    (except the column ``band``, the k that was accepted). Every round sorts its pairs by size and cuts them into launches whose
+    workspace stays within ``workspace_budget`` bytes; a pair whose band does not fit the budget alone comes back with status
+    ``NW_NO_FIT``, the last banded distance (an upper bound; -1 if none was computed) and no CIGAR. -> ``NwBatch``."""
+    sc, sl = _encode(seqs, "seqs")
+    rc, rl = _encode(refs, "refs")
+    n = len(sl)
+    if len(rl) != n:
+        raise ValueError("nw_align: %d seqs against %d refs" % (n, len(rl)))
+    if max([0] + sl.tolist() + rl.tolist()) > NW_MAX_LEN:
+        raise ValueError("nw_align: sequences of up to %d bases are supported" % NW_MAX_LEN)
+    k = int(band)
+    if not 1 <= k <= NW_MAX_BAND:
+        raise ValueError("nw_align: band must be in 1..%d" % NW_MAX_BAND)
+    table = np.zeros((n, len(NW_COLUMNS)), np.int32)
+    table[:, 0] = -1
+    runs = [np.zeros(0, np.uint32)] * n if cigar else None
+    if n == 0:
+        return NwBatch(table, sl, rl, runs)
+    lib = _lib.lib()
+    ip = C.POINTER(C.c_int32)
+    todo = np.arange(n)
+    while len(todo):
+        size = ((sl[todo].astype(np.int64) + 511) // 512) * np.minimum(rl[todo].astype(np.int64), 511 + np.abs(rl[todo] - sl[todo]) + 2 * k + 1)
+        slices, unfit = _nw_slices(todo[np.argsort(size, kind="stable")], sl, rl, k, int(workspace_budget), lib)
+        for i in unfit:
+            table[i, 1:] = (0, 0, 0, 0, 0, k, NW_NO_FIT)
+        again = []
+        for idx, ms, mr, mb in slices:
+            cnt = len(idx)
+            sel = torch.from_numpy(np.ascontiguousarray(idx))
+            s_dev = sc[sel][:, :max(ms, 1)].contiguous().to(device)
+            r_dev = rc[sel][:, :max(mr, 1)].contiguous().to(device)
+            s_len, r_len = np.ascontiguousarray(sl[idx]), np.ascontiguousarray(rl[idx])
+            nbytes = lib.bh_nw_workspace(cnt, ms, mr, mb)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            res = torch.empty((cnt, len(NW_COLUMNS)), dtype=torch.int32, device=device)
+            ops = n_ops = None
+            stride = 0
+            if cigar:
+                stride = max(1, int((s_len + r_len).max()))
+                ops = torch.empty((cnt, stride), dtype=torch.int32, device=device)
+                n_ops = torch.empty(cnt, dtype=torch.int32, device=device)
+            _lib.check(lib.bh_nw_align(_lib.ptr(s_dev), s_dev.shape[1], s_len.ctypes.data_as(ip), _lib.ptr(r_dev), r_dev.shape[1],
+                                       r_len.ctypes.data_as(ip), cnt, k, _lib.ptr(ws), nbytes, _lib.ptr(res), _lib.ptr(ops), stride,
+                                       _lib.ptr(n_ops), _lib.stream_ptr(s_dev.device)), "bh_nw_align")
+            rows = res.cpu().numpy()
+            table[idx] = rows
+            if (rows[:, 7] > 1).any():
+                raise RuntimeError("nw_align: the traceback left the band of an accepted pair")
+            again.append(idx[rows[:, 7] == 1])
+            if cigar:
+                counts = n_ops.cpu().numpy()
+                width = int(counts.max()) if cnt else 0
+                plane = ops[:, :max(width, 1)].cpu().numpy().view(np.uint32)
+                for row, i in enumerate(idx):
+                    runs[i] = plane[row, :counts[row]].copy()
+        todo = np.concatenate(again) if again else np.zeros(0, np.int64)
+        if len(todo) and k >= NW_MAX_BAND:
+            raise RuntimeError("nw_align: a pair was rejected at the largest band")       # the largest band holds every cell
+        k = min(2 * k, NW_MAX_BAND)
+    return NwBatch(table, sl, rl, runs)
 
 
 def align(*, ref, seq, **scoring):

@@ -351,6 +351,21 @@ extern "C" int bh_sw_align(const void* seqs, long seq_stride, const int32_t* seq
     return bh_k_sw_align(seqs, seq_stride, seq_lengths, refs, ref_stride, ref_lengths, n, match, mismatch, gap_open, gap_extend,
                          workspace, workspace_bytes, result, ops, ops_stride, n_ops, (hipStream_t)stream);
 }
+extern "C" int bh_sg_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, const void* refs, long ref_stride,
+                           const int32_t* ref_lengths, int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace,
+                           size_t workspace_bytes, int32_t* result, uint32_t* ops, long ops_stride, int32_t* n_ops, void* stream) {
+    return bh_k_sg_align(seqs, seq_stride, seq_lengths, refs, ref_stride, ref_lengths, n, match, mismatch, gap_open, gap_extend,
+                         workspace, workspace_bytes, result, ops, ops_stride, n_ops, (hipStream_t)stream);
+}
+extern "C" size_t bh_nw_workspace(int n, int max_seq, int max_ref, long max_band) {
+    return bh_k_nw_workspace(n, max_seq, max_ref, max_band);
+}
+extern "C" int bh_nw_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, const void* refs, long ref_stride,
+                           const int32_t* ref_lengths, int n, int k, void* workspace, size_t workspace_bytes, int32_t* result,
+                           uint32_t* ops, long ops_stride, int32_t* n_ops, void* stream) {
+    return bh_k_nw_align(seqs, seq_stride, seq_lengths, refs, ref_stride, ref_lengths, n, k, workspace, workspace_bytes, result, ops,
+                         ops_stride, n_ops, (hipStream_t)stream);
+}
 extern "C" int bh_signal_normalise(const int16_t* raw, const long* offsets, const float* cal_scale, const float* cal_offset, int n_reads,
                                    int strategy, double quantile_a, double quantile_b, double shift_mult, double scale_mult,
                                    double fixed_shift, double fixed_scale, int do_trim, double* shift, double* scale, int* weak,

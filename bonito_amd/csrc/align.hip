@@ -13,6 +13,11 @@
 // in the workspace). Each cell leaves 4 traceback bits (2: source of H, 1: E extended, 1: F extended); the 8 cells of a lane
 // and a step make one dword, stored as [pass][step][lane], so a wave's store is one contiguous 256 bytes.
 // Traceback kernel: one pair per thread walks the bits back from the end cell, counts the ops and writes the run-length ops.
+//
+// Semi-global mode (template parameter SG; bh_sg_align, the counterpart of parasail.sg_trace_scan_32 behind the reference's duplex end
+// repair, bonito/cli/duplex.py:240-243): H without the floor at 0, H(i,0) = H(0,j) = 0, the end cell is the largest H over the last row
+// and the last column (the smallest i, then the smallest j), the walk stops on reaching row 0 or column 0, and the CIGAR covers both
+// sequences completely - head and tail overhangs come out as one I or D run each.
 #include "common.h"
 #include "kernels.h"
 #include <vector>
@@ -23,6 +28,7 @@ constexpr int SW_R = 8;                     // query rows per lane
 constexpr int SW_ROWS = WAVE * SW_R;        // query rows per pass
 constexpr int SW_MAX_LEN = 4096;
 constexpr int SW_MAX_PARAM = 32767;         // |score parameter| bound: 4096 * 32767 < 2^31
+constexpr int SW_NONE = -2147483647 - 1;     // semi-global: "no end cell yet", below every H
 constexpr int SW_NEG = -(1 << 30);          // E / F "minus infinity": NEG - extend cannot wrap, and no H - open reaches it
 
 struct SwArgs {
@@ -41,10 +47,12 @@ __device__ __forceinline__ int wave_shr1(int first, int v) {
     return __builtin_amdgcn_update_dpp(first, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
 }
 
+// SG: the semi-global mode (H without the floor at 0, the end cell on the last row or the last column)
+template <bool SG>
 __global__ __launch_bounds__(WAVE) void sw_forward_kernel(SwArgs a) {
     const int pair = blockIdx.x, lane = threadIdx.x;
     const int m = a.seq_len[pair], n = a.ref_len[pair];
-    int best = 0, besti = -1, bestj = -1;
+    int best = SG ? SW_NONE : 0, besti = -1, bestj = -1;
     if (m > 0 && n > 0) {
         const int8_t* seq = a.seq + (long)pair * a.seq_stride;
         const int8_t* ref = a.ref + (long)pair * a.ref_stride;
@@ -57,7 +65,7 @@ __global__ __launch_bounds__(WAVE) void sw_forward_kernel(SwArgs a) {
 #pragma unroll
             for (int r = 0; r < SW_R; ++r) {
                 q[r] = row0 + r < m ? (int)seq[row0 + r] : 0;
-                H[r] = 0; E[r] = SW_NEG; bH[r] = 0; bJ[r] = 0;
+                H[r] = 0; E[r] = SW_NEG; bH[r] = SG ? SW_NONE : 0; bJ[r] = 0;
             }
             int hdiag = 0, h_out = 0, f_out = SW_NEG, c_out = 0;
             const int2* bin = a.bound + ((size_t)pair * 2 + (p & 1)) * a.bound_stride;
@@ -89,11 +97,12 @@ __global__ __launch_bounds__(WAVE) void sw_forward_kernel(SwArgs a) {
                             const int fo = hu - open, fe = fu - ext;
                             const int e = max(eo, ee), f = max(fo, fe);
                             const int d = hd + s;
-                            const int h = max(max(max(d, e), f), 0);
-                            // stop at H = 0, then the diagonal, then E, then F; E / F: the open wins a tie
-                            const unsigned src = h == 0 ? 0u : h == d ? 1u : h == e ? 2u : 3u;
+                            const int h = SG ? max(max(d, e), f) : max(max(max(d, e), f), 0);
+                            // stop at H = 0 (local mode only), then the diagonal, then E, then F; E / F: the open wins a tie
+                            const unsigned src = !SG && h == 0 ? 0u : h == d ? 1u : h == e ? 2u : 3u;
                             bits |= (src | (ee > eo ? 4u : 0u) | (fe > fo ? 8u : 0u)) << (4 * r);
-                            if (h > bH[r]) { bH[r] = h; bJ[r] = j; }         // strict: the smallest j of a row
+                            // strict: the smallest j of a row; semi-global: only the last column and the last row can end
+                            if ((!SG || j == n - 1 || row0 + r == m - 1) && h > bH[r]) { bH[r] = h; bJ[r] = j; }
                             hd = H[r]; H[r] = h; E[r] = e; hu = h; fu = f;
                         }
                         h_out = hu; f_out = fu;
@@ -133,13 +142,23 @@ __global__ __launch_bounds__(WAVE) void sw_forward_kernel(SwArgs a) {
 }
 
 // ops: 0 '=', 1 'X', 2 'I', 3 'D'; a run is (length << 2) | op
+// SG: the walk stops on reaching row 0 or column 0, and the CIGAR covers both sequences completely: what lies before the first and
+// after the last aligned column comes out as one I or D run each (the counts include them)
+template <bool SG>
 __global__ __launch_bounds__(WAVE) void sw_traceback_kernel(SwArgs a, int npairs) {
     const int pair = blockIdx.x * WAVE + threadIdx.x;
     if (pair >= npairs) return;
     const int m = a.seq_len[pair], n = a.ref_len[pair];
     const int score = a.endcell[pair * 4 + 0], ei = a.endcell[pair * 4 + 1], ej = a.endcell[pair * 4 + 2];
     int* res = a.result + (long)pair * 10;
-    if (score <= 0 || ei < 0 || ej < 0 || ei >= m || ej >= n) {
+    if (SG && (m == 0 || n == 0)) {                                          // nothing to align: one run over the other sequence
+        const int len = m + n;
+        res[0] = 0; res[1] = 0; res[2] = 0; res[3] = m; res[4] = n; res[5] = 0; res[6] = -1; res[7] = 0; res[8] = -1; res[9] = len > 0;
+        if (a.ops && len) a.ops[(long)pair * a.ops_stride] = ((unsigned)len << 2) | (m ? 2u : 3u);
+        if (a.n_ops) a.n_ops[pair] = len > 0;
+        return;
+    }
+    if ((!SG && score <= 0) || ei < 0 || ej < 0 || ei >= m || ej >= n) {
         res[0] = 0; res[1] = 0; res[2] = 0; res[3] = 0; res[4] = 0; res[5] = 0; res[6] = -1; res[7] = 0; res[8] = -1; res[9] = 0;
         if (a.n_ops) a.n_ops[pair] = 0;
         return;
@@ -151,26 +170,35 @@ __global__ __launch_bounds__(WAVE) void sw_traceback_kernel(SwArgs a, int npairs
     const int S = n + WAVE - 1;
     int cnt[4] = {0, 0, 0, 0};
     int i = ei, j = ej, state = 0, run_op = -1, run_len = 0, nruns = 0;
-    auto emit = [&](int op) {
-        cnt[0] += op == 0; cnt[1] += op == 1; cnt[2] += op == 2; cnt[3] += op == 3;
-        if (op == run_op) { ++run_len; return; }
+    auto emit = [&](int op, int len = 1) {
+        cnt[0] += op == 0 ? len : 0; cnt[1] += op == 1 ? len : 0; cnt[2] += op == 2 ? len : 0; cnt[3] += op == 3 ? len : 0;
+        if (op == run_op) { run_len += len; return; }
         if (run_len) {
             if (ops && nruns < a.ops_stride) ops[nruns] = ((unsigned)run_len << 2) | (unsigned)run_op;
             ++nruns;
         }
-        run_op = op; run_len = 1;
+        run_op = op; run_len = len;
     };
+    if (SG) {                                                                // the end cell lies on the last row or the last column
+        if (n - 1 - ej > 0) emit(3, n - 1 - ej);
+        if (m - 1 - ei > 0) emit(2, m - 1 - ei);
+    }
     for (int it = 0; it < m + n && i >= 0 && j >= 0; ++it) {                // every turn consumes a base: at most m + n turns
         const int ln = (i & (SW_ROWS - 1)) >> 3;
         const unsigned bits = trace[((size_t)(i / SW_ROWS) * S + j + ln) * WAVE + ln] >> (4 * (i & 7));
         if (state == 0) {
             const unsigned src = bits & 3u;
-            if (src == 0) break;
+            if (!SG && src == 0) break;
             if (src == 1) { emit(seq[i] == ref[j] ? 0 : 1); --i; --j; continue; }
             state = src == 2 ? 1 : 2;
         }
         if (state == 1) { emit(3); state = (bits & 4u) ? 1 : 0; --j; }
         else { emit(2); state = (bits & 8u) ? 2 : 0; --i; }
+    }
+    const int si = i, sj = j;                                                // one before the first aligned column
+    if (SG) {
+        if (si >= 0) emit(2, si + 1);
+        if (sj >= 0) emit(3, sj + 1);
     }
     if (run_len) {
         if (ops && nruns < a.ops_stride) ops[nruns] = ((unsigned)run_len << 2) | (unsigned)run_op;
@@ -181,7 +209,7 @@ __global__ __launch_bounds__(WAVE) void sw_traceback_kernel(SwArgs a, int npairs
         for (int x = 0, y = w - 1; x < y; ++x, --y) { const unsigned v = ops[x]; ops[x] = ops[y]; ops[y] = v; }
     }
     res[0] = score; res[1] = cnt[0]; res[2] = cnt[1]; res[3] = cnt[2]; res[4] = cnt[3];
-    res[5] = j + 1; res[6] = ej; res[7] = i + 1; res[8] = ei; res[9] = nruns;
+    res[5] = sj + 1; res[6] = ej; res[7] = si + 1; res[8] = ei; res[9] = nruns;
     if (a.n_ops) a.n_ops[pair] = nruns;
 }
 
@@ -207,35 +235,38 @@ size_t bh_k_sw_workspace(int n, int max_seq, int max_ref) {
     return bh::sw_layout(n, max_seq, max_ref, &L) ? L.total : 0;
 }
 
-int bh_k_sw_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,
-                  int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace, size_t workspace_bytes,
-                  int* result, unsigned* ops, long ops_stride, int* n_ops, hipStream_t stream) {
+template <bool SG>
+static int affine_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,
+                        int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace, size_t workspace_bytes,
+                        int* result, unsigned* ops, long ops_stride, int* n_ops, hipStream_t stream) {
     using namespace bh;
-    BH_REQUIRE(n > 0, "sw_align: n must be positive (got %d)", n);
-    BH_REQUIRE(seqs && refs && seq_lens && ref_lens && workspace && result, "sw_align: null pointer");
-    BH_REQUIRE(match >= 1 && match <= SW_MAX_PARAM, "sw_align: match must be in 1..%d (got %d)", SW_MAX_PARAM, match);
-    BH_REQUIRE(mismatch < match && mismatch >= -SW_MAX_PARAM, "sw_align: mismatch must be in %d..match-1 (got %d)", -SW_MAX_PARAM,
+    const char* who = SG ? "sg" : "sw";
+    BH_REQUIRE(n > 0, "%s_align: n must be positive (got %d)", who, n);
+    BH_REQUIRE(seqs && refs && seq_lens && ref_lens && workspace && result, "%s_align: null pointer", who);
+    BH_REQUIRE(match >= 1 && match <= SW_MAX_PARAM, "%s_align: match must be in 1..%d (got %d)", who, SW_MAX_PARAM, match);
+    BH_REQUIRE(mismatch < match && mismatch >= -SW_MAX_PARAM, "%s_align: mismatch must be in %d..match-1 (got %d)", who, -SW_MAX_PARAM,
                mismatch);
-    BH_REQUIRE(gap_extend >= 1, "sw_align: gap_extend must be at least 1 (got %d)", gap_extend);
-    BH_REQUIRE(gap_open >= gap_extend && gap_open <= SW_MAX_PARAM, "sw_align: gap_open must be in gap_extend..%d (got open %d, extend %d)",
+    BH_REQUIRE(gap_extend >= 1, "%s_align: gap_extend must be at least 1 (got %d)", who, gap_extend);
+    BH_REQUIRE(gap_open >= gap_extend && gap_open <= SW_MAX_PARAM, "%s_align: gap_open must be in gap_extend..%d (got open %d, extend %d)", who,
                SW_MAX_PARAM, gap_open, gap_extend);
-    BH_REQUIRE(seq_stride >= 0 && ref_stride >= 0 && ops_stride >= 0, "sw_align: negative stride");
-    BH_REQUIRE(!n_ops || ops, "sw_align: n_ops without an ops buffer");
+    BH_REQUIRE(seq_stride >= 0 && ref_stride >= 0 && ops_stride >= 0, "%s_align: negative stride", who);
+    BH_REQUIRE(!n_ops || ops, "%s_align: n_ops without an ops buffer", who);
     int max_seq = 0, max_ref = 0;
     for (int i = 0; i < n; ++i) {
         const int m = seq_lens[i], r = ref_lens[i];
-        BH_REQUIRE(m >= 0 && r >= 0, "sw_align: pair %d has a negative length (%d, %d)", i, m, r);
-        BH_REQUIRE(m <= seq_stride && r <= ref_stride, "sw_align: pair %d: lengths (%d, %d) exceed the row strides (%ld, %ld)", i, m, r,
+        BH_REQUIRE(m >= 0 && r >= 0, "%s_align: pair %d has a negative length (%d, %d)", who, i, m, r);
+        BH_REQUIRE(m <= seq_stride && r <= ref_stride, "%s_align: pair %d: lengths (%d, %d) exceed the row strides (%ld, %ld)", who, i, m, r,
                    seq_stride, ref_stride);
-        BH_REQUIRE(m <= SW_MAX_LEN && r <= SW_MAX_LEN, "sw_align: pair %d: lengths (%d, %d) exceed the supported %d", i, m, r, SW_MAX_LEN);
-        const long need = m && r ? (long)m + r - 1 : 0;                     // every op consumes a base, the first one two
-        BH_REQUIRE(!ops || need <= ops_stride, "sw_align: pair %d may need %ld CIGAR runs, the ops rows hold %ld", i, need, ops_stride);
+        BH_REQUIRE(m <= SW_MAX_LEN && r <= SW_MAX_LEN, "%s_align: pair %d: lengths (%d, %d) exceed the supported %d", who, i, m, r, SW_MAX_LEN);
+        // every op consumes a base, the first one two; the semi-global CIGAR may begin or end with an overhang run
+        const long need = SG ? (long)m + r : m && r ? (long)m + r - 1 : 0;
+        BH_REQUIRE(!ops || need <= ops_stride, "%s_align: pair %d may need %ld CIGAR runs, the ops rows hold %ld", who, i, need, ops_stride);
         max_seq = m > max_seq ? m : max_seq;
         max_ref = r > max_ref ? r : max_ref;
     }
     SwLayout L;
-    BH_REQUIRE(sw_layout(n, max_seq, max_ref, &L), "sw_align: unsupported shape");
-    BH_REQUIRE(workspace_bytes >= L.total, "sw_align: workspace of %zu bytes, %zu needed (bh_sw_workspace(%d, %d, %d))", workspace_bytes,
+    BH_REQUIRE(sw_layout(n, max_seq, max_ref, &L), "%s_align: unsupported shape", who);
+    BH_REQUIRE(workspace_bytes >= L.total, "%s_align: workspace of %zu bytes, %zu needed (bh_sw_workspace(%d, %d, %d))", who, workspace_bytes,
                L.total, n, max_seq, max_ref);
     char* ws = (char*)workspace;
     // the lengths are host arrays (they were just validated): one blocking copy to the head of the workspace, ordered on the stream
@@ -245,9 +276,23 @@ int bh_k_sw_align(const void* seqs, long seq_stride, const int* seq_lens, const 
     SwArgs a{(const int8_t*)seqs, seq_stride, (const int8_t*)refs, ref_stride, (const int*)ws, (const int*)ws + n,
              match, mismatch, gap_open, gap_extend, (unsigned*)(ws + L.trace), L.trace_stride, (int2*)(ws + L.bound), L.bound_stride,
              (int*)(ws + L.endcell), result, ops, ops_stride, n_ops};
-    hipLaunchKernelGGL(sw_forward_kernel, dim3(n), dim3(WAVE), 0, stream, a);
+    hipLaunchKernelGGL(sw_forward_kernel<SG>, dim3(n), dim3(WAVE), 0, stream, a);
     BH_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(sw_traceback_kernel, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), 0, stream, a, n);
+    hipLaunchKernelGGL(sw_traceback_kernel<SG>, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), 0, stream, a, n);
     BH_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+int bh_k_sw_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,
+                  int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace, size_t workspace_bytes,
+                  int* result, unsigned* ops, long ops_stride, int* n_ops, hipStream_t stream) {
+    return affine_align<false>(seqs, seq_stride, seq_lens, refs, ref_stride, ref_lens, n, match, mismatch, gap_open, gap_extend,
+                               workspace, workspace_bytes, result, ops, ops_stride, n_ops, stream);
+}
+
+int bh_k_sg_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,
+                  int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace, size_t workspace_bytes,
+                  int* result, unsigned* ops, long ops_stride, int* n_ops, hipStream_t stream) {
+    return affine_align<true>(seqs, seq_stride, seq_lens, refs, ref_stride, ref_lens, n, match, mismatch, gap_open, gap_extend,
+                              workspace, workspace_bytes, result, ops, ops_stride, n_ops, stream);
 }

@@ -145,6 +145,16 @@ size_t bh_k_sw_workspace(int n, int max_seq, int max_ref);
 int bh_k_sw_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,
                   int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace, size_t workspace_bytes,
                   int* result, unsigned* ops, long ops_stride, int* n_ops, hipStream_t stream);
+// the semi-global mode of the same kernels (free end gaps on both sequences, the CIGAR covers both completely); bh_k_sw_workspace
+int bh_k_sg_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,
+                  int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace, size_t workspace_bytes,
+                  int* result, unsigned* ops, long ops_stride, int* n_ops, hipStream_t stream);
+
+// nw.hip (banded global alignment under unit costs with a traceback; one band half-width k per call; the lengths are host arrays)
+size_t bh_k_nw_workspace(int n, int max_seq, int max_ref, long max_band);
+int bh_k_nw_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,
+                  int n, int k, void* workspace, size_t workspace_bytes, int* result, unsigned* ops, long ops_stride, int* n_ops,
+                  hipStream_t stream);
 
 // beam.hip: the decode stage on koi-layout scores. The three calls share ONE workspace layout (decode_workspace); a beam search's
 // launches - backward scan, forward / posterior scan (fused into the beam kernel or not, on the helper stream or not), beam kernel

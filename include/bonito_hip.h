@@ -24,6 +24,9 @@
  *   bh_sw_align
  *        parasail.sw_trace_striped_32(seq, ref, 8, 4, parasail.dnafull) behind evaluate's align() and util.accuracy
  *                                                                              bonito/cli/evaluate.py:37-67, bonito/util.py:346-368
+ *   bh_nw_align / bh_sg_align
+ *        edlib.align(query, ref, task="path") and parasail.sg_trace_scan_32(query, ref, 10, 2, dnafull) behind the basespace
+ *        duplex caller                                                         bonito/cli/duplex.py:224-300
  *   bh_ctc_greedy_decode / bh_ctc_beam_search
  *        fast_ctc_decode.viterbi_search / beam_search                          bonito/ctc/model.py:39-46
  *   bh_linear, bh_conv1d_*, bh_lstm_layer, ...  (operator level, used by the parity tests)
@@ -280,6 +283,39 @@ size_t bh_sw_workspace(int n, int max_seq, int max_ref);
 int bh_sw_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, const void* refs, long ref_stride,
                 const int32_t* ref_lengths, int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace,
                 size_t workspace_bytes, int32_t* result, uint32_t* ops, long ops_stride, int32_t* n_ops, void* stream);
+
+/* Semi-global mode of the affine aligner: parasail.sg_trace_scan_32(query, ref, 10, 2, dnafull) behind the reference's duplex end
+ * repair (bonito/cli/duplex.py:240-243). The recurrences of bh_sw_align without the floor at 0; H(i,0) = H(0,j) = 0 (end gaps are free
+ * on both sequences at both ends), E and F start at minus infinity. End cell: the largest H over the last row and the last column,
+ * among equals the smallest i, then the smallest j. Traceback: the diagonal, then E, then F; in E / F the open wins a tie; it stops on
+ * reaching row 0 or column 0. The CIGAR covers BOTH sequences completely: what lies before the first and after the last aligned
+ * column comes out as one I (seq) or D (ref) run each, merged with an equal neighbour. Arguments, workspace (bh_sw_workspace), limits
+ * and errors as bh_sw_align, except: ops_stride must hold seq_len + ref_len runs; the counts of the result row include the overhang
+ * runs, the four start / end columns describe the aligned part; a pair with an empty sequence has score 0 and a single I or D run
+ * over the other one (no run when both are empty), starts 0 and ends -1. The score may be negative. */
+int bh_sg_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, const void* refs, long ref_stride,
+                const int32_t* ref_lengths, int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace,
+                size_t workspace_bytes, int32_t* result, uint32_t* ops, long ops_stride, int32_t* n_ops, void* stream);
+
+/* Banded global alignment under unit costs with a traceback: edlib.align(query, ref, task="path") behind the reference's duplex caller
+ * (bonito/cli/duplex.py:246-248). n pairs, one wave per pair, sequences of up to 65536 bases, arguments as bh_sw_align.
+ *   D(0,0) = 0, D(i,0) = i, D(0,j) = j
+ *   D(i,j) = min(D(i-1,j-1) + [seq_i != ref_j], D(i,j-1) + 1 (D: consumes a ref base), D(i-1,j) + 1 (I: consumes a seq base))
+ *   Traceback from (m,n): among the predecessors that attain the minimum the diagonal first, then D, then I.
+ * k (1..65536) is the band's half-width: with delta = ref_len - seq_len only the cells whose diagonal j - i lies in
+ *   [min(0, delta) - k, max(0, delta) + k] are computed, every other cell counts as +infinity. A pair is ACCEPTED when its banded
+ *   distance d satisfies floor((d - |delta|) / 2) <= k; distance and CIGAR then equal those of the full matrix. A rejected pair is to
+ *   be run again with a larger k (the caller's loop: align.nw_align doubles it).
+ * result (DEVICE int32 [n][8]): distance, counts of = X I D, number of runs, k, status. status 0: accepted. status 1: rejected, the
+ *   band was too narrow: distance is an upper bound, counts and runs are 0, no ops are written.
+ * ops / n_ops as bh_sw_align; ops_stride must hold seq_len + ref_len runs. A pair with an empty sequence has a single I or D run.
+ * workspace: DEVICE, bh_nw_workspace(n, max seq length, max ref length, max_band) bytes, max_band = the largest
+ *   |ref_len - seq_len| + 2 k + 1 of the batch (0 = unsupported shape). 2 traceback bits per cell of a pass's band window:
+ *   n * ceil(max_seq / 512) * (min(max_ref, 511 + max_band) + 63) * 128 bytes plus a small head; never seq * ref. */
+size_t bh_nw_workspace(int n, int max_seq, int max_ref, long max_band);
+int bh_nw_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, const void* refs, long ref_stride,
+                const int32_t* ref_lengths, int n, int k, void* workspace, size_t workspace_bytes, int32_t* result, uint32_t* ops,
+                long ops_stride, int32_t* n_ops, void* stream);
 
 /* Signal ingest on the device: replaces Read.__init__'s numpy work (bonito/reader.py:122-166 normalisation + trim, the pA
  * scaling and the trim threshold of bonito/pod5.py:52-67) and util.chunk + the fp16 cast (bonito/util.py:142-161, crf/basecall.py:31) for raw
