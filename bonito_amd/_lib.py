@@ -69,6 +69,11 @@ SIGNATURES = {
     "bh_crf_seq_logz_grad": (_i, [_vp, _i, _i, _i, _i, _f, _l, _l, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _l, _i, _i, _vp]),
     "bh_crf_logz_dense_grad_workspace": (_sz, [_i, _i, _i]),
     "bh_crf_logz_dense_grad": (_i, [_vp, _i, _i, _i, _i, _f, _l, _l, _vp, _vp, _vp, _vp, _l, _l, _i, _vp]),
+    "bh_ctc_loss_workspace": (_sz, [_i, _i, _i, _i]),
+    "bh_ctc_loss": (_i, [_vp, _i, _i, _i, _i, _l, _l, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bh_ctc_loss_grad_workspace": (_sz, [_i, _i, _i, _i]),
+    "bh_ctc_loss_grad": (_i, [_vp, _i, _i, _i, _i, _l, _l, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _i, _i, _vp]),
+    "bh_ctc_loss_last_kernel": (_i, []),
     "bh_sw_workspace": (_sz, [_i, _i, _i]),
     "bh_sw_align": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _l, _vp, _vp]),
     "bh_sg_align": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _l, _vp, _vp]),
@@ -127,6 +132,10 @@ CONV_KERNELS = {"none": 0, "first": 1, "ws_384": 20, "ws_96": 21, "front3_384": 
 
 def conv_igemm_code(ntt, fs):
     return CONV_KERNELS["igemm_base"] + 10 * ntt + int(fs)
+
+
+# enum bh_ctc_loss_kernel of include/bonito_hip.h: the instance table of csrc/ctc_loss.hip (code -> the largest Lmax it serves)
+CTC_LOSS_KERNELS = {1: 31, 2: 63, 4: 127, 8: 255, 104: 511, 108: 1023, 116: 2047}
 
 
 # enum bh_lstm_family of include/bonito_hip.h (tests/test_abi.py keeps the two together)

@@ -3,7 +3,8 @@
 reference_lengths.npy) with the HIP engine -- the arguments of the reference's bonito/cli/evaluate.py:140-155.
 
 Per batch: engine forward, ``decode_batch`` (posterior decoding) and ``loss(..., reduction='none')``, i.e.
--ln P(reference | scores) / reference length per chunk from the sequence-likelihood kernel. After the calling loop every called
+-ln P(reference | scores) / reference length per chunk from the sequence-likelihood kernel. A bonito.ctc model (no ``decode_batch``)
+is decoded by prefix beam search of width 5 and scored by the CTC loss kernel (the 'loss' entry of its dict). After the calling loop every called
 sequence is aligned against its reference in ONE ``align.sw_align`` call (Smith-Waterman on the device, the reference's parasail
 arguments; evaluate.py:37-67). Printed: the reference's block (accuracy, sub / ins / del rates, lengths and clips; evaluate.py:117-129)
 plus mean and median loss. With ``--output_dir``: seqs.fasta, refs.fasta and summ.txt (per-chunk TSV: loss and the AlignResult columns).
@@ -110,6 +111,16 @@ def summ_lines(table, seq_len, ref_len, losses):
     return lines
 
 
+def decode_batch(model, scores):
+    """The called sequence of every chunk: the model's own ``decode_batch`` (CRF family), else - bonito.ctc - the prefix beam search of
+    ctc/basecall.py:decode_grouped at the reference's beam width 5 (evaluate.py:110) over the [T, N, C] log-probabilities."""
+    if hasattr(model, "decode_batch"):
+        return model.decode_batch(scores)
+    from bonito_amd.ctc.basecall import decode_grouped
+    lps = scores.permute(1, 0, 2).to(torch.float32)
+    return [v["sequence"] for _, v in decode_grouped(model, ((i, {"scores": lp}) for i, lp in enumerate(lps)), beamsize=5)]
+
+
 def main(args):
     init(args.seed, args.device)
     if args.directory is None:
@@ -131,8 +142,9 @@ def main(args):
         n = torch.from_numpy(np.asarray(lengths[lo:lo + args.batchsize]).astype(np.int32))
         t = t[:, :max(int(n.max()), 1)]
         scores = model(x)
-        seqs.extend(model.decode_batch(scores))
-        losses.append(model.loss(scores, t, n, reduction="none").cpu().numpy())
+        seqs.extend(decode_batch(model, scores))
+        loss = model.loss(scores, t, n, reduction="none")
+        losses.append((loss["loss"] if isinstance(loss, dict) else loss).cpu().numpy())
     losses = np.concatenate(losses) if losses else np.zeros(0, np.float32)
     refs = [decode_ref(t[:n], model.alphabet) for t, n in zip(targets, lengths)]
     print("* aligning")

@@ -344,6 +344,23 @@ extern "C" int bh_crf_logz_dense_grad(const void* scores, int N, int T, int stat
     return bh_k_crf_logz_dense_grad(scores, N, T, state_len, layout_5s, blank_score, stride_n, stride_t, weight, workspace,
                                     logz_out, grad, g_stride_n, g_stride_t, grad_fp32, (hipStream_t)stream);
 }
+extern "C" size_t bh_ctc_loss_workspace(int N, int T, int C, int Lmax) { return bh_k_ctc_loss_workspace(N, T, C, Lmax, 0); }
+extern "C" int bh_ctc_loss(const void* log_probs, int logp_fp32, int N, int T, int C, long stride_t, long stride_n, const void* targets,
+                           int Lmax, int target_bytes, const int32_t* target_lengths, const float* smooth_w, void* workspace,
+                           float* nll_out, float* smooth_out, void* stream) {
+    return bh_k_ctc_loss(log_probs, logp_fp32, N, T, C, stride_t, stride_n, targets, target_bytes, Lmax, target_lengths, smooth_w,
+                         nullptr, nullptr, workspace, nll_out, smooth_out, nullptr, 0, 0, 0, 0, 0, (hipStream_t)stream);
+}
+extern "C" size_t bh_ctc_loss_grad_workspace(int N, int T, int C, int Lmax) { return bh_k_ctc_loss_workspace(N, T, C, Lmax, 1); }
+extern "C" int bh_ctc_loss_grad(const void* log_probs, int logp_fp32, int N, int T, int C, long stride_t, long stride_n,
+                                const void* targets, int Lmax, int target_bytes, const int32_t* target_lengths, const float* smooth_w,
+                                const float* weight, const float* smooth_weight, void* workspace, float* nll_out, float* smooth_out,
+                                void* grad, long g_stride_t, long g_stride_n, int grad_fp32, int accumulate, void* stream) {
+    return bh_k_ctc_loss(log_probs, logp_fp32, N, T, C, stride_t, stride_n, targets, target_bytes, Lmax, target_lengths, smooth_w,
+                         weight, smooth_weight, workspace, nll_out, smooth_out, grad, g_stride_t, g_stride_n, grad_fp32, accumulate, 1,
+                         (hipStream_t)stream);
+}
+extern "C" int bh_ctc_loss_last_kernel(void) { return bh_k_ctc_loss_last_kernel(); }
 extern "C" size_t bh_sw_workspace(int n, int max_seq, int max_ref) { return bh_k_sw_workspace(n, max_seq, max_ref); }
 extern "C" int bh_sw_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, const void* refs, long ref_stride,
                            const int32_t* ref_lengths, int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace,

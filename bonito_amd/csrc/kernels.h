@@ -140,6 +140,14 @@ int bh_k_crf_logz_dense_grad(const void* scores, int N, int T, int state_len, in
                              const float* weight, void* workspace, float* out, void* grad, long g_n, long g_t, int grad_fp32,
                              hipStream_t stream);
 
+// ctc_loss.hip (the CTC loss of bonito.ctc: nll, the label-smoothing numerator and - with_grad - the gradient, from one launch)
+size_t bh_k_ctc_loss_workspace(int N, int T, int C, int Lmax, int grad);
+int bh_k_ctc_loss(const void* log_probs, int logp_fp32, int N, int T, int C, long s_t, long s_n, const void* targets, int target_bytes,
+                  int Lmax, const int* lens, const float* smooth_w, const float* weight, const float* smooth_weight, void* workspace,
+                  float* nll, float* smooth, void* grad, long g_t, long g_n, int grad_fp32, int accumulate, int with_grad,
+                  hipStream_t stream);
+int bh_k_ctc_loss_last_kernel();   // test hook: the bh_ctc_loss_kernel code of the instance that served the last call; not thread-safe
+
 // align.hip (Smith-Waterman, affine gaps, traceback; the lengths are host arrays)
 size_t bh_k_sw_workspace(int n, int max_seq, int max_ref);
 int bh_k_sw_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,

@@ -7,13 +7,38 @@ identical ``state_dict()`` keys (``encoder.encoder.<i>.conv.<j>.{depthwise,point
 
 ``model(x)`` runs the HIP engine (depthwise conv kernel, MFMA pointwise GEMMs with folded BatchNorm and the
 residual add fused, 1x1 decoder + log_softmax) and returns log-probabilities in the reference's TNC layout.
-The CPU Rust decoders of fast_ctc_decode (:11,39-46) are replaced by bonito_amd.ctc.decode (HIP).
+The CPU Rust decoders of fast_ctc_decode (:11,39-46) are replaced by bonito_amd.ctc.decode (HIP), and
+``torch.nn.functional.ctc_loss`` behind ``ctc_label_smoothing_loss`` / ``loss`` (:48-57) by csrc/ctc_loss.hip.
 """
 import torch
 from torch.nn import BatchNorm1d, Conv1d, Dropout, Module, ModuleList, Sequential
 
 from bonito_amd.engine import HipEncoder, lower_ctc
 from bonito_amd.nn import NoTorchCompute, Permute, _no_forward, layers
+
+
+class _CtcLoss(torch.autograd.Function):
+    """(nll_n / max(len_n, 1) [N], sum_n smooth_n) of device log_probs with the backward: ONE launch per group of chunks computes the
+    values and d loss_n / d log_probs = -occ / max(len_n, 1), kept in fp32; the backward scales it by the upstream gradient of every
+    chunk and adds upstream x weights[c] for the smoothing sum. Chunks with an infinite loss get a zero gradient."""
+
+    @staticmethod
+    def forward(ctx, log_probs, targets, lengths, weights):
+        from bonito_amd import decode
+        lens = lengths.to(device=log_probs.device, dtype=torch.float32).clamp(min=1)
+        inv = 1.0 / lens
+        occ = torch.empty(log_probs.shape, dtype=torch.float32, device=log_probs.device)
+        nll, smooth, occ = decode.ctc_nll_grad(log_probs, targets, lengths, weights, weight=inv, out=occ, layout="TNC")
+        ctx.save_for_backward(occ, torch.isfinite(nll), torch.as_tensor(weights, dtype=torch.float32).to(log_probs.device))
+        ctx.dtype = log_probs.dtype
+        return nll / lens, smooth.sum()                                     # (the expression of the no-grad path, bit for bit)
+
+    @staticmethod
+    def backward(ctx, g_loss, g_smooth):
+        occ, finite, weights = ctx.saved_tensors
+        g = occ * g_loss.to(torch.float32)[None, :, None]
+        g = g + finite.to(torch.float32)[None, :, None] * (g_smooth.to(torch.float32) * weights)[None, None, :]
+        return g.to(ctx.dtype), None, None, None
 
 
 class TCSConv1d(Module):
@@ -152,3 +177,38 @@ class Model(Module):
         else:
             seq, path = ctc_decode.beam_search(x, self.alphabet, beamsize, threshold)
         return (seq, path) if return_path else seq
+
+    def ctc_label_smoothing_loss(self, log_probs, targets, lengths, weights=None, *, reduction="mean"):
+        """The reference's dict {'total_loss', 'loss', 'label_smooth_loss'} (ctc/model.py:48-54) from the device kernel
+        (csrc/ctc_loss.hip): loss = mean over n of nll_n / max(len_n, 1) (ctc_loss(reduction='mean')), label_smooth_loss =
+        -sum(log_probs * weights) / (T N C), default weights [0.4, 0.1 / (C - 1), ...]. log_probs: device fp16 / fp32 [T, N, C]
+        (fp32 is read natively, fp16 is widened in the kernel as the reference's .to(float32) does). reduction='none' puts the
+        per-chunk nll_n / max(len_n, 1) into 'loss' (and loss + label_smooth_loss per chunk into 'total_loss').
+        With requires_grad the result is differentiable (one launch computes the values and the posterior state occupancies; the
+        backward is a scale of them plus the weights[c] / (T N C) term). The kernel's gradient is the TRUE derivative with respect
+        to log_probs; torch's native ctc_loss backward returns exp(log_probs) - occ, which is the same thing after log_softmax's
+        backward. A chunk whose target cannot fit has an infinite loss and a ZERO gradient (torch: NaN)."""
+        if reduction not in ("mean", "none"):
+            raise ValueError("reduction must be 'mean' or 'none'")
+        if log_probs.requires_grad and not log_probs.is_cuda:
+            raise NoTorchCompute("bonito_amd differentiates the CTC loss on a HIP device only; got a %s tensor with requires_grad"
+                                 % log_probs.device)
+        if log_probs.dim() != 3:
+            raise ValueError("log_probs must be [T, N, C], got shape %s" % (tuple(log_probs.shape),))
+        from bonito_amd import decode
+        T, N, C = log_probs.shape
+        if weights is None:
+            weights = torch.cat([torch.tensor([0.4]), (0.1 / (C - 1)) * torch.ones(C - 1)])
+        weights = torch.as_tensor(weights, dtype=torch.float32)
+        if log_probs.requires_grad:
+            per_chunk, smooth = _CtcLoss.apply(log_probs, targets, lengths, weights)
+        else:
+            nll, smooth = decode.ctc_nll(log_probs, targets, lengths, weights, layout="TNC")
+            per_chunk = nll / lengths.to(device=nll.device, dtype=torch.float32).clamp(min=1)
+            smooth = smooth.sum()
+        loss = per_chunk.mean() if reduction == "mean" else per_chunk
+        label_smoothing_loss = -smooth / float(T * N * C)
+        return {"total_loss": loss + label_smoothing_loss, "loss": loss, "label_smooth_loss": label_smoothing_loss}
+
+    def loss(self, log_probs, targets, lengths, *, reduction="mean"):
+        return self.ctc_label_smoothing_loss(log_probs, targets, lengths, reduction=reduction)

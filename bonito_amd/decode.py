@@ -500,3 +500,137 @@ def seq_logprob(scores, sequences, blank_score=2.0):
     num = seq_logz(scores, targets, lengths, sl, blank_score, free_start=True)
     den = logz_any(scores, sl, blank_score)
     return (num.double() - den).cpu()
+
+
+# ---- the CTC loss of bonito.ctc (csrc/ctc_loss.hip) -------------------------------------------------------------------------------------
+# bytes of alpha workspace per launch of ctc_nll_grad: T x (2 Lmax + 1) x 4 bytes per chunk, 1.85 GB for 256 chunks of bonito.ctc's training
+# shape (T = 1334, targets up to 675), which one launch should hold: a chunk is a workgroup, and half a batch leaves half the device idle
+CTC_WORKSPACE_BUDGET = 4 << 30
+
+
+def _ctc_args(log_probs, targets, lengths, weights, layout):
+    """Checks and views shared by ctc_nll / ctc_nll_grad -> (log_probs, tnc, T, N, C, targets, lengths, weights)."""
+    if log_probs.dim() != 3:
+        raise ValueError("log_probs must be [T, N, C] or [N, T, C], got shape %s" % (tuple(log_probs.shape),))
+    if targets.dim() != 2 or lengths.dim() != 1 or targets.shape[0] != lengths.shape[0]:
+        raise ValueError("targets must be [N, Lmax] and lengths [N]")
+    N = int(targets.shape[0])
+    if layout is None:
+        layout = "TNC" if log_probs.shape[1] == N else "NTC"               # [T, N, C] (the reference's) wins where both fit
+    if layout not in ("TNC", "NTC"):
+        raise ValueError("layout must be 'TNC' or 'NTC'")
+    tnc = layout == "TNC"
+    if log_probs.shape[1 if tnc else 0] != N:
+        raise ValueError("%d target rows for log_probs of shape %s (%s)" % (N, tuple(log_probs.shape), layout))
+    T, C = int(log_probs.shape[0 if tnc else 1]), int(log_probs.shape[2])
+    if not 2 <= C <= 8:
+        raise ValueError("the CTC loss kernel takes 2..8 classes, got %d" % C)
+    if N < 1 or T < 1:
+        raise ValueError("empty problem: N %d, T %d" % (N, T))
+    if targets.shape[1] > 2047:
+        raise ValueError("target rows of %d labels exceed the supported 2047" % targets.shape[1])
+    if targets.dtype.is_floating_point or lengths.dtype.is_floating_point:
+        raise TypeError("targets and lengths must be integers")
+    if not log_probs.is_cuda:
+        raise _lib.HipEngineError("log_probs must live on a HIP device (no CPU fallback)")
+    if log_probs.dtype not in (torch.float16, torch.float32):
+        raise TypeError("log_probs must be fp16 or fp32, got %s" % log_probs.dtype)
+    if not lengths.is_cuda:                                                # host lengths are checked here; device lengths by the kernel (NaN)
+        lo, hi = int(lengths.min()), int(lengths.max())
+        if lo < 0 or hi > targets.shape[1]:
+            raise ValueError("target lengths must lie in 0..%d (got %d..%d)" % (targets.shape[1], lo, hi))
+    dev = log_probs.device
+    log_probs = log_probs.detach()
+    if log_probs.stride(2) != 1:
+        log_probs = log_probs.contiguous()
+    if targets.dtype not in (torch.int8, torch.int32):
+        targets = targets.to(torch.int32)
+    targets = targets.to(dev).contiguous()
+    lengths = lengths.to(device=dev, dtype=torch.int32).contiguous()
+    if weights is not None:
+        weights = torch.as_tensor(weights, dtype=torch.float32).detach().to(dev).contiguous()
+        if weights.shape != (C,):
+            raise ValueError("weights must be [C] = [%d]" % C)
+    return log_probs, tnc, T, N, C, targets, lengths, weights
+
+
+def _sub(t, lo, hi):
+    return None if t is None else t[lo:hi]
+
+
+def ctc_nll(log_probs, targets, lengths, weights=None, layout=None):
+    """torch.nn.functional.ctc_loss(reduction='none') on the device (bh_ctc_loss), blank = class 0: (nll float32 [N], smooth).
+    log_probs: device fp16 / fp32 [T, N, C] or [N, T, C] (`layout`; by default [T, N, C] when its second axis matches the targets), any
+    strides with a dense class axis, fp32 read natively. targets [N, Lmax] int8 / int32 / int64 (labels 1..C-1, 0 = padding), lengths
+    [N] on the host or the device. smooth[n] = sum_t sum_c weights[c] * log_probs[t, n, c] (None without `weights`). A target that
+    cannot fit gives nll = +inf; a length outside 0..Lmax or a label outside 1..C-1 gives NaN."""
+    if log_probs.requires_grad:
+        from bonito_amd.nn import NoTorchCompute
+        raise NoTorchCompute("this entry point returns plain tensors: for log_probs with requires_grad use Model.loss, which carries "
+                             "the backward")
+    lp, tnc, T, N, Cn, targets, lengths, weights = _ctc_args(log_probs, targets, lengths, weights, layout)
+    lib = _lib.lib()
+    dev = lp.device
+    Lmax = int(targets.shape[1])
+    s_t, s_n = (lp.stride(0), lp.stride(1)) if tnc else (lp.stride(1), lp.stride(0))
+    ws = torch.empty(lib.bh_ctc_loss_workspace(N, T, Cn, Lmax), dtype=torch.uint8, device=dev)
+    nll = torch.empty(N, dtype=torch.float32, device=dev)
+    smooth = torch.empty(N, dtype=torch.float32, device=dev) if weights is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.bh_ctc_loss(_lib.ptr(lp), int(lp.dtype == torch.float32), N, T, Cn, s_t, s_n, _lib.ptr(targets) if Lmax else None,
+                                   Lmax, targets.element_size(), _lib.ptr(lengths), _lib.ptr(weights), _lib.ptr(ws), _lib.ptr(nll),
+                                   _lib.ptr(smooth), _lib.stream_ptr(dev)), "bh_ctc_loss")
+    return nll, smooth
+
+
+def ctc_nll_grad(log_probs, targets, lengths, weights=None, weight=None, smooth_weight=None, out=None, accumulate=False, layout=None,
+                 workspace_budget=None):
+    """ctc_nll AND its gradient from one launch per group of chunks (bh_ctc_loss_grad): (nll, smooth, grad), all on the device.
+    grad[t, n, c] (+)= -weight[n] * occ[t, c] + smooth_weight[n] * weights[c], where occ is the posterior probability that the path
+    is, at step t, in a state of class c. THIS IS THE TRUE DERIVATIVE of nll with respect to log_probs; torch's native ctc_loss
+    backward returns exp(log_probs) - occ instead, the derivative with respect to the logits in front of a log_softmax, and the two
+    are identical after log_softmax's backward (g - exp(lp) * sum_c g). grad has the shape and dtype of `log_probs`, or is written
+    into ``out`` (fp16 / fp32, same shape, own strides, dense class axis); ``accumulate=True`` adds into it. A chunk whose target
+    cannot fit has nll = +inf and a ZERO gradient (this project's definition; torch gives NaN). The N chunks are split into groups
+    whose alpha workspace (T x (2 Lmax + 1) x 4 bytes per chunk) stays under ``workspace_budget`` bytes (CTC_WORKSPACE_BUDGET); every
+    chunk is computed by itself, so the result does not depend on the split, and it is bit-identical from call to call."""
+    lp, tnc, T, N, Cn, targets, lengths, weights = _ctc_args(log_probs, targets, lengths, weights, layout)
+    if accumulate and out is None:
+        raise ValueError("accumulate=True needs out")
+    if smooth_weight is not None and weights is None:
+        raise ValueError("smooth_weight needs weights")
+    dev = lp.device
+    if out is None:
+        out = torch.empty(lp.shape, dtype=lp.dtype, device=dev)
+    else:
+        if tuple(out.shape) != tuple(lp.shape) or out.device != dev:
+            raise ValueError("out must have the shape %s and the device of log_probs" % (tuple(lp.shape),))
+        if out.dtype not in (torch.float16, torch.float32):
+            raise TypeError("out must be fp16 or fp32, got %s" % out.dtype)
+        if out.stride(2) != 1:
+            raise ValueError("the class axis of out must be dense")
+        if out.requires_grad:
+            raise ValueError("out must not require grad")
+    weight, smooth_weight = _weight(weight, N, dev), _weight(smooth_weight, N, dev)
+    lib = _lib.lib()
+    Lmax = int(targets.shape[1])
+    s_t, s_n = (lp.stride(0), lp.stride(1)) if tnc else (lp.stride(1), lp.stride(0))
+    g_t, g_n = (out.stride(0), out.stride(1)) if tnc else (out.stride(1), out.stride(0))
+    budget = CTC_WORKSPACE_BUDGET if workspace_budget is None else int(workspace_budget)
+    per = lib.bh_ctc_loss_grad_workspace(1, T, Cn, Lmax) - 512
+    group = max(1, min(N, budget // max(per, 1)))
+    ws = torch.empty(lib.bh_ctc_loss_grad_workspace(group, T, Cn, Lmax), dtype=torch.uint8, device=dev)
+    nll = torch.empty(N, dtype=torch.float32, device=dev)
+    smooth = torch.empty(N, dtype=torch.float32, device=dev) if weights is not None else None
+    esz, gsz = lp.element_size(), out.element_size()
+    with torch.cuda.device(dev):
+        st = _lib.stream_ptr(dev)
+        for lo in range(0, N, group):
+            hi = min(N, lo + group)
+            _lib.check(lib.bh_ctc_loss_grad(
+                C.c_void_p(lp.data_ptr() + lo * s_n * esz), int(lp.dtype == torch.float32), hi - lo, T, Cn, s_t, s_n,
+                _lib.ptr(targets[lo:hi]) if Lmax else None, Lmax, targets.element_size(), _lib.ptr(lengths[lo:hi]), _lib.ptr(weights),
+                _lib.ptr(_sub(weight, lo, hi)), _lib.ptr(_sub(smooth_weight, lo, hi)), _lib.ptr(ws), _lib.ptr(nll[lo:hi]),
+                _lib.ptr(_sub(smooth, lo, hi)), C.c_void_p(out.data_ptr() + lo * g_n * gsz), g_t, g_n, int(out.dtype == torch.float32),
+                int(bool(accumulate)), st), "bh_ctc_loss_grad")
+    return nll, smooth, out

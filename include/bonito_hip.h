@@ -21,6 +21,9 @@
  *   bh_crf_seq_logz_grad / bh_crf_logz_dense_grad
  *        the backward of koi.ctc.{logZ_cu, logZ_cu_sparse} (autograd of CTC_CRF.ctc_loss) and SequenceDist.posteriors
  *                                                                              bonito/crf/model.py:47-67,126-139
+ *   bh_ctc_loss / bh_ctc_loss_grad
+ *        torch.nn.functional.ctc_loss (and its backward) behind Model.ctc_label_smoothing_loss / Model.loss
+ *                                                                              bonito/ctc/model.py:48-57
  *   bh_sw_align
  *        parasail.sw_trace_striped_32(seq, ref, 8, 4, parasail.dnafull) behind evaluate's align() and util.accuracy
  *                                                                              bonito/cli/evaluate.py:37-67, bonito/util.py:346-368
@@ -258,6 +261,59 @@ size_t bh_crf_logz_dense_grad_workspace(int N, int T, int state_len);
 int bh_crf_logz_dense_grad(const void* scores, int N, int T, int state_len, int layout_5s, float blank_score, long stride_n,
                            long stride_t, const float* weight, void* workspace, float* logz_out, void* grad, long g_stride_n,
                            long g_stride_t, int grad_fp32, void* stream);
+
+/* ---- The CTC loss of bonito.ctc (csrc/ctc_loss.hip): torch.nn.functional.ctc_loss behind Model.ctc_label_smoothing_loss ----------
+ * (bonito/ctc/model.py:48-57), with the numerator of the label-smoothing term and - in the _grad entry - the gradient, ONE launch.
+ * Definition (torch's, blank = class 0): l' = the target with blanks interleaved, S = 2 len + 1 states,
+ *     alpha_0[0] = lp_0[0], alpha_0[1] = lp_0[l'_1],
+ *     alpha_t[s] = lp_t[l'_s] + logsumexp(alpha_{t-1}[s], alpha_{t-1}[s-1], alpha_{t-1}[s-2])   (s-2 only when l'_s != 0 and l'_s != l'_{s-2})
+ *     nll = -logaddexp(alpha_{T-1}[S-1], alpha_{T-1}[S-2]);  beta = the mirror scan;
+ *     occ[t][c] = sum over the states s with l'_s = c of P(the path is in s at step t | target).
+ * log_probs: fp16 (logp_fp32 = 0) or fp32 (1), element strides (stride_t, stride_n), the class axis dense: [T][N][C] and [N][T][C]
+ *   both go in without a copy. targets: [N][Lmax] int8 / int32 (target_bytes 1 / 4), labels 1..C-1, 0 = padding (may be NULL when
+ *   Lmax = 0). target_lengths: device int32 [N].
+ * nll_out[N] float. smooth_out[N] float = sum_t sum_c smooth_w[c] * lp[t][n][c] (classes with smooth_w[c] = 0 are left out), the
+ *   numerator of the reference's label-smoothing term; smooth_w: device float [C]; smooth_out NULL = not computed.
+ * bh_ctc_loss_grad:  grad[t][n][c] (+)= -weight[n] * occ[t][c] + smooth_weight[n] * smooth_w[c].  weight: device float [N], NULL = 1;
+ *   smooth_weight: device float [N], NULL = 0 (needs smooth_w). grad: fp16 (grad_fp32 = 0) or fp32 (1) with its own element strides
+ *   (g_stride_t, g_stride_n), the class axis dense. accumulate = 1 adds into grad; accumulate = 0 writes every element of the chunk's
+ *   T rows exactly once. The occupancies of a step are summed in integer fixed point at scale 2^30 (they sum to 1): the result is
+ *   bit-identical from call to call.
+ *   THE GRADIENT IS THE TRUE DERIVATIVE of nll with respect to log_probs, -occ. torch's native ctc_loss backward returns
+ *   exp(lp) - occ, the derivative with respect to the logits in front of a log_softmax; the two are identical after log_softmax's
+ *   backward  g - exp(lp) * sum_c g.
+ * This project's definitions where torch yields NaN:
+ *   - a target that cannot fit (len + number of adjacent repeats > T), or whose every alignment crosses a -inf log-prob: nll = +inf
+ *     and a ZERO gradient (nothing added, or zeros on overwrite, the smoothing term included), as in bh_crf_seq_logz_grad;
+ *   - a state that a -inf log-prob makes unreachable contributes occupancy 0, not NaN;
+ *   - len < 0, len > Lmax or a label outside 1..C-1 within len: nll = NaN and no gradient is written.
+ * Supported range (an error, never a truncation): 2 <= C <= 8, T >= 1, N >= 1, 0 <= Lmax <= 2047; len = 0 is valid
+ *   (nll = -sum_t lp_t[0]). Argument errors (range, null pointers, strides smaller than C, overlapping rows of grad) are found on the
+ *   host before anything is launched.
+ * workspace: bh_ctc_loss_workspace / bh_ctc_loss_grad_workspace(N, T, C, Lmax) bytes (0 = unsupported shape); the gradient keeps every
+ *   alpha_t in fp32: N * T * (2 Lmax + 1 rounded up to the instance's states per thread) * 4 bytes.
+ * TEST HOOK bh_ctc_loss_last_kernel: the instance (states per launch = 64 or 256 threads x states per thread; the first that holds
+ *   2 Lmax + 1) that served the last call of this process, one of the codes below; 0 = none yet. Process-wide, NOT thread-safe. */
+enum bh_ctc_loss_kernel {
+    BH_CTC_LOSS_K_NONE = 0,
+    BH_CTC_LOSS_K_W1 = 1,         /* one wave, 1 state per thread: Lmax <= 31 */
+    BH_CTC_LOSS_K_W2 = 2,         /* one wave, 2: Lmax <= 63 */
+    BH_CTC_LOSS_K_W4 = 4,         /* one wave, 4: Lmax <= 127 */
+    BH_CTC_LOSS_K_W8 = 8,         /* one wave, 8: Lmax <= 255 */
+    BH_CTC_LOSS_K_M4 = 104,       /* four waves, 4: Lmax <= 511 */
+    BH_CTC_LOSS_K_M8 = 108,       /* four waves, 8: Lmax <= 1023 */
+    BH_CTC_LOSS_K_M16 = 116       /* four waves, 16: Lmax <= 2047 */
+};
+size_t bh_ctc_loss_workspace(int N, int T, int C, int Lmax);
+int bh_ctc_loss(const void* log_probs, int logp_fp32, int N, int T, int C, long stride_t, long stride_n, const void* targets,
+                int Lmax, int target_bytes, const int32_t* target_lengths, const float* smooth_w, void* workspace, float* nll_out,
+                float* smooth_out, void* stream);
+size_t bh_ctc_loss_grad_workspace(int N, int T, int C, int Lmax);
+int bh_ctc_loss_grad(const void* log_probs, int logp_fp32, int N, int T, int C, long stride_t, long stride_n, const void* targets,
+                     int Lmax, int target_bytes, const int32_t* target_lengths, const float* smooth_w, const float* weight,
+                     const float* smooth_weight, void* workspace, float* nll_out, float* smooth_out, void* grad, long g_stride_t,
+                     long g_stride_n, int grad_fp32, int accumulate, void* stream);
+int bh_ctc_loss_last_kernel(void);
 
 /* ---- Smith-Waterman local alignment with affine gaps and a traceback (csrc/align.hip) ----------------------------------
  * n pairs of a called sequence `seq` (the query, index i) and a known sequence `ref` (index j). seqs / refs: DEVICE int8 planes
