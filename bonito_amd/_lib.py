@@ -79,6 +79,11 @@ SIGNATURES = {
     "bh_sg_align": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _l, _vp, _vp]),
     "bh_nw_workspace": (_sz, [_i, _i, _i, _l]),
     "bh_nw_align": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _vp, _sz, _vp, _vp, _l, _vp, _vp]),
+    "bh_map_sketch_tile": (_i, []),
+    "bh_map_sketch_workspace": (_sz, [_i, _l]),
+    "bh_map_sketch": (_i, [_vp, _l, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _l, _vp, _vp]),
+    "bh_map_seed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _l, _vp, _vp, _vp, _l, _vp, _vp, _i, _i, _vp, _vp, _vp, _l, _vp]),
+    "bh_map_chain": (_i, [_vp, _vp, _vp, _i, _l, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "bh_set_option": (_i, [C.c_char_p, _i]),
     "bh_signal_normalise": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                             _i, _vp, _vp, _vp, _vp, _vp]),
@@ -112,6 +117,7 @@ SIGNATURES = {
     "bh_host_chunk_rows": (_l, [_vp, _l, _i, _i, _l, _l, _vp]),
     "bh_host_format_read": (_l, [_vp, _vp, _vp, _vp, _i, _l, _l, _i, _i, _i, _i, _i, _i, C.c_double, C.c_char_p, C.c_char_p, _l, _l,
                                  _vp, _l, _vp, _vp]),
+    "bh_host_map_finish": (_l, [_vp, _l, _vp, _l, _l, _vp, _l, _l, _vp, _l, _vp, _l, _vp, _l, _vp]),
     "bh_host_mean_qscore": (C.c_double, [C.c_char_p, _l]),
     "bh_host_svb16_decode": (_l, [_vp, _l, _l, _vp]),
     "bh_lstm_workspace": (_sz, [_i, _i]),

@@ -185,7 +185,23 @@ def main(args, argv=None):
                              norm_params=model.config.get("standardisation") if (model.config.get("scaling") or {}).get(
                                  "strategy") == "pa" else model.config.get("normalisation"),
                              n_max=args.max_reads or None, raw=args.device_ingest, rank=rank, world=world)
-    mode = "sam" if args.sam else ("fasta" if args.fasta else "fastq")
+    mode = "sam" if args.sam or (args.reference and not args.fastq) else ("fasta" if args.fasta else "fastq")
+    aligner = None
+    if args.reference and mode == "fastq":
+        log("> warning: did you really want aligned fastq?\n")           # the reference's words (cli/basecaller.py:40-41); no mapping
+    elif args.reference:
+        if args.mm2_preset is not None:
+            log("> notice: --mm2-preset is accepted and ignored (the device mapper has no presets)\n")
+        from bonito_amd.aligner import Aligner
+        log("> loading reference\n")
+        try:
+            aligner = Aligner(args.reference, device=args.device)           # every rank builds its own index
+        except (OSError, ValueError) as exc:
+            sys.stderr.write("> error: %s\n" % exc)
+            return 1
+        if not aligner:
+            sys.stderr.write("> failed to load/build index\n")
+            return 1
     pa = (model.config.get("scaling") or {}).get("strategy") == "pa"
     raw_kw = dict(scaling_strategy=model.config.get("scaling"),
                   norm_params=model.config.get("standardisation") if pa else model.config.get("normalisation"),
@@ -196,7 +212,7 @@ def main(args, argv=None):
         raise SystemExit("> error: --device-ingest needs a CRF model")
 
     def make_records(mdl, rds):
-        if records_fn is not None:
+        if records_fn is not None and aligner is None:
             # CRF family: stitching, string compaction and the record text of a read are ONE library call (crf/basecall.py
             # records_from_planes); the triples are what io.format_record makes of basecall()'s results, byte for byte
             return records_fn(mdl, rds, mode, reverse=args.revcomp, rna=args.rna, batchsize=bc["batchsize"],
@@ -206,6 +222,10 @@ def main(args, argv=None):
         kw = {"lanes": args.lanes} if args.lanes > 1 and "lanes" in names else {}
         results = basecall(mdl, rds, reverse=args.revcomp, rna=args.rna, batchsize=bc["batchsize"],
                            chunksize=bc["chunksize"], overlap=bc["overlap"], **kw)
+        if aligner is not None:
+            # --reference: the Python record path (basecall -> align_map -> format_record); the fused record path has no mapping
+            from bonito_amd.aligner import align_map
+            results = align_map(aligner, results)
         return parallel.format_stream(results, mode, args.min_qscore)
 
     records = make_records(model, reads)
@@ -244,7 +264,7 @@ def main(args, argv=None):
         if rank != 0:
             parallel.shutdown()
             return 0
-    writer = Writer(mode, records, fd=out, summary_path=None if args.no_summary else args.summary, preformatted=True)
+    writer = Writer(mode, records, fd=out, summary_path=None if args.no_summary else args.summary, preformatted=True, aligner=aligner)
     writer.start()
     writer.join()
     duration = perf_counter() - t0
@@ -337,8 +357,15 @@ def argparser():
                              "192...512-wide fp16 models: the recurrent kernel pairs rings, 2.97 -> 1.8 ms per layer and 512 chunks at "
                              "384 hidden units, and two such launches per layer keep the pipeline full; results do not depend on it)")
     parser.add_argument("--min-qscore", default=0.0, type=float)
-    parser.add_argument("--sam", action="store_true", default=False, help="write unaligned SAM instead of FASTQ")
-    parser.add_argument("--fasta", action="store_true", default=False)
+    parser.add_argument("--sam", action="store_true", default=False, help="write SAM instead of FASTQ")
+    parser.add_argument("--fastq", action="store_true", default=False, help="with --reference: write FASTQ (without mappings) after all")
+    aligned = parser.add_mutually_exclusive_group()                     # FASTA has nowhere to put a mapping: the two are refused together
+    aligned.add_argument("--fasta", action="store_true", default=False)
+    aligned.add_argument("--reference", default=None,
+                        help="FASTA (plain or .gz): map every call with the device mapper and write aligned SAM (the default mode "
+                             "becomes SAM) plus the alignment columns of the summary")
+    parser.add_argument("--mm2-preset", default=None, type=str, help="accepted and ignored: the device mapper has no presets")
+    parser.add_argument("--alignment-threads", default=8, type=int, help="accepted and ignored: mapping runs on the device")
     parser.add_argument("--summary", default="summary.tsv")
     parser.add_argument("--no-summary", action="store_true", default=False)
     return parser

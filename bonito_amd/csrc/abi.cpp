@@ -383,6 +383,27 @@ extern "C" int bh_nw_align(const void* seqs, long seq_stride, const int32_t* seq
     return bh_k_nw_align(seqs, seq_stride, seq_lengths, refs, ref_stride, ref_lengths, n, k, workspace, workspace_bytes, result, ops,
                          ops_stride, n_ops, (hipStream_t)stream);
 }
+extern "C" int bh_map_sketch_tile(void) { return bh_k_map_sketch_tile(); }
+extern "C" size_t bh_map_sketch_workspace(int n, long total_len) { return bh_k_map_sketch_workspace(n, total_len); }
+extern "C" int bh_map_sketch(const void* codes, long stride, const int32_t* lengths, int n, int k, int w, void* workspace,
+                             size_t workspace_bytes, int64_t* keys, int32_t* pos, int8_t* strand, long capacity, int32_t* offsets,
+                             void* stream) {
+    return bh_k_map_sketch(codes, stride, lengths, n, k, w, workspace, workspace_bytes, (long long*)keys, pos, strand, capacity, offsets,
+                           (hipStream_t)stream);
+}
+extern "C" int bh_map_seed(const int64_t* qkeys, const int32_t* qpos, const int8_t* qstrand, const int32_t* q_offsets,
+                           const int32_t* q_lengths, int n, long n_min, const int64_t* ukeys, const int32_t* ustart,
+                           const int32_t* ucount, long n_ukeys, const int32_t* rpos, const int8_t* rstrand, int k, int max_occ,
+                           int32_t* counts, const int64_t* offsets, int64_t* anchors, long capacity, void* stream) {
+    return bh_k_map_seed((const long long*)qkeys, qpos, qstrand, q_offsets, q_lengths, n, n_min, (const long long*)ukeys, ustart, ucount,
+                         n_ukeys, rpos, rstrand, k, max_occ, counts, (const long long*)offsets, (long long*)anchors, capacity,
+                         (hipStream_t)stream);
+}
+extern "C" int bh_map_chain(const int64_t* anchors, const int32_t* contigs, const int32_t* offsets, int n, long n_anchors, int k,
+                            int max_dist, int bandwidth, int32_t* f, int32_t* p, int32_t* chain, int32_t* result, void* stream) {
+    return bh_k_map_chain((const long long*)anchors, contigs, offsets, n, n_anchors, k, max_dist, bandwidth, f, p, chain, result,
+                          (hipStream_t)stream);
+}
 extern "C" int bh_signal_normalise(const int16_t* raw, const long* offsets, const float* cal_scale, const float* cal_offset, int n_reads,
                                    int strategy, double quantile_a, double quantile_b, double shift_mult, double scale_mult,
                                    double fixed_shift, double fixed_scale, int do_trim, double* shift, double* scale, int* weak,

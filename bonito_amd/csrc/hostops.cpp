@@ -297,3 +297,58 @@ extern "C" long bh_host_svb16_decode(const uint8_t* in, long n_in, long count, i
     }
     return (long)(data - in);
 }
+
+// One mapped read (bonito_amd/aligner.py): the = X I D runs of its pieces walked over the read and the contig -> the M I D CIGAR with
+// equal neighbours merged, its text, NM, MD, matching and total columns. A column matches when both codes are the same base 1..4.
+extern "C" long bh_host_map_finish(const uint32_t* runs, long n_runs, const int8_t* q, long q_len, long q_st, const int8_t* r, long r_len,
+                                   long r_st, uint32_t* cigar, long cigar_cap, char* cigar_text, long cigar_text_cap, char* md, long md_cap,
+                                   int64_t* counts) {
+    if (n_runs < 0 || (n_runs && !runs) || !q || !r || !cigar || !cigar_text || !md || !counts || q_st < 0 || r_st < 0) return -1;
+    static const char letters[] = "?ACGTN", ops[] = "MID";
+    long qi = q_st, ri = r_st, nm = 0, mlen = 0, blen = 0, n_cigar = 0, text = 0, mdn = 0, run = 0;
+    long cur_len = 0;
+    int cur_op = -1;
+    auto flush = [&]() -> bool {
+        if (cur_op < 0) return true;
+        if (n_cigar >= cigar_cap || text + 24 > cigar_text_cap) return false;
+        cigar[n_cigar++] = ((uint32_t)cur_len << 2) | (uint32_t)cur_op;
+        text += snprintf(cigar_text + text, 24, "%ld%c", cur_len, ops[cur_op]);
+        return true;
+    };
+    for (long i = 0; i < n_runs; ++i) {
+        const long len = runs[i] >> 2;
+        const int op4 = (int)(runs[i] & 3), op = op4 <= 1 ? 0 : op4 - 1;         // = and X are M
+        if (len == 0) continue;
+        if (op != 1 && ri + len > r_len) return -1;
+        if (op != 2 && qi + len > q_len) return -1;
+        if (op == cur_op) cur_len += len;
+        else {
+            if (!flush()) return -3;
+            cur_op = op; cur_len = len;
+        }
+        blen += len;
+        if (op == 0) {
+            for (long x = 0; x < len; ++x) {
+                const int a = q[qi + x], b = r[ri + x];
+                if (a == b && a >= 1 && a <= 4) { ++run; ++mlen; continue; }
+                if (mdn + 24 > md_cap) return -3;
+                mdn += snprintf(md + mdn, 24, "%ld%c", run, letters[b >= 1 && b <= 4 ? b : 5]);
+                run = 0; ++nm;
+            }
+            qi += len; ri += len;
+        } else if (op == 1) {
+            nm += len; qi += len;
+        } else {
+            if (mdn + 24 + len > md_cap) return -3;
+            mdn += snprintf(md + mdn, 24, "%ld^", run);
+            for (long x = 0; x < len; ++x) { const int b = r[ri + x]; md[mdn++] = letters[b >= 1 && b <= 4 ? b : 5]; }
+            run = 0; nm += len; ri += len;
+        }
+    }
+    if (!flush()) return -3;
+    if (mdn + 24 > md_cap) return -3;
+    mdn += snprintf(md + mdn, 24, "%ld", run);
+    counts[0] = nm; counts[1] = mlen; counts[2] = blen; counts[3] = n_cigar; counts[4] = text; counts[5] = mdn;
+    counts[6] = qi; counts[7] = ri;
+    return 0;
+}

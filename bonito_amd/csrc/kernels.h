@@ -158,6 +158,18 @@ int bh_k_sg_align(const void* seqs, long seq_stride, const int* seq_lens, const 
                   int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace, size_t workspace_bytes,
                   int* result, unsigned* ops, long ops_stride, int* n_ops, hipStream_t stream);
 
+// mapper.hip (the read mapper: minimizer sketch, seeding against a sorted index, chaining; the sketch's lengths are a host array)
+int bh_k_map_sketch_tile();
+size_t bh_k_map_sketch_workspace(int n, long total_len);
+int bh_k_map_sketch(const void* codes, long stride, const int* lengths, int n, int k, int w, void* workspace, size_t workspace_bytes,
+                    long long* keys, int* pos, int8_t* strand, long capacity, int* offsets, hipStream_t stream);
+int bh_k_map_seed(const long long* qkeys, const int* qpos, const int8_t* qstrand, const int* q_offsets, const int* q_lengths, int n,
+                  long n_min, const long long* ukeys, const int* ustart, const int* ucount, long n_ukeys, const int* rpos,
+                  const int8_t* rstrand, int k, int max_occ, int* counts, const long long* offsets, long long* anchors, long capacity,
+                  hipStream_t stream);
+int bh_k_map_chain(const long long* anchors, const int* contigs, const int* offsets, int n, long n_anchors, int k, int max_dist,
+                   int bandwidth, int* f, int* p, int* chain, int* result, hipStream_t stream);
+
 // nw.hip (banded global alignment under unit costs with a traceback; one band half-width k per call; the lengths are host arrays)
 size_t bh_k_nw_workspace(int n, int max_seq, int max_ref, long max_band);
 int bh_k_nw_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,

@@ -1,7 +1,8 @@
 """
 Basecall output: FASTQ / FASTA / unaligned SAM text and ``summary.tsv`` -- the host-side formatting of
 /root/reference bonito/io.py (encode_moves 57-70, write_fastq 97-105, sam_record 135-166, summary 169-226,
-Writer 400-469) without pysam / mappy (alignment and BAM/CRAM need those wheels and are out of scope).
+Writer 400-469) without pysam / mappy: aligned SAM text and the alignment columns of the summary come from the mappings of
+bonito_amd/aligner.py (the device mapper, mappy's field names); BAM/CRAM need pysam and are out of scope.
 SAM tags follow documentation/SAM.md:39-55: ``mv:B:c,<stride>,<moves...>``, ``qs:f`` (mean q-score),
 ``ns:i`` (samples incl. trimmed), ``ts:i`` (trimmed samples), ``RG:Z``.
 """
@@ -17,6 +18,11 @@ __version__ = "0.1.0"
 
 summary_field_names = ["filename", "read_id", "run_id", "channel", "mux", "start_time", "duration", "template_start",
                        "template_duration", "sequence_length_template", "mean_qscore_template"]
+alignment_field_names = ["alignment_genome", "alignment_genome_start", "alignment_genome_end", "alignment_strand_start",
+                         "alignment_strand_end", "alignment_direction", "alignment_length", "alignment_num_aligned",
+                         "alignment_num_correct", "alignment_num_insertions", "alignment_num_deletions",
+                         "alignment_num_substitutions", "alignment_mapq", "alignment_strand_coverage", "alignment_identity",
+                         "alignment_accuracy"]
 
 
 def mean_qscore(qstring):
@@ -47,17 +53,37 @@ def write_fastq(header, sequence, qstring, fd=sys.stdout, tags=None, sep="\t"):
     fd.write("%s\n+\n%s\n" % (sequence, qstring))
 
 
-def sam_header(groups, sep="\t"):
+def sam_header(groups, sep="\t", aligner=None):
+    """With an aligner the header names its contigs (@SQ, what pysam writes from reference_names / reference_lengths in the
+    reference's Writer, io.py:416-425) and the mapper (@PG ID:aligner)."""
     hd = sep.join(["@HD", "VN:1.5", "SO:unknown", "ob:%s" % __version__])
     pg = sep.join(["@PG", "ID:basecaller", "PN:bonito_amd", "VN:%s" % __version__, "CL:%s" % " ".join(sys.argv),
                    "DS:MI355X engine"])
-    return "\n".join([hd, pg, *groups]) + "\n"
+    if aligner is None:
+        return "\n".join([hd, pg, *groups]) + "\n"
+    sq = [sep.join(["@SQ", "SN:%s" % name, "LN:%d" % len(aligner.seq(name))]) for name in aligner.seq_names]
+    pg2 = sep.join(["@PG", "ID:aligner", "PN:bonito_amd", "VN:%s" % __version__, "DS:device mapper"])
+    return "\n".join([hd, *sq, pg, pg2, *groups]) + "\n"
+
+
+_COMPLEMENT = str.maketrans("ACGTacgt", "TGCAtgca")
+
+
+def revcomp(sequence):
+    return sequence[::-1].translate(_COMPLEMENT)
 
 
 def sam_record(read_id, sequence, qstring, mapping=None, tags=None, sep="\t"):
-    if mapping is not None:
-        raise NotImplementedError("alignment is out of scope for this build (needs mappy)")
-    record = [read_id, 4, "*", 0, 0, "*", "*", 0, 0, sequence, qstring, "NM:i:0"]
+    if mapping:
+        # the reference's record (bonito/io.py:139-157) as it stands: on the minus strand the sequence is reverse-complemented and the
+        # soft-clips swap ends, but the q-string is written as basecalled, NOT reversed
+        plus = mapping.strand == +1
+        softclip = ["%sS" % mapping.q_st if mapping.q_st else "", mapping.cigar_str,
+                    "%sS" % (len(sequence) - mapping.q_en) if len(sequence) - mapping.q_en else ""]
+        record = [read_id, 0 if plus else 16, mapping.ctg, mapping.r_st + 1, mapping.mapq, "".join(softclip if plus else softclip[::-1]),
+                  "*", 0, 0, sequence if plus else revcomp(sequence), qstring, "NM:i:%s" % mapping.NM, "MD:Z:%s" % mapping.MD]
+    else:
+        record = [read_id, 4, "*", 0, 0, "*", "*", 0, 0, sequence, qstring, "NM:i:0"]
     if tags is not None:
         record.extend(tags)
     return sep.join(map(str, record))
@@ -71,9 +97,25 @@ def read_tags(read, res, mean_q):
     return tags
 
 
-def summary_row(read, seqlen, qscore):
-    return [read.filename, read.read_id, read.run_id, read.channel, read.mux, read.start, read.duration,
-            read.template_start, read.template_duration, seqlen, qscore]
+def summary_row(read, seqlen, qscore, alignment=False):
+    """alignment: False = no alignment columns; a mapping = the reference's 16 columns (bonito/io.py:229-251); None = its row for
+    an unmapped read (io.py:253-256)."""
+    fields = [read.filename, read.read_id, read.run_id, read.channel, read.mux, read.start, read.duration,
+              read.template_start, read.template_duration, seqlen, qscore]
+    if alignment:
+        ins = sum(count for count, op in alignment.cigar if op == 1)
+        dels = sum(count for count, op in alignment.cigar if op == 2)
+        subs = alignment.NM - ins - dels
+        length = alignment.blen
+        matches = length - ins - dels
+        correct = alignment.mlen
+        plus = alignment.strand == +1
+        fields.extend([alignment.ctg, alignment.r_st, alignment.r_en, alignment.q_st if plus else seqlen - alignment.q_en,
+                       alignment.q_en if plus else seqlen - alignment.q_st, "+" if plus else "-", length, matches, correct, ins, dels,
+                       subs, alignment.mapq, (alignment.q_en - alignment.q_st) / seqlen, correct / matches, correct / length])
+    elif alignment is None:
+        fields.extend(["*", -1, -1, -1, -1, "*", 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0])
+    return fields
 
 
 def signal_samples(read):
@@ -109,8 +151,9 @@ def format_record(read, res, mode, min_qscore=0.0):
         tags = read_tags(read, res, mean_q)
         text = "@%s %s\n%s\n+\n%s\n" % (read.read_id, "\t".join(tags), seq, "!" * len(seq) if no_quals else qstring)
     else:
-        text = sam_record(read.read_id, seq, "*" if no_quals else qstring, tags=read_tags(read, res, mean_q)) + "\n"
-    return text, summary_row(read, len(seq), mean_q), log
+        text = sam_record(read.read_id, seq, "*" if no_quals else qstring, res.get("mapping"), tags=read_tags(read, res, mean_q)) + "\n"
+    # a result that went through aligner.align_map carries "mapping" (None = unmapped): the summary then has the alignment columns
+    return text, summary_row(read, len(seq), mean_q, alignment=res["mapping"] if "mapping" in res else False), log
 
 
 class Writer(Thread):
@@ -121,8 +164,9 @@ class Writer(Thread):
     text may be `bytes` / a memoryview and a row the rendered TSV line as `bytes` (the packed blocks of parallel.ordered_records, the
     library's record text taken as it is): they go to the binary layer of `fd` without a str round trip."""
 
-    def __init__(self, mode, iterator, fd=sys.stdout, min_qscore=0.0, summary_path=None, groups=(), preformatted=False):
+    def __init__(self, mode, iterator, fd=sys.stdout, min_qscore=0.0, summary_path=None, groups=(), preformatted=False, aligner=None):
         super().__init__()
+        self.aligner = aligner   # its contigs go to the SAM header, the alignment columns to the summary's
         assert mode in ("fastq", "fasta", "sam")
         self.mode, self.iterator, self.fd = mode, iterator, fd
         self.min_qscore, self.summary_path, self.groups = min_qscore, summary_path, groups
@@ -135,9 +179,9 @@ class Writer(Thread):
             summary = open(self.summary_path, "w", newline="") if self.summary_path else None
             tsv = csv.writer(summary, delimiter="\t") if summary else None
             if tsv:
-                tsv.writerow(summary_field_names)
+                tsv.writerow(summary_field_names + (alignment_field_names if self.aligner is not None else []))
             if self.mode == "sam":
-                self.fd.write(sam_header(self.groups))
+                self.fd.write(sam_header(self.groups, aligner=self.aligner))
             raw = getattr(self.fd, "buffer", None)          # the binary layer under a text file (sys.stdout, open(..., "w")); None for StringIO
             dirty = self.mode == "sam"                      # text written through the str layer and not yet flushed
             for item in self.iterator:

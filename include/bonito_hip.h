@@ -30,6 +30,9 @@
  *   bh_nw_align / bh_sg_align
  *        edlib.align(query, ref, task="path") and parasail.sg_trace_scan_32(query, ref, 10, 2, dnafull) behind the basespace
  *        duplex caller                                                         bonito/cli/duplex.py:224-300
+ *   bh_map_sketch / bh_map_seed / bh_map_chain
+ *        mappy.Aligner(reference).map(sequence) behind `bonito basecaller --reference`, as far as seeding and chaining go; defined by
+ *        tests/mapper_ref.py, minimap2 parity is not claimed                   bonito/aligner.py:1-63
  *   bh_ctc_greedy_decode / bh_ctc_beam_search
  *        fast_ctc_decode.viterbi_search / beam_search                          bonito/ctc/model.py:39-46
  *   bh_linear, bh_conv1d_*, bh_lstm_layer, ...  (operator level, used by the parity tests)
@@ -373,6 +376,53 @@ int bh_nw_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, c
                 const int32_t* ref_lengths, int n, int k, void* workspace, size_t workspace_bytes, int32_t* result, uint32_t* ops,
                 long ops_stride, int32_t* n_ops, void* stream);
 
+/* The read mapper ("Mapper"): what `bonito basecaller --reference` gets from mappy / minimap2 (bonito/aligner.py),
+ * DEFINED by the restatement tests/mapper_ref.py, not by minimap2: seeds, chain scores, mapq and tie-breaks are this project's.
+ * Three steps on the device; sorting and the prefix sums between them are the caller's; the base alignment is bh_nw_align.
+ *
+ * bh_map_sketch: the (k, w)-minimizers of n sequences, 11 <= k <= 28, 1 <= w <= 64.
+ *   codes (DEVICE int8 [n][stride]): 1..4 = A C G T, anything else = no base (padding behind a sequence included); lengths: HOST.
+ *   The k-mer ending at p has the 2k-bit values fw (first base in the top bits) and rv (its reverse complement); its key is the smaller
+ *   of mix(fw), mix(rv) (mix: the seven-step invertible map spelt out in tests/mapper_ref.py), the strand bit says that mix(rv) was the
+ *   smaller; a k-mer with a non-base, or with mix(fw) = mix(rv), has no key. The window ending at p holds the k-mer ends
+ *   max(k - 1, p - w + 1) .. p; windows end at every p >= min(k + w - 2, len - 1); a window selects the leftmost of its smallest keys.
+ *   Output (DEVICE): keys[o], pos[o] (the k-mer's last base), strand[o] for the distinct selected positions of sequence 0 in position
+ *   order, then those of sequence 1, ...; offsets (int32 [n + 1]): where each sequence's minimizers start, offsets[n] = their number.
+ *   capacity: entries in keys / pos / strand; at least sum(max(0, len - k + 1)), one per k-mer (an error otherwise, never truncation).
+ *   workspace: DEVICE, bh_map_sketch_workspace(n, sum of the lengths) bytes (0 = unsupported). A workgroup covers
+ *   bh_map_sketch_tile() window ends of one sequence. With n = 1 the stride is not read (a contig inside a longer buffer).
+ *   Errors (rc != 0): k or w out of range, a negative length, a length beyond the stride, lengths that total 2^31 or more, an output
+ *   or workspace that is too small.
+ * bh_map_seed: one anchor per (query minimizer, occurrence of its key in the index), for the n <= 1024 reads of one sketch call.
+ *   Query side: keys / pos / strand / offsets as bh_map_sketch wrote them, n_min = offsets[n] (HOST), q_lengths (DEVICE int32 [n]).
+ *   Index side (DEVICE): ukeys (the distinct keys, increasing), ustart / ucount (the run of each key in rpos / rstrand), rpos (position
+ *   of the k-mer's last base in the concatenated reference, below 2^31) and rstrand, sorted by (key, rpos). A key with more than
+ *   max_occ occurrences gives no anchor.
+ *   Called with offsets = NULL it writes counts[q], the anchors of query minimizer q; called again with their exclusive prefix sums in
+ *   offsets (int64 [n_min]) it writes anchors[offsets[q] + j] = read << 53 | strand << 52 | rpos << 21 | qpos', strand = query strand xor
+ *   reference strand, qpos' = qpos, on strand 1 q_length - qpos + k - 2 (the same k-mer's last base on the reverse-complemented
+ *   read; reads of fewer than 2^21 bases). Sorting these words sorts by (read, strand, contig, rpos, qpos'). Nothing beyond capacity
+ *   is written.
+ * bh_map_chain: the chaining DP, the primary chain and s2 for n <= 1024 reads, one wave per read.
+ *   anchors: the sorted words; contigs (int32 per anchor): the contig of rpos; offsets (int32 [n + 1]): each read's anchors.
+ *   f[i] = max(k, max_j f[j] + min(dq, dr, k) - cost(|dr - dq|)) over j = i - 64 .. i - 1 of the same read, strand and contig with
+ *   0 < dq <= max_dist, 0 < dr <= max_dist, |dr - dq| <= bandwidth; cost(0) = 0, cost(g) = ((5 g) >> 5) + (floor(log2 g) >> 1). A
+ *   predecessor is taken only when its score exceeds k, among equal scores the largest j. p[i]: the predecessor (index within the
+ *   read) or -1. The chain ends at the largest f, among equals the smallest index; chain (int32, the read's slice): its anchors from
+ *   the LAST to the first. result (int32 [n][4]): anchors in the chain, s1 (its f), s2 (the largest f on another strand or contig or
+ *   with rpos outside the chain's [first, last] rpos; 0 if none), index of the end anchor (0, 0, 0, -1 for a read without anchors).
+ *   Errors: n, k, max_dist or bandwidth out of range, 2^31 anchors or more. */
+int bh_map_sketch_tile(void);
+size_t bh_map_sketch_workspace(int n, long total_len);
+int bh_map_sketch(const void* codes, long stride, const int32_t* lengths, int n, int k, int w, void* workspace, size_t workspace_bytes,
+                  int64_t* keys, int32_t* pos, int8_t* strand, long capacity, int32_t* offsets, void* stream);
+int bh_map_seed(const int64_t* qkeys, const int32_t* qpos, const int8_t* qstrand, const int32_t* q_offsets, const int32_t* q_lengths,
+                int n, long n_min, const int64_t* ukeys, const int32_t* ustart, const int32_t* ucount, long n_ukeys,
+                const int32_t* rpos, const int8_t* rstrand, int k, int max_occ, int32_t* counts, const int64_t* offsets,
+                int64_t* anchors, long capacity, void* stream);
+int bh_map_chain(const int64_t* anchors, const int32_t* contigs, const int32_t* offsets, int n, long n_anchors, int k, int max_dist,
+                 int bandwidth, int32_t* f, int32_t* p, int32_t* chain, int32_t* result, void* stream);
+
 /* Signal ingest on the device: replaces Read.__init__'s numpy work (bonito/reader.py:122-166 normalisation + trim, the pA
  * scaling and the trim threshold of bonito/pod5.py:52-67) and util.chunk + the fp16 cast (bonito/util.py:142-161, crf/basecall.py:31) for raw
  * int16 reads, with the reference's arithmetic reproduced bit for bit. All pointers are device pointers.
@@ -638,6 +688,16 @@ long bh_host_format_read(const int8_t* const* base, const long* plane_stride, co
                          long T, long length, int chunksize, int overlap, int stride, int reverse, int rna, int mode,
                          double min_qscore, const char* read_id, const char* run_id, long num_samples, long trimmed_samples,
                          char* out, long out_cap, long* seq_len, double* mean_q);
+/* Host only. One mapped read of the mapper (bh_map_*; bonito_amd/aligner.py): runs = the run words of bh_nw_align for its pieces, in
+ * order ((length << 2) | op, ops = X I D = 0 1 2 3), walked over the read's codes q (on the aligned strand) from q_st and the contig's
+ * codes r from r_st (1..4 = A C G T, anything else = no base) -> cigar: the run words of the M I D CIGAR ((length << 2) | 0 1 2; = and
+ * X are M, equal neighbours merged), cigar_text: the same as text (not terminated), md: the MD string (not terminated; a column matches
+ * when both codes are the same base; other reference codes print as N). counts (int64 [8]): NM, matching columns, all columns, CIGAR
+ * runs, bytes of cigar_text, bytes of md, the query and the reference position behind the last column. Returns 0; -1 = bad
+ * arguments or runs that leave a sequence; -3 = cigar_cap (runs), cigar_text_cap or md_cap (bytes) too small: n_runs runs,
+ * 24 bytes per run and 24 bytes per run plus 2 per column always suffice. */
+long bh_host_map_finish(const uint32_t* runs, long n_runs, const int8_t* q, long q_len, long q_st, const int8_t* r, long r_len, long r_st,
+                        uint32_t* cigar, long cigar_cap, char* cigar_text, long cigar_text_cap, char* md, long md_cap, int64_t* counts);
 /* Mean q-score of a phred string, averaged in error-probability space (bonito/util.py mean_qscore_from_qstring). */
 double bh_host_mean_qscore(const char* qstring, long n);
 /* pod5 signal codec, inner layer (bonito_amd/pod5.py; replaces the pod5 wheel behind /root/reference bonito/pod5.py:52 `read.signal`):
