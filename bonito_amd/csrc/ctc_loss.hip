@@ -16,7 +16,7 @@
 //     * a state that a -inf log-prob makes unreachable contributes occupancy 0;
 //     * len < 0, len > Lmax or a label outside 1..C-1: nll = NaN and no gradient is written.
 //
-// One workgroup per chunk, the geometry of seq_grad_kernel: thread `tid` owns the P consecutive states tid P .. tid P + P - 1 in
+// One workgroup per chunk, the instance list of seq_chain.h (which also holds lse2, the label read and grad_put): thread `tid` owns the P consecutive states tid P .. tid P + P - 1 in
 // registers. With an even P the blank / label pattern of a thread's states is known at compile time, a blank never takes the s-2 term,
 // and ONE value crosses a thread boundary forwards (alpha[s-1] of the left neighbour's last state; the one-state-per-thread instance
 // passes s-2 as well) and two backwards - by wave shift in the one-wave form, through a double-buffered LDS table in the four-wave
@@ -31,6 +31,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "seq_chain.h"
 
 namespace bh {
 namespace {
@@ -57,10 +58,6 @@ struct CtcArgs {
     int g32, accumulate;
 };
 
-__device__ __forceinline__ float ctc_lse2(float a, float b) {
-    const float m = fmaxf(a, b), d = fminf(a, b) - m;
-    return m == -INFINITY ? m : m + __logf(1.0f + __expf(d));
-}
 __device__ __forceinline__ float ctc_lse3(float a, float b, float c) {
     const float m = fmaxf(fmaxf(a, b), c);
     return m == -INFINITY ? m : m + __logf(__expf(a - m) + __expf(b - m) + __expf(c - m));
@@ -70,17 +67,7 @@ __device__ __forceinline__ float ctc_ld(const CtcArgs& p, long at) {
 }
 __device__ __forceinline__ int ctc_target(const CtcArgs& p, int n, int len, int j) {      // label j of the chunk; 0 outside the target
     if (j < 0 || j >= len) return 0;
-    const long at = (long)n * p.Lmax + j;
-    return p.tbytes == 1 ? (int)((const int8_t*)p.targets)[at] : ((const int*)p.targets)[at];
-}
-__device__ __forceinline__ void ctc_grad_put(void* g, long at, float v, bool g32, bool add) {
-    if (g32) {
-        float* q = (float*)g + at;
-        *q = add ? *q + v : v;
-    } else {
-        half_t* q = (half_t*)g + at;
-        *q = (half_t)(add ? (float)*q + v : v);
-    }
+    return label_at(p.targets, p.tbytes, (long)n * p.Lmax + j);
 }
 
 // P states per thread; MULTI: four waves; GRAD: the backward pass; CM: the class sums kept per thread (C <= CM)
@@ -199,7 +186,7 @@ __global__ __launch_bounds__(256) void ctc_loss_kernel(CtcArgs p) {
                     const float x1 = i >= 1 ? a[i - 1] : prev1;
                     const float x2 = i >= 2 ? a[i - 2] : (i == 1 ? prev1 : prev2);
                     const bool lbl = (P % 2 == 0) ? (i & 1) != 0 : true;
-                    const float m = lbl ? ctc_lse3(a[i], x1, (fmask >> i) & 1 ? x2 : -INFINITY) : ctc_lse2(a[i], x1);
+                    const float m = lbl ? ctc_lse3(a[i], x1, (fmask >> i) & 1 ? x2 : -INFINITY) : lse2(a[i], x1);
                     a[i] = lv[u][i] + m;
                 }
                 if (stores) {
@@ -217,7 +204,7 @@ __global__ __launch_bounds__(256) void ctc_loss_kernel(CtcArgs p) {
         if (s == S - 2) s_end[1] = a[i];
     }
     __syncthreads();
-    const float logz = ctc_lse2(s_end[0], s_end[1]);
+    const float logz = lse2(s_end[0], s_end[1]);
     if (tid == 0) p.nll[n] = -logz;
     if constexpr (!GRAD) return;
 
@@ -227,7 +214,7 @@ __global__ __launch_bounds__(256) void ctc_loss_kernel(CtcArgs p) {
         if (!add)
             for (int e = tid; e < T * C; e += NT) {
                 const int t = e / C, c = e - t * C;
-                ctc_grad_put(p.grad, gbase + (long)t * p.g_t + c, 0.0f, g32, false);
+                grad_put(p.grad, gbase + (long)t * p.g_t + c, 0.0f, g32, false);
             }
         return;
     }
@@ -249,7 +236,7 @@ __global__ __launch_bounds__(256) void ctc_loss_kernel(CtcArgs p) {
         if (tid < C) {
             const unsigned* q = wsum + buf * 4 * CTC_MAX_C + tid;
             const unsigned v = q[0] + q[CTC_MAX_C] + q[2 * CTC_MAX_C] + q[3 * CTC_MAX_C];
-            ctc_grad_put(p.grad, gbase + (long)t * p.g_t + tid, w * (float)v + swc, g32, add);
+            grad_put(p.grad, gbase + (long)t * p.g_t + tid, w * (float)v + swc, g32, add);
         }
     };
     float b[P];
@@ -291,7 +278,7 @@ __global__ __launch_bounds__(256) void ctc_loss_kernel(CtcArgs p) {
                     const float y1 = i + 1 < P ? b[i + 1 < P ? i + 1 : 0] : nxt1;
                     const float y2 = i + 2 < P ? b[i + 2 < P ? i + 2 : 0] : (i + 2 == P ? nxt1 : nxt2);
                     const bool lbl = (P % 2 == 0) ? (i & 1) != 0 : true;
-                    const float m = lbl ? ctc_lse3(b[i], y1, (gmask >> i) & 1 ? y2 : -INFINITY) : ctc_lse2(b[i], y1);
+                    const float m = lbl ? ctc_lse3(b[i], y1, (gmask >> i) & 1 ? y2 : -INFINITY) : lse2(b[i], y1);
                     const unsigned q = (unsigned)(__expf(av[u][i] + m - logz) * CTC_FIX_ONE + 0.5f);
                     if (lbl) {
 #pragma unroll
@@ -320,7 +307,7 @@ __global__ __launch_bounds__(256) void ctc_loss_kernel(CtcArgs p) {
                     if ((lane & 7) == 0) wsum[(buf * 4 + wave) * CTC_MAX_C + (lane >> 3)] = mine;
                     buf ^= 1;
                 } else {
-                    if (writer) ctc_grad_put(p.grad, gbase + (long)t * p.g_t + wc, w * (float)mine + swc, g32, add);
+                    if (writer) grad_put(p.grad, gbase + (long)t * p.g_t + wc, w * (float)mine + swc, g32, add);
                 }
                 loadb(u, t - U);
             }
@@ -332,24 +319,17 @@ __global__ __launch_bounds__(256) void ctc_loss_kernel(CtcArgs p) {
     }
 }
 
+// the kernels of the instance list (seq_chain.h), in its order; the first row that holds 2 Lmax + 1 states serves the call.
+// id: enum bh_ctc_loss_kernel = the states per thread, + 100 in the four-wave form
 typedef void (*CtcKernel)(CtcArgs);
-// THE instance table: states per launch = threads x per; the first row that holds 2 Lmax + 1 states serves the call
-struct CtcInstance { int id, threads, per; CtcKernel fwd, grad5, grad8; };
-#define BH_CTC_ROW(ID, NT, PP, MULTI) \
-    {ID, NT, PP, ctc_loss_kernel<PP, MULTI, false, 5>, ctc_loss_kernel<PP, MULTI, true, 5>, ctc_loss_kernel<PP, MULTI, true, 8>}
-const CtcInstance kCtcInstances[] = {
-    BH_CTC_ROW(BH_CTC_LOSS_K_W1, 64, 1, false),   BH_CTC_ROW(BH_CTC_LOSS_K_W2, 64, 2, false),   BH_CTC_ROW(BH_CTC_LOSS_K_W4, 64, 4, false),
-    BH_CTC_ROW(BH_CTC_LOSS_K_W8, 64, 8, false),   BH_CTC_ROW(BH_CTC_LOSS_K_M4, 256, 4, true),   BH_CTC_ROW(BH_CTC_LOSS_K_M8, 256, 8, true),
-    BH_CTC_ROW(BH_CTC_LOSS_K_M16, 256, 16, true),
-};
+struct CtcKernels { int id; CtcKernel fwd, grad5, grad8; };
+#define BH_CTC_ROW(NT, P, MULTI) \
+    {(MULTI ? 100 : 0) + P, ctc_loss_kernel<P, MULTI, false, 5>, ctc_loss_kernel<P, MULTI, true, 5>, ctc_loss_kernel<P, MULTI, true, 8>},
+const CtcKernels kCtcKernels[] = {BH_SEQ_INSTANCES(BH_CTC_ROW)};
 #undef BH_CTC_ROW
+static_assert(BH_CTC_LOSS_K_W1 == 1 && BH_CTC_LOSS_K_W8 == 8 && BH_CTC_LOSS_K_M4 == 104 && BH_CTC_LOSS_K_M16 == 116, "instance codes");
 
-const CtcInstance* ctc_instance(int Lmax) {
-    if (Lmax < 0) return nullptr;
-    for (const CtcInstance& r : kCtcInstances)
-        if (2 * (long)Lmax + 1 <= (long)r.threads * r.per) return &r;
-    return nullptr;
-}
+int ctc_instance(int Lmax) { return Lmax < 0 ? -1 : seq_instance(2 * (long)Lmax + 1); }
 
 int g_ctc_loss_last_kernel = 0;    // bh_k_ctc_loss_last_kernel (test hook, not thread-safe)
 
@@ -360,11 +340,11 @@ int bh_k_ctc_loss_last_kernel() { return bh::g_ctc_loss_last_kernel; }
 
 size_t bh_k_ctc_loss_workspace(int N, int T, int C, int Lmax, int grad) {
     if (N <= 0 || T <= 0 || C < 2 || C > bh::CTC_MAX_C || Lmax > 2047) return 0;
-    const bh::CtcInstance* r = bh::ctc_instance(Lmax);
-    if (!r) return 0;
+    const int row = bh::ctc_instance(Lmax);
+    if (row < 0) return 0;
     if (!grad) return 512;                                                  // the forward keeps nothing
-    const int S = 2 * Lmax + 1;
-    return (size_t)N * T * ((S + r->per - 1) / r->per * r->per) * sizeof(float) + 512;
+    const int S = 2 * Lmax + 1, per = bh::kSeqGeometry[row].per;
+    return (size_t)N * T * ((S + per - 1) / per * per) * sizeof(float) + 512;
 }
 
 int bh_k_ctc_loss(const void* log_probs, int logp_fp32, int N, int T, int C, long s_t, long s_n, const void* targets, int target_bytes,
@@ -390,14 +370,15 @@ int bh_k_ctc_loss(const void* log_probs, int logp_fp32, int N, int T, int C, lon
         const bool nt = (T == 1 || g_t >= C) && (N == 1 || g_n >= (long)(T - 1) * g_t + C);      // [N][T][C]-like
         BH_REQUIRE(tn || nt, "%s: bad strides (g_stride_t %ld, g_stride_n %ld): the rows of grad overlap", who, g_t, g_n);
     }
-    const CtcInstance* r = ctc_instance(Lmax);
-    BH_REQUIRE(r != nullptr, "%s: no instance for Lmax %d", who, Lmax);
-    const int S = 2 * Lmax + 1;
+    const int row = ctc_instance(Lmax);
+    BH_REQUIRE(row >= 0, "%s: no instance for Lmax %d", who, Lmax);
+    const CtcKernels& r = kCtcKernels[row];
+    const int S = 2 * Lmax + 1, per = kSeqGeometry[row].per;
     CtcArgs a{log_probs, logp_fp32, N, T, C, s_t, s_n, targets, target_bytes, Lmax, lens, smooth_w, weight, smooth_weight,
-              (float*)workspace, (S + r->per - 1) / r->per * r->per, nll, smooth, grad, g_t, g_n, grad_fp32, accumulate};
-    const CtcKernel fn = !with_grad ? r->fwd : (C <= 5 ? r->grad5 : r->grad8);
-    hipLaunchKernelGGL(fn, dim3(N), dim3(r->threads), 0, stream, a);
-    g_ctc_loss_last_kernel = r->id;
+              (float*)workspace, (S + per - 1) / per * per, nll, smooth, grad, g_t, g_n, grad_fp32, accumulate};
+    const CtcKernel fn = !with_grad ? r.fwd : (C <= 5 ? r.grad5 : r.grad8);
+    hipLaunchKernelGGL(fn, dim3(N), dim3(kSeqGeometry[row].threads), 0, stream, a);
+    g_ctc_loss_last_kernel = r.id;
     BH_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -34,10 +34,14 @@
 // Supported range (checked, never truncated): 1 <= state_len <= 5, 1 <= T, Lmax + 1 - state_len <= 4096, labels 0..4.
 // target_lengths live on the device, so a chunk whose length is below state_len (fixed start) or above Lmax yields NaN; the Python
 // surface rejects both before anything is launched.
+//
+// lse2 / lse_n, the label read, the chain pieces (problem description, gather offsets, ring load, hand-off, Log-scan step), the
+// dense pieces and the (threads, positions per thread) instance list are in seq_chain.h, which seqdist_grad.hip builds on as well.
 #include <math.h>
 
 #include "common.h"
 #include "kernels.h"
+#include "seq_chain.h"
 
 namespace bh {
 
@@ -45,43 +49,25 @@ constexpr int SU = 4;            // prefetch depth (time steps)
 constexpr int STB = 64;          // traceback block (time steps)
 
 struct SeqArgs {
-    const half_t* scores;
-    int N, T, k, five;
-    float blank;
-    long s_n, s_t;
-    const void* targets;         // [N][Lmax] int8 or int32
-    int tbytes, Lmax;
-    const int* lens;             // [N]
+    ChainArgs c;
     unsigned long long* bits;    // [N][T][waves * P] (Max scan)
     const float* inject;         // [N][T] (free start) or null
     float* out;                  // [N]
     int* align;                  // [N][T] (Max scan)
 };
 
-__device__ __forceinline__ float lse2(float a, float b) {
-    const float m = fmaxf(a, b), d = fminf(a, b) - m;
-    return m == -INFINITY ? m : m + __logf(1.0f + __expf(d));
-}
-
-__device__ __forceinline__ int target0(const SeqArgs& p, int n, int i) {   // targets0[i]; 0 beyond the row
-    if (i >= p.Lmax) return 0;
-    const long at = (long)n * p.Lmax + i;
-    int v = p.tbytes == 1 ? (int)((const int8_t*)p.targets)[at] : ((const int*)p.targets)[at];
-    v -= 1;
-    return v < 0 ? 0 : (v > 3 ? 3 : v);
-}
-
 template <int P, bool MULTI, bool VIT>
 __global__ __launch_bounds__(256) void seq_scan_kernel(SeqArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int n = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
-    const int len = p.lens[n];
-    const int npos = len + 1 - p.k;
+    const ChainArgs& c = p.c;
+    const int n = blockIdx.x, tid = threadIdx.x, NT = blockDim.x, T = c.T;
+    const int len = c.lens[n];
+    const int npos = len + 1 - c.k;
     const bool free_start = p.inject != nullptr;
-    if (len > p.Lmax || (npos <= 0 && !free_start)) {                       // argument error on the device: NaN, never a truncated answer
+    if (len > c.Lmax || (npos <= 0 && !free_start)) {                       // argument error on the device: NaN, never a truncated answer
         if (tid == 0) p.out[n] = __builtin_nanf("");
         if (VIT)
-            for (int t = tid; t < p.T; t += NT) p.align[(long)n * p.T + t] = -1;
+            for (int t = tid; t < T; t += NT) p.align[(long)n * T + t] = -1;
         return;
     }
     if (npos <= 0) return;                                                  // free start, shorter than k: seq_prefix_kernel wrote the result
@@ -89,26 +75,14 @@ __global__ __launch_bounds__(256) void seq_scan_kernel(SeqArgs p) {
     // ---- the chain: gather offsets of this thread's positions ----
     int so[P], mo[P];
 #pragma unroll
-    for (int i = 0; i < P; ++i) {
-        const int j = tid * P + i;
-        int kmer = 0;
-        for (int d = 0; d < p.k; ++d) kmer = kmer * 4 + target0(p, n, j + d);
-        const int b = j > 0 ? target0(p, n, j - 1) : 0;
-        so[i] = 5 * kmer;
-        mo[i] = p.five ? 5 * kmer + 1 + b : 4 * kmer + b;
-    }
-    const half_t* sc = p.scores + (long)n * p.s_n;
-    const float* inj = free_start ? p.inject + (long)n * p.T : nullptr;
+    for (int i = 0; i < P; ++i) chain_offsets(c, n, tid * P + i, so[i], mo[i]);
+    const half_t* sc = c.scores + (long)n * c.s_n;
+    const float* inj = free_start ? p.inject + (long)n * T : nullptr;
 
     float sv[SU][P], mv[SU][P], iv[SU];
     auto load = [&](int slot, int t) {
-        const int tt = min(t, p.T - 1);                                     // (rows beyond the end are never used)
-        const half_t* row = sc + (long)tt * p.s_t;
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-            sv[slot][i] = p.five ? (float)row[so[i]] : p.blank;
-            mv[slot][i] = (float)row[mo[i]];
-        }
+        const int tt = min(t, T - 1);                                       // (rows beyond the end are never used)
+        chain_load(c, sc + (long)tt * c.s_t, so, mo, sv[slot], mv[slot]);
         iv[slot] = free_start ? inj[tt] : -INFINITY;
     };
 
@@ -120,41 +94,29 @@ __global__ __launch_bounds__(256) void seq_scan_kernel(SeqArgs p) {
     float* edge = (float*)smem;                                             // [2][NT] (MULTI)
     int cb = 0;
     const int WP = (NT / WAVE) * P;
-    unsigned long long* bits = VIT ? p.bits + (long)n * p.T * WP : nullptr;
+    unsigned long long* bits = VIT ? p.bits + (long)n * T * WP : nullptr;
 
 #pragma unroll
     for (int u = 0; u < SU; ++u) load(u, u);
-    for (int t0 = 0; t0 < p.T; t0 += SU) {
+    for (int t0 = 0; t0 < T; t0 += SU) {
 #pragma unroll
         for (int u = 0; u < SU; ++u) {
             const int t = t0 + u;
-            if (t < p.T) {                                                  // uniform across the workgroup
-                float prev;
-                if constexpr (MULTI) {
-                    edge[cb * NT + tid] = a[P - 1];
-                    __syncthreads();
-                    prev = tid ? edge[cb * NT + tid - 1] : -INFINITY;
-                    cb ^= 1;
+            if (t < T) {                                                    // uniform across the workgroup
+                const float prev = chain_from_left<MULTI>(a[P - 1], edge, cb, tid, NT);
+                if constexpr (!VIT) {
+                    chain_log_step(a, prev, sv[u], mv[u]);
+                    if (free_start && tid == 0) a[0] = lse2(a[0], iv[u]);
                 } else {
-                    prev = __shfl_up(a[P - 1], 1);
-                    if (tid == 0) prev = -INFINITY;
-                }
-                unsigned moved = 0;
+                    unsigned moved = 0;
 #pragma unroll
-                for (int i = P - 1; i >= 0; --i) {                          // descending: position i reads the OLD alpha of i - 1
-                    const float in = (i ? a[i - 1] : prev) + mv[u][i];
-                    const float st = a[i] + sv[u][i];
-                    if constexpr (VIT) {
+                    for (int i = P - 1; i >= 0; --i) {                      // descending: position i reads the OLD alpha of i - 1
+                        const float in = (i ? a[i - 1] : prev) + mv[u][i];
+                        const float st = a[i] + sv[u][i];
                         const bool m = in > st;                             // ties: stay
                         a[i] = m ? in : st;
                         moved |= (unsigned)m << i;
-                    } else {
-                        a[i] = lse2(st, in);
                     }
-                }
-                if constexpr (!VIT) {
-                    if (free_start && tid == 0) a[0] = lse2(a[0], iv[u]);
-                } else {
                     const int lane = tid & 63, w = tid >> 6;
                     unsigned long long mine = 0;
 #pragma unroll
@@ -170,20 +132,18 @@ __global__ __launch_bounds__(256) void seq_scan_kernel(SeqArgs p) {
     }
 
     // ---- result: alpha_T[npos - 1] ----
-    {
-        const int last = npos - 1;
-        if (last / P == tid) {
-            float r = a[0];
+    const int last = npos - 1;
+    if (last / P == tid) {
+        float r = a[0];
 #pragma unroll
-            for (int i = 1; i < P; ++i)
-                if (last % P == i) r = a[i];
-            p.out[n] = r;
-        }
+        for (int i = 1; i < P; ++i)
+            if (last % P == i) r = a[i];
+        p.out[n] = r;
     }
     if constexpr (VIT) {
-        int* al = p.align + (long)n * p.T;
-        if (npos - 1 > p.T) {                                               // no alignment exists (best = -inf was written above)
-            for (int t = tid; t < p.T; t += NT) al[t] = -1;
+        int* al = p.align + (long)n * T;
+        if (last > T) {                                                     // no alignment exists (best = -inf was written above)
+            for (int t = tid; t < T; t += NT) al[t] = -1;
             return;
         }
         __threadfence();   // the traceback bits of this workgroup -> visible to its own later loads
@@ -192,8 +152,8 @@ __global__ __launch_bounds__(256) void seq_scan_kernel(SeqArgs p) {
         unsigned long long* stage = (unsigned long long*)(smem + 2 * NT * sizeof(float));   // [STB][WP]
         int* res = (int*)(stage + STB * WP);                                                // [STB]
         int* s_pos = res + STB;
-        if (tid == 0) *s_pos = npos - 1;
-        for (int thi = p.T; thi > 0; thi -= STB) {
+        if (tid == 0) *s_pos = last;
+        for (int thi = T; thi > 0; thi -= STB) {
             const int tlo = max(0, thi - STB);
             const int nw = (thi - tlo) * WP;
             for (int e = tid; e < nw; e += NT) stage[e] = bits[(long)tlo * WP + e];
@@ -224,7 +184,7 @@ struct PrefixArgs {
 
 __global__ __launch_bounds__(384) void seq_prefix_kernel(PrefixArgs q) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const SeqArgs& p = q.s;
+    const ChainArgs& p = q.s.c;
     float* D = (float*)smem;                                                // [2][total]
     const int n = blockIdx.x, x = threadIdx.x, k = p.k;
     const int len = p.lens[n];
@@ -269,20 +229,13 @@ __global__ __launch_bounds__(384) void seq_prefix_kernel(PrefixArgs q) {
             if (t < p.T) {                                                  // uniform across the workgroup
                 const float* d = D + cb * q.total;
                 if (active) {
-                    float c[4], m = -INFINITY;
+                    float c[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const float pa = lvl == 1 ? (float)t * p.blank : d[off_prev + r * cnt + u];
                         c[r] = pa + ring[v][r];
-                        m = fmaxf(m, c[r]);
                     }
-                    float in = m;
-                    if (m != -INFINITY) {
-                        float sum = 0.0f;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) sum += __expf(c[r] - m);
-                        in = m + __logf(sum);
-                    }
+                    const float in = lse_n<true>(c);
                     if (lvl < k) D[(cb ^ 1) * q.total + off + u] = lse2(d[off + u] + p.blank, in);
                     else inj[t] = in;
                 }
@@ -310,7 +263,7 @@ __global__ __launch_bounds__(384) void seq_prefix_kernel(PrefixArgs q) {
                 r = m + __logf(sum);
             }
         }
-        p.out[n] = r;
+        q.s.out[n] = r;
     }
 }
 
@@ -332,12 +285,7 @@ __global__ __launch_bounds__(1024) void crf_dense_logz_kernel(DenseArgs p) {
     if (active) al[j] = 0.0f;
     __syncthreads();
     float ring[SU][5];
-    auto load = [&](int slot, int t) {
-        const half_t* row = sc + (long)min(t, p.T - 1) * p.s_t;
-        ring[slot][0] = p.five ? (float)row[0] : p.blank;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ring[slot][1 + r] = (float)row[(p.five ? 1 : 0) + r];
-    };
+    auto load = [&](int slot, int t) { dense_load(p, sc + (long)min(t, p.T - 1) * p.s_t, ring[slot]); };
     int cb = 0;
 #pragma unroll
     for (int v = 0; v < SU; ++v) load(v, v);
@@ -345,54 +293,30 @@ __global__ __launch_bounds__(1024) void crf_dense_logz_kernel(DenseArgs p) {
 #pragma unroll
         for (int v = 0; v < SU; ++v) {
             if (t0 + v < p.T) {                                             // uniform across the workgroup
-                const float* a = al + cb * S;
-                if (active) {
-                    float c[5];
-                    c[0] = a[j] + ring[v][0];
-                    float m = c[0];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        c[1 + r] = a[r * q + (j >> 2)] + ring[v][1 + r];
-                        m = fmaxf(m, c[1 + r]);
-                    }
-                    float sum = 0.0f;
-#pragma unroll
-                    for (int e = 0; e < 5; ++e) sum += __expf(c[e] - m);
-                    al[(cb ^ 1) * S + j] = m + __logf(sum);
-                }
+                if (active) al[(cb ^ 1) * S + j] = dense_step(al + cb * S, j, q, ring[v]);
                 cb ^= 1;
                 __syncthreads();
                 load(v, t0 + v + SU);
             }
         }
     }
-    if (j == 0) {
-        const float* a = al + cb * S;
-        float m = a[0];
-        for (int i = 1; i < S; ++i) m = fmaxf(m, a[i]);
-        float sum = 0.0f;
-        for (int i = 0; i < S; ++i) sum += __expf(a[i] - m);
-        p.out[n] = m + __logf(sum);
-    }
+    if (j == 0) p.out[n] = dense_final(al + cb * S, S);
 }
 
-// geometry of the chain kernel for rows of up to Lmax labels: threads per chunk and positions per thread (0 = out of range)
-static void seq_geometry(int Lmax, int k, int* threads, int* per) {
-    int pm = Lmax + 1 - k;
-    if (pm < 1) pm = 1;
-    *threads = pm <= 512 ? 64 : 256;
-    *per = 0;
-    if (pm <= 512) { for (int P = 1; P <= 8; P *= 2) if (pm <= 64 * P) { *per = P; break; } }
-    else { for (int P = 4; P <= 16; P *= 2) if (pm <= 256 * P) { *per = P; break; } }
-}
+// the chain kernels of the instance list, in its order
+typedef void (*SeqKernel)(SeqArgs);
+struct SeqKernels { SeqKernel max, log; };
+#define BH_SEQ_ROW(NT, P, MULTI) {seq_scan_kernel<P, MULTI, true>, seq_scan_kernel<P, MULTI, false>},
+static const SeqKernels kSeqKernels[] = {BH_SEQ_INSTANCES(BH_SEQ_ROW)};
+#undef BH_SEQ_ROW
 
 }  // namespace bh
 
 size_t bh_k_crf_seq_workspace(int N, int T, int Lmax, int state_len) {
     if (N <= 0 || T <= 0 || Lmax < 0 || state_len < 1 || state_len > 5) return 0;
-    int threads, per;
-    bh::seq_geometry(Lmax, state_len, &threads, &per);
-    if (per == 0) return 0;
+    const int row = bh::chain_instance(Lmax, state_len);
+    if (row < 0) return 0;
+    const int threads = bh::kSeqGeometry[row].threads, per = bh::kSeqGeometry[row].per;
     const size_t bits = (size_t)N * T * (threads / 64) * per * sizeof(unsigned long long);
     const size_t inj = (size_t)N * T * sizeof(float);
     return (bits > inj ? bits : inj) + 512;
@@ -403,16 +327,12 @@ int bh_k_crf_seq(const void* scores, int N, int T, int state_len, int layout_5s,
                  const void* targets, int target_bytes, int Lmax, const int* lens, void* workspace, float* out, int* align,
                  int mode, hipStream_t stream) {
     using namespace bh;
-    BH_REQUIRE(state_len >= 1 && state_len <= 5, "crf_seq: state_len must be in 1..5 (got %d)", state_len);
-    BH_REQUIRE(N > 0 && T > 0, "crf_seq: empty problem N=%d T=%d", N, T);
-    BH_REQUIRE(layout_5s == 0 || layout_5s == 1, "crf_seq: layout_5s must be 0 or 1 (got %d)", layout_5s);
-    BH_REQUIRE(target_bytes == 1 || target_bytes == 4, "crf_seq: targets must be int8 or int32 (target_bytes %d)", target_bytes);
-    BH_REQUIRE(Lmax >= (mode == 2 ? 0 : state_len), "crf_seq: rows of %d labels are shorter than state_len %d", Lmax, state_len);
+    if (int rc = chain_check("crf_seq", state_len, N, T, layout_5s, target_bytes, Lmax, mode == 2 ? 0 : state_len)) return rc;
     BH_REQUIRE(mode != 2 || !layout_5s, "crf_seq: the free-start sum is defined on the koi layout only");
-    int threads, P;
-    seq_geometry(Lmax, state_len, &threads, &P);
-    BH_REQUIRE(P != 0, "crf_seq: Lmax + 1 - state_len = %d positions exceed the supported 4096", Lmax + 1 - state_len);
-    SeqArgs a{(const half_t*)scores, N, T, state_len, layout_5s, blank, s_n, s_t, targets, target_bytes, Lmax, lens,
+    int row;
+    if (int rc = chain_instance_check("crf_seq", Lmax, state_len, &row)) return rc;
+    const int threads = kSeqGeometry[row].threads, P = kSeqGeometry[row].per;
+    SeqArgs a{{(const half_t*)scores, N, T, state_len, layout_5s, blank, s_n, s_t, targets, target_bytes, Lmax, lens},
               (unsigned long long*)workspace, nullptr, out, align};
     if (mode == 2) {
         int total = 0;
@@ -423,16 +343,9 @@ int bh_k_crf_seq(const void* scores, int N, int T, int state_len, int layout_5s,
         BH_CHECK_HIP(hipGetLastError());
         a.inject = (const float*)workspace;
     }
-    const bool multi = threads > 64, vit = mode == 1;
+    const bool vit = mode == 1;
     const size_t lds = 2 * threads * sizeof(float) + (vit ? (size_t)STB * (threads / 64) * P * 8 + STB * 4 + 16 : 0);
-#define BH_SEQ(PP, MULTI)                                                                                                  \
-    if (P == PP && multi == MULTI) {                                                                                       \
-        if (vit) hipLaunchKernelGGL((seq_scan_kernel<PP, MULTI, true>), dim3(N), dim3(threads), lds, stream, a);          \
-        else hipLaunchKernelGGL((seq_scan_kernel<PP, MULTI, false>), dim3(N), dim3(threads), lds, stream, a);             \
-    }
-    BH_SEQ(1, false) BH_SEQ(2, false) BH_SEQ(4, false) BH_SEQ(8, false)
-    BH_SEQ(4, true) BH_SEQ(8, true) BH_SEQ(16, true)
-#undef BH_SEQ
+    hipLaunchKernelGGL(vit ? kSeqKernels[row].max : kSeqKernels[row].log, dim3(N), dim3(threads), lds, stream, a);
     BH_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -440,9 +353,7 @@ int bh_k_crf_seq(const void* scores, int N, int T, int state_len, int layout_5s,
 int bh_k_crf_logz_dense(const void* scores, int N, int T, int state_len, int layout_5s, float blank, long s_n, long s_t,
                         float* out, hipStream_t stream) {
     using namespace bh;
-    BH_REQUIRE(state_len >= 1 && state_len <= 5, "crf_logz_dense: state_len must be in 1..5 (got %d)", state_len);
-    BH_REQUIRE(N > 0 && T > 0, "crf_logz_dense: empty problem N=%d T=%d", N, T);
-    BH_REQUIRE(layout_5s == 0 || layout_5s == 1, "crf_logz_dense: layout_5s must be 0 or 1 (got %d)", layout_5s);
+    if (int rc = dense_check("crf_logz_dense", state_len, N, T, layout_5s)) return rc;
     const int S = 1 << (2 * state_len);
     DenseArgs a{(const half_t*)scores, N, T, S, layout_5s, blank, s_n, s_t, out};
     hipLaunchKernelGGL(crf_dense_logz_kernel, dim3(N), dim3(S < 64 ? 64 : S), (size_t)2 * S * sizeof(float), stream, a);

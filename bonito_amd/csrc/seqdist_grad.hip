@@ -9,9 +9,9 @@
 //     p_move[t][j] = exp(alpha_t[j-1] + move_t[j] + beta_{t+1}[j] - logz)
 //     grad[n][t][c] (+)= weight[n] * (sum of p over the edges whose gathered score element is c).
 //   In the koi layout the stay edge is the scalar blank_score: it has no element and gets no gradient.
-//   One workgroup per chunk, one launch, the geometry of seq_scan_kernel. The forward pass is that kernel's Log scan, operation for
-//   operation (logz is bit-identical to bh_crf_seq_logz), and stores every alpha_t to the workspace; each thread later reads back only
-//   what it wrote itself. The backward pass keeps beta in registers as the forward keeps alpha; thread `tid` scores the stay edge of its
+//   One workgroup per chunk, one launch, the geometry of seq_scan_kernel. The forward pass is that kernel's Log scan - both are written
+//   in the chain pieces of seq_chain.h, so logz is bit-identical to bh_crf_seq_logz by construction - and stores every alpha_t to the
+//   workspace; each thread later reads back only what it wrote itself. The backward pass keeps beta in registers as the forward keeps alpha; thread `tid` scores the stay edge of its
 //   positions and the move edge that LEAVES each of them, so the one value that crosses threads is move_t[j0] + beta_{t+1}[j0] of the
 //   right neighbour's first position - by wave shift in the one-wave form, through LDS in the four-wave form.
 //   REPEATED K-MERS. Several positions can gather the same score element at the same step (a homopolymer is the extreme case). A path takes
@@ -27,7 +27,7 @@
 //   accumulate = 0: every element of the chunk's T rows is written exactly once (the elements no edge gathers get zeros).
 //
 // Dense gradient (bh_crf_logz_dense_grad): the posteriors of CTC_CRF.logZ, the mirror of crf_dense_logz_kernel. One thread per state;
-//   the forward stores alpha [T][S] in fp32, the backward keeps beta[s] in the register of thread s and passes the four
+//   the forward (the dense pieces of seq_chain.h, as in that kernel) stores alpha [T][S] in fp32, the backward keeps beta[s] in the register of thread s and passes the four
 //   move_t[s'][r] + beta_{t+1}[s'] terms to the predecessor states through a double-buffered LDS table. Thread s' writes the 5 (4 in the
 //   koi layout) elements of its state: every element of the chunk's rows exactly once, deterministic by construction.
 //     grad[n][t][5s'+0]   = weight[n] * exp(alpha_t[s'] + stay_t[s'] + beta_{t+1}[s'] - logZ)
@@ -36,22 +36,17 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "seq_chain.h"
 
 namespace bh {
-namespace {
+namespace {                                  // (file-local: args, kernels and their table)
 
 constexpr int GU = 4;                        // prefetch depth (time steps), both directions (2 at 16 positions per thread: registers)
 constexpr float FIX_ONE = 1073741824.0f;     // 2^30: fixed-point scale of the per-step posterior accumulator
 constexpr int NO_OWNER = 0x7fffffff;
 
 struct SeqGradArgs {
-    const half_t* scores;
-    int N, T, k, five;
-    float blank;
-    long s_n, s_t;
-    const void* targets;         // [N][Lmax] int8 or int32
-    int tbytes, Lmax;
-    const int* lens;             // [N]
+    ChainArgs c;
     const float* weight;         // [N] or null (= 1)
     float* alpha;                // [N][T][apitch]
     int apitch, C;
@@ -61,36 +56,14 @@ struct SeqGradArgs {
     int g32, accumulate;
 };
 
-__device__ __forceinline__ float lse2(float a, float b) {                   // (the expression of seqdist.hip)
-    const float m = fmaxf(a, b), d = fminf(a, b) - m;
-    return m == -INFINITY ? m : m + __logf(1.0f + __expf(d));
-}
-
-__device__ __forceinline__ int target0(const SeqGradArgs& p, int n, int i) {   // targets0[i]; 0 beyond the row
-    if (i >= p.Lmax) return 0;
-    const long at = (long)n * p.Lmax + i;
-    int v = p.tbytes == 1 ? (int)((const int8_t*)p.targets)[at] : ((const int*)p.targets)[at];
-    v -= 1;
-    return v < 0 ? 0 : (v > 3 ? 3 : v);
-}
-
-__device__ __forceinline__ void grad_put(void* g, long at, float v, bool g32, bool add) {
-    if (g32) {
-        float* q = (float*)g + at;
-        *q = add ? *q + v : v;
-    } else {
-        half_t* q = (half_t*)g + at;
-        *q = (half_t)(add ? (float)*q + v : v);
-    }
-}
-
 template <int P, bool MULTI>
 __global__ __launch_bounds__(256) void seq_grad_kernel(SeqGradArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int n = blockIdx.x, tid = threadIdx.x, NT = blockDim.x, C = p.C;
-    const int len = p.lens[n];
-    const int npos = len + 1 - p.k;
-    if (len > p.Lmax || npos <= 0) {                                        // argument error on the device: NaN and no gradient
+    const ChainArgs& ch = p.c;
+    const int n = blockIdx.x, tid = threadIdx.x, NT = blockDim.x, C = p.C, T = ch.T;
+    const int len = ch.lens[n];
+    const int npos = len + 1 - ch.k;
+    if (len > ch.Lmax || npos <= 0) {                                        // argument error on the device: NaN and no gradient
         if (tid == 0) p.out[n] = __builtin_nanf("");
         return;
     }
@@ -105,12 +78,9 @@ __global__ __launch_bounds__(256) void seq_grad_kernel(SeqGradArgs p) {
     int so[P], mo[P + 1];
 #pragma unroll
     for (int i = 0; i <= P; ++i) {
-        const int j = tid * P + i;
-        int kmer = 0;
-        for (int d = 0; d < p.k; ++d) kmer = kmer * 4 + target0(p, n, j + d);
-        const int b = j > 0 ? target0(p, n, j - 1) : 0;
-        if (i < P) so[i] = 5 * kmer;
-        mo[i] = p.five ? 5 * kmer + 1 + b : 4 * kmer + b;
+        int s;
+        chain_offsets(ch, n, tid * P + i, s, mo[i]);
+        if (i < P) so[i] = s;
     }
 
     // ---- owner table: edge 2j = stay of position j (5S layout), edge 2j + 1 = move j -> j + 1; only edges of the chain's n positions ----
@@ -119,7 +89,7 @@ __global__ __launch_bounds__(256) void seq_grad_kernel(SeqGradArgs p) {
 #pragma unroll
     for (int i = 0; i < P; ++i) {
         const int j = tid * P + i;
-        if (p.five && j < npos) atomicMin(&own[so[i]], 2 * j);
+        if (ch.five && j < npos) atomicMin(&own[so[i]], 2 * j);
         if (j + 1 < npos) atomicMin(&own[mo[i + 1]], 2 * j + 1);
     }
     __syncthreads();
@@ -127,11 +97,11 @@ __global__ __launch_bounds__(256) void seq_grad_kernel(SeqGradArgs p) {
 #pragma unroll
     for (int i = 0; i < P; ++i) {
         const int j = tid * P + i;
-        if (p.five && j < npos && own[so[i]] == 2 * j) own_s |= 1u << i;
+        if (ch.five && j < npos && own[so[i]] == 2 * j) own_s |= 1u << i;
         if (j + 1 < npos && own[mo[i + 1]] == 2 * j + 1) own_m |= 1u << i;
     }
 
-    const half_t* sc = p.scores + (long)n * p.s_n;
+    const half_t* sc = ch.scores + (long)n * ch.s_n;
     constexpr int U = P >= 16 ? 2 : GU;
     float sv[U][P], mv[U][P];
     float a[P];
@@ -139,48 +109,27 @@ __global__ __launch_bounds__(256) void seq_grad_kernel(SeqGradArgs p) {
     for (int i = 0; i < P; ++i) a[i] = -INFINITY;
     if (tid == 0) a[0] = 0.0f;
     const bool stores = tid * P < p.apitch;                                 // apitch is a multiple of P
-    float* aw = p.alpha + ((long)n * p.T) * p.apitch + tid * P;
+    float* aw = p.alpha + ((long)n * T) * p.apitch + tid * P;
     int cb = 0;
-    const bool fits = npos - 1 <= p.T;                                      // uniform
+    const bool fits = npos - 1 <= T;                                        // uniform
 
     // ---- forward: the Log scan of seq_scan_kernel; alpha_t (before step t) goes to the workspace ----
     if (fits) {
-        auto load = [&](int slot, int t) {
-            const int tt = min(t, p.T - 1);                                 // (rows beyond the end are never used)
-            const half_t* row = sc + (long)tt * p.s_t;
-#pragma unroll
-            for (int i = 0; i < P; ++i) {
-                sv[slot][i] = p.five ? (float)row[so[i]] : p.blank;
-                mv[slot][i] = (float)row[mo[i]];
-            }
+        auto load = [&](int slot, int t) {                                  // (rows beyond the end are never used)
+            chain_load(ch, sc + (long)min(t, T - 1) * ch.s_t, so, mo, sv[slot], mv[slot]);
         };
 #pragma unroll
         for (int u = 0; u < U; ++u) load(u, u);
-        for (int t0 = 0; t0 < p.T; t0 += U) {
+        for (int t0 = 0; t0 < T; t0 += U) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int t = t0 + u;
-                if (t < p.T) {                                              // uniform across the workgroup
+                if (t < T) {                                                // uniform across the workgroup
                     if (stores) {
 #pragma unroll
                         for (int i = 0; i < P; ++i) aw[(long)t * p.apitch + i] = a[i];
                     }
-                    float prev;
-                    if constexpr (MULTI) {
-                        edge[cb * NT + tid] = a[P - 1];
-                        __syncthreads();
-                        prev = tid ? edge[cb * NT + tid - 1] : -INFINITY;
-                        cb ^= 1;
-                    } else {
-                        prev = __shfl_up(a[P - 1], 1);
-                        if (tid == 0) prev = -INFINITY;
-                    }
-#pragma unroll
-                    for (int i = P - 1; i >= 0; --i) {                      // descending: position i reads the OLD alpha of i - 1
-                        const float in = (i ? a[i - 1] : prev) + mv[u][i];
-                        const float st = a[i] + sv[u][i];
-                        a[i] = lse2(st, in);
-                    }
+                    chain_log_step(a, chain_from_left<MULTI>(a[P - 1], edge, cb, tid, NT), sv[u], mv[u]);
                     load(u, t + U);
                 }
             }
@@ -203,14 +152,14 @@ __global__ __launch_bounds__(256) void seq_grad_kernel(SeqGradArgs p) {
 
     if (!(logz > -INFINITY)) {                                              // no alignment: the gradient is defined as zero
         if (!add)
-            for (int t = 0; t < p.T; ++t)
+            for (int t = 0; t < T; ++t)
                 for (int c = tid; c < C; c += NT) grad_put(p.grad, gbase + (long)t * p.g_t + c, 0.0f, g32, false);
         return;
     }
     if (!add) {                                                             // the elements no edge gathers: zeros, each written once
         for (int c = tid; c < C; c += NT)
             if (own[c] == NO_OWNER)
-                for (int t = 0; t < p.T; ++t) grad_put(p.grad, gbase + (long)t * p.g_t + c, 0.0f, g32, false);
+                for (int t = 0; t < T; ++t) grad_put(p.grad, gbase + (long)t * p.g_t + c, 0.0f, g32, false);
     }
     const float w = (p.weight ? p.weight[n] : 1.0f) * (1.0f / FIX_ONE);
 
@@ -218,13 +167,9 @@ __global__ __launch_bounds__(256) void seq_grad_kernel(SeqGradArgs p) {
     float av[U][P];
     auto loadb = [&](int slot, int t) {
         const int tt = max(t, 0);
-        const half_t* row = sc + (long)tt * p.s_t;
+        chain_load(ch, sc + (long)tt * ch.s_t, so, mo, sv[slot], mv[slot]);
 #pragma unroll
-        for (int i = 0; i < P; ++i) {
-            sv[slot][i] = p.five ? (float)row[so[i]] : p.blank;
-            mv[slot][i] = (float)row[mo[i]];
-            av[slot][i] = stores ? aw[(long)tt * p.apitch + i] : -INFINITY;
-        }
+        for (int i = 0; i < P; ++i) av[slot][i] = stores ? aw[(long)tt * p.apitch + i] : -INFINITY;
     };
     auto flush = [&](int t, int buf) {                                      // the owners of step t's elements: read, clear, one write each
         unsigned* ac = acc + buf * C;
@@ -247,33 +192,24 @@ __global__ __launch_bounds__(256) void seq_grad_kernel(SeqGradArgs p) {
 #pragma unroll
     for (int i = 0; i < P; ++i) b[i] = (tid * P + i == npos - 1) ? 0.0f : -INFINITY;
 #pragma unroll
-    for (int u = 0; u < U; ++u) loadb(u, p.T - 1 - u);
+    for (int u = 0; u < U; ++u) loadb(u, T - 1 - u);
     int buf = 0;
-    for (int t0 = p.T - 1; t0 >= 0; t0 -= U) {
+    for (int t0 = T - 1; t0 >= 0; t0 -= U) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int t = t0 - u;
             if (t >= 0) {                                                   // uniform across the workgroup
                 const float x = mv[u][0] + b[0];                            // move_t[j0] + beta_{t+1}[j0] for the left neighbour
-                float nxt;
-                if constexpr (MULTI) {
-                    edge[cb * NT + tid] = x;
-                    __syncthreads();
-                    nxt = tid + 1 < NT ? edge[cb * NT + tid + 1] : -INFINITY;
-                    cb ^= 1;
-                } else {
-                    __syncthreads();                                        // (one wave: orders the accumulator, costs no wait on others)
-                    nxt = __shfl_down(x, 1);
-                    if (tid == NT - 1) nxt = -INFINITY;
-                }
-                if (t < p.T - 1) flush(t + 1, buf ^ 1);
+                if constexpr (!MULTI) __syncthreads();                      // (one wave: orders the accumulator, costs no wait on others)
+                const float nxt = chain_from_right<MULTI>(x, edge, cb, tid, NT);
+                if (t < T - 1) flush(t + 1, buf ^ 1);
                 unsigned* ac = acc + buf * C;
 #pragma unroll
                 for (int i = 0; i < P; ++i) {                               // ascending: position i reads the OLD beta of i + 1
                     const float in = i + 1 < P ? mv[u][i + 1] + b[i + 1] : nxt;
                     const float st = sv[u][i] + b[i];
                     const float base = av[u][i] - logz;
-                    if (p.five) {
+                    if (ch.five) {
                         const unsigned q = (unsigned)(__expf(base + st) * FIX_ONE + 0.5f);
                         if (q) atomicAdd(&ac[so[i]], q);
                     }
@@ -317,12 +253,7 @@ __global__ __launch_bounds__(1024) void crf_dense_grad_kernel(DenseGradArgs p) {
     if (active) al[j] = 0.0f;
     __syncthreads();
     float ring[GU][5];
-    auto load = [&](int slot, int t) {
-        const half_t* row = sc + (long)max(0, min(t, p.T - 1)) * p.s_t;
-        ring[slot][0] = p.five ? (float)row[0] : p.blank;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ring[slot][1 + r] = (float)row[(p.five ? 1 : 0) + r];
-    };
+    auto load = [&](int slot, int t) { dense_load(p, sc + (long)max(0, min(t, p.T - 1)) * p.s_t, ring[slot]); };
     // ---- forward: crf_dense_logz_kernel, alpha_t (before step t) kept ----
     int cb = 0;
 #pragma unroll
@@ -334,18 +265,7 @@ __global__ __launch_bounds__(1024) void crf_dense_grad_kernel(DenseGradArgs p) {
                 const float* a = al + cb * S;
                 if (active) {
                     aw[(long)(t0 + v) * S + j] = a[j];
-                    float c[5];
-                    c[0] = a[j] + ring[v][0];
-                    float m = c[0];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        c[1 + r] = a[r * q + (j >> 2)] + ring[v][1 + r];
-                        m = fmaxf(m, c[1 + r]);
-                    }
-                    float sum = 0.0f;
-#pragma unroll
-                    for (int e = 0; e < 5; ++e) sum += __expf(c[e] - m);
-                    al[(cb ^ 1) * S + j] = m + __logf(sum);
+                    al[(cb ^ 1) * S + j] = dense_step(a, j, q, ring[v]);
                 }
                 cb ^= 1;
                 __syncthreads();
@@ -354,12 +274,7 @@ __global__ __launch_bounds__(1024) void crf_dense_grad_kernel(DenseGradArgs p) {
         }
     }
     if (j == 0) {
-        const float* a = al + cb * S;
-        float m = a[0];
-        for (int i = 1; i < S; ++i) m = fmaxf(m, a[i]);
-        float sum = 0.0f;
-        for (int i = 0; i < S; ++i) sum += __expf(a[i] - m);
-        const float r = m + __logf(sum);
+        const float r = dense_final(al + cb * S, S);
         p.out[n] = r;
         s_logz[0] = r;
     }
@@ -408,16 +323,9 @@ __global__ __launch_bounds__(1024) void crf_dense_grad_kernel(DenseGradArgs p) {
                 if (active) {                                               // state j's successors (j % q) 4 + b hold j as predecessor r = j / q
                     float c[5];
                     c[0] = ring[v][0] + beta;
-                    float m = c[0];
 #pragma unroll
-                    for (int bb = 0; bb < 4; ++bb) {
-                        c[1 + bb] = x[4 * ((j % q) * 4 + bb) + j / q];
-                        m = fmaxf(m, c[1 + bb]);
-                    }
-                    float sum = 0.0f;
-#pragma unroll
-                    for (int e = 0; e < 5; ++e) sum += __expf(c[e] - m);
-                    beta = m + __logf(sum);
+                    for (int bb = 0; bb < 4; ++bb) c[1 + bb] = x[4 * ((j % q) * 4 + bb) + j / q];
+                    beta = lse_n(c);
                 }
                 cb ^= 1;
                 loadb(v, t - GU);
@@ -426,15 +334,11 @@ __global__ __launch_bounds__(1024) void crf_dense_grad_kernel(DenseGradArgs p) {
     }
 }
 
-// geometry of the chain kernels (the table of seqdist.hip): threads per chunk and positions per thread (0 = out of range)
-void seq_geometry(int Lmax, int k, int* threads, int* per) {
-    int pm = Lmax + 1 - k;
-    if (pm < 1) pm = 1;
-    *threads = pm <= 512 ? 64 : 256;
-    *per = 0;
-    if (pm <= 512) { for (int P = 1; P <= 8; P *= 2) if (pm <= 64 * P) { *per = P; break; } }
-    else { for (int P = 4; P <= 16; P *= 2) if (pm <= 256 * P) { *per = P; break; } }
-}
+// the gradient kernels of the instance list, in its order
+typedef void (*SeqGradKernel)(SeqGradArgs);
+#define BH_SEQ_GRAD_ROW(NT, P, MULTI) seq_grad_kernel<P, MULTI>,
+const SeqGradKernel kSeqGradKernels[] = {BH_SEQ_INSTANCES(BH_SEQ_GRAD_ROW)};
+#undef BH_SEQ_GRAD_ROW
 
 int alpha_pitch(int Lmax, int k, int P) {                                   // positions kept per step: the chain, rounded up to whole threads
     int pm = Lmax + 1 - k;
@@ -447,35 +351,25 @@ int alpha_pitch(int Lmax, int k, int P) {                                   // p
 
 size_t bh_k_crf_seq_grad_workspace(int N, int T, int Lmax, int state_len) {
     if (N <= 0 || T <= 0 || Lmax < 0 || state_len < 1 || state_len > 5) return 0;
-    int threads, per;
-    bh::seq_geometry(Lmax, state_len, &threads, &per);
-    if (per == 0) return 0;
-    return (size_t)N * T * bh::alpha_pitch(Lmax, state_len, per) * sizeof(float) + 512;
+    const int row = bh::chain_instance(Lmax, state_len);
+    if (row < 0) return 0;
+    return (size_t)N * T * bh::alpha_pitch(Lmax, state_len, bh::kSeqGeometry[row].per) * sizeof(float) + 512;
 }
 
 int bh_k_crf_seq_grad(const void* scores, int N, int T, int state_len, int layout_5s, float blank, long s_n, long s_t,
                       const void* targets, int target_bytes, int Lmax, const int* lens, const float* weight, void* workspace,
                       float* out, void* grad, long g_n, long g_t, int grad_fp32, int accumulate, hipStream_t stream) {
     using namespace bh;
-    BH_REQUIRE(state_len >= 1 && state_len <= 5, "crf_seq_grad: state_len must be in 1..5 (got %d)", state_len);
-    BH_REQUIRE(N > 0 && T > 0, "crf_seq_grad: empty problem N=%d T=%d", N, T);
-    BH_REQUIRE(layout_5s == 0 || layout_5s == 1, "crf_seq_grad: layout_5s must be 0 or 1 (got %d)", layout_5s);
-    BH_REQUIRE(target_bytes == 1 || target_bytes == 4, "crf_seq_grad: targets must be int8 or int32 (target_bytes %d)", target_bytes);
-    BH_REQUIRE(Lmax >= state_len, "crf_seq_grad: rows of %d labels are shorter than state_len %d", Lmax, state_len);
+    if (int rc = chain_check("crf_seq_grad", state_len, N, T, layout_5s, target_bytes, Lmax, state_len)) return rc;
     BH_REQUIRE((grad_fp32 == 0 || grad_fp32 == 1) && (accumulate == 0 || accumulate == 1), "crf_seq_grad: flags must be 0 or 1");
-    int threads, P;
-    seq_geometry(Lmax, state_len, &threads, &P);
-    BH_REQUIRE(P != 0, "crf_seq_grad: Lmax + 1 - state_len = %d positions exceed the supported 4096", Lmax + 1 - state_len);
+    int row;
+    if (int rc = chain_instance_check("crf_seq_grad", Lmax, state_len, &row)) return rc;
+    const int threads = kSeqGeometry[row].threads, P = kSeqGeometry[row].per;
     const int C = (layout_5s ? 5 : 4) << (2 * state_len);
-    SeqGradArgs a{(const half_t*)scores, N, T, state_len, layout_5s, blank, s_n, s_t, targets, target_bytes, Lmax, lens, weight,
+    SeqGradArgs a{{(const half_t*)scores, N, T, state_len, layout_5s, blank, s_n, s_t, targets, target_bytes, Lmax, lens}, weight,
                   (float*)workspace, alpha_pitch(Lmax, state_len, P), C, out, grad, g_n, g_t, grad_fp32, accumulate};
-    const bool multi = threads > 64;
     const size_t lds = (2 * threads + 4) * sizeof(float) + (size_t)3 * C * sizeof(int);
-#define BH_SEQ_GRAD(PP, MULTI)                                                                                             \
-    if (P == PP && multi == MULTI) hipLaunchKernelGGL((seq_grad_kernel<PP, MULTI>), dim3(N), dim3(threads), lds, stream, a);
-    BH_SEQ_GRAD(1, false) BH_SEQ_GRAD(2, false) BH_SEQ_GRAD(4, false) BH_SEQ_GRAD(8, false)
-    BH_SEQ_GRAD(4, true) BH_SEQ_GRAD(8, true) BH_SEQ_GRAD(16, true)
-#undef BH_SEQ_GRAD
+    hipLaunchKernelGGL(kSeqGradKernels[row], dim3(N), dim3(threads), lds, stream, a);
     BH_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -489,9 +383,7 @@ int bh_k_crf_logz_dense_grad(const void* scores, int N, int T, int state_len, in
                              const float* weight, void* workspace, float* out, void* grad, long g_n, long g_t, int grad_fp32,
                              hipStream_t stream) {
     using namespace bh;
-    BH_REQUIRE(state_len >= 1 && state_len <= 5, "crf_logz_dense_grad: state_len must be in 1..5 (got %d)", state_len);
-    BH_REQUIRE(N > 0 && T > 0, "crf_logz_dense_grad: empty problem N=%d T=%d", N, T);
-    BH_REQUIRE(layout_5s == 0 || layout_5s == 1, "crf_logz_dense_grad: layout_5s must be 0 or 1 (got %d)", layout_5s);
+    if (int rc = dense_check("crf_logz_dense_grad", state_len, N, T, layout_5s)) return rc;
     BH_REQUIRE(grad_fp32 == 0 || grad_fp32 == 1, "crf_logz_dense_grad: grad_fp32 must be 0 or 1 (got %d)", grad_fp32);
     const int S = 1 << (2 * state_len);
     DenseGradArgs a{(const half_t*)scores, N, T, S, layout_5s, blank, s_n, s_t, weight, (float*)workspace, out, grad, g_n, g_t,

@@ -95,6 +95,36 @@ def test_fixture_log_scan_loss_and_alignments(name):
         assert nrm.shape == x.shape and float(decode.logz_any(nrm, sl).abs().max()) < 0.5
 
 
+def _eighths_case(npos, five):
+    """Two chunks at state_len 1 whose rows hold `npos` labels, T = npos + 67 (the traceback crosses an LDS block of 64 steps even at
+    npos = 1): row 0 a homopolymer of length npos, row 1 random labels of length max(1, npos - 2), so that its end position is not a
+    thread's last slot. Scores are multiples of 1/8 in [-4, 4]: every partial sum of a path is exact in fp32."""
+    rng = np.random.default_rng(7000 + npos)
+    N, T = 2, npos + 67
+    raw = (rng.integers(-32, 33, size=(T, N, 20) if five else (N, T, 16)) / 8).astype(np.float16)
+    lengths = np.array([npos, max(1, npos - 2)], np.int32)
+    targets = rng.integers(1, 5, size=(N, npos)).astype(np.int8)
+    targets[0] = 3
+    targets[1, lengths[1]:] = 0
+    return raw, (raw.transpose(1, 0, 2) if five else raw), targets, lengths
+
+
+@pytest.mark.parametrize("five", [False, True])
+@pytest.mark.parametrize("npos", [1, 64, 65, 128, 129, 256, 257, 512, 513, 1024, 1025, 2048, 2049, 4096])
+def test_max_scan_geometry_every_positions_per_thread(npos, five):
+    """Every (threads, positions per thread) instance of the Max scan, at both edges of its range: a call picks its instance by Lmax, so
+    the fixtures (small) and the workload size (Lmax 833) reach two of the seven. On multiples of 1/8 the fp32 scan is exact, so the
+    kernel returns the alignment and the score of the fp64 restatement, ties included: equality, no tolerance."""
+    blank = None if five else 2.0
+    raw, ntc, targets, lengths = _eighths_case(npos, five)
+    ra, rb = sr.max_scan(ntc, targets, lengths, 1, five, blank)
+    assert (ra[:, -1] == lengths - 1).all() and np.isfinite(rb).all()
+    align, best = decode.seq_viterbi(torch.from_numpy(raw).cuda(), torch.from_numpy(targets), torch.from_numpy(lengths), 1, blank)
+    print("npos %d %s: best %s, %d cells of the alignment differ" % (npos, "5S" if five else "koi", best.numpy(), int((align.numpy() != ra).sum())))
+    assert (align.numpy() == ra).all()
+    assert (best.numpy().astype(np.float64) == rb).all()
+
+
 def _strided(N, T, C, time_major, gen_seed, pad=8, offset=24):
     """Seeded scores in a padded, offset buffer: the view handed to the kernels is neither contiguous nor at the start of its buffer."""
     g = torch.Generator(device="cuda").manual_seed(gen_seed)
