@@ -84,6 +84,9 @@ SIGNATURES = {
     "bh_map_sketch": (_i, [_vp, _l, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _l, _vp, _vp]),
     "bh_map_seed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _l, _vp, _vp, _vp, _l, _vp, _vp, _i, _i, _vp, _vp, _vp, _l, _vp]),
     "bh_map_chain": (_i, [_vp, _vp, _vp, _i, _l, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "bh_map_extend_max": (_i, []),
+    "bh_map_extend_band": (_i, []),
+    "bh_map_extend": (_i, [_vp, _l, _vp, _i, _vp, _l, _vp, _i, _vp, _vp, _i, _vp]),
     "bh_set_option": (_i, [C.c_char_p, _i]),
     "bh_signal_normalise": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                             _i, _vp, _vp, _vp, _vp, _vp]),

@@ -5,7 +5,9 @@ Read mapping on the device: the engine's counterpart of ``mappy.Aligner`` and ``
 The mapper is DEFINED by the restatement tests/mapper_ref.py ("Mapper") and equals it bit for bit; it is not
 minimap2: seeds, chain scores, mapq, tie-breaks and the missing drop-off extension at the ends all differ. Kernels: csrc/mapper.hip
 (``bh_map_sketch``, ``bh_map_seed``, ``bh_map_chain``) and csrc/nw.hip through ``align.nw_align`` for the bases; sorting and prefix
-sums are torch's. Spans and pieces are numpy on the host; CIGAR merge, NM and MD are one host library call per read. There is no host fallback for the device steps.
+sums are torch's. With ``extend_ends`` the alignment is carried beyond the outermost anchors by ``bh_map_extend`` (a banded
+extension without drop-off, defined by tests/mapper_ext_ref.py); off by default, and then nothing changes. Spans and pieces are
+numpy on the host; CIGAR merge, NM and MD are one host library call per read. There is no host fallback for the device steps.
 """
 import ctypes as C
 import gzip
@@ -21,6 +23,7 @@ PIECE = 16384                                    # query bases per nw_align piec
 MAX_READS = 1024                                 # reads per seed / chain call (the read index has 10 bits in an anchor word)
 MAX_READ_LEN = (1 << 21) - 1
 QBITS, RBITS = 21, 31
+EXT_MAX, EXT_BAND = 512, 32                      # end extension: query bases per tail at most, the band's half-width
 _LUT = np.full(256, 5, np.int8)                  # 1..4 = A C G T, 5 = any other byte
 _LUT[np.frombuffer(b"ACGT", np.uint8)] = (1, 2, 3, 4)
 _COMP = np.array([0, 4, 3, 2, 1, 5], np.int8)
@@ -113,7 +116,8 @@ class Aligner:
     """``Aligner(reference.fasta)``: reads the contigs, sketches them on the device and keeps the sorted minimizer index and the
     reference codes resident there. ``map_batch(sequences)`` -> a ``Mapping`` or None per sequence."""
 
-    def __init__(self, reference_path, k=15, w=10, max_occ=64, device="cuda", max_dist=5000, bandwidth=500, min_cnt=3, min_score=40):
+    def __init__(self, reference_path, k=15, w=10, max_occ=64, device="cuda", max_dist=5000, bandwidth=500, min_cnt=3, min_score=40,
+                 extend_ends=False):
         if isinstance(reference_path, (list, tuple)):                                # contigs given directly: [(name, sequence)]
             contigs = [(str(n), str(s).upper()) for n, s in reference_path]
         elif str(reference_path).endswith(".mmi"):
@@ -125,7 +129,8 @@ class Aligner:
             raise ValueError("w must be in 1..64")
         self.k, self.w, self.max_occ, self.device = int(k), int(w), int(max_occ), device
         self.max_dist, self.bandwidth, self.min_cnt, self.min_score = int(max_dist), int(bandwidth), int(min_cnt), int(min_score)
-        self.timings = dict(sketch_seed=0.0, chain=0.0, base=0.0, host=0.0)      # seconds, summed over map_batch calls
+        self.extend_ends = bool(extend_ends)
+        self.timings = dict(sketch_seed=0.0, chain=0.0, base=0.0, host=0.0, extend=0.0)      # seconds, summed over map_batch calls
         self.set_contigs(contigs if isinstance(reference_path, (list, tuple)) else read_fasta(reference_path))
 
     def set_contigs(self, contigs):
@@ -225,8 +230,9 @@ class Aligner:
                    "bh_map_chain")
         return off, contig, f, p, chain, result
 
-    def anchors_of(self, sequences):
-        """Sketch and seed a batch of at most MAX_READS reads -> (sorted anchor words on the device, list of code arrays)"""
+    def anchors_of(self, sequences, keep_plane=False):
+        """Sketch and seed a batch of at most MAX_READS reads -> (sorted anchor words on the device, list of code arrays); with
+        keep_plane the uploaded read plane stays in ``self._plane`` (codes, lengths; both on the device) for ``extend``"""
         n = len(sequences)
         codes = [encode(s) for s in sequences]
         lens = np.array([len(c) for c in codes], np.int32)
@@ -237,19 +243,43 @@ class Aligner:
             plane[i, :len(c)] = c
         dev_plane = torch.from_numpy(plane).to(self.device)
         qkeys, qpos, qstrand, qoff = self._sketch(dev_plane, plane.shape[1], lens)
+        self._plane = (dev_plane, torch.from_numpy(lens).to(self.device)) if keep_plane else None
         n_min = int(qoff[n])
         if n_min == 0:
             return torch.zeros(0, dtype=torch.int64, device=self.device), codes
         return self._seed(qkeys, qpos, qstrand, qoff, torch.from_numpy(lens).to(self.device), n, n_min), codes
 
+    def extend(self, plane, lens, ends):
+        """The read plane and lengths on the device, numpy int32 ends [n, 6] (read row, strand, side, position on the aligned strand,
+        position in the concatenated reference, the contig's limit on that side) -> (numpy result [n, 4]: score, query bases,
+        reference bases, runs; a list of the run words per end, in read order). One ``bh_map_extend`` launch."""
+        ends = np.ascontiguousarray(ends, np.int32).reshape(-1, 6)
+        n = len(ends)
+        if n == 0:
+            return np.zeros((0, 4), np.int32), []
+        cap = 2 * EXT_MAX + EXT_BAND
+        dev_ends = torch.from_numpy(ends).to(self.device)
+        result = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+        runs = torch.empty((n, cap), dtype=torch.int32, device=self.device)
+        _lib.check(_lib.lib().bh_map_extend(_lib.ptr(plane), int(plane.shape[1]), _lib.ptr(lens), int(plane.shape[0]), _lib.ptr(self._ref),
+                                            int(self._ref.numel()), _lib.ptr(dev_ends), n, _lib.ptr(result), _lib.ptr(runs), cap,
+                                            _lib.stream_ptr(plane.device)), "bh_map_extend")
+        res = result.cpu().numpy()
+        if (res[:, 3] < 0).any():
+            raise RuntimeError("bh_map_extend: end %d does not fit its read or its contig" % int(np.argmax(res[:, 3] < 0)))
+        width = int(res[:, 3].max())
+        words = runs[:, :max(width, 1)].cpu().numpy().view(np.uint32)
+        return res, [words[i, :res[i, 3]] for i in range(n)]
+
     # ---- the batch ---------------------------------------------------------------------------------------------------------------
 
-    def map_batch(self, sequences):
-        """-> [Mapping or None] in the order given"""
+    def map_batch(self, sequences, extend_ends=None):
+        """-> [Mapping or None] in the order given; extend_ends: None = the constructor's value"""
+        extend = self.extend_ends if extend_ends is None else bool(extend_ends)
         sequences = [s.upper() for s in sequences]
         out = []
         for lo in range(0, len(sequences), MAX_READS):
-            out.extend(self._map_chunk(sequences[lo:lo + MAX_READS]))
+            out.extend(self._map_chunk(sequences[lo:lo + MAX_READS], extend))
         return out
 
     def _tick(self, name, t0):
@@ -258,12 +288,13 @@ class Aligner:
         self.timings[name] += t1 - t0
         return t1
 
-    def _map_chunk(self, sequences):
+    def _map_chunk(self, sequences, extend=False):
         n = len(sequences)
         if n == 0 or not self or not hasattr(self, "_ukeys"):
             return [None] * n
         t = time.perf_counter()
-        anchors, codes = self.anchors_of(sequences)
+        anchors, codes = self.anchors_of(sequences, keep_plane=extend)
+        read_plane, self._plane = self._plane, None
         t = self._tick("sketch_seed", t)
         if anchors.numel() == 0:
             return [None] * n
@@ -305,12 +336,25 @@ class Aligner:
 
         sp, rp = plane(seq_rows), plane(ref_rows)
         t = self._tick("host", t)
+        if extend:                                                                   # both ends of every mapping in one launch
+            ends = np.empty((2 * len(plans), 6), np.int32)
+            for x, (i, ci, strand, q, r, q_st, q_en, r_st, r_en, _first, _np, _mq) in enumerate(plans):
+                s0 = int(self._starts[ci])
+                ends[2 * x] = (i, strand, 0, q_st, s0 + r_st, s0)
+                ends[2 * x + 1] = (i, strand, 1, q_en, s0 + r_en, s0 + len(r))
+            ext, ext_runs = self.extend(read_plane[0], read_plane[1], ends)
+            t = self._tick("extend", t)
         nw = nw_align(sp, rp, cigar=True, device=self.device)
         if (nw.status != 0).any():
             raise RuntimeError("map_batch: a piece did not fit nw_align's workspace budget")
         t = self._tick("base", t)
-        for i, ci, strand, q, r, q_st, q_en, r_st, r_en, first, npieces, mapq in plans:
-            cigar, cigar_str, nm, md, mlen, blen = finish(np.concatenate(nw.runs[first:first + npieces]), q, r, q_st, r_st)
+        for x, (i, ci, strand, q, r, q_st, q_en, r_st, r_en, first, npieces, mapq) in enumerate(plans):
+            runs = list(nw.runs[first:first + npieces])
+            if extend:
+                runs = [ext_runs[2 * x], *runs, ext_runs[2 * x + 1]]
+                q_st, r_st = q_st - int(ext[2 * x, 1]), r_st - int(ext[2 * x, 2])
+                q_en, r_en = q_en + int(ext[2 * x + 1, 1]), r_en + int(ext[2 * x + 1, 2])
+            cigar, cigar_str, nm, md, mlen, blen = finish(np.concatenate(runs), q, r, q_st, r_st)
             if strand:                                                               # on the read as given, like mappy's
                 q_st, q_en = len(q) - q_en, len(q) - q_st
             out[i] = Mapping(ctg=self.seq_names[ci], r_st=r_st, r_en=r_en, q_st=q_st, q_en=q_en, strand=-1 if strand else 1, mapq=mapq,

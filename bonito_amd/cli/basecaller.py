@@ -139,8 +139,29 @@ def launch(args, argv):
     return 0
 
 
+def save_ctc_refusal(args, world=1):
+    """``--save-ctc`` implies ``--extend-ends`` (a label is the reference under the alignment: it must reach the ends of the chunk's
+    call). -> the message with which the options are refused, or None. Checked in front of everything else: no model is loaded."""
+    if not getattr(args, "save_ctc", False):
+        return None
+    args.extend_ends = True
+    if args.fasta or args.fastq:
+        return "> error: --save-ctc writes aligned SAM; --fasta / --fastq cannot be combined with it"
+    if not args.reference:
+        return "> a reference is needed to output ctc training data"               # the reference's words (cli/basecaller.py:82-84)
+    if args.devices or world > 1:
+        return "> error: --save-ctc runs on one device (the training set is shuffled and written by one process); drop --devices"
+    if args.device_ingest:
+        return "> error: --save-ctc cuts the normalised signal into chunks on the host; --device-ingest cannot be combined with it"
+    return None
+
+
 def main(args, argv=None):
     from bonito_amd import parallel
+    refusal = save_ctc_refusal(args, parallel.env_rank_world()[1])
+    if refusal:
+        sys.stderr.write(refusal + "\n")
+        return 1
     # several lanes (narrow models, the 8-bit path) need more hardware queues than the runtime's default of four, or their streams
     # share queues and serialise; must be set before the HIP runtime starts. Measured harmless for the one-lane models.
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
@@ -195,7 +216,7 @@ def main(args, argv=None):
         from bonito_amd.aligner import Aligner
         log("> loading reference\n")
         try:
-            aligner = Aligner(args.reference, device=args.device)           # every rank builds its own index
+            aligner = Aligner(args.reference, device=args.device, extend_ends=getattr(args, "extend_ends", False))   # every rank builds its own index
         except (OSError, ValueError) as exc:
             sys.stderr.write("> error: %s\n" % exc)
             return 1
@@ -218,6 +239,9 @@ def main(args, argv=None):
             return records_fn(mdl, rds, mode, reverse=args.revcomp, rna=args.rna, batchsize=bc["batchsize"],
                               chunksize=bc["chunksize"], overlap=bc["overlap"], lanes=args.lanes, per_call=args.per_call,
                               min_qscore=args.min_qscore, raw=raw_kw)
+        return parallel.format_stream(call_and_map(mdl, rds), mode, args.min_qscore)
+
+    def call_and_map(mdl, rds):
         names = basecall.__code__.co_varnames
         kw = {"lanes": args.lanes} if args.lanes > 1 and "lanes" in names else {}
         results = basecall(mdl, rds, reverse=args.revcomp, rna=args.rna, batchsize=bc["batchsize"],
@@ -226,7 +250,18 @@ def main(args, argv=None):
             # --reference: the Python record path (basecall -> align_map -> format_record); the fused record path has no mapping
             from bonito_amd.aligner import align_map
             results = align_map(aligner, results)
-        return parallel.format_stream(results, mode, args.min_qscore)
+        return results
+
+    if getattr(args, "save_ctc", False):
+        # the reference's flow (cli/basecaller.py:118-127,146-148): every read is cut into chunks that are basecalled, mapped and
+        # filtered as reads of their own; the accepted ones and the reference under their alignments are the training set
+        from bonito_amd.io import CTCWriter, ctc_output_directory
+        from bonito_amd.reader import read_chunks
+        pieces = (piece for read in reads for piece in read_chunks(read, chunksize=bc["chunksize"], overlap=bc["overlap"]))
+        writer = CTCWriter("sam", call_and_map(model, pieces), aligner, fd=out, min_accuracy=args.min_accuracy_save_ctc,
+                           min_qscore=args.min_qscore, rna=args.rna, summary_path=None if args.no_summary else args.summary,
+                           output_directory=args.ctc_output_dir or ctc_output_directory())
+        return _drive(writer, world, [])
 
     records = make_records(model, reads)
     records = _fault_hook(records, rank, world)
@@ -265,6 +300,13 @@ def main(args, argv=None):
             parallel.shutdown()
             return 0
     writer = Writer(mode, records, fd=out, summary_path=None if args.no_summary else args.summary, preformatted=True, aligner=aligner)
+    return _drive(writer, world, lost_ranks, t0)
+
+
+def _drive(writer, world, lost_ranks, t0=None):
+    """Run the writer thread (it pulls the whole pipeline) and report like the reference (cli/basecaller.py:156-164)."""
+    from bonito_amd import parallel
+    t0 = perf_counter() if t0 is None else t0
     writer.start()
     writer.join()
     duration = perf_counter() - t0
@@ -364,6 +406,17 @@ def argparser():
     aligned.add_argument("--reference", default=None,
                         help="FASTA (plain or .gz): map every call with the device mapper and write aligned SAM (the default mode "
                              "becomes SAM) plus the alignment columns of the summary")
+    parser.add_argument("--extend-ends", action="store_true", default=False,
+                        help="with --reference: carry every alignment beyond its outermost anchors (a banded extension of up to 512 "
+                             "bases at either end) instead of leaving the ends soft-clipped")
+    parser.add_argument("--save-ctc", action="store_true", default=False,
+                        help="with --reference: cut the reads into chunks, basecall and map them, and write the accepted chunks and "
+                             "the reference under their alignments as chunks.npy / references.npy / reference_lengths.npy "
+                             "(implies --extend-ends)")
+    parser.add_argument("--min-accuracy-save-ctc", default=0.99, type=float)
+    parser.add_argument("--ctc-output-dir", default=None,
+                        help="where --save-ctc writes its arrays; default: the directory of the file behind stdout, or the "
+                             "working directory when stdout is a terminal or a pipe")
     parser.add_argument("--mm2-preset", default=None, type=str, help="accepted and ignored: the device mapper has no presets")
     parser.add_argument("--alignment-threads", default=8, type=int, help="accepted and ignored: mapping runs on the device")
     parser.add_argument("--summary", default="summary.tsv")

@@ -404,6 +404,12 @@ extern "C" int bh_map_chain(const int64_t* anchors, const int32_t* contigs, cons
     return bh_k_map_chain((const long long*)anchors, contigs, offsets, n, n_anchors, k, max_dist, bandwidth, f, p, chain, result,
                           (hipStream_t)stream);
 }
+extern "C" int bh_map_extend_max(void) { return bh_k_map_extend_max(); }
+extern "C" int bh_map_extend_band(void) { return bh_k_map_extend_band(); }
+extern "C" int bh_map_extend(const int8_t* reads, long stride, const int32_t* read_len, int n_reads, const int8_t* ref, long ref_len,
+                             const int32_t* ends, int n_ends, int32_t* result, uint32_t* runs, int runs_cap, void* stream) {
+    return bh_k_map_extend(reads, stride, read_len, n_reads, ref, ref_len, ends, n_ends, result, runs, runs_cap, (hipStream_t)stream);
+}
 extern "C" int bh_signal_normalise(const int16_t* raw, const long* offsets, const float* cal_scale, const float* cal_offset, int n_reads,
                                    int strategy, double quantile_a, double quantile_b, double shift_mult, double scale_mult,
                                    double fixed_shift, double fixed_scale, int do_trim, double* shift, double* scale, int* weak,

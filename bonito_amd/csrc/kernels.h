@@ -169,6 +169,11 @@ int bh_k_map_seed(const long long* qkeys, const int* qpos, const int8_t* qstrand
                   hipStream_t stream);
 int bh_k_map_chain(const long long* anchors, const int* contigs, const int* offsets, int n, long n_anchors, int k, int max_dist,
                    int bandwidth, int* f, int* p, int* chain, int* result, hipStream_t stream);
+// end extension of the mappings (one wave per end; every array is a device array, an end that does not fit is flagged, not read)
+int bh_k_map_extend_max();
+int bh_k_map_extend_band();
+int bh_k_map_extend(const int8_t* reads, long stride, const int* read_len, int n_reads, const int8_t* ref, long ref_len, const int* ends,
+                    int n_ends, int* result, unsigned* runs, int runs_cap, hipStream_t stream);
 
 // nw.hip (banded global alignment under unit costs with a traceback; one band half-width k per call; the lengths are host arrays)
 size_t bh_k_nw_workspace(int n, int max_seq, int max_ref, long max_band);

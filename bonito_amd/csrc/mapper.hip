@@ -276,6 +276,137 @@ __global__ __launch_bounds__(256) void map_chain_kernel(ChainArgs a) {
     if (lane == 0) { res[0] = len; res[1] = best_f; res[2] = s2; res[3] = best_i; }
 }
 
+// ---- end extension (the definition is tests/mapper_ext_ref.py) ---------------------------------------------------------------------
+// One wave per end, four ends per workgroup. The band |j - i| <= 32 is marched over anti-diagonals a = i + j: the cells of one
+// anti-diagonal all have the parity of a, so at most 33 of the 65 diagonals are live in a step and lane t holds the diagonal
+// d = 2 t - 32 + (a & 1). The diagonal predecessor (i-1, j-1) is this lane's value two steps back; (i-1, j) is the diagonal d + 1 and
+// (i, j-1) the diagonal d - 1 of the step before: one of them is this lane's own previous value, the other its neighbour's (lane
+// t + 1 on odd steps, lane t - 1 on even ones), one __shfl per step. Cells outside the matrix or the band hold EXT_NEG exactly, so
+// a predecessor that does not exist never wins. The two traceback bits of a cell go to LDS (8 rows x 2 parities per word, one word
+// column per lane, 8.6 KB per wave); the walk back and the run-length encoding follow in the same kernel.
+constexpr int EXT_MAX = 512, EXT_BAND = 32, EXT_LANES = EXT_BAND + 1;
+constexpr int EXT_TB_WORDS = (EXT_MAX / 8 + 1) * EXT_LANES;
+constexpr int EXT_NEG = -(1 << 28), EXT_BIAS = 1 << 20;
+constexpr int EXT_MATCH = 2, EXT_PENALTY = 4;
+
+struct ExtArgs {
+    const int8_t* reads; long stride; const int* read_len; int n_reads;
+    const int8_t* ref; long ref_len;
+    const int* ends; int n_ends;
+    int* result; unsigned* runs; int runs_cap;
+};
+
+struct ExtLds {
+    unsigned tb[EXT_TB_WORDS];               // [row >> 3][lane]: 4 bits per row, the even anti-diagonal's cell in the low two
+    int8_t q[EXT_MAX];                       // the query tail, nearest base first: 1..4, 0 = no base
+    int8_t r[EXT_MAX + EXT_BAND];            // the reference tail: 1..4, 5 = no base (never equal to a query code that is none)
+};
+
+__device__ __forceinline__ void ext_wave_sync() {                        // LDS written by other lanes of this wave is read behind this
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(256) void map_extend_kernel(ExtArgs a) {
+    __shared__ ExtLds s_all[4];
+    const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+    const int e = blockIdx.x * 4 + wave;
+    if (e >= a.n_ends) return;                                           // whole waves leave together; there is no workgroup barrier
+    ExtLds& s = s_all[wave];
+    const int* en = a.ends + (long)e * 6;
+    const int row = en[0], strand = en[1], side = en[2], qp = en[3];
+    const long rp = en[4], lim = en[5];
+    int* res = a.result + (long)e * 4;
+    unsigned* out = a.runs + (long)e * a.runs_cap;
+    bool ok = row >= 0 && row < a.n_reads && (strand == 0 || strand == 1) && (side == 0 || side == 1) && rp >= 0 && rp <= a.ref_len
+              && lim >= 0 && lim <= a.ref_len && (side ? lim >= rp : lim <= rp);
+    const int len = ok ? a.read_len[row] : 0;
+    ok = ok && len >= 0 && len <= a.stride && qp >= 0 && qp <= len;
+    if (!ok) {                                                           // an end that does not fit its read or the reference: nothing is read
+        if (lane == 0) { res[0] = 0; res[1] = 0; res[2] = 0; res[3] = -1; }
+        return;
+    }
+    const int m = min(side ? len - qp : qp, EXT_MAX);
+    const int n = (int)min(side ? lim - rp : rp - lim, (long)(m + EXT_BAND));
+    if (m == 0 || n == 0) {                                              // every cell but (0,0) is negative
+        if (lane == 0) { res[0] = 0; res[1] = 0; res[2] = 0; res[3] = 0; }
+        return;
+    }
+    const int8_t* rd = a.reads + (long)row * a.stride;
+    for (int x = lane; x < m; x += WAVE) {
+        const int p = side ? qp + x : qp - 1 - x;                        // position on the aligned strand
+        int c = strand ? rd[len - 1 - p] : rd[p];
+        c = c >= 1 && c <= 4 ? (strand ? 5 - c : c) : 0;
+        s.q[x] = (int8_t)c;
+    }
+    for (int x = lane; x < n; x += WAVE) {
+        const int c = a.ref[side ? rp + x : rp - 1 - x];
+        s.r[x] = (int8_t)(c >= 1 && c <= 4 ? c : 5);
+    }
+    ext_wave_sync();
+    const int t = lane;
+    int prev1 = t == EXT_BAND / 2 ? 0 : EXT_NEG;                         // a = 0: the cell (0,0) on the diagonal 0
+    int prev2 = EXT_NEG;
+    int best_s = 0, best_i = 0, best_j = 0;                              // (0,0); a lane meets its cells in the order of i + j
+    for (int ad = 1; ad <= m + n; ++ad) {
+        const int p = ad & 1;
+        const int d = 2 * t - EXT_BAND + p;
+        const int nb = __shfl(prev1, (p ? t + 1 : t - 1) & (WAVE - 1), WAVE);
+        const int up = p ? nb : prev1;                                   // (i-1, j)
+        const int left = p ? prev1 : (t == 0 ? EXT_NEG : nb);            // (i, j-1)
+        const int i = (ad - d) >> 1, j = (ad + d) >> 1;
+        int v = EXT_NEG;
+        if (t <= EXT_BAND - p && i >= 0 && j >= 0 && i <= m && j <= n) {
+            unsigned dir = 0;
+            if (i >= 1 && j >= 1) v = prev2 + (s.q[i - 1] == s.r[j - 1] ? EXT_MATCH : -EXT_PENALTY);
+            if (up - EXT_PENALTY > v) { v = up - EXT_PENALTY; dir = 1; }
+            if (left - EXT_PENALTY > v) { v = left - EXT_PENALTY; dir = 2; }
+            unsigned* w = &s.tb[(i >> 3) * EXT_LANES + t];
+            const int sh = (i & 7) * 4 + p * 2;
+            *w = (*w & ~(3u << sh)) | (dir << sh);
+            if (v > best_s) { best_s = v; best_i = i; best_j = j; }
+        }
+        prev2 = prev1;
+        prev1 = v;
+    }
+    // (S + 2^20) << 32 | (65535 - (i + j)) << 16 | (65535 - i): every field is non-negative and fits its width (0 <= S + 2^20 < 2^21,
+    // i + j <= 1056, i <= 512), so the larger word has the larger S, among equal S the smaller i + j, among those the smaller i
+    unsigned long long key = ((unsigned long long)(unsigned)(best_s + EXT_BIAS) << 32) | ((unsigned)(0xFFFF - (best_i + best_j)) << 16)
+                             | (unsigned)(0xFFFF - best_i);
+    key = wave_max_u64(key);
+    const int score = (int)(key >> 32) - EXT_BIAS;
+    const int ei = 0xFFFF - (int)(key & 0xFFFF), ej = 0xFFFF - (int)((key >> 16) & 0xFFFF) - ei;
+    ext_wave_sync();
+    // every lane walks (the LDS reads are one address); lane 0 writes. The first walk counts the runs, the second stores them: in walk
+    // order at the left end (the reversed tails run towards the span), in the opposite order at the right end
+    int n_runs = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        int i = ei, j = ej, k = 0, cur = -1, cnt = 0;
+        while (i > 0 || j > 0) {
+            const int dd = min(max(j - i + EXT_BAND, 0), 2 * EXT_BAND);   // a path never leaves the band; the index stays inside anyway
+            const unsigned dir = (s.tb[(i >> 3) * EXT_LANES + (dd >> 1)] >> ((i & 7) * 4 + (dd & 1) * 2)) & 3u;
+            int op;
+            if (dir == 0 && i > 0 && j > 0) { op = s.q[i - 1] == s.r[j - 1] ? 0 : 1; --i; --j; }
+            else if ((dir == 1 && i > 0) || j == 0) { op = 2; --i; }
+            else { op = 3; --j; }
+            if (op == cur) { ++cnt; continue; }
+            if (cur >= 0) {
+                if (pass && lane == 0) out[side ? n_runs - 1 - k : k] = ((unsigned)cnt << 2) | (unsigned)cur;
+                ++k;
+            }
+            cur = op;
+            cnt = 1;
+        }
+        if (cur >= 0) {
+            if (pass && lane == 0) out[side ? n_runs - 1 - k : k] = ((unsigned)cnt << 2) | (unsigned)cur;
+            ++k;
+        }
+        n_runs = k;
+    }
+    if (lane == 0) { res[0] = score; res[1] = ei; res[2] = ej; res[3] = n_runs; }
+}
+
 struct SketchLayout { size_t len, tile_start, tile_count, tile_off, total; };
 
 static long sketch_tiles(int len) { return len > 0 ? ((long)len + SK_TILE - 1) / SK_TILE : 0; }
@@ -381,6 +512,23 @@ int bh_k_map_chain(const long long* anchors, const int* contigs, const int* offs
     BH_REQUIRE(n_anchors == 0 || (anchors && contigs && f && p && chain), "map_chain: null pointer");
     ChainArgs a{anchors, contigs, offsets, n, k, max_dist, bandwidth, f, p, chain, result};
     hipLaunchKernelGGL(map_chain_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, a);
+    BH_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int bh_k_map_extend_max() { return bh::EXT_MAX; }
+int bh_k_map_extend_band() { return bh::EXT_BAND; }
+
+int bh_k_map_extend(const int8_t* reads, long stride, const int* read_len, int n_reads, const int8_t* ref, long ref_len, const int* ends,
+                    int n_ends, int* result, unsigned* runs, int runs_cap, hipStream_t stream) {
+    using namespace bh;
+    BH_REQUIRE(n_ends >= 0, "map_extend: n_ends must not be negative (got %d)", n_ends);
+    BH_REQUIRE(runs_cap >= 2 * EXT_MAX + EXT_BAND, "map_extend: runs_cap must be at least %d (got %d)", 2 * EXT_MAX + EXT_BAND, runs_cap);
+    BH_REQUIRE(n_reads >= 0 && stride >= 0 && ref_len >= 0 && ref_len < (1l << 31), "map_extend: negative count, stride or reference length, or a reference of 2^31 bases or more");
+    if (n_ends == 0) return 0;
+    BH_REQUIRE(reads && read_len && ref && ends && result && runs, "map_extend: null pointer");
+    ExtArgs a{reads, stride, read_len, n_reads, ref, ref_len, ends, n_ends, result, runs, runs_cap};
+    hipLaunchKernelGGL(map_extend_kernel, dim3((unsigned)((n_ends + 3) / 4)), dim3(256), 0, stream, a);
     BH_CHECK_HIP(hipGetLastError());
     return 0;
 }

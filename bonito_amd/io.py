@@ -211,3 +211,127 @@ class Writer(Thread):
                 summary.close()
         except BaseException as exc:       # surfaced by the caller after join()
             self.error = exc
+
+
+class RejectCounter(dict):
+    """Counts the reasons for which chunks are rejected (bonito/io.py:505-510)."""
+
+    def __call__(self, reject_condition, condition_name):
+        if reject_condition:
+            self[condition_name] = self.get(condition_name, 0) + 1
+        return reject_condition
+
+
+def typical_indices(x, n=2.5):
+    """Indices of the values strictly within n standard deviations of the mean (bonito/io.py:29-32)."""
+    mu, sd = np.mean(x), np.std(x)
+    idx, = np.where((mu - n * sd < x) & (x < mu + n * sd))
+    return idx
+
+
+def ctc_output_directory(fd=1):
+    """Where the reference's CTCWriter puts its arrays (bonito/io.py:605): the directory of the regular file behind stdout, '.' when
+    stdout is a terminal, a pipe or anything else without a directory of its own."""
+    import os
+    import stat
+    try:
+        if os.isatty(fd) or not stat.S_ISREG(os.fstat(fd).st_mode):
+            return "."
+        path = os.path.realpath("/dev/fd/%d" % fd)
+    except OSError:
+        return "."
+    directory = os.path.dirname(path)
+    return directory if directory and not path.startswith("/proc/") and os.path.isdir(directory) else "."
+
+
+class CTCWriter(Thread):
+    """``basecaller --save-ctc`` (bonito/io.py:513-616): consumes (chunk, result) pairs whose results went through ``align_map``, keeps
+    the chunks whose call maps with at least `min_accuracy` and `min_coverage` to an N-free stretch of the reference, writes their SAM
+    records to `fd` as they come and, at the end, ``chunks.npy`` (float16 [n, chunksize]), ``references.npy`` (uint8, A C G T = 1 2 3 4,
+    zero-padded) and ``reference_lengths.npy`` (uint16) to `output_directory`, rows of typical length only and shuffled with numpy's
+    global generator; the summary holds the same rows in the same order. The label of a chunk is the reference under its alignment,
+    which is why the mappings must have their ends extended (``Aligner(extend_ends=True)``)."""
+
+    def __init__(self, mode, iterator, aligner, fd=sys.stdout, min_coverage=0.90, min_accuracy=0.99, groups=(), min_qscore=0.0,
+                 rna=False, summary_path="summary.tsv", output_directory="."):
+        super().__init__()
+        assert mode == "sam"
+        self.mode, self.iterator, self.aligner, self.fd = mode, iterator, aligner, fd
+        self.min_coverage, self.min_accuracy, self.min_qscore, self.rna = min_coverage, min_accuracy, min_qscore or 0.0, rna
+        self.groups, self.summary_path, self.output_directory = groups, summary_path, output_directory
+        self.log = []
+        self.rejected = RejectCounter()
+        self.shapes = None           # the shapes of the three arrays once they are written
+        self.error = None
+
+    def run(self):
+        try:
+            self._run()
+        except BaseException as exc:       # surfaced by the caller after join()
+            self.error = exc
+
+    def _run(self):
+        import os
+        chunks, targets, lengths, rows = [], [], [], []
+        reject = self.rejected
+        self.fd.write(sam_header(self.groups, aligner=self.aligner))
+        for read, res in self.iterator:
+            seq, qstring = res["sequence"], res["qstring"]
+            mean_q = res["mean_qscore"] if "mean_qscore" in res else (mean_qscore(qstring) if len(qstring) else 0.0)
+            mapping = res.get("mapping")
+            self.log.append((read.read_id, len(read.signal)))
+            if reject(mean_q < self.min_qscore, "low_qscore"):
+                continue
+            if reject(len(seq) == 0, "zerolen_sequence"):
+                continue
+            if reject(not mapping, "no_mapping"):
+                continue
+            cov = (mapping.q_en - mapping.q_st) / len(seq)
+            acc = mapping.mlen / mapping.blen
+            refseq = self.aligner.seq(mapping.ctg, mapping.r_st, mapping.r_en)
+            if reject(acc < self.min_accuracy, "low_accuracy%.2f" % self.min_accuracy):
+                continue
+            if reject(cov < self.min_coverage, "low_coverage%.2f" % self.min_coverage):
+                continue
+            if reject(bool(set(refseq) - set("ACGT")), "N_in_sequence"):      # N, and any other letter that is no label
+                continue
+            self.fd.write(sam_record(read.read_id, seq, qstring, mapping) + "\n")
+            rows.append(summary_row(read, len(seq), mean_q, alignment=mapping))
+            if mapping.strand == -1:
+                refseq = revcomp(refseq)
+            target = ["ACGT".index(base) + 1 for base in refseq]
+            targets.append(target[::-1] if self.rna else target)      # an RNA call is already reversed: back to signal order
+            chunks.append(read.signal)
+            lengths.append(len(target))
+        self.fd.flush()
+        if len(chunks) == 0:
+            sys.stderr.write("> no suitable ctc data to write\n")
+            return
+        chunks = np.array(chunks, dtype=np.float16)
+        targets_ = np.zeros((chunks.shape[0], max(lengths)), dtype=np.uint8)
+        for idx, target in enumerate(targets):
+            targets_[idx, :len(target)] = target
+        lengths = np.array(lengths, dtype=np.uint16)
+        indices = np.random.permutation(typical_indices(lengths))
+        chunks, targets_, lengths = chunks[indices], targets_[indices], lengths[indices]
+        if self.summary_path:
+            with open(self.summary_path, "w", newline="") as summary:
+                tsv = csv.writer(summary, delimiter="\t")
+                tsv.writerow(summary_field_names + alignment_field_names)
+                for idx in indices:
+                    tsv.writerow(rows[idx])
+        os.makedirs(self.output_directory, exist_ok=True)
+        np.save(os.path.join(self.output_directory, "chunks.npy"), chunks)
+        np.save(os.path.join(self.output_directory, "references.npy"), targets_)
+        np.save(os.path.join(self.output_directory, "reference_lengths.npy"), lengths)
+        self.shapes = (chunks.shape, targets_.shape, lengths.shape)
+        sys.stderr.write("> Chunks rejected from training data:\n")
+        for condition_name, count in reject.items():
+            sys.stderr.write(" - %s: %d\n" % (condition_name, count))
+        sys.stderr.write("> written ctc training data to %s\n" % self.output_directory)
+        sys.stderr.write("  - chunks.npy with shape (%s)\n" % ",".join(map(str, chunks.shape)))
+        sys.stderr.write("  - references.npy with shape (%s)\n" % ",".join(map(str, targets_.shape)))
+        sys.stderr.write("  - reference_lengths.npy shape (%s)\n" % ",".join(map(str, lengths.shape)))
+
+    def stop(self):
+        self.join()

@@ -89,6 +89,41 @@ class Read:
         return "Read('%s')" % self.read_id
 
 
+class ReadChunk:
+    """One fixed-size window of a read, a read of its own for `basecall` and the writers (bonito/reader.py:89-104): the parent's
+    identity fields, the id ``<read_id>:<i>:<n>`` and, like the reference, the parent's untrimmed start and duration as the template's."""
+
+    def __init__(self, read, chunk, i, n):
+        self.read_id = "%s:%i:%i" % (read.read_id, i, n)
+        self.run_id = read.run_id
+        self.filename = read.filename
+        self.mux = read.mux
+        self.channel = read.channel
+        self.start = read.start
+        self.duration = read.duration
+        self.template_start = self.start
+        self.template_duration = self.duration
+        self.signal = chunk
+
+    def __repr__(self):
+        return "ReadChunk('%s')" % self.read_id
+
+
+def read_chunks(read, chunksize=4000, overlap=400):
+    """Split a read into `ReadChunk`s of exactly `chunksize` samples, `chunksize - overlap` apart, the last one ending with the
+    signal (bonito/reader.py:107-119): the first (len - chunksize) % (chunksize - overlap) samples belong to no chunk, and a read
+    shorter than `chunksize` gives none. The chunks are views of the read's signal."""
+    signal = read.signal
+    if len(signal) < chunksize:
+        return
+    step = chunksize - overlap
+    offset = (len(signal) - chunksize) % step
+    n = (len(signal) - offset - chunksize) // step + 1
+    for i in range(n):
+        lo = offset + i * step
+        yield ReadChunk(read, signal[lo:lo + chunksize], i + 1, n)
+
+
 class RawRead:
     """A read whose signal is still raw int16 ADC samples: normalisation / trim / chunking happen on the device
     (bonito_amd.signal, crf.basecall.basecall_raw), which fills in `shift`, `scale`, `trimmed_samples`. Same identity

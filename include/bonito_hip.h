@@ -30,7 +30,7 @@
  *   bh_nw_align / bh_sg_align
  *        edlib.align(query, ref, task="path") and parasail.sg_trace_scan_32(query, ref, 10, 2, dnafull) behind the basespace
  *        duplex caller                                                         bonito/cli/duplex.py:224-300
- *   bh_map_sketch / bh_map_seed / bh_map_chain
+ *   bh_map_sketch / bh_map_seed / bh_map_chain / bh_map_extend
  *        mappy.Aligner(reference).map(sequence) behind `bonito basecaller --reference`, as far as seeding and chaining go; defined by
  *        tests/mapper_ref.py, minimap2 parity is not claimed                   bonito/aligner.py:1-63
  *   bh_ctc_greedy_decode / bh_ctc_beam_search
@@ -422,6 +422,28 @@ int bh_map_seed(const int64_t* qkeys, const int32_t* qpos, const int8_t* qstrand
                 int64_t* anchors, long capacity, void* stream);
 int bh_map_chain(const int64_t* anchors, const int32_t* contigs, const int32_t* offsets, int n, long n_anchors, int k, int max_dist,
                  int bandwidth, int32_t* f, int32_t* p, int32_t* chain, int32_t* result, void* stream);
+
+/* bh_map_extend: end extension of mappings beyond their outermost anchors (`Aligner(extend_ends=True)`, `basecaller --extend-ends` and
+ * `--save-ctc`), DEFINED by tests/mapper_ext_ref.py and equal to it bit for bit. One wave per end, all arrays DEVICE arrays.
+ *   reads (int8 [n_reads][stride]): the read codes as given, 1..4 = A C G T, anything else = no base; read_len (int32 [n_reads]).
+ *   ref (int8 [ref_len]): the concatenated reference codes, ref_len < 2^31.
+ *   ends (int32 [n_ends][6]): read row, strand (0 / 1), side (0 = left, 1 = right), the span's start (left) or end (right) on the
+ *   ALIGNED strand of the read (on strand 1 the base at p is the complement of reads[row][len - 1 - p]), the same in the concatenated
+ *   reference, and the contig's limit on that side (left: its first base; right: one behind its last): a tail never leaves its contig.
+ *   Tails (nearest base first): Q = the up to bh_map_extend_max() = 512 query bases beyond the span, R = the up to
+ *   len(Q) + bh_map_extend_band() = len(Q) + 32 reference bases. S(0,0) = 0; only cells with |j - i| <= 32 exist;
+ *   S(i,j) = max(S(i-1,j-1) + (Q[i-1] == R[j-1], a base of ACGT ? +2 : -4), S(i-1,j) - 4, S(i,j-1) - 4). End cell: the largest S, (0,0)
+ *   included, then the smallest i + j, then the smallest i. Path back to (0,0): diagonal, then (i-1,j) (I), then (i,j-1) (D). There
+ *   is no drop-off heuristic; tails beyond 512 bases stay clipped.
+ *   result (int32 [n_ends][4]): score, query bases, reference bases, number of runs; (0, 0, 0, -1) for an end that does not fit its
+ *   read, its contig limit or the reference (nothing of it is read). runs (uint32 [n_ends][runs_cap]): count << 2 | op over
+ *   = X I D = 0 1 2 3 in READ order at both sides (left runs + the span's runs + right runs is the whole alignment);
+ *   runs_cap >= 2 * 512 + 32. Nothing else of result / runs is written.
+ *   Errors: a null pointer, n_ends < 0, runs_cap too small, a negative count or stride. n_ends == 0 returns 0 without a launch. */
+int bh_map_extend_max(void);
+int bh_map_extend_band(void);
+int bh_map_extend(const int8_t* reads, long stride, const int32_t* read_len, int n_reads, const int8_t* ref, long ref_len,
+                  const int32_t* ends, int n_ends, int32_t* result, uint32_t* runs, int runs_cap, void* stream);
 
 /* Signal ingest on the device: replaces Read.__init__'s numpy work (bonito/reader.py:122-166 normalisation + trim, the pA
  * scaling and the trim threshold of bonito/pod5.py:52-67) and util.chunk + the fp16 cast (bonito/util.py:142-161, crf/basecall.py:31) for raw
