@@ -111,6 +111,7 @@ SIGNATURES = {
     "bh_ctc_beam_search_workspace": (_sz, [_l, _i, _i, _i]),
     "bh_ctc_beam_search": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "bh_dwconv1d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "bh_ctc_head": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _vp]),
     "bh_rotary_table": (_i, [_i, _i, _vp]),
     "bh_attention": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "bh_attention_prerotated": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

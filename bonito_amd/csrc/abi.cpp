@@ -130,7 +130,7 @@ extern "C" int bh_attention_prerotated(const void* qkv, void* out, int N, int T,
 }
 extern "C" int bh_rmsnorm_residual(const void* a, const void* x, const float* w, void* out, long M, int D, float alpha,
                                    float eps, void* stream) {
-    BH_REQUIRE(a && x && w && out && M > 0, "rmsnorm_residual: bad arguments");
+    BH_REQUIRE(a && w && out && M > 0, "rmsnorm_residual: bad arguments");      // x == NULL: `a` already holds the residual sum
     return bh_k_rmsnorm_residual(a, x, w, out, M, D, alpha, eps, (hipStream_t)stream);
 }
 extern "C" int bh_ctc_greedy_decode(const float* logp, const long* offsets, int R, int classes, float qscale, float qbias,
@@ -153,6 +153,11 @@ extern "C" int bh_dwconv1d(const void* in, const float* w, void* out, int N, int
     const int lout = conv_out_len(Lin, K, stride, pad);
     BH_REQUIRE(lout > 0, "dwconv1d: input too short");
     return bh_k_dwconv(in, w, out, N, Lin, lout, C, K, stride, pad, (hipStream_t)stream);
+}
+extern "C" int bh_ctc_head(const void* in, const float* w, const float* bias, void* out, long M, int features, int classes,
+                           void* stream) {
+    BH_REQUIRE(in && w && bias && out && M > 0, "ctc_head: bad arguments");
+    return bh_k_ctc_head(in, w, bias, out, M, features, classes, (hipStream_t)stream);
 }
 extern "C" size_t bh_lstm_workspace(int N, int H) { return bh_k_lstm_ws_bytes(N, H); }
 extern "C" int bh_lstm_layer(const void* gates_in, const void* whh_packed, void* h_out, int T, int N, int H,

@@ -125,6 +125,7 @@ int bh_k_ctc_head(const void* in, const float* w, const float* bias, void* out, 
                "ctc_head: need classes<=8 and features%%8==0 (classes=%d features=%d)", classes, features);
     HeadArgs a{(const half_t*)in, w, bias, (half_t*)out, M, features, classes};
     const size_t lds = (size_t)classes * features * 4;
+    BH_REQUIRE(lds <= 64 * 1024, "ctc_head: %d classes x %d features of fp32 weights do not fit 64 KiB of LDS", classes, features);
     hipLaunchKernelGGL(ctc_head_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), lds, stream, a);
     BH_CHECK_HIP(hipGetLastError());
     return 0;

@@ -17,6 +17,8 @@ def viterbi_search_batch(logps, alphabet, qscale=1.0, qbias=0.0, device="cuda"):
         return []
     dev = torch.device(device)
     lens = [int(x.shape[0]) for x in logps]
+    if not any(lens):                  # nothing to decode: an empty tensor has no device address to hand to the kernel
+        return [("", "", []) for _ in lens]
     offs = torch.tensor(np.concatenate([[0], np.cumsum(lens)]), dtype=torch.int64)
     flat = torch.cat([torch.as_tensor(x, dtype=torch.float32) for x in logps]).contiguous().to(dev)
     total, Cc = flat.shape
@@ -54,6 +56,8 @@ def beam_search_batch(logps, alphabet, beam_size=5, beam_cut_threshold=1e-3, dev
         return []
     dev = torch.device(device)
     lens = [int(x.shape[0]) for x in logps]
+    if not any(lens):
+        return [("", []) for _ in lens]
     offs = torch.tensor(np.concatenate([[0], np.cumsum(lens)]), dtype=torch.int64)
     flat = torch.cat([torch.as_tensor(x, dtype=torch.float32) for x in logps]).contiguous().to(dev)
     total, Cc = flat.shape

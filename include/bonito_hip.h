@@ -673,6 +673,12 @@ int bh_ctc_beam_search(const float* logp, const long* offsets, int R, int classe
 /* depthwise conv (TCSConv1d.depthwise, ctc/model.py:99-103): in/out fp16 channel-minor [N][L][C], w fp32 device [C][K] */
 int bh_dwconv1d(const void* in, const float* w, void* out, int N, int Lin, int C, int K, int stride, int pad,
                 void* stream);
+/* CTC head (Decoder, ctc/model.py:195-207): the 1x1 decoder convolution and log_softmax over the classes in one kernel.
+ * in fp16 [M][features], w fp32 device [classes][features], bias fp32 device [classes] -> out fp16 [M][classes] log-probabilities
+ * (fp32 logits and softmax, one rounding at the store). 1 <= classes <= 8, features a positive multiple of 8, and the weights
+ * (classes * features * 4 bytes) must fit 64 KiB of LDS; anything else is refused on the host. */
+int bh_ctc_head(const void* in, const float* w, const float* bias, void* out, long M, int features, int classes,
+                void* stream);
 /* rotary cos/sin table (host): out[t][i][0..1] = cos, sin(t * 10000^(-2i/dim)), i < dim/2, fp32
  * (flash_attn.layers.rotary.RotaryEmbedding(dim, interleaved=False), bonito/transformer/model.py:55,73) */
 int bh_rotary_table(int T, int dim, float* out);
@@ -686,7 +692,10 @@ int bh_attention(const void* qkv, void* out, const float* cos_sin, int N, int T,
  * right <= 144 (flash_attn_qkvpacked_func proper, bonito/transformer/model.py:60; softmax in base 2 on pre-scaled scores). Any other
  * window is an error (nonzero return, output untouched): such a layer is served by bh_attention, in the engine too. */
 int bh_attention_prerotated(const void* qkv, void* out, int N, int T, int nhead, int head_dim, int win_left, int win_right, void* stream);
-/* out = rmsnorm(a + alpha * x) * w (fp32 statistics): RMSNorm(x, residual) of bonito/transformer/model.py:110-111,125-128 */
+/* out = rmsnorm(a + alpha * x) * w (fp32 statistics, eps inside the root): RMSNorm(x, residual) of bonito/transformer/model.py:110-111,125-128.
+ * a, x, out fp16 [M][D], w fp32 device [D]; D a multiple of 8, 8 <= D <= 1024. x == NULL means that `a` already holds the residual sum
+ * (the engine can fuse alpha * x into the epilogue of the producing GEMM); alpha is then not read. `out` must not alias `a` or `x`:
+ * the engine never calls it in place, and in-place is not a supported call. */
 int bh_rmsnorm_residual(const void* a, const void* x, const float* w, void* out, long M, int D, float alpha,
                         float eps, void* stream);
 /* recurrent weights: torch W_hh [4H][H] fp32 (host) -> MFMA-fragment order fp16 (host, 4*H*H halves) */

@@ -9,18 +9,23 @@ of the label's MEAN probability over its run ([EXT]: mean-vs-max is not verifiab
 import numpy as np
 
 
-def phred(prob, scale=1.0, bias=0.0):
+def phred_float(prob, scale=1.0, bias=0.0):
+    """The quality before it is rounded to a character."""
     p = max(1.0 - float(prob), 1e-4)
-    q = -10.0 * np.log10(np.float32(p)) * scale + bias
-    return int(np.rint(np.float32(q))) + 33
+    return np.float32(-10.0 * np.log10(np.float32(p)) * scale + bias)
 
 
-def viterbi_search(logp, alphabet, qscale=1.0, qbias=0.0):
-    """logp: [T, C] float array of log-probabilities -> (sequence, qstring, path)."""
+def phred(prob, scale=1.0, bias=0.0):
+    return int(np.rint(phred_float(prob, scale, bias))) + 33
+
+
+def viterbi_search(logp, alphabet, qscale=1.0, qbias=0.0, return_qfloat=False):
+    """logp: [T, C] float array of log-probabilities -> (sequence, qstring, path); with return_qfloat also the unrounded
+    quality of every base (float32 array), for checks that allow a character to differ only next to a rounding boundary."""
     lp = np.asarray(logp, dtype=np.float32)
     T = lp.shape[0]
-    labels = lp.argmax(axis=1)          # ties: lowest label (numpy argmax)
-    seq, qs, path = [], [], []
+    labels = lp.argmax(axis=1) if T else np.zeros(0, np.int64)          # ties: lowest label (numpy argmax)
+    seq, qs, path, qf = [], [], [], []
     t = 0
     prev = 0
     while t < T:
@@ -31,10 +36,13 @@ def viterbi_search(logp, alphabet, qscale=1.0, qbias=0.0):
                 u += 1
             prob = float(np.exp(lp[t:u, lab].astype(np.float64)).mean())
             seq.append(alphabet[lab])
-            qs.append(chr(phred(prob, qscale, qbias)))
+            qf.append(phred_float(prob, qscale, qbias))
+            qs.append(chr(int(np.rint(qf[-1])) + 33))
             path.append(t)
         prev = lab
         t += 1
+    if return_qfloat:
+        return "".join(seq), "".join(qs), path, np.asarray(qf, dtype=np.float32)
     return "".join(seq), "".join(qs), path
 
 
