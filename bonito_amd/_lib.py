@@ -74,6 +74,11 @@ SIGNATURES = {
     "bh_ctc_loss_grad_workspace": (_sz, [_i, _i, _i, _i]),
     "bh_ctc_loss_grad": (_i, [_vp, _i, _i, _i, _i, _l, _l, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _l, _i, _i, _vp]),
     "bh_ctc_loss_last_kernel": (_i, []),
+    "bh_lstm_train_saved_bytes": (_sz, [_i, _i, _i]),
+    "bh_lstm_train_backward_workspace": (_sz, [_i, _i, _i]),
+    "bh_lstm_train_workgroups": (_i, [_i]),
+    "bh_lstm_train_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "bh_lstm_train_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "bh_sw_workspace": (_sz, [_i, _i, _i]),
     "bh_sw_align": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _l, _vp, _vp]),
     "bh_sg_align": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _l, _vp, _vp]),

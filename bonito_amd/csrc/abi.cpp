@@ -366,6 +366,19 @@ extern "C" int bh_ctc_loss_grad(const void* log_probs, int logp_fp32, int N, int
                          (hipStream_t)stream);
 }
 extern "C" int bh_ctc_loss_last_kernel(void) { return bh_k_ctc_loss_last_kernel(); }
+extern "C" size_t bh_lstm_train_saved_bytes(int T, int N, int H) { return bh_k_lstm_train_saved_bytes(T, N, H); }
+extern "C" size_t bh_lstm_train_backward_workspace(int T, int N, int H) { return bh_k_lstm_train_backward_workspace(T, N, H); }
+extern "C" int bh_lstm_train_workgroups(int N) { return bh_k_lstm_train_workgroups(N); }
+extern "C" int bh_lstm_train_forward(const void* x, const float* w_ih, const float* w_hh, const float* bias, int T, int N, int H,
+                                     int reverse, void* h_out, void* saved, size_t saved_bytes, void* stream) {
+    return bh_k_lstm_train_forward(x, w_ih, w_hh, bias, T, N, H, reverse, h_out, saved, saved_bytes, (hipStream_t)stream);
+}
+extern "C" int bh_lstm_train_backward(const void* x, const float* w_ih, const float* w_hh, const void* h, const void* saved, const void* dh,
+                                      int T, int N, int H, int reverse, void* dx, float* dw_ih, float* dw_hh, float* dbias, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    return bh_k_lstm_train_backward(x, w_ih, w_hh, h, saved, dh, T, N, H, reverse, dx, dw_ih, dw_hh, dbias, workspace, workspace_bytes,
+                                    (hipStream_t)stream);
+}
 extern "C" size_t bh_sw_workspace(int n, int max_seq, int max_ref) { return bh_k_sw_workspace(n, max_seq, max_ref); }
 extern "C" int bh_sw_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, const void* refs, long ref_stride,
                            const int32_t* ref_lengths, int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace,

@@ -148,6 +148,16 @@ int bh_k_ctc_loss(const void* log_probs, int logp_fp32, int N, int T, int C, lon
                   hipStream_t stream);
 int bh_k_ctc_loss_last_kernel();   // test hook: the bh_ctc_loss_kernel code of the instance that served the last call; not thread-safe
 
+// lstm_train.hip (one LSTM layer for training: the forward that keeps the gates and c, and the backward; every pointer a device pointer)
+size_t bh_k_lstm_train_saved_bytes(int T, int N, int H);
+size_t bh_k_lstm_train_backward_workspace(int T, int N, int H);
+int bh_k_lstm_train_workgroups(int N);       // workgroups of the two recurrent kernels: one per tile of 16 chunks
+int bh_k_lstm_train_forward(const void* x, const float* w_ih, const float* w_hh, const float* bias, int T, int N, int H, int reverse,
+                            void* h_out, void* saved, size_t saved_bytes, hipStream_t stream);
+int bh_k_lstm_train_backward(const void* x, const float* w_ih, const float* w_hh, const void* h, const void* saved, const void* dh, int T,
+                             int N, int H, int reverse, void* dx, float* dw_ih, float* dw_hh, float* dbias, void* workspace,
+                             size_t workspace_bytes, hipStream_t stream);
+
 // align.hip (Smith-Waterman, affine gaps, traceback; the lengths are host arrays)
 size_t bh_k_sw_workspace(int n, int max_seq, int max_ref);
 int bh_k_sw_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,

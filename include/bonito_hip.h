@@ -24,6 +24,8 @@
  *   bh_ctc_loss / bh_ctc_loss_grad
  *        torch.nn.functional.ctc_loss (and its backward) behind Model.ctc_label_smoothing_loss / Model.loss
  *                                                                              bonito/ctc/model.py:48-57
+ *   bh_lstm_train_forward / bh_lstm_train_backward
+ *        torch.nn.LSTM under autocast, and its autograd, as the reference's LSTM layer wraps it   bonito/nn.py:353-397
  *   bh_sw_align
  *        parasail.sw_trace_striped_32(seq, ref, 8, 4, parasail.dnafull) behind evaluate's align() and util.accuracy
  *                                                                              bonito/cli/evaluate.py:37-67, bonito/util.py:346-368
@@ -317,6 +319,39 @@ int bh_ctc_loss_grad(const void* log_probs, int logp_fp32, int N, int T, int C, 
                      const float* smooth_weight, void* workspace, float* nll_out, float* smooth_out, void* grad, long g_stride_t,
                      long g_stride_n, int grad_fp32, int accumulate, void* stream);
 int bh_ctc_loss_last_kernel(void);
+
+/* ---- One LSTM layer for training (csrc/lstm_train.hip): the forward that keeps what the backward needs, and the backward --------
+ * The layer is torch.nn.LSTM, one layer, one direction (bonito/nn.py:353-397): gates in the order i, f, g, o, h_0 = c_0 = 0,
+ * insize == size == H, reverse = 1 runs the time loop backwards:
+ *     a_t = x_t W_ih^T + h_{t-1} W_hh^T + b      c_t = sig(f) c_{t-1} + sig(i) tanh(g)      h_t = sig(o) tanh(c_t)
+ * and from the last processed step to the first
+ *     d_t = dh_t + da_{t+1} W_hh                 dc_t = dc_{t+1} sig(f_{t+1}) + d_t sig(o) (1 - tanh^2 c_t)
+ *     da_t = (dc_t tanh(g) sig'(i), dc_t c_{t-1} sig'(f), dc_t sig(i) (1 - tanh^2 g), d_t tanh(c_t) sig'(o))
+ *     dx_t = da_t W_ih     dW_ih = sum_t da_t^T x_t     dW_hh = sum_t da_t^T h_{t-1}     db = sum_{t,n} da_t
+ * EVERY pointer is a device pointer. x, h_out / h, dh, dx: fp16 [T][N][H], 16-byte aligned. w_ih, w_hh: FP32 [4H][H]; bias: fp32 [4H]
+ *   (b_ih + b_hh) or NULL. The kernels use the round-to-nearest fp16 values of the weights (converted on the device in every call:
+ *   an optimiser rewrites them every step, so nothing is packed on the host); every sum is fp32, c is fp32 from step to step and
+ *   where it is saved, the cell arithmetic is that of the inference kernels (lstm_cell of csrc/lstm.hip). dw_ih, dw_hh: fp32 [4H][H],
+ *   dbias: fp32 [4H] or NULL = not computed; all three are OVERWRITTEN, summed in fp32 in an order that depends on the shape alone -
+ *   no floating-point atomics, every output is byte-identical from call to call.
+ * saved (bh_lstm_train_saved_bytes): written by the forward, read by the backward of the same T, N, H, reverse: the input projection
+ *   x W_ih^T + b as fp16, overwritten in place by the post-activation gates sig(i), sig(f), tanh(g), sig(o) [T][N][4H] fp16; c [T][N][H]
+ *   fp32; the fp16 weights (and scratch of the forward). workspace (bh_lstm_train_backward_workspace): da [T][N][4H] fp16, the fp16
+ *   weights as the backward reads them, the partial sums of the weight gradients. Both are the caller's, 16-byte aligned; a buffer that is too small is an error.
+ * Gradients are not clamped: da is stored as fp16, as autocast stores it. A non-finite dh in one chunk makes that chunk's dx and the
+ *   weight gradients non-finite; the other chunks' dx keep their bytes. Chunks are independent of each other in h and dx: a chunk
+ *   has the same bytes whatever else is in the batch, and whether or not N fills the last tile of 16 chunks.
+ * Supported (an error with a message, never a substitute): H % 32 == 0, 32 <= H <= 1024, T >= 1, N >= 1, T * N < 2^29.
+ * Stream-ordered; nothing is allocated and nothing synchronises inside. The recurrent kernels give a tile of 16 chunks to one
+ *   workgroup for all T steps (bh_lstm_train_workgroups(N) of them): workgroups never wait for each other. */
+size_t bh_lstm_train_saved_bytes(int T, int N, int H);               /* 0 = unsupported shape */
+size_t bh_lstm_train_backward_workspace(int T, int N, int H);        /* 0 = unsupported shape */
+int bh_lstm_train_workgroups(int N);
+int bh_lstm_train_forward(const void* x, const float* w_ih, const float* w_hh, const float* bias, int T, int N, int H, int reverse,
+                          void* h_out, void* saved, size_t saved_bytes, void* stream);
+int bh_lstm_train_backward(const void* x, const float* w_ih, const float* w_hh, const void* h, const void* saved, const void* dh, int T,
+                           int N, int H, int reverse, void* dx, float* dw_ih, float* dw_hh, float* dbias, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 /* ---- Smith-Waterman local alignment with affine gaps and a traceback (csrc/align.hip) ----------------------------------
  * n pairs of a called sequence `seq` (the query, index i) and a known sequence `ref` (index j). seqs / refs: DEVICE int8 planes
