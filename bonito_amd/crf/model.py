@@ -282,6 +282,122 @@ class SeqdistModel(Module):
             raise NoTorchCompute("bonito_amd models only run on a HIP device; got a %s tensor" % x.device)
         return self._engine(x)(x)
 
+    def forward_train(self, x):
+        """The forward of a training step: x cuda fp16 [N,1,L] -> scores in the shape, layout and dtype of ``forward(x)``, INSIDE
+        autograd, so that ``self.loss(self.forward_train(x), targets, lengths).backward()`` leaves a gradient on every trainable
+        parameter. The parameters are the fp32 master weights on x's device; every layer rounds them to fp16 on the device in every
+        call (autocast's arithmetic: bonito_amd.train_ops, bonito_amd.rnn). Serves the LSTM family - conv x3 -> permute -> LSTM x n ->
+        [linear] -> linearcrfencoder [-> clamp] - with the folding rules of ``engine.lower``: a Clamp after a Convolution or the head
+        is fused into it, Permute([2,0,1]) is folded into the producing convolution's store, Permute([1,0,2]) after the head is a
+        no-op. Anything else is refused with a ValueError that names the layer. The inference engine is neither built nor dropped."""
+        from bonito_amd import nn as bnn, rnn, train_ops
+        from bonito_amd.engine import _flatten
+        if getattr(self, "_quantize", False):
+            raise ValueError("forward_train: quantize (the 8-bit recurrent path) has no training forward; call use_hip(quantize=False)")
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float16 or x.dim() != 3 or x.shape[1] != 1:
+            raise ValueError("forward_train: x must be a float16 tensor [N,1,L], got %s"
+                             % ("%s %s" % (x.dtype, tuple(x.shape)) if isinstance(x, torch.Tensor) else type(x).__name__))
+        mods = _flatten(self.encoder)
+        def clamp_after(i):
+            return (float(mods[i + 1].min), float(mods[i + 1].max)) if i + 1 < len(mods) and isinstance(mods[i + 1], bnn.Clamp) else None
+
+        def next_compute(i):            # the layer that consumes layer i's output, and whether a Permute([2,0,1]) lies between
+            tm = False
+            for m in mods[i + 1:]:
+                if isinstance(m, bnn.Permute):
+                    tm = tm or list(m.dims) == [2, 0, 1]
+                elif not isinstance(m, (bnn.Clamp, bnn.MakeContiguous)):
+                    return m, tm
+            return None, tm
+
+        # every refusal comes before the first launch; what is wrong on any device is judged first
+        for i, m in enumerate(mods):
+            name = "layer %d (%s)" % (i, type(m).__name__)
+            if isinstance(m, bnn.Convolution):
+                if m.norm is not None:
+                    raise ValueError("forward_train: %s carries a norm (%s); a normalised convolution has no training backward yet"
+                                     % (name, getattr(m.norm, "name", type(m.norm).__name__)))
+                if m.conv.groups != 1 or m.conv.dilation[0] != 1:
+                    raise ValueError("forward_train: %s is a grouped / dilated (depthwise, QuartzNet) convolution, which has no training "
+                                     "backward" % name)
+                clamp = clamp_after(i)
+                if isinstance(next_compute(i)[0], bnn.Convolution) and m.conv.out_channels % 8 and clamp is not None \
+                        and not clamp[0] <= 0.0 <= clamp[1]:
+                    raise ValueError("forward_train: %s has %d channels, served by zero padding, and its clamp range %s does not contain 0"
+                                     % (name, m.conv.out_channels, clamp))
+            elif isinstance(m, bnn.LSTM):
+                r = m.rnn
+                if r.num_layers != 1 or r.bidirectional or r.input_size != r.hidden_size or getattr(r, "proj_size", 0) \
+                        or not rnn.supported_hidden_size(r.hidden_size):
+                    raise ValueError("forward_train: %s is not an LSTM the device layer serves (one layer, one direction, insize == size, "
+                                     "a multiple of 32 in 32..1024)" % name)
+            elif isinstance(m, bnn.Permute):
+                if list(m.dims) not in ([2, 0, 1], [0, 2, 1], [1, 0, 2]):
+                    raise ValueError("forward_train: %s with dims %s cannot be folded" % (name, list(m.dims)))
+            elif not isinstance(m, (bnn.LinearCRFEncoder, bnn.Linear, bnn.Clamp, bnn.MakeContiguous)) or isinstance(m, bnn.LinearUpsample):
+                raise ValueError("forward_train: %s has no training forward (the LSTM family of CRF models is served: convolutions, "
+                                 "LSTMs, linear, linearcrfencoder, clamp)" % name)
+            for pname, p in m.named_parameters():
+                if p.dtype != torch.float32:
+                    raise ValueError("forward_train: %s holds %s parameters (%s); training needs the fp32 master weights - call "
+                                     "model.float()" % (name, str(p.dtype).replace("torch.", ""), pname))
+        if not x.is_cuda:
+            raise NoTorchCompute("forward_train runs on a HIP device only; x is a %s tensor" % x.device)
+        for i, m in enumerate(mods):
+            for pname, p in m.named_parameters():
+                if p.device != x.device:
+                    raise ValueError("forward_train: layer %d (%s) has %s on %s, x is on %s" % (i, type(m).__name__, pname, p.device, x.device))
+
+        h = x.reshape(x.shape[0], x.shape[2])       # [N][L]: one input channel
+        layout = "signal"                           # -> "nlc" [N][L][C] -> "tnc" [T][N][C] -> "ntc" scores
+        pad_in = 0                                  # zero channels the convolution in front added to its output
+        i = 0
+        while i < len(mods):
+            m = mods[i]
+            name = "layer %d (%s)" % (i, type(m).__name__)
+            if isinstance(m, bnn.Convolution):
+                if layout not in ("signal", "nlc"):
+                    raise ValueError("forward_train: %s follows the permute to time-major activations" % name)
+                c = m.conv
+                if (c.in_channels == 1) != (layout == "signal"):
+                    raise ValueError("forward_train: %s expects %d input channels" % (name, c.in_channels))
+                clamp = clamp_after(i)
+                nxt, tm = next_compute(i)
+                w, b = c.weight, c.bias
+                if pad_in:
+                    w = torch.nn.functional.pad(w, (0, 0, 0, pad_in))
+                pad_in = -c.out_channels % 8 if isinstance(nxt, bnn.Convolution) else 0
+                if pad_in:              # zero output channels up to a multiple of 8: they stay exactly zero through swish / relu / tanh
+                    w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, pad_in))
+                    b = None if b is None else torch.nn.functional.pad(b, (0, pad_in))
+                if tm and not isinstance(nxt, bnn.LSTM):
+                    raise ValueError("forward_train: %s stores time-major for a layer that is no LSTM" % name)
+                h = train_ops.conv1d(h, w, b, c.stride[0], c.padding[0], m.activation, clamp, tm)
+                layout = "tnc" if tm else "nlc"
+                i += 2 if clamp is not None else 1
+            elif isinstance(m, bnn.LSTM):
+                if layout != "tnc":
+                    raise ValueError("forward_train: %s must follow permute [2,0,1]" % name)
+                h = rnn.lstm_module(m, h)
+                i += 1
+            elif isinstance(m, (bnn.LinearCRFEncoder, bnn.Linear)):
+                if layout != "tnc":
+                    raise ValueError("forward_train: %s needs the time-major output of the LSTM stack" % name)
+                head = isinstance(m, bnn.LinearCRFEncoder)
+                clamp = clamp_after(i)
+                h = train_ops.linear(h, m.linear.weight, m.linear.bias, m.activation if head else None,
+                                     (m.scale if m.scale else None) if head else None, clamp, head)
+                if head:
+                    layout = "ntc"
+                i += 2 if clamp is not None else 1
+            elif isinstance(m, bnn.Clamp):
+                raise ValueError("forward_train: %s follows no convolution, linear or head to be fused into" % name)
+            else:                       # Permute / MakeContiguous: folded
+                i += 1
+        if layout != "ntc":
+            raise ValueError("forward_train: the encoder does not end in a linearcrfencoder")
+        return h
+
     def decode_batch(self, x, blank_score=2.0):
         """Posterior decoding of engine scores [N, T, 4S] (cuda fp16) -> list of strings
         (reference crf/model.py:196-199: viterbi over log(posteriors + 1e-8))."""

@@ -379,6 +379,34 @@ extern "C" int bh_lstm_train_backward(const void* x, const float* w_ih, const fl
     return bh_k_lstm_train_backward(x, w_ih, w_hh, h, saved, dh, T, N, H, reverse, dx, dw_ih, dw_hh, dbias, workspace, workspace_bytes,
                                     (hipStream_t)stream);
 }
+extern "C" size_t bh_conv1d_train_workspace(int N, int Lin, int Cin, int Cout, int K, int stride, int pad) {
+    return bh_k_conv_train_workspace(N, Lin, Cin, Cout, K, stride, pad);
+}
+extern "C" int bh_conv1d_train_forward(const void* x, const float* w, const float* bias, int N, int Lin, int Cin, int Cout, int K, int stride,
+                                       int pad, int act, float clamp_lo, float clamp_hi, long os_n, long os_t, void* y, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    return bh_k_conv_train_forward(x, w, bias, N, Lin, Cin, Cout, K, stride, pad, act, clamp_lo, clamp_hi, os_n, os_t, y, workspace,
+                                   workspace_bytes, (hipStream_t)stream);
+}
+extern "C" int bh_conv1d_train_backward(const void* x, const float* w, const float* bias, const void* y, const void* dy, int N, int Lin, int Cin,
+                                        int Cout, int K, int stride, int pad, int act, float clamp_lo, float clamp_hi, long os_n, long os_t,
+                                        void* dx, float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream) {
+    return bh_k_conv_train_backward(x, w, bias, y, dy, N, Lin, Cin, Cout, K, stride, pad, act, clamp_lo, clamp_hi, os_n, os_t, dx, dw, db,
+                                    workspace, workspace_bytes, (hipStream_t)stream);
+}
+extern "C" size_t bh_linear_train_workspace(int T, int N, int K, int C) { return bh_k_linear_train_workspace(T, N, K, C); }
+extern "C" int bh_linear_train_forward(const void* x, const float* w, const float* bias, int T, int N, int K, int C, int act, float scale,
+                                       float clamp_lo, float clamp_hi, int batch_major, void* y, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+    return bh_k_linear_train_forward(x, w, bias, T, N, K, C, act, scale, clamp_lo, clamp_hi, batch_major, y, workspace, workspace_bytes,
+                                     (hipStream_t)stream);
+}
+extern "C" int bh_linear_train_backward(const void* x, const float* w, const void* y, const void* dy, int T, int N, int K, int C, int act,
+                                        float scale, float clamp_lo, float clamp_hi, int batch_major, void* dx, float* dw, float* db,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    return bh_k_linear_train_backward(x, w, y, dy, T, N, K, C, act, scale, clamp_lo, clamp_hi, batch_major, dx, dw, db, workspace,
+                                      workspace_bytes, (hipStream_t)stream);
+}
 extern "C" size_t bh_sw_workspace(int n, int max_seq, int max_ref) { return bh_k_sw_workspace(n, max_seq, max_ref); }
 extern "C" int bh_sw_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, const void* refs, long ref_stride,
                            const int32_t* ref_lengths, int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace,

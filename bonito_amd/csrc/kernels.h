@@ -158,6 +158,22 @@ int bh_k_lstm_train_backward(const void* x, const float* w_ih, const float* w_hh
                              int N, int H, int reverse, void* dx, float* dw_ih, float* dw_hh, float* dbias, void* workspace,
                              size_t workspace_bytes, hipStream_t stream);
 
+// train_layers.hip (the convolution and the linear / CRF-head layer for training: forward on the rounded master weights, and the backward)
+size_t bh_k_conv_train_workspace(int N, int Lin, int Cin, int Cout, int K, int stride, int pad);
+int bh_k_conv_train_forward(const void* x, const float* w, const float* bias, int N, int Lin, int Cin, int Cout, int K, int stride, int pad,
+                            int act, float clamp_lo, float clamp_hi, long os_n, long os_t, void* y, void* workspace, size_t workspace_bytes,
+                            hipStream_t stream);
+int bh_k_conv_train_backward(const void* x, const float* w, const float* bias, const void* y, const void* dy, int N, int Lin, int Cin, int Cout,
+                             int K, int stride, int pad, int act, float clamp_lo, float clamp_hi, long os_n, long os_t, void* dx, float* dw,
+                             float* db, void* workspace, size_t workspace_bytes, hipStream_t stream);
+size_t bh_k_linear_train_workspace(int T, int N, int K, int C);
+int bh_k_linear_train_forward(const void* x, const float* w, const float* bias, int T, int N, int K, int C, int act, float scale,
+                              float clamp_lo, float clamp_hi, int batch_major, void* y, void* workspace, size_t workspace_bytes,
+                              hipStream_t stream);
+int bh_k_linear_train_backward(const void* x, const float* w, const void* y, const void* dy, int T, int N, int K, int C, int act, float scale,
+                               float clamp_lo, float clamp_hi, int batch_major, void* dx, float* dw, float* db, void* workspace,
+                               size_t workspace_bytes, hipStream_t stream);
+
 // align.hip (Smith-Waterman, affine gaps, traceback; the lengths are host arrays)
 size_t bh_k_sw_workspace(int n, int max_seq, int max_ref);
 int bh_k_sw_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,

@@ -1,0 +1,296 @@
+"""
+The convolution and the linear / CRF-head layer for training on the device: forward on the rounded master weights, backward, and their
+autograd (csrc/train_layers.hip; the arithmetic is stated in include/bonito_hip.h under bh_conv1d_train_forward).
+
+    y = conv1d_forward(x, weight, bias, stride, padding, activation, clamp, time_major)     # x fp16 [N][Lin][Cin] ([N][Lin] for Cin == 1)
+    dx, dw, db = conv1d_backward(x, weight, bias, y, dy, stride, padding, activation, clamp, time_major)
+    y = conv1d(x, weight, bias, stride, padding, activation, clamp, time_major)             # differentiable
+    y = linear_forward(x, weight, bias, activation, scale, clamp, batch_major_out)          # x fp16 [T][N][K]
+    dx, dw, db = linear_backward(x, weight, y, dy, activation, scale, clamp, batch_major_out)
+    y = linear(x, weight, bias, activation, scale, clamp, batch_major_out)                  # differentiable
+
+Activations are channel-minor: a convolution returns [N][Lout][Cout], or time-major [Lout][N][Cout] (the permute in front of the LSTM
+stack, folded into the store). weight and bias are the fp32 master tensors in torch's layout ([Cout][Cin][K], [C][K]).
+
+torch allocates and orders the streams; every number is computed by libbonito_hip.so. There is no PyTorch fallback: CPU tensors raise
+NoTorchCompute, an unsupported shape or dtype raises ValueError before anything is launched.
+"""
+import math
+
+import torch
+
+from bonito_amd import _lib
+from bonito_amd.nn import NoTorchCompute
+
+__all__ = ["conv1d_forward", "conv1d_backward", "conv1d", "linear_forward", "linear_backward", "linear", "conv_out_len"]
+
+_INF = float("inf")
+
+
+def conv_out_len(Lin, K, stride, padding):
+    return (Lin + 2 * padding - K) // stride + 1
+
+
+def _act(activation, allowed, what):
+    name = activation if activation is None or isinstance(activation, str) else getattr(activation, "name", type(activation).__name__.lower())
+    if name == "silu":
+        name = "swish"
+    if name not in allowed:
+        raise ValueError("%s: activation %r is not supported (one of %s)" % (what, name, ", ".join(str(a) for a in allowed)))
+    return _lib.BH_ACT[name]
+
+
+def _clamp(clamp, what):
+    if clamp is None:
+        return -_INF, _INF
+    lo, hi = float(clamp[0]), float(clamp[1])
+    if not lo <= hi:
+        raise ValueError("%s: clamp range (%g, %g) is empty" % (what, lo, hi))
+    return lo, hi
+
+
+def _devices(tensors, what):
+    """Shapes and dtypes are judged first (they are wrong on any device); then every tensor must be on one HIP device."""
+    first = tensors[0][1]
+    for name, t in tensors:
+        if t.device.type != "cuda":
+            raise NoTorchCompute("%s runs on a HIP device only; %s is a %s tensor" % (what, name, t.device))
+        if t.device != first.device:
+            raise ValueError("%s: %s is on %s, %s on %s" % (what, name, t.device, tensors[0][0], first.device))
+
+
+def _tensors(named, what):
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a tensor, got %s" % (what, name, type(t).__name__))
+
+
+def _master(t, shape, name, what):
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: %s must be %s, got %s" % (what, name, tuple(shape), tuple(t.shape)))
+    if t.dtype != torch.float32:
+        raise ValueError("%s: %s must be float32 (the master weights), got %s" % (what, name, t.dtype))
+
+
+def _half(t, shape, name, what):
+    if t.dtype != torch.float16 or tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: %s must be float16 %s, got %s %s" % (what, name, tuple(shape), t.dtype, tuple(t.shape)))
+
+
+# ---- convolution ------------------------------------------------------------------------------------------------------------------------
+def _conv_check(x, weight, bias, stride, padding, activation, clamp, what, dtypes=(torch.float16,), devices=True):
+    named = [("x", x), ("weight", weight)] + ([("bias", bias)] if bias is not None else [])
+    _tensors(named, what)
+    if weight.dim() != 3:
+        raise ValueError("%s: weight must be [Cout][Cin][K], got %s" % (what, tuple(weight.shape)))
+    Cout, Cin, K = weight.shape
+    if x.dtype not in dtypes:
+        raise ValueError("%s: x must be %s, got %s" % (what, " or ".join(str(d).replace("torch.", "") for d in dtypes), x.dtype))
+    if not ((x.dim() == 3 and x.shape[2] == Cin) or (x.dim() == 2 and Cin == 1)) or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("%s: x must be [N][Lin][%d]%s, got %s" % (what, Cin, " or [N][Lin]" if Cin == 1 else "", tuple(x.shape)))
+    _master(weight, (Cout, Cin, K), "weight", what)
+    if bias is not None:
+        _master(bias, (Cout,), "bias", what)
+    N, Lin = int(x.shape[0]), int(x.shape[1])
+    stride, padding = int(stride), int(padding)
+    act = _act(activation, (None, "none", "swish", "tanh", "relu"), what)
+    lo, hi = _clamp(clamp, what)
+    if not (Cin == 1 or Cin % 8 == 0) or Cout % 4 != 0:
+        raise ValueError("%s: Cin must be 1 or a multiple of 8 and Cout a multiple of 4 (Cin=%d Cout=%d)" % (what, Cin, Cout))
+    if not (1 <= K <= 32 and 1 <= stride <= 8 and 0 <= padding < K and Lin + 2 * padding >= K):
+        raise ValueError("%s: K <= 32, stride <= 8, padding < K and one whole window are needed (K=%d stride=%d padding=%d Lin=%d)"
+                         % (what, K, stride, padding, Lin))
+    if devices:
+        _devices(named, what)
+    return N, Lin, int(Cin), int(Cout), int(K), stride, padding, act, lo, hi
+
+
+def _conv_strides(N, Lout, Cout, time_major):
+    return (Cout, N * Cout) if time_major else (Lout * Cout, Cout)
+
+
+def conv1d_forward(x, weight, bias=None, stride=1, padding=0, activation=None, clamp=None, time_major=False):
+    """-> y fp16 [N][Lout][Cout], or [Lout][N][Cout] with time_major: the bytes bh_conv1d_first / bh_conv1d give on the rounded weights."""
+    N, Lin, Cin, Cout, K, stride, padding, act, lo, hi = _conv_check(x, weight, bias, stride, padding, activation, clamp, "conv1d_forward")
+    x, weight = x.contiguous(), weight.detach().contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    lib = _lib.lib()
+    nbytes = lib.bh_conv1d_train_workspace(N, Lin, Cin, Cout, K, stride, padding)
+    if nbytes == 0:
+        raise ValueError("conv1d_forward: shape N=%d Lin=%d Cin=%d Cout=%d K=%d stride=%d padding=%d is not supported"
+                         % (N, Lin, Cin, Cout, K, stride, padding))
+    Lout = conv_out_len(Lin, K, stride, padding)
+    os_n, os_t = _conv_strides(N, Lout, Cout, time_major)
+    with torch.cuda.device(x.device):
+        y = torch.empty((Lout, N, Cout) if time_major else (N, Lout, Cout), dtype=torch.float16, device=x.device)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _lib.check(lib.bh_conv1d_train_forward(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), N, Lin, Cin, Cout, K, stride, padding, act, lo, hi,
+                                               os_n, os_t, _lib.ptr(y), _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device)),
+                   "bh_conv1d_train_forward")
+    return y
+
+
+def conv1d_backward(x, weight, bias, y, dy, stride=1, padding=0, activation=None, clamp=None, time_major=False, need_dx=True,
+                    need_db=True):
+    """-> (dx fp16 in the shape of x or None, dw fp32 [Cout][Cin][K], db fp32 [Cout] or None) from y and the upstream gradient dy (both
+    fp16 in the layout conv1d_forward returned)."""
+    what = "conv1d_backward"
+    N, Lin, Cin, Cout, K, stride, padding, act, lo, hi = _conv_check(x, weight, bias, stride, padding, activation, clamp, what, devices=False)
+    _tensors([("y", y), ("dy", dy)], what)
+    Lout = conv_out_len(Lin, K, stride, padding)
+    shape = (Lout, N, Cout) if time_major else (N, Lout, Cout)
+    _half(y, shape, "y", what)
+    _half(dy, shape, "dy", what)
+    _devices([("x", x), ("weight", weight), ("y", y), ("dy", dy)] + ([("bias", bias)] if bias is not None else []), what)
+    x, weight, y, dy = x.contiguous(), weight.detach().contiguous(), y.contiguous(), dy.contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    lib = _lib.lib()
+    nbytes = lib.bh_conv1d_train_workspace(N, Lin, Cin, Cout, K, stride, padding)
+    if nbytes == 0:
+        raise ValueError("%s: shape N=%d Lin=%d Cin=%d Cout=%d K=%d stride=%d padding=%d is not supported"
+                         % (what, N, Lin, Cin, Cout, K, stride, padding))
+    os_n, os_t = _conv_strides(N, Lout, Cout, time_major)
+    with torch.cuda.device(x.device):
+        dx = torch.empty(x.shape, dtype=torch.float16, device=x.device) if need_dx else None
+        dw = torch.empty((Cout, Cin, K), dtype=torch.float32, device=x.device)
+        db = torch.empty(Cout, dtype=torch.float32, device=x.device) if need_db else None
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _lib.check(lib.bh_conv1d_train_backward(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y), _lib.ptr(dy), N, Lin, Cin, Cout, K,
+                                                stride, padding, act, lo, hi, os_n, os_t, _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
+                                                _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device)), "bh_conv1d_train_backward")
+    return dx, dw, db
+
+
+class _Conv1d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding, activation, clamp, time_major):
+        x16 = x if x.dtype == torch.float16 else x.to(torch.float16)
+        y = conv1d_forward(x16, weight, bias, stride, padding, activation, clamp, time_major)
+        ctx.save_for_backward(x16, weight, bias, y)
+        ctx.args = (stride, padding, activation, clamp, time_major)
+        ctx.x_dtype = x.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x16, weight, bias, y = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dw, db = conv1d_backward(x16, weight, bias, y, dy.to(torch.float16), *ctx.args, need_dx=need[0],
+                                     need_db=bias is not None and need[2])
+        return (dx.to(ctx.x_dtype) if need[0] else None, dw if need[1] else None, db if bias is not None and need[2] else None,
+                None, None, None, None, None)
+
+
+def conv1d(x, weight, bias=None, stride=1, padding=0, activation=None, clamp=None, time_major=False):
+    """y fp16 of one convolution with its activation and clamp, differentiable with respect to x (fp16 or fp32; fp32 is cast to fp16 and
+    its gradient comes back as fp32), weight and bias, each where requires_grad is set. An input channel count that is neither 1 nor a
+    multiple of 8 (the 4 channels behind a first_conv_size = 4 layer) is served by zero channels: x and weight are padded to the next
+    multiple of 8 and the gradients sliced back."""
+    what = "conv1d"
+    both = (torch.float16, torch.float32)
+    _tensors([("x", x), ("weight", weight)], what)
+    if weight.dim() == 3 and x.dim() == 3 and weight.shape[1] != 1 and weight.shape[1] % 8 != 0 and x.shape[2] == weight.shape[1]:
+        if x.dtype not in both:
+            raise ValueError("conv1d: x must be float16 or float32, got %s" % x.dtype)
+        _master(weight, weight.shape, "weight", what)
+        _devices([("x", x), ("weight", weight)], what)
+        extra = -weight.shape[1] % 8
+        x = torch.nn.functional.pad(x, (0, extra))
+        weight = torch.nn.functional.pad(weight, (0, 0, 0, extra))
+    _conv_check(x, weight, bias, stride, padding, activation, clamp, what, dtypes=both)
+    return _Conv1d.apply(x, weight, bias, int(stride), int(padding), activation, clamp, bool(time_major))
+
+
+# ---- linear -----------------------------------------------------------------------------------------------------------------------------
+def _linear_check(x, weight, bias, activation, scale, clamp, what, dtypes=(torch.float16,), devices=True):
+    named = [("x", x), ("weight", weight)] + ([("bias", bias)] if bias is not None else [])
+    _tensors(named, what)
+    if weight.dim() != 2:
+        raise ValueError("%s: weight must be [C][K], got %s" % (what, tuple(weight.shape)))
+    C, K = weight.shape
+    if x.dtype not in dtypes:
+        raise ValueError("%s: x must be %s, got %s" % (what, " or ".join(str(d).replace("torch.", "") for d in dtypes), x.dtype))
+    if x.dim() != 3 or x.shape[2] != K or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("%s: x must be [T][N][%d] with T, N >= 1, got %s" % (what, K, tuple(x.shape)))
+    _master(weight, (C, K), "weight", what)
+    if bias is not None:
+        _master(bias, (C,), "bias", what)
+    act = _act(activation, (None, "none", "tanh"), what)
+    lo, hi = _clamp(clamp, what)
+    scale = 1.0 if scale is None else float(scale)
+    if scale == 0.0 or not math.isfinite(scale):
+        raise ValueError("%s: scale must be finite and not 0, got %r" % (what, scale))
+    if K % 8 != 0 or C % 8 != 0:
+        raise ValueError("%s: K and C must be multiples of 8 (K=%d C=%d)" % (what, K, C))
+    if devices:
+        _devices(named, what)
+    return int(x.shape[0]), int(x.shape[1]), int(K), int(C), act, scale, lo, hi
+
+
+def linear_forward(x, weight, bias=None, activation=None, scale=None, clamp=None, batch_major_out=False):
+    """-> Y fp16 [T][N][C], or [N][T][C] with batch_major_out (what Model.forward returns): the bytes of bh_linear on the rounded weights."""
+    T, N, K, C, act, scale, lo, hi = _linear_check(x, weight, bias, activation, scale, clamp, "linear_forward")
+    x, weight = x.contiguous(), weight.detach().contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    lib = _lib.lib()
+    nbytes = lib.bh_linear_train_workspace(T, N, K, C)
+    if nbytes == 0:
+        raise ValueError("linear_forward: shape T=%d N=%d K=%d C=%d is not supported" % (T, N, K, C))
+    with torch.cuda.device(x.device):
+        y = torch.empty((N, T, C) if batch_major_out else (T, N, C), dtype=torch.float16, device=x.device)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _lib.check(lib.bh_linear_train_forward(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), T, N, K, C, act, scale, lo, hi,
+                                               int(bool(batch_major_out)), _lib.ptr(y), _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device)),
+                   "bh_linear_train_forward")
+    return y
+
+
+def linear_backward(x, weight, y, dy, activation=None, scale=None, clamp=None, batch_major_out=False, need_dx=True, need_db=True):
+    """-> (dx fp16 [T][N][K] or None, dw fp32 [C][K], db fp32 [C] or None) from Y and the upstream gradient dy (fp16, in Y's layout)."""
+    what = "linear_backward"
+    T, N, K, C, act, scale, lo, hi = _linear_check(x, weight, None, activation, scale, clamp, what, devices=False)
+    _tensors([("y", y), ("dy", dy)], what)
+    shape = (N, T, C) if batch_major_out else (T, N, C)
+    _half(y, shape, "y", what)
+    _half(dy, shape, "dy", what)
+    _devices([("x", x), ("weight", weight), ("y", y), ("dy", dy)], what)
+    x, weight, y, dy = x.contiguous(), weight.detach().contiguous(), y.contiguous(), dy.contiguous()
+    lib = _lib.lib()
+    nbytes = lib.bh_linear_train_workspace(T, N, K, C)
+    if nbytes == 0:
+        raise ValueError("%s: shape T=%d N=%d K=%d C=%d is not supported" % (what, T, N, K, C))
+    with torch.cuda.device(x.device):
+        dx = torch.empty((T, N, K), dtype=torch.float16, device=x.device) if need_dx else None
+        dw = torch.empty((C, K), dtype=torch.float32, device=x.device)
+        db = torch.empty(C, dtype=torch.float32, device=x.device) if need_db else None
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _lib.check(lib.bh_linear_train_backward(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(y), _lib.ptr(dy), T, N, K, C, act, scale, lo, hi,
+                                                int(bool(batch_major_out)), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), nbytes,
+                                                _lib.stream_ptr(x.device)), "bh_linear_train_backward")
+    return dx, dw, db
+
+
+class _Linear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, activation, scale, clamp, batch_major_out):
+        x16 = x if x.dtype == torch.float16 else x.to(torch.float16)
+        y = linear_forward(x16, weight, bias, activation, scale, clamp, batch_major_out)
+        ctx.save_for_backward(x16, weight, y)
+        ctx.args = (activation, scale, clamp, batch_major_out)
+        ctx.x_dtype, ctx.has_bias = x.dtype, bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x16, weight, y = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want_db = ctx.has_bias and need[2]
+        dx, dw, db = linear_backward(x16, weight, y, dy.to(torch.float16), *ctx.args, need_dx=need[0], need_db=want_db)
+        return (dx.to(ctx.x_dtype) if need[0] else None, dw if need[1] else None, db if want_db else None, None, None, None, None)
+
+
+def linear(x, weight, bias=None, activation=None, scale=None, clamp=None, batch_major_out=False):
+    """Y fp16 of one linear layer or CRF head (activation none or tanh, scale, clamp), differentiable with respect to x (fp16 or fp32;
+    fp32 is cast to fp16 and its gradient comes back as fp32), weight and bias, each where requires_grad is set."""
+    _linear_check(x, weight, bias, activation, scale, clamp, "linear", dtypes=(torch.float16, torch.float32))
+    return _Linear.apply(x, weight, bias, activation, scale, clamp, bool(batch_major_out))

@@ -353,6 +353,44 @@ int bh_lstm_train_backward(const void* x, const float* w_ih, const float* w_hh, 
                            int N, int H, int reverse, void* dx, float* dw_ih, float* dw_hh, float* dbias, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---- The convolution and the linear / CRF-head layer for training (csrc/train_layers.hip): forward on the rounded master weights, backward ----
+ * With bh_lstm_train_* and bh_crf_seq_logz_grad these are all layers of an LSTM-family CRF model (SeqdistModel.forward_train).
+ * Arithmetic (that of autocast training, as for the LSTM layer): activations and their gradients are fp16; w and bias are fp32 DEVICE
+ *   tensors in torch's layout, rounded to nearest fp16 on the device in every call; every sum is fp32; dw and db are fp32 and
+ *   OVERWRITTEN. No floating-point atomics: the rows are split into blocks by a rule of the shape alone and the partial sums are added
+ *   in block order, so two calls give equal bytes.
+ * Convolution: x fp16 [N][Lin][Cin] channel-minor ([N][Lin] for Cin == 1), w [Cout][Cin][K], y = clamp(act(conv(x, w) + bias), lo, hi)
+ *   written at n * os_n + t * os_t + c (os_n = Cout, os_t = N * Cout stores time-major [T][N][C]), Lout = (Lin + 2 pad - K) / stride + 1.
+ *   forward: y has the bytes of bh_conv1d_first / bh_conv1d on the same rounded weights and bias; the workspace then BEGINS with the
+ *   weights as those kernels read them (Cin > 1: the bytes of bh_conv1d_pack, bh_conv1d_packed_halves halves; Cin == 1: fp32 [Cout][K]).
+ *   backward, dy in the layout of y:  dz = dy * m * act'(z) stored as fp16, m = [lo < y < hi] read from the STORED y (strictly inside;
+ *   m = 1 for lo = -inf, hi = +inf), act' at z recomputed in fp32 from x and the rounded weights;  db[c] = sum dz;
+ *   dw[co][ci][k] = sum_{n,t} dz[n][t][co] x[n][t s - p + k][ci];  dx[n][l][ci] = sum_{co,k: (l+p-k) mod s = 0} w[co][ci][k] dz[n][(l+p-k)/s][co]
+ *   as fp16 in the layout of x. dx and db may be NULL = not computed.
+ *   Supported: Cin == 1 or Cin % 8 == 0, Cout % 4 == 0, K <= 32, stride <= 8, pad < K, Lin + 2 pad >= K, os_n and os_t multiples of 4.
+ * Linear: x fp16 [M][K] with rows m = t * N + n, w [C][K], Y = clamp(act(x w^T + bias) * scale, lo, hi), act none or tanh;
+ *   batch_major = 1 stores Y as [N][T][C] (the engine's row remap, what bh_encoder_forward returns), 0 as [T][N][C].
+ *   forward: the bytes of bh_linear on the rounded weights.  backward, dy in the layout of Y:  dZ[m][c] = dy * m * scale * act' as fp16,
+ *   m from the stored Y, tanh' = 1 - (Y / scale)^2 from the stored Y;  dx = dZ w (fp16, through bh_linear on the transposed rounded
+ *   weights), dw = dZ^T x, db = sum dZ. dx and db may be NULL. A fixed blank column (expand_blanks) is never materialised.
+ *   Supported: K % 8 == 0, C % 8 == 0, T * N < 2^31; T * N * C may pass 2^31 elements (64-bit offsets throughout).
+ * workspace (bh_*_train_workspace, one size for forward and backward of a shape; 0 = unsupported shape): the caller's, 16-byte aligned.
+ * Anything unsupported returns nonzero with bh_last_error() set, launches nothing and leaves every output untouched.
+ * Stream-ordered; nothing is allocated and nothing synchronises inside. */
+size_t bh_conv1d_train_workspace(int N, int Lin, int Cin, int Cout, int K, int stride, int pad);
+int bh_conv1d_train_forward(const void* x, const float* w, const float* bias, int N, int Lin, int Cin, int Cout, int K, int stride, int pad,
+                            int act, float clamp_lo, float clamp_hi, long os_n, long os_t, void* y, void* workspace, size_t workspace_bytes,
+                            void* stream);
+int bh_conv1d_train_backward(const void* x, const float* w, const float* bias, const void* y, const void* dy, int N, int Lin, int Cin, int Cout,
+                             int K, int stride, int pad, int act, float clamp_lo, float clamp_hi, long os_n, long os_t, void* dx, float* dw,
+                             float* db, void* workspace, size_t workspace_bytes, void* stream);
+size_t bh_linear_train_workspace(int T, int N, int K, int C);
+int bh_linear_train_forward(const void* x, const float* w, const float* bias, int T, int N, int K, int C, int act, float scale,
+                            float clamp_lo, float clamp_hi, int batch_major, void* y, void* workspace, size_t workspace_bytes, void* stream);
+int bh_linear_train_backward(const void* x, const float* w, const void* y, const void* dy, int T, int N, int K, int C, int act, float scale,
+                             float clamp_lo, float clamp_hi, int batch_major, void* dx, float* dw, float* db, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* ---- Smith-Waterman local alignment with affine gaps and a traceback (csrc/align.hip) ----------------------------------
  * n pairs of a called sequence `seq` (the query, index i) and a known sequence `ref` (index j). seqs / refs: DEVICE int8 planes
  * [n][stride] of the codes 1..4 (decode.encode_sequences), 0 = padding. seq_lengths / ref_lengths: HOST int32 [n] (they are
