@@ -138,6 +138,7 @@ SIGNATURES = {
     "bh_lstm_workspace": (_sz, [_i, _i]),
     "bh_lstm_layer": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "bh_lstm_q8_layer": (_i, [_vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "bh_lstm_q8_layer_split": (_i, [_vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "bh_lstm_layer_family": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "bh_lstm_launch_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i]),
     "bh_encoder_debug_read": (_i, [_vp, _vp, _sz, _sz]),

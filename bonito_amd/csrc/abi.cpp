@@ -183,10 +183,16 @@ extern "C" int bh_lstm_layer(const void* gates_in, const void* whh_packed, void*
 // Operator level (parity tests): one Q8-1 recurrent layer straight from fp32 host weights. Packs, uploads, quantises x with
 // the static scale 127 / bound, runs the 8-bit kernel and synchronises. `sums` (optional) receives the exact int32 partial sums
 // [T][N][4H][2] (input part, recurrent part) the gate arithmetic started from; `hq_frag` (optional) the int8 output in
-// fragment order [T][N/16][ceil(H/64)][64][16].
-extern "C" int bh_lstm_q8_layer(const void* x, float bound, const float* w_ih, const float* w_hh, const float* bias, int T, int N,
-                                int H, int reverse, int variant, void* h16_out, int8_t* hq_frag, int32_t* sums, void* stream_) {
-    BH_REQUIRE(x && w_ih && w_hh && h16_out && T > 0 && N > 0 && N % 16 == 0, "lstm_q8_layer: bad arguments");
+// fragment order [T][N/16][ceil(H/64)][64][16]. The kernel instance follows from the outputs asked for, as in forward_lstm_q8:
+// sums -> <LAST, DBG> (tests only), else h16_out -> <LAST> (the last recurrent layer), else hq_frag alone -> neither (the layers
+// before it). max_rings_per_launch > 0 caps the rings of one launch below what the device holds, so that the split loop runs on
+// small batches; it never raises the device's figure. bh_lstm_q8_layer is the same call with max_rings_per_launch = 0.
+extern "C" int bh_lstm_q8_layer_split(const void* x, float bound, const float* w_ih, const float* w_hh, const float* bias, int T, int N,
+                                      int H, int reverse, int variant, void* h16_out, int8_t* hq_frag, int32_t* sums,
+                                      int max_rings_per_launch, void* stream_) {
+    BH_REQUIRE(x && w_ih && w_hh && T > 0 && N > 0 && N % 16 == 0 && max_rings_per_launch >= 0, "lstm_q8_layer: bad arguments");
+    BH_REQUIRE(h16_out || hq_frag, "lstm_q8_layer: neither h16_out nor hq_frag given");
+    BH_REQUIRE(h16_out || !sums, "lstm_q8_layer: sums need h16_out (the instance that dumps them also writes the fp16 rows)");
     const int U = bh_k_lstm_q8_units(H, variant);
     BH_REQUIRE(U != 0, "lstm_q8_layer: hidden size %d is not covered by the 8-bit kernel", H);
     hipStream_t st = (hipStream_t)stream_;
@@ -205,13 +211,14 @@ extern "C" int bh_lstm_q8_layer(const void* x, float bound, const float* w_ih, c
     int rc = bh_k_quantise_rows(x, xq.p, T, N, H, R, bound, st);
     if (!rc) rc = bh_k_lstm_q8_arm(ex.p, R, H, st);
     if (rc) return rc;
-    const int per = bh_k_lstm_q8_geometry(H, variant).rings_per_launch(bh_cu_count());
+    int per = bh_k_lstm_q8_geometry(H, variant).rings_per_launch(bh_cu_count());
     BH_REQUIRE(per >= 1, "lstm_q8_layer: device has too few CUs for hidden size %d", H);
+    if (max_rings_per_launch > 0) per = std::min(per, max_rings_per_launch);
     for (int r0 = 0; r0 < R; r0 += per) {
         const int nr = std::min(per, R - r0);
         rc = bh_k_lstm_layer_q8((const char*)xq.p + (size_t)r0 * tile, q_wih.p, q_whh.p, (const float*)q_sx.p, (const float*)q_sh.p,
                                 (const float*)q_b.p, hq_frag ? (char*)hq_frag + (size_t)r0 * tile : nullptr,
-                                (char*)h16_out + (size_t)r0 * 16 * H * 2, (char*)ex.p + (size_t)r0 * tile, T, N, H, R, nr, reverse,
+                                h16_out ? (char*)h16_out + (size_t)r0 * 16 * H * 2 : nullptr, (char*)ex.p + (size_t)r0 * tile, T, N, H, R, nr, reverse,
                                 (int*)err.p, st, (int*)ws.p, 0, variant, sums ? sums + (size_t)r0 * 16 * 4 * H * 2 : nullptr,
                                 (unsigned)bh::g_opt.lstm_max_spins);
         if (rc) return rc;
@@ -221,6 +228,10 @@ extern "C" int bh_lstm_q8_layer(const void* x, float bound, const float* w_ih, c
     BH_CHECK_HIP(hipStreamSynchronize(st));
     BH_REQUIRE(flag == 0, "lstm_q8_layer: exchange timeout in the recurrent kernel");
     return 0;
+}
+extern "C" int bh_lstm_q8_layer(const void* x, float bound, const float* w_ih, const float* w_hh, const float* bias, int T, int N,
+                                int H, int reverse, int variant, void* h16_out, int8_t* hq_frag, int32_t* sums, void* stream_) {
+    return bh_lstm_q8_layer_split(x, bound, w_ih, w_hh, bias, T, N, H, reverse, variant, h16_out, hq_frag, sums, 0, stream_);
 }
 // Operator level (parity tests): one fp16 recurrent layer on a chosen kernel family from fp32 host weights, packed by the functions
 // bh_encoder_create packs with (lstm_pack.h), in the layouts the instance wants, and launched the way forward_lstm launches it.

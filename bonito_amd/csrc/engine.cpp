@@ -61,6 +61,7 @@ struct Layer {
     bool pointwise = false;     // K=1, stride 1 convolution executed by the GEMM kernel (supports the residual add)
     // 8-bit recurrent path (Q8-1, lstm_q8.hip): int8 weight tiles, per-row scales (s_ih * bound/127, s_hh/127), bound of the input
     bool q8 = false;
+    bool q8_only = false;       // no fp16 family has an instance for this width (144, 336): the "lstm_q8" A/B switch cannot turn it off
     int q_variant = 0;
     float q_bound = 1.0f;
     DevBuf q_wih, q_whh, q_sx, q_sh;
@@ -308,7 +309,7 @@ static LstmPlan lstm_plan(const bh_encoder* e, const Layer& l, int Np) {
     const bh_layer_t& d = l.d;
     const int H = d.out_size;
     const bool regs = lstm_admits(d, BH_LSTM_WAVE);             // W_hh stays in registers (else: wide or streaming kernel)
-    const bool q8 = l.q8 && e->lstm_q8 && d.in_size == H;       // clears everything below
+    const bool q8 = l.q8 && (e->lstm_q8 || l.q8_only) && d.in_size == H;       // clears everything below
     const bool wide = !q8 && !regs && e->lstm_wide && lstm_admits(d, BH_LSTM_WIDE);
     const bool fused = !q8 && e->lstm_fused && lstm_admits(d, BH_LSTM_FUSED);
     const bool share = fused && e->lstm_fused >= 2 && lstm_admits(d, BH_LSTM_WGX);
@@ -386,8 +387,11 @@ static int create_lstm(bh_encoder* e, size_t i, const bh_layer_t& d, CreateState
     const int H = d.out_size, I = d.in_size;
     BH_REQUIRE(d.w0 && d.w1 && H > 0 && I > 0, "encoder_create: layer %zu: malformed lstm", i);
     const std::vector<const bh_lstm_instance*> rows = lstm_admitted(d);
-    BH_REQUIRE(!rows.empty() && I % 8 == 0,
-               "encoder_create: layer %zu: lstm needs hidden %% 32 == 0 (<= 512) or %% 64 == 0 (<= 1024), insize %% 8 == 0 (got %d, %d)", i, H, I);
+    // a width that only the 8-bit kernel has an instance for (144, 336) runs where the layer is quantised, and nowhere else
+    BH_REQUIRE((!rows.empty() || lstm_admits_q8(d)) && I % 8 == 0,
+               "encoder_create: layer %zu: lstm needs hidden %% 32 == 0 (<= 512) or %% 64 == 0 (<= 1024), or a quantised layer of a width "
+               "the 8-bit kernel serves, insize %% 8 == 0 (got %d, %d)", i, H, I);
+    L.q8_only = rows.empty();
     std::vector<float> b((size_t)4 * H);
     lstm_pack_bias(BH_LSTM_W_ROWS, d.b0, d.b1, H, b.data());
     int rc = upload_f32(L.b0, b.data(), b.size());

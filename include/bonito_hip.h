@@ -95,7 +95,8 @@ typedef struct bh_layer {
     int32_t scale_factor;               /* upsample */
     int32_t groups;      /* conv: 1 */
     int32_t add_residual;               /* conv (pointwise): add the pending residual projection before the activation */
-    int32_t quantize;    /* lstm: 1 = 8-bit recurrent path Q8-1 where the kernel covers the shape (koi's `quantize`, crf/model.py:245) */
+    int32_t quantize;    /* lstm: 1 = 8-bit recurrent path Q8-1 where the kernel covers the shape (koi's `quantize`, crf/model.py:245);
+                            hidden sizes 144 and 336 have an 8-bit kernel and no fp16 one: such a layer is accepted only with quantize = 1 */
     int32_t reserved_i[1];
     float scale;         /* linear_crf: multiply after activation (0 = none) */
     float clamp_lo, clamp_hi;           /* clamp */
@@ -538,11 +539,19 @@ int bh_signal_chunks(const int16_t* raw, const long* offsets, const float* cal_s
 
 /* Operator level (parity tests): one recurrent layer of the 8-bit path Q8-1 (koi's `quantize`, bonito/crf/model.py:245; the
  * arithmetic is defined in oracle/lstm_q8_ref.py) from fp32 HOST weights W_ih, W_hh [4H][H] and bias [4H] (b_ih + b_hh, or NULL).
- * x: device fp16 [T][N][H], N % 16 == 0, quantised with the static scale 127 / bound; h16_out: device fp16 [T][N][H];
- * hq_frag (or NULL): device int8 output in MFMA fragment order [T][N/16][ceil(H/64)][64][16]; sums (or NULL): device int32
- * [T][N][4H][2] = the exact integer sums (input part, recurrent part) per gate row. variant: see "lstm_q8_variant". Synchronises. */
+ * x: device fp16 [T][N][H], N % 16 == 0, quantised with the static scale 127 / bound; h16_out (or NULL): device fp16 [T][N][H];
+ * hq_frag (or NULL): device int8 output in MFMA fragment order [T][N/16][ceil(H/64)][64][16] (padding units of the last k-step,
+ * H % 64 != 0, are not written); sums (or NULL): device int32 [T][N][4H][2] = the exact integer sums (input part, recurrent part)
+ * per gate row. The outputs choose the kernel instance the way the engine does: sums -> the debug instance (needs h16_out); else
+ * h16_out -> the last recurrent layer's; hq_frag alone -> the one of the layers before it. Giving neither output is an error.
+ * variant: see "lstm_q8_variant". Synchronises. */
 int bh_lstm_q8_layer(const void* x, float bound, const float* w_ih, const float* w_hh, const float* bias, int T, int N, int H,
                      int reverse, int variant, void* h16_out, int8_t* hq_frag, int32_t* sums, void* stream);
+/* The same call with the launch split forced. max_rings_per_launch: 0 = as many rings per launch as the device holds (which is
+ * bh_lstm_q8_layer); n > 0 = at most n, never more than the device holds, so that the split into several launches runs on a small batch. */
+int bh_lstm_q8_layer_split(const void* x, float bound, const float* w_ih, const float* w_hh, const float* bias, int T, int N, int H,
+                           int reverse, int variant, void* h16_out, int8_t* hq_frag, int32_t* sums, int max_rings_per_launch,
+                           void* stream);
 
 /* The recurrent kernel families of csrc/lstm.hip (BH_LSTM_Q8: csrc/lstm_q8.hip). The widths named below are read off the instance
  * table of lstm.hip (bh_lstm_launch_plan reports it); tests/test_gpu_lstm.py keeps an independent list. */
