@@ -53,23 +53,32 @@ def accuracy_of(num_correct, num_mismatches, num_insertions, num_deletions):
     return np.divide(c, total, out=np.zeros_like(total, dtype=np.float64), where=total > 0)
 
 
-class SwBatch:
-    """Results of one ``sw_align`` call in the caller's order: ``table`` int32 [n, 10] (``COLUMNS``), ``seq_len`` / ``ref_len``,
-    ``cigar`` (list of strings, or None); every column is an attribute, ``batch[i]`` is an ``AlignResult``."""
+class _Batch:
+    """What ``SwBatch`` and ``NwBatch`` share: ``table`` int32 [n, len(columns)], ``seq_len`` / ``ref_len``, every column an attribute."""
+    columns = ()
 
-    def __init__(self, table, seq_len, ref_len, cigar=None):
-        self.table = np.asarray(table, np.int32).reshape(-1, len(COLUMNS))
+    def __init__(self, table, seq_len, ref_len):
+        self.table = np.asarray(table, np.int32).reshape(-1, len(self.columns))
         self.seq_len = np.asarray(seq_len, np.int32)
         self.ref_len = np.asarray(ref_len, np.int32)
-        self.cigar = cigar
 
     def __len__(self):
         return self.table.shape[0]
 
     def __getattr__(self, name):
-        if name in COLUMNS:
-            return self.table[:, COLUMNS.index(name)]
+        if name in self.columns:
+            return self.table[:, self.columns.index(name)]
         raise AttributeError(name)
+
+
+class SwBatch(_Batch):
+    """Results of one ``sw_align`` call in the caller's order: ``table`` int32 [n, 10] (``COLUMNS``), ``seq_len`` / ``ref_len``,
+    ``cigar`` (list of strings, or None); every column is an attribute, ``batch[i]`` is an ``AlignResult``."""
+    columns = COLUMNS
+
+    def __init__(self, table, seq_len, ref_len, cigar=None):
+        super().__init__(table, seq_len, ref_len)
+        self.cigar = cigar
 
     @property
     def accuracy(self):
@@ -107,23 +116,54 @@ def _encode(x, what):
     return codes, lens.numpy().astype(np.int32)
 
 
-def _slices(order, seq_len, ref_len, budget, lib):
-    """Cut the size-sorted pairs into runs whose bh_sw_workspace stays within the budget."""
-    out, lo = [], 0
+def _slices(order, seq_len, ref_len, band, budget, workspace):
+    """Cut the size-sorted pairs into runs whose workspace(count, max seq, max ref, max band) stays within the budget -> (runs of
+    (indices, max seq, max ref, max band), indices of the pairs that do not fit alone)."""
+    out, unfit, lo = [], [], 0
     while lo < len(order):
-        hi, ms, mr = lo, 0, 0
+        hi, ms, mr, mb = lo, 0, 0, 1
         while hi < len(order):
-            s, r = max(ms, int(seq_len[order[hi]])), max(mr, int(ref_len[order[hi]]))
-            if lib.bh_sw_workspace(hi - lo + 1, s, r) > budget:
+            i = order[hi]
+            s, r, b = max(ms, int(seq_len[i])), max(mr, int(ref_len[i])), max(mb, int(band[i]))
+            if workspace(hi - lo + 1, s, r, b) > budget:
                 break
-            hi, ms, mr = hi + 1, s, r
+            hi, ms, mr, mb = hi + 1, s, r, b
         if hi == lo:
-            raise ValueError("sw_align: workspace_budget of %d bytes cannot hold one pair of lengths (%d, %d), which needs %d"
-                             % (budget, seq_len[order[lo]], ref_len[order[lo]],
-                                lib.bh_sw_workspace(1, int(seq_len[order[lo]]), int(ref_len[order[lo]]))))
-        out.append((order[lo:hi], ms, mr))
+            unfit.append(order[lo])
+            lo += 1
+            continue
+        out.append((order[lo:hi], ms, mr, mb))
         lo = hi
-    return out
+    return out, unfit
+
+
+def _launch(entry, extra, nbytes, width, codes, lens, idx, ms, mr, need, device):
+    """One launch of the entry point named ``entry`` over the pairs ``idx`` (maxima ms, mr; ``extra``: its arguments between the pair
+    count and the workspace of ``nbytes`` bytes; ``need``: per pair the most CIGAR runs, or None for no CIGAR) -> (the int32 result
+    rows [len(idx), width], per pair its uint32 runs - views of one plane cut to the widest count - or None)."""
+    k = len(idx)
+    sel = torch.from_numpy(np.ascontiguousarray(idx))
+    s_dev = codes[0][sel][:, :max(ms, 1)].contiguous().to(device)
+    r_dev = codes[1][sel][:, :max(mr, 1)].contiguous().to(device)
+    s_len, r_len = np.ascontiguousarray(lens[0][idx]), np.ascontiguousarray(lens[1][idx])
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    res = torch.empty((k, width), dtype=torch.int32, device=device)
+    ops = n_ops = None
+    stride = 0
+    if need is not None:
+        stride = max(1, int(need[idx].max()))
+        ops = torch.empty((k, stride), dtype=torch.int32, device=device)
+        n_ops = torch.empty(k, dtype=torch.int32, device=device)
+    ip = C.POINTER(C.c_int32)
+    _lib.check(getattr(_lib.lib(), entry)(_lib.ptr(s_dev), s_dev.shape[1], s_len.ctypes.data_as(ip), _lib.ptr(r_dev), r_dev.shape[1],
+                                          r_len.ctypes.data_as(ip), k, *extra, _lib.ptr(ws), nbytes, _lib.ptr(res), _lib.ptr(ops),
+                                          stride, _lib.ptr(n_ops), _lib.stream_ptr(s_dev.device)), entry)
+    rows = res.cpu().numpy()
+    if need is None:
+        return rows, None
+    counts = n_ops.cpu().numpy()
+    plane = ops[:, :max(int(counts.max()), 1)].cpu().numpy().view(np.uint32)
+    return rows, [plane[row, :counts[row]] for row in range(k)]
 
 
 def sw_align(seqs, refs, match=5, mismatch=-4, gap_open=8, gap_extend=4, cigar=False, workspace_budget=DEFAULT_WORKSPACE_BUDGET,
@@ -159,36 +199,22 @@ def _affine(name, seqs, refs, match, mismatch, gap_open, gap_extend, cigar, work
     if n == 0:
         return SwBatch(table, sl, rl, cigars)
     lib = _lib.lib()
-    entry = lib.bh_sg_align if sg else lib.bh_sw_align
     passes = (sl.astype(np.int64) + 511) // 512
     order = np.argsort(passes * (rl.astype(np.int64) + 63), kind="stable")
-    ip = C.POINTER(C.c_int32)
-    for idx, ms, mr in _slices(order, sl, rl, int(workspace_budget), lib):
-        k = len(idx)
-        sel = torch.from_numpy(np.ascontiguousarray(idx))
-        s_dev = sc[sel][:, :max(ms, 1)].contiguous().to(device)
-        r_dev = rc[sel][:, :max(mr, 1)].contiguous().to(device)
-        s_len, r_len = np.ascontiguousarray(sl[idx]), np.ascontiguousarray(rl[idx])
-        nbytes = lib.bh_sw_workspace(k, ms, mr)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        res = torch.empty((k, len(COLUMNS)), dtype=torch.int32, device=device)
-        ops = n_ops = None
-        stride = 0
+    slices, unfit = _slices(order, sl, rl, np.ones(n, np.int64), int(workspace_budget), lambda k, s, r, b: lib.bh_sw_workspace(k, s, r))
+    if unfit:
+        i = unfit[0]
+        raise ValueError("sw_align: workspace_budget of %d bytes cannot hold one pair of lengths (%d, %d), which needs %d"
+                         % (int(workspace_budget), sl[i], rl[i], lib.bh_sw_workspace(1, int(sl[i]), int(rl[i]))))
+    need = None
+    if cigar:
+        need = sl + rl if sg else np.where((sl > 0) & (rl > 0), sl + rl - 1, 0)
+    for idx, ms, mr, _ in slices:
+        table[idx], runs = _launch("bh_sg_align" if sg else "bh_sw_align", (int(match), int(mismatch), int(gap_open), int(gap_extend)),
+                                   lib.bh_sw_workspace(len(idx), ms, mr), len(COLUMNS), (sc, rc), (sl, rl), idx, ms, mr, need, device)
         if cigar:
-            stride = max(1, int((s_len + r_len).max() if sg else np.where((s_len > 0) & (r_len > 0), s_len + r_len - 1, 0).max()))
-            ops = torch.empty((k, stride), dtype=torch.int32, device=device)
-            n_ops = torch.empty(k, dtype=torch.int32, device=device)
-        _lib.check(entry(_lib.ptr(s_dev), s_dev.shape[1], s_len.ctypes.data_as(ip), _lib.ptr(r_dev), r_dev.shape[1],
-                         r_len.ctypes.data_as(ip), k, int(match), int(mismatch), int(gap_open), int(gap_extend),
-                         _lib.ptr(ws), nbytes, _lib.ptr(res), _lib.ptr(ops), stride, _lib.ptr(n_ops),
-                         _lib.stream_ptr(s_dev.device)), "bh_sg_align" if sg else "bh_sw_align")
-        table[idx] = res.cpu().numpy()
-        if cigar:
-            counts = n_ops.cpu().numpy()
-            width = int(counts.max()) if k else 0
-            runs = ops[:, :max(width, 1)].cpu().numpy().view(np.uint32)
-            for row, i in enumerate(idx):
-                cigars[i] = runs_to_cigar(runs[row, :counts[row]])
+            for i, r in zip(idx, runs):
+                cigars[i] = runs_to_cigar(r)
     return SwBatch(table, sl, rl, cigars)
 
 
@@ -203,16 +229,15 @@ NW_WORKSPACE_BUDGET = 8 << 30
 NW_OK, NW_NO_FIT = 0, 2                          # status: accepted / the band the pair needs does not fit the workspace budget
 
 
-class NwBatch:
+class NwBatch(_Batch):
     """Results of one ``nw_align`` call in the caller's order: ``table`` int32 [n, 8] (``NW_COLUMNS``), ``seq_len`` / ``ref_len``,
     ``runs`` (per pair the uint32 runs of bh_nw_align, or None; no runs where status is not 0), ``cigar`` (the same as strings, made
     on first use: long reads have thousands of runs each) and ``ops(i)`` (the same as [(length, op character)]); every column is an
     attribute."""
+    columns = NW_COLUMNS
 
     def __init__(self, table, seq_len, ref_len, runs=None):
-        self.table = np.asarray(table, np.int32).reshape(-1, len(NW_COLUMNS))
-        self.seq_len = np.asarray(seq_len, np.int32)
-        self.ref_len = np.asarray(ref_len, np.int32)
+        super().__init__(table, seq_len, ref_len)
         self.runs = runs
         self._cigar = None
 
@@ -225,36 +250,6 @@ class NwBatch:
     def ops(self, i):
         r = self.runs[i]
         return list(zip((r >> 2).tolist(), [OPS[c] for c in (r & 3).tolist()]))
-
-    def __len__(self):
-        return self.table.shape[0]
-
-    def __getattr__(self, name):
-        if name in NW_COLUMNS:
-            return self.table[:, NW_COLUMNS.index(name)]
-        raise AttributeError(name)
-
-
-def _nw_slices(order, seq_len, ref_len, k, budget, lib):
-    """Cut the size-sorted pairs into runs whose bh_nw_workspace at half-width k stays within the budget -> (runs of (indices, max
-    seq, max ref, max band), indices of the pairs that do not fit alone)."""
-    out, unfit, lo = [], [], 0
-    band = np.abs(ref_len.astype(np.int64) - seq_len) + 2 * k + 1
-    while lo < len(order):
-        hi, ms, mr, mb = lo, 0, 0, 1
-        while hi < len(order):
-            i = order[hi]
-            s, r, b = max(ms, int(seq_len[i])), max(mr, int(ref_len[i])), max(mb, int(band[i]))
-            if lib.bh_nw_workspace(hi - lo + 1, s, r, b) > budget:
-                break
-            hi, ms, mr, mb = hi + 1, s, r, b
-        if hi == lo:
-            unfit.append(order[lo])
-            lo += 1
-            continue
-        out.append((order[lo:hi], ms, mr, mb))
-        lo = hi
-    return out, unfit
 
 
 def nw_align(seqs, refs, cigar=True, band=NW_FIRST_BAND, workspace_budget=NW_WORKSPACE_BUDGET, device="cuda"):
@@ -282,43 +277,25 @@ def nw_align(seqs, refs, cigar=True, band=NW_FIRST_BAND, workspace_budget=NW_WOR
     if n == 0:
         return NwBatch(table, sl, rl, runs)
     lib = _lib.lib()
-    ip = C.POINTER(C.c_int32)
+    need = sl + rl if cigar else None                                       # every op consumes a base
     todo = np.arange(n)
     while len(todo):
-        size = ((sl[todo].astype(np.int64) + 511) // 512) * np.minimum(rl[todo].astype(np.int64), 511 + np.abs(rl[todo] - sl[todo]) + 2 * k + 1)
-        slices, unfit = _nw_slices(todo[np.argsort(size, kind="stable")], sl, rl, k, int(workspace_budget), lib)
+        band = np.abs(rl.astype(np.int64) - sl) + 2 * k + 1
+        size = ((sl[todo].astype(np.int64) + 511) // 512) * np.minimum(rl[todo].astype(np.int64), 511 + band[todo])
+        slices, unfit = _slices(todo[np.argsort(size, kind="stable")], sl, rl, band, int(workspace_budget), lib.bh_nw_workspace)
         for i in unfit:
             table[i, 1:] = (0, 0, 0, 0, 0, k, NW_NO_FIT)
         again = []
         for idx, ms, mr, mb in slices:
-            cnt = len(idx)
-            sel = torch.from_numpy(np.ascontiguousarray(idx))
-            s_dev = sc[sel][:, :max(ms, 1)].contiguous().to(device)
-            r_dev = rc[sel][:, :max(mr, 1)].contiguous().to(device)
-            s_len, r_len = np.ascontiguousarray(sl[idx]), np.ascontiguousarray(rl[idx])
-            nbytes = lib.bh_nw_workspace(cnt, ms, mr, mb)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            res = torch.empty((cnt, len(NW_COLUMNS)), dtype=torch.int32, device=device)
-            ops = n_ops = None
-            stride = 0
-            if cigar:
-                stride = max(1, int((s_len + r_len).max()))
-                ops = torch.empty((cnt, stride), dtype=torch.int32, device=device)
-                n_ops = torch.empty(cnt, dtype=torch.int32, device=device)
-            _lib.check(lib.bh_nw_align(_lib.ptr(s_dev), s_dev.shape[1], s_len.ctypes.data_as(ip), _lib.ptr(r_dev), r_dev.shape[1],
-                                       r_len.ctypes.data_as(ip), cnt, k, _lib.ptr(ws), nbytes, _lib.ptr(res), _lib.ptr(ops), stride,
-                                       _lib.ptr(n_ops), _lib.stream_ptr(s_dev.device)), "bh_nw_align")
-            rows = res.cpu().numpy()
+            rows, got = _launch("bh_nw_align", (k,), lib.bh_nw_workspace(len(idx), ms, mr, mb), len(NW_COLUMNS), (sc, rc), (sl, rl), idx,
+                                ms, mr, need, device)
             table[idx] = rows
             if (rows[:, 7] > 1).any():
                 raise RuntimeError("nw_align: the traceback left the band of an accepted pair")
             again.append(idx[rows[:, 7] == 1])
             if cigar:
-                counts = n_ops.cpu().numpy()
-                width = int(counts.max()) if cnt else 0
-                plane = ops[:, :max(width, 1)].cpu().numpy().view(np.uint32)
-                for row, i in enumerate(idx):
-                    runs[i] = plane[row, :counts[row]].copy()
+                for i, r in zip(idx, got):
+                    runs[i] = r.copy()
         todo = np.concatenate(again) if again else np.zeros(0, np.int64)
         if len(todo) and k >= NW_MAX_BAND:
             raise RuntimeError("nw_align: a pair was rejected at the largest band")       # the largest band holds every cell

@@ -11,41 +11,30 @@
 // F of a strip and the reference base move to the next lane with one DPP wave shift each; lane 0 is fed from a register chunk
 // (64 columns per coalesced load: the reference bases and, from the second pass on, the boundary row the previous pass left
 // in the workspace). Each cell leaves 4 traceback bits (2: source of H, 1: E extended, 1: F extended); the 8 cells of a lane
-// and a step make one dword, stored as [pass][step][lane], so a wave's store is one contiguous 256 bytes.
+// and a step make one dword, stored as [pass][step][lane] (trace_at, pair_align.h: the parts shared with nw.hip), so a wave's store is
+// one contiguous 256 bytes.
 // Traceback kernel: one pair per thread walks the bits back from the end cell, counts the ops and writes the run-length ops.
 //
 // Semi-global mode (template parameter SG; bh_sg_align, the counterpart of parasail.sg_trace_scan_32 behind the reference's duplex end
 // repair, bonito/cli/duplex.py:240-243): H without the floor at 0, H(i,0) = H(0,j) = 0, the end cell is the largest H over the last row
 // and the last column (the smallest i, then the smallest j), the walk stops on reaching row 0 or column 0, and the CIGAR covers both
 // sequences completely - head and tail overhangs come out as one I or D run each.
-#include "common.h"
 #include "kernels.h"
-#include <vector>
+#include "pair_align.h"
 
 namespace bh {
 
-constexpr int SW_R = 8;                     // query rows per lane
-constexpr int SW_ROWS = WAVE * SW_R;        // query rows per pass
 constexpr int SW_MAX_LEN = 4096;
 constexpr int SW_MAX_PARAM = 32767;         // |score parameter| bound: 4096 * 32767 < 2^31
 constexpr int SW_NONE = -2147483647 - 1;     // semi-global: "no end cell yet", below every H
 constexpr int SW_NEG = -(1 << 30);          // E / F "minus infinity": NEG - extend cannot wrap, and no H - open reaches it
 
-struct SwArgs {
-    const int8_t* seq; long seq_stride;
-    const int8_t* ref; long ref_stride;
-    const int* seq_len; const int* ref_len;   // device copies at the head of the workspace
+struct SwArgs : PairArgs {
     int match, mismatch, open, ext;
     unsigned* trace; size_t trace_stride;     // dwords per pair
     int2* bound; size_t bound_stride;         // [pair][2][bound_stride] (H, F) of the last row of a pass, ping-pong by pass parity
     int* endcell;                             // [pair][4]: score, end_i, end_j
-    int* result; unsigned* ops; long ops_stride; int* n_ops;
 };
-
-// value of the lane below (lane - 1); lane 0, which has no source, keeps `first`
-__device__ __forceinline__ int wave_shr1(int first, int v) {
-    return __builtin_amdgcn_update_dpp(first, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-}
 
 // SG: the semi-global mode (H without the floor at 0, the end cell on the last row or the last column)
 template <bool SG>
@@ -57,13 +46,13 @@ __global__ __launch_bounds__(WAVE) void sw_forward_kernel(SwArgs a) {
         const int8_t* seq = a.seq + (long)pair * a.seq_stride;
         const int8_t* ref = a.ref + (long)pair * a.ref_stride;
         const int S = n + WAVE - 1;                                          // steps of one pass
-        const int passes = (m + SW_ROWS - 1) / SW_ROWS;
+        const int passes = (m + PA_ROWS - 1) / PA_ROWS;
         const int match = a.match, mismatch = a.mismatch, open = a.open, ext = a.ext;
         for (int p = 0; p < passes; ++p) {
-            const int row0 = p * SW_ROWS + lane * SW_R;
-            int q[SW_R], H[SW_R], E[SW_R], bH[SW_R], bJ[SW_R];
+            const int row0 = p * PA_ROWS + lane * PA_R;
+            int q[PA_R], H[PA_R], E[PA_R], bH[PA_R], bJ[PA_R];
 #pragma unroll
-            for (int r = 0; r < SW_R; ++r) {
+            for (int r = 0; r < PA_R; ++r) {
                 q[r] = row0 + r < m ? (int)seq[row0 + r] : 0;
                 H[r] = 0; E[r] = SW_NEG; bH[r] = SG ? SW_NONE : 0; bJ[r] = 0;
             }
@@ -71,8 +60,9 @@ __global__ __launch_bounds__(WAVE) void sw_forward_kernel(SwArgs a) {
             const int2* bin = a.bound + ((size_t)pair * 2 + (p & 1)) * a.bound_stride;
             int2* bout = a.bound + ((size_t)pair * 2 + ((p + 1) & 1)) * a.bound_stride;
             const bool keep = p + 1 < passes;                                // the next pass needs this pass's last row
-            unsigned* tr = a.trace + (size_t)pair * a.trace_stride + (size_t)p * S * WAVE + lane;
-            int oh = 0, of = 0;
+            // the lane's word of step 0 (where it would work on column -lane); a step on is WAVE words on
+            unsigned* tr = a.trace + (size_t)pair * a.trace_stride + trace_at(p, S, -lane, row0, 4).word;
+            PassHandoff<2> hand;
             for (int t0 = 0; t0 < S; t0 += WAVE) {
                 const int cj = t0 + lane;
                 const int cchunk = cj < n ? (int)ref[cj] : 0;
@@ -91,7 +81,7 @@ __global__ __launch_bounds__(WAVE) void sw_forward_kernel(SwArgs a) {
                         hdiag = hup;
                         unsigned bits = 0;
 #pragma unroll
-                        for (int r = 0; r < SW_R; ++r) {
+                        for (int r = 0; r < PA_R; ++r) {
                             const int s = q[r] == refc ? match : mismatch;
                             const int eo = H[r] - open, ee = E[r] - ext;
                             const int fo = hu - open, fe = fu - ext;
@@ -108,23 +98,11 @@ __global__ __launch_bounds__(WAVE) void sw_forward_kernel(SwArgs a) {
                         h_out = hu; f_out = fu;
                         tr[(size_t)t * WAVE] = bits;
                     }
-                    if (keep) {                                              // lane 63 has just finished column t - 63
-                        const int c = t - (WAVE - 1);
-                        if (c >= 0) {
-                            if (lane == (c & (WAVE - 1))) {
-                                oh = __builtin_amdgcn_readlane(h_out, WAVE - 1);
-                                of = __builtin_amdgcn_readlane(f_out, WAVE - 1);
-                            }
-                            if ((c & (WAVE - 1)) == WAVE - 1 || c == n - 1) {
-                                const int col = (c & ~(WAVE - 1)) + lane;
-                                if (col <= c) bout[col] = make_int2(oh, of);
-                            }
-                        }
-                    }
+                    if (keep) hand.step(t, n - 1, lane, {h_out, f_out}, bout);
                 }
             }
 #pragma unroll
-            for (int r = 0; r < SW_R; ++r)                                   // ascending rows, strict: the smallest i of a lane
+            for (int r = 0; r < PA_R; ++r)                                   // ascending rows, strict: the smallest i of a lane
                 if (row0 + r < m && bH[r] > best) { best = bH[r]; besti = row0 + r; bestj = bJ[r]; }
         }
     }
@@ -141,7 +119,6 @@ __global__ __launch_bounds__(WAVE) void sw_forward_kernel(SwArgs a) {
     }
 }
 
-// ops: 0 '=', 1 'X', 2 'I', 3 'D'; a run is (length << 2) | op
 // SG: the walk stops on reaching row 0 or column 0, and the CIGAR covers both sequences completely: what lies before the first and
 // after the last aligned column comes out as one I or D run each (the counts include them)
 template <bool SG>
@@ -166,49 +143,32 @@ __global__ __launch_bounds__(WAVE) void sw_traceback_kernel(SwArgs a, int npairs
     const int8_t* seq = a.seq + (long)pair * a.seq_stride;
     const int8_t* ref = a.ref + (long)pair * a.ref_stride;
     const unsigned* trace = a.trace + (size_t)pair * a.trace_stride;
-    unsigned* ops = a.ops ? a.ops + (long)pair * a.ops_stride : nullptr;
+    RunWriter w(a.ops ? a.ops + (long)pair * a.ops_stride : nullptr, a.ops_stride);
     const int S = n + WAVE - 1;
-    int cnt[4] = {0, 0, 0, 0};
-    int i = ei, j = ej, state = 0, run_op = -1, run_len = 0, nruns = 0;
-    auto emit = [&](int op, int len = 1) {
-        cnt[0] += op == 0 ? len : 0; cnt[1] += op == 1 ? len : 0; cnt[2] += op == 2 ? len : 0; cnt[3] += op == 3 ? len : 0;
-        if (op == run_op) { run_len += len; return; }
-        if (run_len) {
-            if (ops && nruns < a.ops_stride) ops[nruns] = ((unsigned)run_len << 2) | (unsigned)run_op;
-            ++nruns;
-        }
-        run_op = op; run_len = len;
-    };
+    int i = ei, j = ej, state = 0;
     if (SG) {                                                                // the end cell lies on the last row or the last column
-        if (n - 1 - ej > 0) emit(3, n - 1 - ej);
-        if (m - 1 - ei > 0) emit(2, m - 1 - ei);
+        if (n - 1 - ej > 0) w.emit(3, n - 1 - ej);
+        if (m - 1 - ei > 0) w.emit(2, m - 1 - ei);
     }
     for (int it = 0; it < m + n && i >= 0 && j >= 0; ++it) {                // every turn consumes a base: at most m + n turns
-        const int ln = (i & (SW_ROWS - 1)) >> 3;
-        const unsigned bits = trace[((size_t)(i / SW_ROWS) * S + j + ln) * WAVE + ln] >> (4 * (i & 7));
+        const TraceAt at = trace_at(i / PA_ROWS, S, j, i, 4);
+        const unsigned bits = trace[at.word] >> at.shift;
         if (state == 0) {
             const unsigned src = bits & 3u;
             if (!SG && src == 0) break;
-            if (src == 1) { emit(seq[i] == ref[j] ? 0 : 1); --i; --j; continue; }
+            if (src == 1) { w.emit(seq[i] == ref[j] ? 0 : 1); --i; --j; continue; }
             state = src == 2 ? 1 : 2;
         }
-        if (state == 1) { emit(3); state = (bits & 4u) ? 1 : 0; --j; }
-        else { emit(2); state = (bits & 8u) ? 2 : 0; --i; }
+        if (state == 1) { w.emit(3); state = (bits & 4u) ? 1 : 0; --j; }
+        else { w.emit(2); state = (bits & 8u) ? 2 : 0; --i; }
     }
     const int si = i, sj = j;                                                // one before the first aligned column
     if (SG) {
-        if (si >= 0) emit(2, si + 1);
-        if (sj >= 0) emit(3, sj + 1);
+        if (si >= 0) w.emit(2, si + 1);
+        if (sj >= 0) w.emit(3, sj + 1);
     }
-    if (run_len) {
-        if (ops && nruns < a.ops_stride) ops[nruns] = ((unsigned)run_len << 2) | (unsigned)run_op;
-        ++nruns;
-    }
-    if (ops) {                                                               // the walk wrote the runs last to first
-        const int w = nruns < a.ops_stride ? nruns : (int)a.ops_stride;
-        for (int x = 0, y = w - 1; x < y; ++x, --y) { const unsigned v = ops[x]; ops[x] = ops[y]; ops[y] = v; }
-    }
-    res[0] = score; res[1] = cnt[0]; res[2] = cnt[1]; res[3] = cnt[2]; res[4] = cnt[3];
+    const int nruns = w.finish();
+    res[0] = score; res[1] = w.cnt[0]; res[2] = w.cnt[1]; res[3] = w.cnt[2]; res[4] = w.cnt[3];
     res[5] = sj + 1; res[6] = ej; res[7] = si + 1; res[8] = ei; res[9] = nruns;
     if (a.n_ops) a.n_ops[pair] = nruns;
 }
@@ -217,8 +177,8 @@ struct SwLayout { size_t endcell, bound, bound_stride, trace, trace_stride, tota
 
 static bool sw_layout(int n, int max_seq, int max_ref, SwLayout* L) {
     if (n <= 0 || max_seq < 0 || max_ref < 0 || max_seq > SW_MAX_LEN || max_ref > SW_MAX_LEN) return false;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t passes = ((size_t)max_seq + SW_ROWS - 1) / SW_ROWS;
+    const auto up = align_up256;
+    const size_t passes = ((size_t)max_seq + PA_ROWS - 1) / PA_ROWS;
     L->endcell = up((size_t)2 * n * sizeof(int));
     L->bound = L->endcell + up((size_t)4 * n * sizeof(int));
     L->bound_stride = passes > 1 ? ((size_t)max_ref + WAVE - 1) / WAVE * WAVE : 0;
@@ -241,46 +201,26 @@ static int affine_align(const void* seqs, long seq_stride, const int* seq_lens, 
                         int* result, unsigned* ops, long ops_stride, int* n_ops, hipStream_t stream) {
     using namespace bh;
     const char* who = SG ? "sg" : "sw";
-    BH_REQUIRE(n > 0, "%s_align: n must be positive (got %d)", who, n);
-    BH_REQUIRE(seqs && refs && seq_lens && ref_lens && workspace && result, "%s_align: null pointer", who);
     BH_REQUIRE(match >= 1 && match <= SW_MAX_PARAM, "%s_align: match must be in 1..%d (got %d)", who, SW_MAX_PARAM, match);
     BH_REQUIRE(mismatch < match && mismatch >= -SW_MAX_PARAM, "%s_align: mismatch must be in %d..match-1 (got %d)", who, -SW_MAX_PARAM,
                mismatch);
     BH_REQUIRE(gap_extend >= 1, "%s_align: gap_extend must be at least 1 (got %d)", who, gap_extend);
     BH_REQUIRE(gap_open >= gap_extend && gap_open <= SW_MAX_PARAM, "%s_align: gap_open must be in gap_extend..%d (got open %d, extend %d)", who,
                SW_MAX_PARAM, gap_open, gap_extend);
-    BH_REQUIRE(seq_stride >= 0 && ref_stride >= 0 && ops_stride >= 0, "%s_align: negative stride", who);
-    BH_REQUIRE(!n_ops || ops, "%s_align: n_ops without an ops buffer", who);
-    int max_seq = 0, max_ref = 0;
-    for (int i = 0; i < n; ++i) {
-        const int m = seq_lens[i], r = ref_lens[i];
-        BH_REQUIRE(m >= 0 && r >= 0, "%s_align: pair %d has a negative length (%d, %d)", who, i, m, r);
-        BH_REQUIRE(m <= seq_stride && r <= ref_stride, "%s_align: pair %d: lengths (%d, %d) exceed the row strides (%ld, %ld)", who, i, m, r,
-                   seq_stride, ref_stride);
-        BH_REQUIRE(m <= SW_MAX_LEN && r <= SW_MAX_LEN, "%s_align: pair %d: lengths (%d, %d) exceed the supported %d", who, i, m, r, SW_MAX_LEN);
-        // every op consumes a base, the first one two; the semi-global CIGAR may begin or end with an overhang run
-        const long need = SG ? (long)m + r : m && r ? (long)m + r - 1 : 0;
-        BH_REQUIRE(!ops || need <= ops_stride, "%s_align: pair %d may need %ld CIGAR runs, the ops rows hold %ld", who, i, need, ops_stride);
-        max_seq = m > max_seq ? m : max_seq;
-        max_ref = r > max_ref ? r : max_ref;
-    }
+    PairArgs head{(const int8_t*)seqs, seq_stride, (const int8_t*)refs, ref_stride, seq_lens, ref_lens, result, ops, ops_stride, n_ops};
+    int max_seq, max_ref;
+    // every op consumes a base, the first one two; the semi-global CIGAR may begin or end with an overhang run
+    if (int rc = pair_batch_begin(who, SW_MAX_LEN, head, n, workspace, &max_seq, &max_ref,
+                                  [](int m, int r) { return SG ? (long)m + r : m && r ? (long)m + r - 1 : 0; })) return rc;
     SwLayout L;
     BH_REQUIRE(sw_layout(n, max_seq, max_ref, &L), "%s_align: unsupported shape", who);
     BH_REQUIRE(workspace_bytes >= L.total, "%s_align: workspace of %zu bytes, %zu needed (bh_sw_workspace(%d, %d, %d))", who, workspace_bytes,
                L.total, n, max_seq, max_ref);
+    if (int rc = pair_lengths_to_device(&head, n, workspace, stream)) return rc;
     char* ws = (char*)workspace;
-    // the lengths are host arrays (they were just validated): one blocking copy to the head of the workspace, ordered on the stream
-    std::vector<int> lens(seq_lens, seq_lens + n);
-    lens.insert(lens.end(), ref_lens, ref_lens + n);
-    BH_CHECK_HIP(hipMemcpyWithStream(ws, lens.data(), lens.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    SwArgs a{(const int8_t*)seqs, seq_stride, (const int8_t*)refs, ref_stride, (const int*)ws, (const int*)ws + n,
-             match, mismatch, gap_open, gap_extend, (unsigned*)(ws + L.trace), L.trace_stride, (int2*)(ws + L.bound), L.bound_stride,
-             (int*)(ws + L.endcell), result, ops, ops_stride, n_ops};
-    hipLaunchKernelGGL(sw_forward_kernel<SG>, dim3(n), dim3(WAVE), 0, stream, a);
-    BH_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(sw_traceback_kernel<SG>, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), 0, stream, a, n);
-    BH_CHECK_HIP(hipGetLastError());
-    return 0;
+    SwArgs a{head, match, mismatch, gap_open, gap_extend, (unsigned*)(ws + L.trace), L.trace_stride, (int2*)(ws + L.bound), L.bound_stride,
+             (int*)(ws + L.endcell)};
+    return pair_launch(sw_forward_kernel<SG>, sw_traceback_kernel<SG>, a, n, stream);
 }
 
 int bh_k_sw_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,

@@ -14,9 +14,8 @@
 // that lane's registers, which are the ring - and a wave-wide max over (score << 32 | index) picks the winner, the largest index among
 // equal scores. f and the predecessor of 64 anchors are stored together. The wave then follows the predecessors from the best anchor,
 // and one more pass over its anchors gives s2.
-#include "common.h"
 #include "kernels.h"
-#include <vector>
+#include "pair_align.h"
 
 namespace bh {
 
@@ -412,7 +411,7 @@ struct SketchLayout { size_t len, tile_start, tile_count, tile_off, total; };
 static long sketch_tiles(int len) { return len > 0 ? ((long)len + SK_TILE - 1) / SK_TILE : 0; }
 
 static void sketch_layout(int n, long tiles, SketchLayout* L) {
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const auto up = align_up256;
     L->len = 0;
     L->tile_start = up((size_t)n * sizeof(int));
     L->tile_count = L->tile_start + up(((size_t)n + 1) * sizeof(int));

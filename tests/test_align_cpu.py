@@ -179,43 +179,67 @@ def test_symbols_are_declared_bound_and_exported_and_workspace_sizes():
         assert handle.bh_sw_workspace(*bad) == 0, bad
 
 
-def test_argument_errors_are_raised_before_any_launch():
+ENTRIES = {"bh_sw_align": (4096, (5, -4, 8, 4)), "bh_sg_align": (4096, (5, -4, 10, 2)), "bh_nw_align": (65536, (64,))}
+
+
+@pytest.mark.parametrize("entry", sorted(ENTRIES))
+def test_argument_errors_are_raised_before_any_launch(entry):
     """Every call below names pointers that are never dereferenced on the device: the checks run on the host first."""
     from bonito_amd import _lib
-    from bonito_amd.align import sw_align
     handle = _lib.lib()
     fake = C.c_void_p(4096)
     ip = C.POINTER(C.c_int32)
+    limit, default = ENTRIES[entry]
+    nw = entry == "bh_nw_align"
+    prefix = entry[3:] + ": "
 
-    def call(seq_lens, ref_lens, seq_stride=64, ref_stride=64, scoring=(5, -4, 8, 4), ws_bytes=None, ops=None, ops_stride=0, n=None):
+    def workspace(n, s, r):
+        return handle.bh_nw_workspace(n, s, r, abs(s - r) + 2 * 64 + 1) if nw else handle.bh_sw_workspace(n, s, r)
+
+    def call(seq_lens, ref_lens, seq_stride=64, ref_stride=64, extra=default, ws_bytes=None, ops=None, ops_stride=0, n=None, n_ops=None):
         sl, rl = np.asarray(seq_lens, np.int32), np.asarray(ref_lens, np.int32)
         n = len(sl) if n is None else n
         if ws_bytes is None:
-            ws_bytes = handle.bh_sw_workspace(max(n, 1), 64, 64)
-        rc = handle.bh_sw_align(fake, seq_stride, sl.ctypes.data_as(ip), fake, ref_stride, rl.ctypes.data_as(ip), n, *scoring,
-                                fake, ws_bytes, fake, ops, ops_stride, None, None)
+            ws_bytes = workspace(max(n, 1), 64, 64)
+        rc = getattr(handle, entry)(fake, seq_stride, sl.ctypes.data_as(ip), fake, ref_stride, rl.ctypes.data_as(ip), n, *extra,
+                                    fake, ws_bytes, fake, ops, ops_stride, n_ops, None)
         return rc, _lib.last_error()
 
-    for kwargs, word in [
-        (dict(seq_lens=[3, -1], ref_lens=[3, 3]), "negative length"),
-        (dict(seq_lens=[3, 3], ref_lens=[3, -2]), "negative length"),
-        (dict(seq_lens=[3, 65], ref_lens=[3, 3]), "exceed the row strides"),
-        (dict(seq_lens=[3, 3], ref_lens=[3, 40], ref_stride=39), "exceed the row strides"),
-        (dict(seq_lens=[5000], ref_lens=[3], seq_stride=8192), "exceed the supported 4096"),
-        (dict(seq_lens=[3], ref_lens=[3], scoring=(5, -4, 3, 4)), "gap_open"),
-        (dict(seq_lens=[3], ref_lens=[3], scoring=(5, -4, 8, 0)), "gap_extend"),
-        (dict(seq_lens=[3], ref_lens=[3], scoring=(0, -4, 8, 4)), "match"),
-        (dict(seq_lens=[3], ref_lens=[3], scoring=(5, 5, 8, 4)), "mismatch"),
-        (dict(seq_lens=[3], ref_lens=[3], scoring=(5, -4, 40000, 4)), "gap_open"),
-        (dict(seq_lens=[60, 64], ref_lens=[60, 64], ws_bytes=handle.bh_sw_workspace(2, 64, 64) - 1), "workspace"),
-        (dict(seq_lens=[60, 64], ref_lens=[60, 64], ws_bytes=0), "workspace"),
-        (dict(seq_lens=[10, 20], ref_lens=[10, 30], ops=fake, ops_stride=48), "CIGAR runs"),
-        (dict(seq_lens=[], ref_lens=[], n=0), "n must be positive"),
-    ]:
+    cases = [
+        (dict(seq_lens=[3, -1], ref_lens=[3, 3]), "pair 1 has a negative length (-1, 3)"),
+        (dict(seq_lens=[3, 3], ref_lens=[3, -2]), "pair 1 has a negative length (3, -2)"),
+        (dict(seq_lens=[3, 65], ref_lens=[3, 3]), "pair 1: lengths (65, 3) exceed the row strides (64, 64)"),
+        (dict(seq_lens=[3, 3], ref_lens=[3, 40], ref_stride=39), "pair 1: lengths (3, 40) exceed the row strides (64, 39)"),
+        (dict(seq_lens=[limit + 904], ref_lens=[3], seq_stride=1 << 17), "pair 0: lengths (%d, 3) exceed the supported %d" % (limit + 904, limit)),
+        (dict(seq_lens=[60, 64], ref_lens=[60, 64], ws_bytes=workspace(2, 64, 64) - 1),
+         "workspace of %d bytes, %d needed (bh_%s_workspace(2, 64, 64" % (workspace(2, 64, 64) - 1, workspace(2, 64, 64), "nw" if nw else "sw")),
+        (dict(seq_lens=[60, 64], ref_lens=[60, 64], ws_bytes=0), "workspace of 0 bytes"),
+        (dict(seq_lens=[10, 20], ref_lens=[10, 30], ops=fake, ops_stride=48),
+         "pair 1 may need %d CIGAR runs, the ops rows hold 48" % (49 if entry == "bh_sw_align" else 50)),
+        (dict(seq_lens=[], ref_lens=[], n=0), "n must be positive (got 0)"),
+        (dict(seq_lens=[], ref_lens=[], n=-3), "n must be positive (got -3)"),
+        (dict(seq_lens=[3], ref_lens=[3], n_ops=fake), "n_ops without an ops buffer"),
+        (dict(seq_lens=[3], ref_lens=[3], seq_stride=-1), "negative stride"),
+    ]
+    if nw:
+        cases += [(dict(seq_lens=[3], ref_lens=[3], extra=(0,)), "the band half-width must be in 1..65536 (got 0)"),
+                  (dict(seq_lens=[3], ref_lens=[3], extra=(65537,)), "the band half-width must be in 1..65536 (got 65537)")]
+    else:
+        g = default[2:]
+        cases += [(dict(seq_lens=[3], ref_lens=[3], extra=(5, -4, 3, 4)), "gap_open must be in gap_extend..32767 (got open 3, extend 4)"),
+                  (dict(seq_lens=[3], ref_lens=[3], extra=(5, -4, 8, 0)), "gap_extend must be at least 1 (got 0)"),
+                  (dict(seq_lens=[3], ref_lens=[3], extra=(0, -4) + g), "match must be in 1..32767 (got 0)"),
+                  (dict(seq_lens=[3], ref_lens=[3], extra=(5, 5) + g), "mismatch must be in -32767..match-1 (got 5)"),
+                  (dict(seq_lens=[3], ref_lens=[3], extra=(5, -4, 40000, 4)), "gap_open must be in gap_extend..32767 (got open 40000, extend 4)")]
+    for kwargs, text in cases:
         rc, msg = call(**kwargs)
-        assert rc != 0 and word in msg, (kwargs, rc, msg)
-    rc = handle.bh_sw_align(None, 64, None, fake, 64, None, 1, 5, -4, 8, 4, fake, 1 << 20, fake, None, 0, None, None)
-    assert rc != 0 and "null pointer" in _lib.last_error()
+        assert rc != 0 and msg.startswith(prefix) and text in msg, (kwargs, rc, msg)
+    rc = getattr(handle, entry)(None, 64, None, fake, 64, None, 1, *default, fake, 1 << 20, fake, None, 0, None, None)
+    assert rc != 0 and _lib.last_error() == prefix + "null pointer"
+
+
+def test_python_surface_errors_are_raised_before_the_device_is_needed():
+    from bonito_amd.align import sw_align
     # the Python surface: letters outside ACGT, unequal list lengths, too long a sequence: raised before the device is needed
     with pytest.raises(ValueError, match="outside ACGT"):
         sw_align(["ACGN"], ["ACGT"])
@@ -226,3 +250,41 @@ def test_argument_errors_are_raised_before_any_launch():
     with pytest.raises(ValueError, match="padding"):
         sw_align(np.array([[1, 0, 2]], np.int8), np.array([[1, 2, 3]], np.int8))
     assert len(sw_align([], [])) == 0
+
+
+def test_workspace_sizes_and_slices_equal_the_parent_commit():
+    """tests/golden/align_parent.json was written by tests/golden/make_golden_align_parent.py at the commit it names, before the
+    aligners' shared parts were folded: the workspace functions return the same bytes for every argument of the sweep, and the one
+    slicer cuts the seeded length pairs into the slices the two former slicers made (where the local aligner's raised, the first
+    pair that does not fit is the one the message named). Budgets: 1 MiB, 8 MiB, 1 GiB and one that 40 pairs fill to the byte."""
+    import json
+    from bonito_amd import _lib
+    from bonito_amd.align import _slices
+    with open(os.path.join(ROOT, "tests", "golden", "align_parent.json")) as fh:
+        gold = json.load(fh)
+    lib = _lib.lib()
+    assert len(gold["sw_workspace"]) == 4 * 6 * 6 and len(gold["nw_workspace"]) == 4 * 7 * 7 * 4
+    for n, s, r, want in gold["sw_workspace"]:
+        assert lib.bh_sw_workspace(n, s, r) == want, (n, s, r)
+    for n, s, r, b, want in gold["nw_workspace"]:
+        assert lib.bh_nw_workspace(n, s, r, b) == want, (n, s, r, b)
+    sl, rl = np.array(gold["seq_len"], np.int32), np.array(gold["ref_len"], np.int32)
+    assert len(sl) == 200 and len(gold["sw_slices"]) == 8 and len(gold["nw_slices"]) == 8
+    one = np.ones(len(sl), np.int64)
+    for row in gold["sw_slices"]:
+        pick = np.arange(len(sl)) if row["pairs"] == "all" else np.flatnonzero((sl <= 1000) & (rl <= 1000))
+        order = pick[np.argsort(((sl[pick].astype(np.int64) + 511) // 512) * (rl[pick].astype(np.int64) + 63), kind="stable")]
+        got, unfit = _slices(order, sl, rl, one, row["budget"], lambda k, s, r, b: lib.bh_sw_workspace(k, s, r))
+        if "raises" in row:
+            i = unfit[0]
+            assert "one pair of lengths (%d, %d), which needs %d" % (sl[i], rl[i], lib.bh_sw_workspace(1, int(sl[i]), int(rl[i]))) \
+                in row["raises"], row
+        else:
+            assert not unfit and [[idx.tolist(), ms, mr] for idx, ms, mr, _ in got] == row["slices"], row["budget"]
+    for row in gold["nw_slices"]:
+        k = row["k"]
+        band = np.abs(rl.astype(np.int64) - sl) + 2 * k + 1
+        size = ((sl.astype(np.int64) + 511) // 512) * np.minimum(rl.astype(np.int64), 511 + band)
+        got, unfit = _slices(np.argsort(size, kind="stable"), sl, rl, band, row["budget"], lib.bh_nw_workspace)
+        assert [[idx.tolist(), ms, mr, mb] for idx, ms, mr, mb in got] == row["slices"], (row["budget"], k)
+        assert [int(i) for i in unfit] == row["unfit"], (row["budget"], k)

@@ -210,7 +210,7 @@ def test_guard_bytes_around_the_output_buffers():
     n, lib, ip = len(seqs), _lib.lib(), C.POINTER(C.c_int32)
     s_dev, r_dev = sc.contiguous().cuda(), rc.contiguous().cuda()
     stride, pad, fill = int((sl + rl).max()), 64, 0x5A5A5A5A
-    for name, width in (("nw", 8), ("sg", 10)):
+    for name, width in (("nw", 8), ("sg", 10), ("sw", 10)):
         res = torch.full((n * width + 2 * pad,), fill, dtype=torch.int32, device="cuda")
         ops = torch.full((n * stride + 2 * pad,), fill, dtype=torch.int32, device="cuda")
         cnt = torch.full((n + 2 * pad,), fill, dtype=torch.int32, device="cuda")
@@ -223,13 +223,14 @@ def test_guard_bytes_around_the_output_buffers():
                                        rl.ctypes.data_as(ip), n, 512, _lib.ptr(ws), nbytes, ptrs[0], ptrs[1], stride, ptrs[2],
                                        _lib.stream_ptr(s_dev.device)), "bh_nw_align")
             want = [dr.nw(s, r) for s, r in zip(seqs, refs)]
-        else:
+        else:                                                                 # the semi-global and the local mode of one kernel pair
+            entry, scoring = (lib.bh_sg_align, dr.SG_DEFAULT) if name == "sg" else (lib.bh_sw_align, (5, -4, 8, 4))
             nbytes = lib.bh_sw_workspace(n, int(sl.max()), int(rl.max()))
             ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-            _lib.check(lib.bh_sg_align(_lib.ptr(s_dev), s_dev.shape[1], sl.ctypes.data_as(ip), _lib.ptr(r_dev), r_dev.shape[1],
-                                       rl.ctypes.data_as(ip), n, 5, -4, 10, 2, _lib.ptr(ws), nbytes, ptrs[0], ptrs[1], stride, ptrs[2],
-                                       _lib.stream_ptr(s_dev.device)), "bh_sg_align")
-            want = [dr.sg(s, r, *dr.SG_DEFAULT) for s, r in zip(seqs, refs)]
+            _lib.check(entry(_lib.ptr(s_dev), s_dev.shape[1], sl.ctypes.data_as(ip), _lib.ptr(r_dev), r_dev.shape[1],
+                             rl.ctypes.data_as(ip), n, *scoring, _lib.ptr(ws), nbytes, ptrs[0], ptrs[1], stride, ptrs[2],
+                             _lib.stream_ptr(s_dev.device)), "bh_%s_align" % name)
+            want = [(dr.sg if name == "sg" else ar.sw)(s, r, *scoring) for s, r in zip(seqs, refs)]
         torch.cuda.synchronize()
         res, ops, cnt = res.cpu().numpy(), ops.cpu().numpy(), cnt.cpu().numpy()
         for t in (res, ops, cnt):
