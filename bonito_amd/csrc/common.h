@@ -62,6 +62,9 @@ __device__ __forceinline__ float4_t mfma16(half8_t a, half8_t b, float4_t c) {
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
+// offsets of the regions of a workspace or saved buffer
+inline size_t align_up256(size_t v) { return (v + 255) / 256 * 256; }
+
 }  // namespace bh
 
 // Host-side error plumbing for the C ABI (thread-local message, int status).

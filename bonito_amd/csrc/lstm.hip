@@ -35,6 +35,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lstm_cell.h"
 #include "options.h"
 
 namespace bh {
@@ -91,29 +92,6 @@ typedef unsigned long long __attribute__((may_alias)) u64_alias_t;
 // Gate-math tanh: the exp form has absolute error ~1e-7 everywhere, which is all the recurrence needs
 // (h and c are consumed at fp16 / additive precision); the relative-accuracy branch of common.h's tanhf_ is skipped.
 __device__ __forceinline__ float tanh_gate(float x) { return __builtin_fmaf(-2.0f, rcpf_(__expf(2.0f * x) + 1.0f), 1.0f); }
-
-// One cell update from the four gate pre-activations (torch order i, f, g, o). The contractions are spelled out so
-// that every kernel variant of this file produces the same bits for the same pre-activations; the returned h is
-// forced into [-1, 1] so that a non-finite value can never alias the exchange sentinel.
-__device__ __forceinline__ float lstm_cell(float ai, float af, float ag, float ao, float& c) {
-    // Transcendental issue (quarter rate) is what the gate arithmetic costs, so the five activations share
-    // reciprocals: with E_x = exp(-x),
-    //     c' = c * sig(f) + sig(i) * tanh(g) = (c * Di * Dg + (1 - Eg2) * Df) / (Df * Di * Dg),   D_x = 1 + E_x, Eg2 = exp(-2g)
-    //     h  = sig(o) * tanh(c')             = (1 - Ec2) / ((1 + Ec2) * Do)
-    // i.e. 5 exp + 2 rcp instead of 5 + 5. Pre-activations are clamped to +-25 (sig(-25) = 1.4e-11, far below what h
-    // can resolve) so that no product of three (1 + E) factors leaves the fp32 range.
-    const float ei = __expf(-__builtin_amdgcn_fmed3f(ai, -25.0f, 25.0f));
-    const float ef = __expf(-__builtin_amdgcn_fmed3f(af, -25.0f, 25.0f));
-    const float eg = __expf(-2.0f * __builtin_amdgcn_fmed3f(ag, -12.5f, 12.5f));
-    const float eo = __expf(-__builtin_amdgcn_fmed3f(ao, -25.0f, 25.0f));
-    const float didg = __fmul_rn(1.0f + ei, 1.0f + eg);
-    const float df = 1.0f + ef;
-    const float num = __builtin_fmaf(c, didg, __fmul_rn(1.0f - eg, df));
-    c = __fmul_rn(num, rcpf_(__fmul_rn(df, didg)));
-    const float ec = __expf(-2.0f * __builtin_amdgcn_fmed3f(c, -12.5f, 12.5f));
-    const float hv = __fmul_rn(1.0f - ec, rcpf_(__fmul_rn(1.0f + ec, 1.0f + eo)));
-    return (fabsf(hv) <= 1.0f) ? hv : 0.0f;
-}
 
 // STREAM = false: W_hh fragments of the wave's slice are register-resident, a workgroup serves one slice of FOUR rings.
 // STREAM = true (hidden sizes the register file cannot hold, H > 512: the 768-wide old-style r9.4.1 models, the 1024-wide v4.3

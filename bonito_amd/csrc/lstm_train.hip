@@ -8,8 +8,8 @@
 //     dx_t = da_t W_ih      dW_ih = sum_t da_t^T x_t      dW_hh = sum_t da_t^T h_{t-1}      db = sum_{t,n} da_t
 // Precision is that of autocast training: x, h, dh, dx fp16; the weights arrive as fp32 DEVICE tensors (the optimiser rewrites them
 // every step) and the kernels use their round-to-nearest fp16 values; every sum is fp32; c is fp32 from step to step and where it is
-// saved; dW_ih, dW_hh, db are fp32. The cell is lstm_cell() of lstm.hip (copied: file-local there), so h has the bits the inference
-// kernels would publish from the same pre-activations.
+// saved; dW_ih, dW_hh, db are fp32. The cell is LstmCell of lstm_cell.h, the one the inference kernels of lstm.hip call, so h has the
+// bits they would publish from the same pre-activations, and the stored gates come from the cell's own exponentials.
 //
 // What is stored between the passes, all in buffers of the caller:
 //     saved     : G [T][N][4H] fp16 - first x W_ih^T + b (bh_k_linear), then overwritten IN PLACE by the recurrent kernel with the
@@ -25,29 +25,20 @@
 // barrier per step. Batch tiles are independent:
 // NO exchange between workgroups, no flags, no spin-waits - the kernels cannot hang, and any number of tiles fits one launch. Rows of a
 // padded tile (chunk >= N) are taken as zeros and never stored, so they reach neither dx nor the weight gradients.
-// Everything parallel over time is a GEMM over the T N rows: the input projection and dx = dA W_ih through bh_k_linear;
-// dW = dA^T [X | H_prev] in an MFMA kernel of this file (both operands are transposed through LDS), split over the rows into partial
-// sums that a second kernel adds IN A FIXED ORDER - no floating-point atomics, the results are byte-identical from call to call.
+// Everything parallel over time is a GEMM over the T N rows: the input projection and dx = dA W_ih through bh_k_linear (linear_rows);
+// dW = dA^T [X | H_prev] and db through reduce_rows, the reduction over rows every training layer shares (train_common.hip, row rule
+// ROWS_LSTM): partial sums over blocks of rows that a second kernel adds IN A FIXED ORDER - no floating-point atomics, the results are
+// byte-identical from call to call. The kernels of this file index with 64 bits throughout.
 // Gradients are not clamped: da is stored as fp16 as autocast stores it, a |da| above 65504 becomes inf (loss scaling is the
 // trainer's business), and a non-finite dh makes its chunk's dx and the weight gradients non-finite while the other chunks keep their bytes.
-#include <math.h>
-
-#include "common.h"
-#include "kernels.h"
+#include "lstm_cell.h"
+#include "train_common.h"
 
 namespace bh {
 namespace {
 
-typedef half8_t __attribute__((may_alias)) half8_alias_t;
-typedef half_t __attribute__((may_alias)) half_alias_t;
-
 constexpr int TILE_N = 16;             // chunks per workgroup of the recurrent kernels
-constexpr int DW_TILE = 64;            // dW kernel: 64 x 64 outputs per workgroup
-constexpr int DW_KSTEP = 32;           // rows of T N per MFMA
-constexpr int DW_LD = DW_KSTEP + 8;    // LDS row pitch in halves (80 bytes: 16-byte aligned, off the power of two)
-constexpr int DB_THREADS = 128;
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline bool shape_ok(int T, int N, int H) { return T >= 1 && N >= 1 && (long)T * N < (1l << 29) && H >= 32 && H <= 1024 && H % 32 == 0; }
 
 struct SavedLayout {
@@ -55,33 +46,11 @@ struct SavedLayout {
     SavedLayout(int T, int N, int H) {
         const size_t rows = (size_t)T * N, npad = (size_t)(N + TILE_N - 1) / TILE_N * TILE_N;
         gates = 0;
-        c = align256(gates + rows * 4 * H * sizeof(half_t));
-        wih = align256(c + rows * H * sizeof(float));
-        whh = align256(wih + (size_t)4 * H * H * sizeof(half_t));
-        hfrag = align256(whh + (size_t)4 * H * H * sizeof(half_t));         // [tiles][2][16 x H]: h of the last two steps, fragment order
-        total = align256(hfrag + 2 * npad * H * sizeof(half_t));
-    }
-};
-
-// how the rows of T N are split for the weight gradients: a function of the shape alone (the order of the sums never varies)
-struct GradSplit {
-    int dw_splits, dw_rows;      // partial sums of dW and the rows each takes (a multiple of DW_KSTEP)
-    int db_splits, db_rows;
-    GradSplit(int T, int N, int H) {
-        const long M = (long)T * N;
-        const int tiles = (4 * H / DW_TILE) * (2 * H / DW_TILE);
-        long s = (M + 511) / 512;
-        const long cap = tiles >= 1024 ? 1 : 1024 / tiles;
-        if (s > cap) s = cap;
-        if (s < 1) s = 1;
-        long rows = ((M + s - 1) / s + DW_KSTEP - 1) / DW_KSTEP * DW_KSTEP;
-        dw_splits = (int)((M + rows - 1) / rows);
-        dw_rows = (int)rows;
-        long b = (M + 255) / 256;
-        if (b > 1024) b = 1024;
-        rows = (M + b - 1) / b;
-        db_splits = (int)((M + rows - 1) / rows);
-        db_rows = (int)rows;
+        c = align_up256(gates + rows * 4 * H * sizeof(half_t));
+        wih = align_up256(c + rows * H * sizeof(float));
+        whh = align_up256(wih + (size_t)4 * H * H * sizeof(half_t));
+        hfrag = align_up256(whh + (size_t)4 * H * H * sizeof(half_t));         // [tiles][2][16 x H]: h of the last two steps, fragment order
+        total = align_up256(hfrag + 2 * npad * H * sizeof(half_t));
     }
 };
 
@@ -89,16 +58,16 @@ struct WorkLayout {
     size_t da, carry, wihT, whhT, dafrag, dw_part, db_part, total;
     WorkLayout(int T, int N, int H) {
         const size_t rows = (size_t)T * N;
-        const GradSplit g(T, N, H);
+        const Split g((long)T * N, 4 * H, 2 * H);        // the rows of dW = dA^T [X | H_prev]
         const size_t npad = (size_t)(N + TILE_N - 1) / TILE_N * TILE_N;
         da = 0;
-        carry = align256(da + rows * 4 * H * sizeof(half_t));
-        wihT = align256(carry + npad * H * sizeof(float));
-        whhT = align256(wihT + (size_t)4 * H * H * sizeof(half_t));
-        dafrag = align256(whhT + (size_t)4 * H * H * sizeof(half_t));       // [tiles][2][16 x 4H]: da of the last two steps, fragment order
-        dw_part = align256(dafrag + 2 * npad * 4 * H * sizeof(half_t));
-        db_part = align256(dw_part + (size_t)g.dw_splits * 4 * H * 2 * H * sizeof(float));
-        total = align256(db_part + (size_t)g.db_splits * 4 * H * sizeof(float));
+        carry = align_up256(da + rows * 4 * H * sizeof(half_t));
+        wihT = align_up256(carry + npad * H * sizeof(float));
+        whhT = align_up256(wihT + (size_t)4 * H * H * sizeof(half_t));
+        dafrag = align_up256(whhT + (size_t)4 * H * H * sizeof(half_t));       // [tiles][2][16 x 4H]: da of the last two steps, fragment order
+        dw_part = align_up256(dafrag + 2 * npad * 4 * H * sizeof(half_t));
+        db_part = align_up256(dw_part + (size_t)g.dw_splits * 4 * H * 2 * H * sizeof(float));
+        total = align_up256(db_part + (size_t)g.db_splits * 4 * H * sizeof(float));
     }
 };
 
@@ -205,26 +174,15 @@ __global__ __launch_bounds__(512) void lstm_train_fwd_kernel(FwdArgs p) {
                     const float ai = acc[0][i] + (float)gin[0][i], af = acc[1][i] + (float)gin[1][i];
                     const float ag = acc[2][i] + (float)gin[2][i], ao = acc[3][i] + (float)gin[3][i];
                     float c = cin[i];
-                    // lstm_cell() of lstm.hip, operation by operation
-                    const float ei = __expf(-__builtin_amdgcn_fmed3f(ai, -25.0f, 25.0f));
-                    const float ef = __expf(-__builtin_amdgcn_fmed3f(af, -25.0f, 25.0f));
-                    const float eg = __expf(-2.0f * __builtin_amdgcn_fmed3f(ag, -12.5f, 12.5f));
-                    const float eo = __expf(-__builtin_amdgcn_fmed3f(ao, -25.0f, 25.0f));
-                    const float didg = __fmul_rn(1.0f + ei, 1.0f + eg);
-                    const float df = 1.0f + ef;
-                    const float num = __builtin_fmaf(c, didg, __fmul_rn(1.0f - eg, df));
-                    c = __fmul_rn(num, rcpf_(__fmul_rn(df, didg)));
-                    const float ec = __expf(-2.0f * __builtin_amdgcn_fmed3f(c, -12.5f, 12.5f));
-                    float hv = __fmul_rn(1.0f - ec, rcpf_(__fmul_rn(1.0f + ec, 1.0f + eo)));
-                    hv = (fabsf(hv) <= 1.0f) ? hv : 0.0f;
+                    const LstmCell cell(ai, af, ag, ao, c);
                     // the gates one by one, for the backward
-                    G[0] = (half_t)rcpf_(1.0f + ei);
-                    G[H] = (half_t)rcpf_(df);
-                    G[2 * H] = (half_t)__fmul_rn(1.0f - eg, rcpf_(1.0f + eg));
-                    G[3 * H] = (half_t)rcpf_(1.0f + eo);
+                    G[0] = (half_t)cell.sig_i();
+                    G[H] = (half_t)cell.sig_f();
+                    G[2 * H] = (half_t)cell.tanh_g();
+                    G[3 * H] = (half_t)cell.sig_o();
                     p.c[row * H + u] = c;
-                    ((half_alias_t*)p.h)[row * H + u] = (half_t)hv;
-                    hnext[frag_index(kg * 4 + i, u)] = (half_t)hv;
+                    ((half_alias_t*)p.h)[row * H + u] = (half_t)cell.h;
+                    hnext[frag_index(kg * 4 + i, u)] = (half_t)cell.h;
                 }
             }
         }
@@ -299,100 +257,10 @@ __global__ __launch_bounds__(512) void lstm_train_bwd_kernel(BwdArgs p) {
     }
 }
 
-struct DwArgs {
-    const half_t* da;       // [M][4H]
-    const half_t* x;        // [M][H]
-    const half_t* h;        // [M][H]
-    float* part;            // [splits][4H][2H]
-    int T, N, H, reverse, rows;
-};
-
-// part[z][r][c] = sum over the rows m of split z of da[m][r] * (c < H ? x[m][c] : h_prev[m][c - H]),  h_prev of the first processed step = 0
-__global__ __launch_bounds__(256) void lstm_train_dw_kernel(DwArgs p) {
-    __shared__ __attribute__((aligned(16))) half_t At[DW_TILE * DW_LD];
-    __shared__ __attribute__((aligned(16))) half_t Bt[DW_TILE * DW_LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int H = p.H, N = p.N;
-    const long M = (long)p.T * N;
-    const int r0 = blockIdx.x * DW_TILE, c0 = blockIdx.y * DW_TILE;
-    const long m_lo = (long)blockIdx.z * p.rows, m_hi = m_lo + p.rows < M ? m_lo + p.rows : M;
-    const int mm = tid >> 3, v = tid & 7;
-    const int c8 = c0 + v * 8;                                              // H % 8 == 0: a vector lies in x or in h, never across
-    const half8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
-    float4_t acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = float4_t{0.0f, 0.0f, 0.0f, 0.0f};
-    for (long m0 = m_lo; m0 < m_hi; m0 += DW_KSTEP) {
-        const long m = m0 + mm;
-        half8_t a8 = zero, b8 = zero;
-        if (m < m_hi) {
-            a8 = *(const half8_t*)(p.da + m * 4 * H + r0 + v * 8);
-            if (c8 < H) {
-                b8 = *(const half8_t*)(p.x + m * H + c8);
-            } else {
-                const long t = m / N, n = m - t * N;
-                const long tp = p.reverse ? t + 1 : t - 1;
-                if (tp >= 0 && tp < p.T) b8 = *(const half8_t*)(p.h + (tp * N + n) * H + (c8 - H));
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            ((half_alias_t*)At)[(v * 8 + j) * DW_LD + mm] = a8[j];
-            ((half_alias_t*)Bt)[(v * 8 + j) * DW_LD + mm] = b8[j];
-        }
-        __syncthreads();
-        const half8_t a = *(const half8_alias_t*)(At + (wave * 16 + (lane & 15)) * DW_LD + (lane >> 4) * 8);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            acc[j] = mfma16(a, *(const half8_alias_t*)(Bt + (j * 16 + (lane & 15)) * DW_LD + (lane >> 4) * 8), acc[j]);
-        __syncthreads();
-    }
-    float* out = p.part + (long)blockIdx.z * 4 * H * 2 * H;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            out[(long)(r0 + wave * 16 + (lane >> 4) * 4 + i) * 2 * H + c0 + j * 16 + (lane & 15)] = acc[j][i];
-}
-
-// part[z][r] = sum over the rows of split z of da[m][r]
-__global__ __launch_bounds__(DB_THREADS) void lstm_train_db_kernel(const half_t* __restrict__ da, float* __restrict__ part, long M, int H,
-                                                                   int rows) {
-    const int r = blockIdx.x * DB_THREADS + threadIdx.x;
-    const long m_lo = (long)blockIdx.y * rows, m_hi = m_lo + rows < M ? m_lo + rows : M;
-    float s = 0.0f;
-    for (long m = m_lo; m < m_hi; ++m) s += (float)da[m * 4 * H + r];
-    part[(long)blockIdx.y * 4 * H + r] = s;
-}
-
-// the partial sums in the order of the splits: dw_ih, dw_hh [4H][H] from part [splits][4H][2H]; dbias [4H] from dbp [db_splits][4H]
-__global__ __launch_bounds__(256) void lstm_train_reduce_kernel(const float* __restrict__ part, int splits, const float* __restrict__ dbp,
-                                                                int db_splits, int H, float* __restrict__ dw_ih, float* __restrict__ dw_hh,
-                                                                float* __restrict__ dbias) {
-    const long nw = 8l * H * H;
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < nw) {
-        float s = part[e];
-        for (int z = 1; z < splits; ++z) s += part[z * nw + e];
-        const long r = e / (2 * H), c = e - r * 2 * H;
-        if (c < H) dw_ih[r * H + c] = s;
-        else dw_hh[r * H + c - H] = s;
-    } else if (dbias && e < nw + 4 * H) {
-        const long r = e - nw;
-        float s = dbp[r];
-        for (int z = 1; z < db_splits; ++z) s += dbp[(long)z * 4 * H + r];
-        dbias[r] = s;
-    }
-}
-
 inline int recurrent_threads(int H) {
     const int tiles = H / 16;
     return 64 * (tiles < 8 ? tiles : 8);
 }
-// bh_k_linear is called on blocks of rows whose [rows][4H] fp16 side stays below 2^31 BYTES (its kernels may index a tensor with 32-bit
-// offsets); the rows of a GEMM are independent, so the blocks change no byte. The kernels of this file index with 64 bits throughout.
-inline long gemm_rows(int H) { return ((1l << 30) / (4 * H)) / 256 * 256; }
-inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
 }  // namespace
 }  // namespace bh
@@ -401,12 +269,15 @@ size_t bh_k_lstm_train_saved_bytes(int T, int N, int H) { return bh::shape_ok(T,
 size_t bh_k_lstm_train_backward_workspace(int T, int N, int H) { return bh::shape_ok(T, N, H) ? bh::WorkLayout(T, N, H).total : 0; }
 int bh_k_lstm_train_workgroups(int N) { return N >= 1 ? (N + bh::TILE_N - 1) / bh::TILE_N : 0; }
 
+#define LSTM_TRAIN_SHAPE(what)                                                                                                    \
+    BH_REQUIRE(T >= 1 && N >= 1, what ": T and N must be positive (got T=%d N=%d)", T, N);                                        \
+    BH_REQUIRE(H >= 32 && H <= 1024 && H % 32 == 0, what ": hidden size %d is not supported (a multiple of 32 in 32..1024)", H);  \
+    BH_REQUIRE((long)T * N < (1l << 29), what ": T * N = %ld rows are too many for one call (below 2^29)", (long)T * N)
+
 int bh_k_lstm_train_forward(const void* x, const float* w_ih, const float* w_hh, const float* bias, int T, int N, int H, int reverse,
                             void* h_out, void* saved, size_t saved_bytes, hipStream_t stream) {
     using namespace bh;
-    BH_REQUIRE(T >= 1 && N >= 1, "lstm_train_forward: T and N must be positive (got T=%d N=%d)", T, N);
-    BH_REQUIRE(H >= 32 && H <= 1024 && H % 32 == 0, "lstm_train_forward: hidden size %d is not supported (a multiple of 32 in 32..1024)", H);
-    BH_REQUIRE((long)T * N < (1l << 29), "lstm_train_forward: T * N = %ld rows are too many for one call (below 2^29)", (long)T * N);
+    LSTM_TRAIN_SHAPE("lstm_train_forward");
     BH_REQUIRE(x && w_ih && w_hh && h_out && saved, "lstm_train_forward: null pointer");
     BH_REQUIRE(aligned16(x) && aligned16(h_out) && aligned16(saved), "lstm_train_forward: x, h_out and saved must be 16-byte aligned");
     BH_REQUIRE(reverse == 0 || reverse == 1, "lstm_train_forward: reverse must be 0 or 1 (got %d)", reverse);
@@ -416,18 +287,13 @@ int bh_k_lstm_train_forward(const void* x, const float* w_ih, const float* w_hh,
     char* sv = (char*)saved;
     half_t* wih16 = (half_t*)(sv + L.wih);
     half_t* whh16 = (half_t*)(sv + L.whh);
-    const int cvt_grid = (4 * H * H + 255) / 256 < 1024 ? (4 * H * H + 255) / 256 : 1024;
-    hipLaunchKernelGGL(lstm_train_weights_kernel, dim3(cvt_grid), dim3(256), 0, stream, w_ih, wih16, (int)W_ROWS, H);
-    hipLaunchKernelGGL(lstm_train_weights_kernel, dim3(cvt_grid), dim3(256), 0, stream, w_hh, whh16, (int)W_FWD, H);
+    const int grid = cvt_grid(4l * H * H);
+    hipLaunchKernelGGL(lstm_train_weights_kernel, dim3(grid), dim3(256), 0, stream, w_ih, wih16, (int)W_ROWS, H);
+    hipLaunchKernelGGL(lstm_train_weights_kernel, dim3(grid), dim3(256), 0, stream, w_hh, whh16, (int)W_FWD, H);
     BH_CHECK_HIP(hipGetLastError());
     // G = x W_ih^T + b over all T N rows, fp16
-    const long rows = (long)T * N;
-    for (long m0 = 0; m0 < rows; m0 += gemm_rows(H)) {
-        const int m = (int)(rows - m0 < gemm_rows(H) ? rows - m0 : gemm_rows(H));
-        if (int rc = bh_k_linear((const half_t*)x + m0 * H, wih16, bias, (half_t*)(sv + L.gates) + m0 * 4 * H, m, 4 * H, H, H, H, 4 * H, ACT_NONE,
-                                 1.0f, -INFINITY, INFINITY, 0, 0, 0, 0, 0, stream))
-            return rc;
-    }
+    if (int rc = linear_rows((const half_t*)x, wih16, bias, (half_t*)(sv + L.gates), T, N, H, 4 * H, ACT_NONE, 1.0f, -INFINITY, INFINITY, false, stream))
+        return rc;
     FwdArgs a{whh16, (half_t*)(sv + L.hfrag), (half_t*)(sv + L.gates), (float*)(sv + L.c), (half_t*)h_out, T, N, H, reverse};
     hipLaunchKernelGGL(lstm_train_fwd_kernel, dim3((N + TILE_N - 1) / TILE_N), dim3(recurrent_threads(H)), 0, stream, a);
     BH_CHECK_HIP(hipGetLastError());
@@ -438,16 +304,13 @@ int bh_k_lstm_train_backward(const void* x, const float* w_ih, const float* w_hh
                              int N, int H, int reverse, void* dx, float* dw_ih, float* dw_hh, float* dbias, void* workspace,
                              size_t workspace_bytes, hipStream_t stream) {
     using namespace bh;
-    BH_REQUIRE(T >= 1 && N >= 1, "lstm_train_backward: T and N must be positive (got T=%d N=%d)", T, N);
-    BH_REQUIRE(H >= 32 && H <= 1024 && H % 32 == 0, "lstm_train_backward: hidden size %d is not supported (a multiple of 32 in 32..1024)", H);
-    BH_REQUIRE((long)T * N < (1l << 29), "lstm_train_backward: T * N = %ld rows are too many for one call (below 2^29)", (long)T * N);
+    LSTM_TRAIN_SHAPE("lstm_train_backward");
     BH_REQUIRE(x && w_ih && w_hh && h && saved && dh && dx && dw_ih && dw_hh && workspace, "lstm_train_backward: null pointer");
     BH_REQUIRE(aligned16(x) && aligned16(h) && aligned16(saved) && aligned16(dh) && aligned16(dx) && aligned16(workspace),
                "lstm_train_backward: x, h, saved, dh, dx and workspace must be 16-byte aligned");
     BH_REQUIRE(reverse == 0 || reverse == 1, "lstm_train_backward: reverse must be 0 or 1 (got %d)", reverse);
     const SavedLayout L(T, N, H);
     const WorkLayout W(T, N, H);
-    const GradSplit g(T, N, H);
     BH_REQUIRE(workspace_bytes >= W.total, "lstm_train_backward: workspace of %zu bytes, bh_lstm_train_backward_workspace(%d, %d, %d) = %zu",
                workspace_bytes, T, N, H, W.total);
     const char* sv = (const char*)saved;
@@ -455,30 +318,15 @@ int bh_k_lstm_train_backward(const void* x, const float* w_ih, const float* w_hh
     half_t* da = (half_t*)(ws + W.da);
     half_t* wihT = (half_t*)(ws + W.wihT);
     half_t* whhT = (half_t*)(ws + W.whhT);
-    float* dw_part = (float*)(ws + W.dw_part);
-    float* db_part = (float*)(ws + W.db_part);
-    const int cvt_grid = (4 * H * H + 255) / 256 < 1024 ? (4 * H * H + 255) / 256 : 1024;
-    hipLaunchKernelGGL(lstm_train_weights_kernel, dim3(cvt_grid), dim3(256), 0, stream, w_ih, wihT, (int)W_COLS, H);
-    hipLaunchKernelGGL(lstm_train_weights_kernel, dim3(cvt_grid), dim3(256), 0, stream, w_hh, whhT, (int)W_BWD, H);
+    const int grid = cvt_grid(4l * H * H);
+    hipLaunchKernelGGL(lstm_train_weights_kernel, dim3(grid), dim3(256), 0, stream, w_ih, wihT, (int)W_COLS, H);
+    hipLaunchKernelGGL(lstm_train_weights_kernel, dim3(grid), dim3(256), 0, stream, w_hh, whhT, (int)W_BWD, H);
     BwdArgs a{whhT, (half_t*)(ws + W.dafrag), (const half_t*)(sv + L.gates), (const float*)(sv + L.c), (const half_t*)dh, da, (float*)(ws + W.carry), T, N, H, reverse};
     hipLaunchKernelGGL(lstm_train_bwd_kernel, dim3((N + TILE_N - 1) / TILE_N), dim3(recurrent_threads(H)), 0, stream, a);
     BH_CHECK_HIP(hipGetLastError());
     // dx = dA W_ih over all T N rows, fp16
-    const long rows = (long)T * N;
-    for (long m0 = 0; m0 < rows; m0 += gemm_rows(H)) {
-        const int m = (int)(rows - m0 < gemm_rows(H) ? rows - m0 : gemm_rows(H));
-        if (int rc = bh_k_linear(da + m0 * 4 * H, wihT, nullptr, (half_t*)dx + m0 * H, m, H, 4 * H, 4 * H, 4 * H, H, ACT_NONE, 1.0f, -INFINITY,
-                                 INFINITY, 0, 0, 0, 0, 0, stream))
-            return rc;
-    }
-    DwArgs d{da, (const half_t*)x, (const half_t*)h, dw_part, T, N, H, reverse, g.dw_rows};
-    hipLaunchKernelGGL(lstm_train_dw_kernel, dim3(4 * H / DW_TILE, 2 * H / DW_TILE, g.dw_splits), dim3(256), 0, stream, d);
-    if (dbias)
-        hipLaunchKernelGGL(lstm_train_db_kernel, dim3(4 * H / DB_THREADS, g.db_splits), dim3(DB_THREADS), 0, stream, da, db_part, (long)T * N, H,
-                           g.db_rows);
-    const long outputs = 8l * H * H + 4 * H;
-    hipLaunchKernelGGL(lstm_train_reduce_kernel, dim3((unsigned)((outputs + 255) / 256)), dim3(256), 0, stream, dw_part, g.dw_splits, db_part,
-                       g.db_splits, H, dw_ih, dw_hh, dbias);
-    BH_CHECK_HIP(hipGetLastError());
-    return 0;
+    if (int rc = linear_rows(da, wihT, nullptr, (half_t*)dx, T, N, 4 * H, H, ACT_NONE, 1.0f, -INFINITY, INFINITY, false, stream)) return rc;
+    // dW_ih, dW_hh = dA^T [X | H_prev] and db = the column sums of dA, over all T N rows
+    const RowRule rule{(const half_t*)x, ROWS_LSTM, H, 0, 0, 0, 0, 0, (const half_t*)h, T, N, reverse};
+    return reduce_rows(da, rule, (long)T * N, 4 * H, 2 * H, (float*)(ws + W.dw_part), (float*)(ws + W.db_part), dw_ih, dw_hh, dbias, stream);
 }

@@ -1,6 +1,5 @@
 // What the two pairwise aligners share: align.hip (Smith-Waterman and its semi-global mode) and nw.hip (banded global alignment).
-// Each piece is written ONCE here and the kernels and entry points of the two files are written in terms of them; mapper.hip takes
-// align_up256 for its own layout.
+// Each piece is written ONCE here and the kernels and entry points of the two files are written in terms of them.
 //
 // Device code: rows per lane and per pass, the DPP wave shift, the hand-off of a pass's last row, the address of a traceback word and
 // the run-length writer of the tracebacks. Host code: the argument checks with the walk over the pairs, the copy of the lengths and
@@ -93,8 +92,6 @@ struct RunWriter {
 };
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-inline size_t align_up256(size_t v) { return (v + 255) / 256 * 256; }
-
 // The checks every entry makes, and the walk over the pairs (a.seq_len / a.ref_len: the caller's host arrays). need(m, r) -> the most
 // CIGAR runs a pair of these lengths can have; it is called once per pair, after the pair's lengths passed.
 template <class Need>

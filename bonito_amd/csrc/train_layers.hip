@@ -17,189 +17,22 @@
 //     gradient is discontinuous. Convolution: act' at z recomputed in fp32 from x and the rounded weights (conv_dz_kernel, an implicit
 //     GEMM on MFMA 16x16x32 whose both operands are 16-byte global loads: a window of the channel-minor x is contiguous; Cin == 1 on the
 //     VALU). Linear: tanh' = 1 - (Y / scale)^2 from the stored Y.
-//     dW = dz^T B over the M rows and db = sum of dz are ONE kernel pair for both layers (atb_kernel + reduce_kernel): B's row m is
-//     X[m] for the linear layer and, for the convolution, the window of K Cin contiguous halves at x[n][t s - p], zero where it hangs
-//     over an edge (RowRule). The rows are split into blocks whose partial sums are added in block order: no floating-point
-//     atomics, equal bytes from call to call.
-//     dx: linear through bh_k_linear on W^T (fp16 copy made by linear_weights_kernel); convolution in conv_dx_kernel, one thread per 8
+//     dW = dz^T B over the M rows and db = sum of dz come from reduce_rows (train_common.hip), the reduction over rows of every
+//     training layer: B's row m is X[m] for the linear layer (ROWS_PLAIN) and, for the convolution, the window of K Cin contiguous
+//     halves at x[n][t s - p], zero where it hangs over an edge (ROWS_CONV). The rows are split into blocks whose partial sums are
+//     added in block order: no floating-point atomics, equal bytes from call to call.
+//     dx: linear through linear_rows on W^T (fp16 copy made by linear_weights_kernel); convolution in conv_dx_kernel, one thread per 8
 //     input channels of one input position, taps with (l + p - k) mod s == 0 only, fp32 sums in a fixed order.
-// Every kernel of this file indexes with 64 bits. bh_k_linear is called on blocks of rows whose operands stay below 2^30 halves.
-#include <math.h>
-
+// Every kernel of this file indexes with 64 bits. bh_k_linear is called through linear_rows (train_common.hip), on blocks of rows whose
+// operands stay below 2^30 halves.
 #include <cmath>
 
-#include "common.h"
-#include "kernels.h"
+#include "train_common.h"
 
 namespace bh {
 namespace {
 
-typedef half8_t __attribute__((may_alias)) half8_alias_t;
-typedef half_t __attribute__((may_alias)) half_alias_t;
-
-constexpr int RT_TILE = 64;            // atb kernel: 64 x 64 outputs per workgroup
-constexpr int RT_KSTEP = 32;           // rows of M per MFMA
-constexpr int RT_LD = RT_KSTEP + 8;    // LDS row pitch in halves (80 bytes: 16-byte aligned, off the power of two)
-constexpr int DB_THREADS = 128;
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 inline int out_len(int Lin, int K, int stride, int pad) { return (Lin + 2 * pad - K) / stride + 1; }
-
-// ---- the reduction over rows: part[z] = A^T B over the rows of block z ------------------------------------------------------------------
-// how the M rows are split: a function of the shape alone (the order of the sums never varies)
-struct Split {
-    int dw_splits, db_splits;
-    long dw_rows, db_rows;       // rows per block (dw_rows a multiple of RT_KSTEP)
-    Split(long M, int R, int Cc) {
-        const long tiles = (long)((R + RT_TILE - 1) / RT_TILE) * ((Cc + RT_TILE - 1) / RT_TILE);
-        long s = (M + 511) / 512;
-        const long cap = tiles >= 1024 ? 1 : 1024 / tiles;
-        if (s > cap) s = cap;
-        if (s < 1) s = 1;
-        long rows = ((M + s - 1) / s + RT_KSTEP - 1) / RT_KSTEP * RT_KSTEP;
-        dw_splits = (int)((M + rows - 1) / rows);
-        dw_rows = rows;
-        long b = (M + 255) / 256;
-        if (b > 1024) b = 1024;
-        rows = (M + b - 1) / b;
-        db_splits = (int)((M + rows - 1) / rows);
-        db_rows = rows;
-    }
-};
-
-// where row m of B lies
-struct RowRule {
-    const half_t* b;
-    int conv;                          // 0: b + m * ld (ld % 8 == 0).  1: the window of position t = m % Lout of chunk n = m / Lout
-    long ld;
-    int Lout, Lin, Cin, stride, pad;   // conv: x [N][Lin][Cin], Cin == 1 or Cin % 8 == 0; column c = k * Cin + ci
-};
-
-__device__ __forceinline__ half8_t load_b8(const RowRule& r, long m, int c8, int Cc) {
-    half8_t v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (c8 >= Cc) return v;
-    if (!r.conv) return *(const half8_t*)(r.b + m * r.ld + c8);
-    const long n = m / r.Lout;
-    const int t = (int)(m - n * r.Lout);
-    if (r.Cin == 1) {
-        const half_t* x = r.b + n * r.Lin;
-        const int l0 = t * r.stride - r.pad + c8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (c8 + j < Cc && l0 + j >= 0 && l0 + j < r.Lin) v[j] = x[l0 + j];
-        return v;
-    }
-    const int k = c8 / r.Cin, ci = c8 - k * r.Cin;      // Cin % 8 == 0: the vector lies in one input position
-    const int l = t * r.stride - r.pad + k;
-    if (l < 0 || l >= r.Lin) return v;
-    return *(const half8_t*)(r.b + (n * r.Lin + l) * r.Cin + ci);
-}
-
-struct AtbArgs {
-    const half_t* a;        // [M][R], R % 4 == 0
-    RowRule b;
-    float* part;            // [splits][R][Cc]
-    long M, rows;
-    int R, Cc;
-};
-
-// part[z][r][c] = sum over the rows m of block z of a[m][r] * B[m][c]   (both operands transposed through LDS, as lstm_train_dw_kernel)
-__global__ __launch_bounds__(256) void atb_kernel(AtbArgs p) {
-    __shared__ __attribute__((aligned(16))) half_t At[RT_TILE * RT_LD];
-    __shared__ __attribute__((aligned(16))) half_t Bt[RT_TILE * RT_LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int R = p.R, Cc = p.Cc;
-    const int r0 = blockIdx.x * RT_TILE, c0 = blockIdx.y * RT_TILE;
-    const long m_lo = (long)blockIdx.z * p.rows, m_hi = m_lo + p.rows < p.M ? m_lo + p.rows : p.M;
-    const int mm = tid >> 3, v = tid & 7;
-    const int r8 = r0 + v * 8, c8 = c0 + v * 8;
-    float4_t acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = float4_t{0.0f, 0.0f, 0.0f, 0.0f};
-    for (long m0 = m_lo; m0 < m_hi; m0 += RT_KSTEP) {
-        const long m = m0 + mm;
-        half8_t a8 = {0, 0, 0, 0, 0, 0, 0, 0}, b8 = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (m < m_hi) {
-            const half_t* ar = p.a + m * R + r8;
-            if ((R & 7) == 0) {
-                if (r8 < R) a8 = *(const half8_t*)ar;
-            } else {
-                if (r8 < R) { const half4_t lo = *(const half4_t*)ar; a8[0] = lo[0]; a8[1] = lo[1]; a8[2] = lo[2]; a8[3] = lo[3]; }
-                if (r8 + 4 < R) { const half4_t hi = *(const half4_t*)(ar + 4); a8[4] = hi[0]; a8[5] = hi[1]; a8[6] = hi[2]; a8[7] = hi[3]; }
-            }
-            b8 = load_b8(p.b, m, c8, Cc);
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            ((half_alias_t*)At)[(v * 8 + j) * RT_LD + mm] = a8[j];
-            ((half_alias_t*)Bt)[(v * 8 + j) * RT_LD + mm] = b8[j];
-        }
-        __syncthreads();
-        const half8_t a = *(const half8_alias_t*)(At + (wave * 16 + (lane & 15)) * RT_LD + (lane >> 4) * 8);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            acc[j] = mfma16(a, *(const half8_alias_t*)(Bt + (j * 16 + (lane & 15)) * RT_LD + (lane >> 4) * 8), acc[j]);
-        __syncthreads();
-    }
-    float* out = p.part + (long)blockIdx.z * R * Cc;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = r0 + wave * 16 + (lane >> 4) * 4 + i, c = c0 + j * 16 + (lane & 15);
-            if (r < R && c < Cc) out[(long)r * Cc + c] = acc[j][i];
-        }
-}
-
-// part[z][r] = sum over the rows of block z of a[m][r]
-__global__ __launch_bounds__(DB_THREADS) void colsum_kernel(const half_t* __restrict__ a, float* __restrict__ part, long M, int R, long rows) {
-    const int r = blockIdx.x * DB_THREADS + threadIdx.x;
-    if (r >= R) return;
-    const long m_lo = (long)blockIdx.y * rows, m_hi = m_lo + rows < M ? m_lo + rows : M;
-    float s = 0.0f;
-    for (long m = m_lo; m < m_hi; ++m) s += (float)a[m * R + r];
-    part[(long)blockIdx.y * R + r] = s;
-}
-
-// the partial sums in the order of the blocks. Cin == 0: dw [R][Cc]. Cin >= 1 (convolution, column c = k Cin + ci): dw [R][Cin][K]
-__global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ part, int splits, const float* __restrict__ dbp, int db_splits,
-                                                     int R, int Cc, int Cin, int K, float* __restrict__ dw, float* __restrict__ db) {
-    const long nw = (long)R * Cc;
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < nw) {
-        float s = part[e];
-        for (int z = 1; z < splits; ++z) s += part[z * nw + e];
-        if (Cin) {
-            const long r = e / Cc;
-            const int c = (int)(e - r * Cc), k = c / Cin, ci = c - k * Cin;
-            dw[(r * Cin + ci) * K + k] = s;
-        } else {
-            dw[e] = s;
-        }
-    } else if (db && e < nw + R) {
-        const long r = e - nw;
-        float s = dbp[r];
-        for (int z = 1; z < db_splits; ++z) s += dbp[(long)z * R + r];
-        db[r] = s;
-    }
-}
-
-// dw = a^T B and db = column sums of a, over M rows; the partial sums go to dw_part / db_part
-int reduce_rows(const half_t* a, const RowRule& b, long M, int R, int Cc, int Cin, int K, float* dw_part, float* db_part, float* dw, float* db,
-                hipStream_t stream) {
-    const Split g(M, R, Cc);
-    AtbArgs d{a, b, dw_part, M, g.dw_rows, R, Cc};
-    hipLaunchKernelGGL(atb_kernel, dim3((R + RT_TILE - 1) / RT_TILE, (Cc + RT_TILE - 1) / RT_TILE, g.dw_splits), dim3(256), 0, stream, d);
-    if (db)
-        hipLaunchKernelGGL(colsum_kernel, dim3((R + DB_THREADS - 1) / DB_THREADS, g.db_splits), dim3(DB_THREADS), 0, stream, a, db_part, M, R,
-                           g.db_rows);
-    const long outputs = (long)R * Cc + R;
-    hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)((outputs + 255) / 256)), dim3(256), 0, stream, dw_part, g.dw_splits, db_part, g.db_splits, R,
-                       Cc, Cin, K, dw, db);
-    BH_CHECK_HIP(hipGetLastError());
-    return 0;
-}
 
 // ---- the master weights, rounded, in the forms the kernels read ---------------------------------------------------------------------------
 // fp32 [Cout][Cin][K] -> fp16 [Cout16][Kp], column k * Cin + c, zero elsewhere: the bytes of bh_conv1d_pack
@@ -228,7 +61,6 @@ __global__ __launch_bounds__(256) void linear_weights_kernel(const float* __rest
         out[transpose ? k * C + c : e] = (half_t)w[e];
     }
 }
-inline int cvt_grid(long n) { return (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024); }
 
 // ---- activation derivative and the clamp's mask ---------------------------------------------------------------------------------------
 __device__ __forceinline__ float act_grad(float z, int act) {
@@ -387,11 +219,11 @@ struct ConvLayout {
         const Split g(M, Cout, K * Cin);
         const size_t wbytes = Cin == 1 ? (size_t)Cout * K * sizeof(float) : (size_t)Kp * ((Cout + 15) / 16 * 16) * sizeof(half_t);
         w = 0;                                  // the packed weights come first: bh_conv1d_packed_halves(Cin, Cout, K) halves
-        bias = align256(w + wbytes);
-        dz = align256(bias + (size_t)Cout * sizeof(float));
-        dw_part = align256(dz + (size_t)M * Cout * sizeof(half_t));
-        db_part = align256(dw_part + (size_t)g.dw_splits * Cout * K * Cin * sizeof(float));
-        total = align256(db_part + (size_t)g.db_splits * Cout * sizeof(float));
+        bias = align_up256(w + wbytes);
+        dz = align_up256(bias + (size_t)Cout * sizeof(float));
+        dw_part = align_up256(dz + (size_t)M * Cout * sizeof(half_t));
+        db_part = align_up256(dw_part + (size_t)g.dw_splits * Cout * K * Cin * sizeof(float));
+        total = align_up256(db_part + (size_t)g.db_splits * Cout * sizeof(float));
     }
 };
 
@@ -415,11 +247,11 @@ struct LinearLayout {
         const long M = (long)T * N;
         const Split g(M, C, K);
         w = 0;                                  // forward: fp16 [C][K]; backward: fp16 [K][C]
-        bias = align256(w + (size_t)C * K * sizeof(half_t));
-        dz = align256(bias + (size_t)C * sizeof(float));
-        dw_part = align256(dz + (size_t)M * C * sizeof(half_t));
-        db_part = align256(dw_part + (size_t)g.dw_splits * C * K * sizeof(float));
-        total = align256(db_part + (size_t)g.db_splits * C * sizeof(float));
+        bias = align_up256(w + (size_t)C * K * sizeof(half_t));
+        dz = align_up256(bias + (size_t)C * sizeof(float));
+        dw_part = align_up256(dz + (size_t)M * C * sizeof(half_t));
+        db_part = align_up256(dw_part + (size_t)g.dw_splits * C * K * sizeof(float));
+        total = align_up256(db_part + (size_t)g.db_splits * C * sizeof(float));
     }
 };
 
@@ -429,14 +261,6 @@ const char* linear_shape_error(int T, int N, int K, int C) {
     if (K < 8 || K % 8 != 0 || K > 16384) return "K must be a multiple of 8 up to 16384";
     if (C < 8 || C % 8 != 0 || C > 16384) return "C must be a multiple of 8 up to 16384";
     return nullptr;
-}
-// rows of one bh_k_linear call: its kernels may index an operand with 32-bit offsets, so both stay below 2^30 halves; the rows of a GEMM
-// are independent, the blocks change no byte. With the batch-major row map a block is whole time steps (a multiple of N rows).
-inline long gemm_rows(int K, int C, int N, bool whole_steps) {
-    long rows = (1l << 30) / (K > C ? K : C);
-    if (whole_steps) rows = rows / N >= 1 ? rows / N * N : N;
-    else rows = rows / 256 >= 1 ? rows / 256 * 256 : rows;
-    return rows;
 }
 
 struct LinearDzArgs {
@@ -541,8 +365,8 @@ int bh_k_conv_train_backward(const void* x, const float* w, const float* bias, c
     else
         hipLaunchKernelGGL(conv_dz_kernel, dim3((unsigned)((long)N * a.tblocks), (Cout + 63) / 64), dim3(256), 0, stream, a);
     BH_CHECK_HIP(hipGetLastError());
-    const RowRule rule{(const half_t*)x, 1, 0, L.Lout, Lin, Cin, stride, pad};
-    if (int rc = reduce_rows(a.dz, rule, M, Cout, K * Cin, Cin, K, (float*)(ws + L.dw_part), (float*)(ws + L.db_part), dw, db, stream)) return rc;
+    const RowRule rule{(const half_t*)x, ROWS_CONV, 0, L.Lout, Lin, Cin, stride, pad};
+    if (int rc = reduce_rows(a.dz, rule, M, Cout, K * Cin, (float*)(ws + L.dw_part), (float*)(ws + L.db_part), dw, nullptr, db, stream)) return rc;
     if (dx) {
         const long items = (long)N * Lin * (Cin == 1 ? 1 : Cin / 8);
         if (Cin == 1) hipLaunchKernelGGL(conv_first_dx_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, a);
@@ -579,19 +403,7 @@ int bh_k_linear_train_forward(const void* x, const float* w, const float* bias, 
     hipLaunchKernelGGL(linear_weights_kernel, dim3(cvt_grid((long)C * K)), dim3(256), 0, stream, w, w16, C, K, 0);
     if (bias) hipLaunchKernelGGL(round_kernel, dim3(cvt_grid(C)), dim3(256), 0, stream, bias, b16, (long)C);
     BH_CHECK_HIP(hipGetLastError());
-    const long rows = (long)T * N, step = gemm_rows(K, C, N, batch_major != 0);
-    for (long m0 = 0; m0 < rows; m0 += step) {
-        const int m = (int)(rows - m0 < step ? rows - m0 : step);
-        int rc;
-        if (batch_major)      // rows are (t, n): the engine's remap to [N][T][C]; the block starts at time step m0 / N
-            rc = bh_k_linear((const half_t*)x + m0 * K, w16, b16, (half_t*)y + m0 / N * C, m, C, K, K, K, C, act, scale, clamp_lo, clamp_hi, 0, N, 1,
-                             T, N, stream);
-        else
-            rc = bh_k_linear((const half_t*)x + m0 * K, w16, b16, (half_t*)y + m0 * C, m, C, K, K, K, C, act, scale, clamp_lo, clamp_hi, 0, 0, 0, 0,
-                             0, stream);
-        if (rc) return rc;
-    }
-    return 0;
+    return linear_rows((const half_t*)x, w16, b16, (half_t*)y, T, N, K, C, act, scale, clamp_lo, clamp_hi, batch_major != 0, stream);
 }
 
 int bh_k_linear_train_backward(const void* x, const float* w, const void* y, const void* dy, int T, int N, int K, int C, int act, float scale,
@@ -614,14 +426,8 @@ int bh_k_linear_train_backward(const void* x, const float* w, const void* y, con
     if (dx) {      // dx = dz W over all rows, fp16
         hipLaunchKernelGGL(linear_weights_kernel, dim3(cvt_grid((long)C * K)), dim3(256), 0, stream, w, wT, C, K, 1);
         BH_CHECK_HIP(hipGetLastError());
-        const long step = gemm_rows(K, C, N, false);
-        for (long m0 = 0; m0 < rows; m0 += step) {
-            const int m = (int)(rows - m0 < step ? rows - m0 : step);
-            if (int rc = bh_k_linear(dz + m0 * C, wT, nullptr, (half_t*)dx + m0 * K, m, K, C, C, C, K, ACT_NONE, 1.0f, -INFINITY, INFINITY, 0, 0, 0,
-                                     0, 0, stream))
-                return rc;
-        }
+        if (int rc = linear_rows(dz, wT, nullptr, (half_t*)dx, T, N, C, K, ACT_NONE, 1.0f, -INFINITY, INFINITY, false, stream)) return rc;
     }
-    const RowRule rule{(const half_t*)x, 0, K, 0, 0, 0, 0, 0};
-    return reduce_rows(dz, rule, rows, C, K, 0, 0, (float*)(ws + L.dw_part), (float*)(ws + L.db_part), dw, db, stream);
+    const RowRule rule{(const half_t*)x, ROWS_PLAIN, K};
+    return reduce_rows(dz, rule, rows, C, K, (float*)(ws + L.dw_part), (float*)(ws + L.db_part), dw, nullptr, db, stream);
 }

@@ -13,6 +13,7 @@ NoTorchCompute, an unsupported shape or dtype raises ValueError before anything 
 import torch
 
 from bonito_amd import _lib
+from bonito_amd._train import HalfLayer, devices, half, master, tensors
 from bonito_amd.nn import NoTorchCompute
 
 __all__ = ["lstm_forward", "lstm_backward", "lstm", "lstm_module", "supported_hidden_size"]
@@ -23,35 +24,27 @@ def supported_hidden_size(H):
 
 
 def _check(x, w_ih, w_hh, bias, what):
-    tensors = [("x", x), ("w_ih", w_ih), ("w_hh", w_hh)] + ([("bias", bias)] if bias is not None else [])
-    for name, t in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("%s: %s must be a tensor, got %s" % (what, name, type(t).__name__))
+    named = [("x", x), ("w_ih", w_ih), ("w_hh", w_hh)] + ([("bias", bias)] if bias is not None else [])
+    tensors(named, what)
     if x.dim() != 3 or x.shape[0] < 1 or x.shape[1] < 1:
         raise ValueError("%s: x must be [T][N][H] with T, N >= 1, got %s" % (what, tuple(x.shape)))
     T, N, H = x.shape
     if not supported_hidden_size(H):
         raise ValueError("%s: hidden size %d is not supported (a multiple of 32 in 32..1024)" % (what, H))
-    for name, t in (("w_ih", w_ih), ("w_hh", w_hh)):
+    for name, t in named[1:3]:
         if tuple(t.shape) != (4 * H, H):
             raise ValueError("%s: %s must be [%d][%d] (insize == size), got %s" % (what, name, 4 * H, H, tuple(t.shape)))
-        if t.dtype != torch.float32:
-            raise ValueError("%s: %s must be float32 (the master weights), got %s" % (what, name, t.dtype))
+        master(t, t.shape, name, what)
     if bias is not None and (tuple(bias.shape) != (4 * H,) or bias.dtype != torch.float32):
         raise ValueError("%s: bias must be float32 [%d], got %s %s" % (what, 4 * H, bias.dtype, tuple(bias.shape)))
-    for name, t in tensors:                     # shapes and dtypes are judged first: they are wrong on any device
-        if t.device.type != "cuda":
-            raise NoTorchCompute("%s runs on a HIP device only; %s is a %s tensor" % (what, name, t.device))
-        if t.device != x.device:
-            raise ValueError("%s: %s is on %s, x on %s" % (what, name, t.device, x.device))
+    devices(named, what)
     return T, N, H
 
 
 def _half3(t, shape, name, what):
     if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
         raise NoTorchCompute("%s runs on a HIP device only; %s is not a device tensor" % (what, name))
-    if t.dtype != torch.float16 or tuple(t.shape) != tuple(shape):
-        raise ValueError("%s: %s must be float16 %s, got %s %s" % (what, name, tuple(shape), t.dtype, tuple(t.shape)))
+    half(t, shape, name, what)
     return t.contiguous()
 
 
@@ -98,32 +91,22 @@ def lstm_backward(x, w_ih, w_hh, h, saved, dh, reverse=False, need_bias=True):
     return dx, dw_ih, dw_hh, db
 
 
-class _Lstm(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w_ih, w_hh, bias, reverse):
-        x16 = x if x.dtype == torch.float16 else x.to(torch.float16)
-        h, saved = lstm_forward(x16, w_ih, w_hh, bias, reverse)
-        ctx.save_for_backward(x16, w_ih, w_hh, h, saved)
-        ctx.reverse, ctx.x_dtype, ctx.has_bias = bool(reverse), x.dtype, bias is not None
-        return h
-
-    @staticmethod
-    def backward(ctx, dh):
-        x16, w_ih, w_hh, h, saved = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        dx, dw_ih, dw_hh, db = lstm_backward(x16, w_ih, w_hh, h, saved, dh.to(torch.float16), ctx.reverse,
-                                             need_bias=ctx.has_bias and need[3])
-        return (dx.to(ctx.x_dtype) if need[0] else None, dw_ih if need[1] else None, dw_hh if need[2] else None,
-                db if ctx.has_bias and need[3] else None, None)
-
-
 def lstm(x, w_ih, w_hh, bias=None, reverse=False):
     """h fp16 [T][N][H] of one layer, differentiable with respect to x (fp16 or fp32; fp32 is cast to fp16 and its gradient comes back
     as fp32), the two weight matrices and the bias, each where requires_grad is set."""
     if isinstance(x, torch.Tensor) and x.dtype not in (torch.float16, torch.float32):
         raise ValueError("lstm: x must be float16 or float32, got %s" % x.dtype)
     _check(x, w_ih, w_hh, bias, "lstm")
-    return _Lstm.apply(x, w_ih, w_hh, bias, bool(reverse))
+    reverse = bool(reverse)
+
+    def forward(x16, w_ih, w_hh, bias):
+        h, saved = lstm_forward(x16, w_ih, w_hh, bias, reverse)
+        return h, (x16, w_ih, w_hh, h, saved)
+
+    def backward(kept, dh, need):
+        return lstm_backward(*kept, dh, reverse, need_bias=bias is not None and need[3])
+
+    return HalfLayer.apply(forward, backward, x, w_ih, w_hh, bias)
 
 
 def lstm_module(module, x):

@@ -20,7 +20,7 @@ import math
 import torch
 
 from bonito_amd import _lib
-from bonito_amd.nn import NoTorchCompute
+from bonito_amd._train import HalfLayer, devices as _devices, half as _half, master as _master, tensors as _tensors
 
 __all__ = ["conv1d_forward", "conv1d_backward", "conv1d", "linear_forward", "linear_backward", "linear", "conv_out_len"]
 
@@ -47,34 +47,6 @@ def _clamp(clamp, what):
     if not lo <= hi:
         raise ValueError("%s: clamp range (%g, %g) is empty" % (what, lo, hi))
     return lo, hi
-
-
-def _devices(tensors, what):
-    """Shapes and dtypes are judged first (they are wrong on any device); then every tensor must be on one HIP device."""
-    first = tensors[0][1]
-    for name, t in tensors:
-        if t.device.type != "cuda":
-            raise NoTorchCompute("%s runs on a HIP device only; %s is a %s tensor" % (what, name, t.device))
-        if t.device != first.device:
-            raise ValueError("%s: %s is on %s, %s on %s" % (what, name, t.device, tensors[0][0], first.device))
-
-
-def _tensors(named, what):
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("%s: %s must be a tensor, got %s" % (what, name, type(t).__name__))
-
-
-def _master(t, shape, name, what):
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError("%s: %s must be %s, got %s" % (what, name, tuple(shape), tuple(t.shape)))
-    if t.dtype != torch.float32:
-        raise ValueError("%s: %s must be float32 (the master weights), got %s" % (what, name, t.dtype))
-
-
-def _half(t, shape, name, what):
-    if t.dtype != torch.float16 or tuple(t.shape) != tuple(shape):
-        raise ValueError("%s: %s must be float16 %s, got %s %s" % (what, name, tuple(shape), t.dtype, tuple(t.shape)))
 
 
 # ---- convolution ------------------------------------------------------------------------------------------------------------------------
@@ -161,26 +133,6 @@ def conv1d_backward(x, weight, bias, y, dy, stride=1, padding=0, activation=None
     return dx, dw, db
 
 
-class _Conv1d(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias, stride, padding, activation, clamp, time_major):
-        x16 = x if x.dtype == torch.float16 else x.to(torch.float16)
-        y = conv1d_forward(x16, weight, bias, stride, padding, activation, clamp, time_major)
-        ctx.save_for_backward(x16, weight, bias, y)
-        ctx.args = (stride, padding, activation, clamp, time_major)
-        ctx.x_dtype = x.dtype
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x16, weight, bias, y = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        dx, dw, db = conv1d_backward(x16, weight, bias, y, dy.to(torch.float16), *ctx.args, need_dx=need[0],
-                                     need_db=bias is not None and need[2])
-        return (dx.to(ctx.x_dtype) if need[0] else None, dw if need[1] else None, db if bias is not None and need[2] else None,
-                None, None, None, None, None)
-
-
 def conv1d(x, weight, bias=None, stride=1, padding=0, activation=None, clamp=None, time_major=False):
     """y fp16 of one convolution with its activation and clamp, differentiable with respect to x (fp16 or fp32; fp32 is cast to fp16 and
     its gradient comes back as fp32), weight and bias, each where requires_grad is set. An input channel count that is neither 1 nor a
@@ -198,7 +150,16 @@ def conv1d(x, weight, bias=None, stride=1, padding=0, activation=None, clamp=Non
         x = torch.nn.functional.pad(x, (0, extra))
         weight = torch.nn.functional.pad(weight, (0, 0, 0, extra))
     _conv_check(x, weight, bias, stride, padding, activation, clamp, what, dtypes=both)
-    return _Conv1d.apply(x, weight, bias, int(stride), int(padding), activation, clamp, bool(time_major))
+    args = (int(stride), int(padding), activation, clamp, bool(time_major))
+
+    def forward(x16, weight, bias):
+        y = conv1d_forward(x16, weight, bias, *args)
+        return y, (x16, weight, bias, y)
+
+    def backward(kept, dy, need):
+        return conv1d_backward(*kept, dy, *args, need_dx=need[0], need_db=kept[2] is not None and need[2])
+
+    return HalfLayer.apply(forward, backward, x, weight, bias)
 
 
 # ---- linear -----------------------------------------------------------------------------------------------------------------------------
@@ -270,27 +231,17 @@ def linear_backward(x, weight, y, dy, activation=None, scale=None, clamp=None, b
     return dx, dw, db
 
 
-class _Linear(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias, activation, scale, clamp, batch_major_out):
-        x16 = x if x.dtype == torch.float16 else x.to(torch.float16)
-        y = linear_forward(x16, weight, bias, activation, scale, clamp, batch_major_out)
-        ctx.save_for_backward(x16, weight, y)
-        ctx.args = (activation, scale, clamp, batch_major_out)
-        ctx.x_dtype, ctx.has_bias = x.dtype, bias is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x16, weight, y = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        want_db = ctx.has_bias and need[2]
-        dx, dw, db = linear_backward(x16, weight, y, dy.to(torch.float16), *ctx.args, need_dx=need[0], need_db=want_db)
-        return (dx.to(ctx.x_dtype) if need[0] else None, dw if need[1] else None, db if want_db else None, None, None, None, None)
-
-
 def linear(x, weight, bias=None, activation=None, scale=None, clamp=None, batch_major_out=False):
     """Y fp16 of one linear layer or CRF head (activation none or tanh, scale, clamp), differentiable with respect to x (fp16 or fp32;
     fp32 is cast to fp16 and its gradient comes back as fp32), weight and bias, each where requires_grad is set."""
     _linear_check(x, weight, bias, activation, scale, clamp, "linear", dtypes=(torch.float16, torch.float32))
-    return _Linear.apply(x, weight, bias, activation, scale, clamp, bool(batch_major_out))
+    args = (activation, scale, clamp, bool(batch_major_out))
+
+    def forward(x16, weight, bias):
+        y = linear_forward(x16, weight, bias, *args)
+        return y, (x16, weight, y)
+
+    def backward(kept, dy, need):
+        return linear_backward(*kept, dy, *args, need_dx=need[0], need_db=bias is not None and need[2])
+
+    return HalfLayer.apply(forward, backward, x, weight, bias)

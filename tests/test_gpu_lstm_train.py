@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 MARGIN = 2.0
 GRAD_CLASSES = ("typical", "long_memory", "saturating")
-GRAD_SHAPES = ((37, 5, 32), (64, 16, 96), (24, 16, 384), (300, 16, 96), (4, 16, 1024), (2, 20, 32))      # (T, N, H)
+GRAD_SHAPES = ((37, 5, 32), (64, 16, 96), (24, 16, 384), (300, 16, 96), (4, 16, 1024), (2, 20, 32), (1, 5, 32))      # (T, N, H)
 
 
 @functools.lru_cache(maxsize=None)
@@ -79,6 +79,8 @@ def test_backward_within_twice_the_yardstick(cls, T, N, H, reverse):
     exact, yard = _references(cls, T, N, H, reverse)
     got = _device_run(cls, T, N, H, reverse)[1:]
     assert got[0].dtype == torch.float16 and all(g.dtype == torch.float32 for g in got[1:])
+    if T == 1:                                                                # h_0 = 0: no row of h_prev exists
+        assert int(torch.count_nonzero(got[2])) == 0
     failed = []
     for name, g, e, y in zip(tr.NAMES, got, exact, yard):
         dk, dy = tr.dist(g, e), tr.dist(y, e)

@@ -199,6 +199,27 @@ def test_workspace_sizes_refuse_unsupported_shapes():
         assert lib.bh_linear_train_workspace(*bad) == 0, bad
 
 
+def test_buffer_sizes_equal_the_parent_commit():
+    """tests/golden/train_parent.json was written by tests/golden/make_golden_train_parent.py at the commit it names, before the
+    layers shared one reduction over rows. The partial sums of the weight gradients are the tail of every workspace, so equal sizes
+    mean equal block counts: the order of the sums. The table holds every CONV_CASES and LINEAR_CASES row, and for the LSTM layer
+    shapes where the cap on the blocks binds (H = 1024) and where the last block is short (150 x 20 at H = 64)."""
+    import json
+    from bonito_amd import _lib
+    with open(ROOT + "/tests/golden/train_parent.json") as fh:
+        gold = json.load(fh)
+    lib = _lib.lib()
+    assert len(gold["lstm"]) == 6 * 5 and len(gold["linear"]) == len(tl.LINEAR_CASES)
+    assert {(r[0], r[2], r[3], r[4], r[5], r[1]) for r in gold["conv"]} >= set(tl.CONV_CASES)
+    assert [64, 150, 20] in [[r[2], r[0], r[1]] for r in gold["lstm"]] and [1024, 600, 64] in [[r[2], r[0], r[1]] for r in gold["lstm"]]
+    for T, N, H, saved, work in gold["lstm"]:
+        assert lib.bh_lstm_train_saved_bytes(T, N, H) == saved and lib.bh_lstm_train_backward_workspace(T, N, H) == work, (T, N, H)
+    for *shape, want in gold["conv"]:
+        assert lib.bh_conv1d_train_workspace(*shape) == want, shape
+    for *shape, want in gold["linear"]:
+        assert lib.bh_linear_train_workspace(*shape) == want, shape
+
+
 def test_entry_points_refuse_before_any_device_call():
     """The argument checks stand in front of every launch: the pointers below are never read."""
     import ctypes as C

@@ -1,0 +1,90 @@
+#!/usr/bin/env python3
+"""sha256 of what the training layers compute on a few small, seeded cases: the record that a change of the code left every byte alone.
+
+    python tools/train_bytes.py [--out FILE]
+
+Only the public functions of bonito_amd.rnn and bonito_amd.train_ops are called, so the same file runs in a checkout of an earlier
+commit; run it there and here on the same device and compare the two lines (hashes of device output depend on the toolchain and are
+not a committed golden). Inputs come from the generators of the tests (tests/lstm_ref.py, tests/lstm_train_ref.py,
+tests/train_layers_ref.py; fixed seeds).
+
+    LSTM (T, N, H, direction)   several blocks of rows with a short last one, T N % 32 != 0, a padded batch tile, T = 1 (no h_prev row
+                                exists), both directions; h, dx, dw_ih, dw_hh, db with a bias gradient and dx, dw_ih, dw_hh without
+    convolution                 CONV_CASES rows 0, 3, 4, 7, clamp on and off: y, dx, dw, db
+    linear                      LINEAR_CASES rows 1, 3, 4, both row maps: y, dx, dw, db
+
+Prints one JSON line {case: {tensor: sha256}}."""
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import lstm_ref as lr  # noqa: E402
+import lstm_train_ref as tr  # noqa: E402
+import train_layers_ref as tl  # noqa: E402
+from bonito_amd import rnn, train_ops  # noqa: E402
+
+LSTM_CASES = ((150, 20, 64, False), (600, 5, 32, False), (37, 5, 32, True), (3, 37, 128, True), (1, 5, 32, False), (1, 5, 32, True),
+              (24, 16, 384, False))
+CONV_ROWS = (0, 3, 4, 7)
+LINEAR_ROWS = (1, 3, 4)
+
+
+def sha(t):
+    return None if t is None else hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("train_bytes: no HIP device; nothing is hashed without one")
+    dev = torch.device("cuda:0")
+    res = {}
+    for T, N, H, reverse in LSTM_CASES:
+        x, w_ih, w_hh, bias = (None if t is None else t.to(dev) for t in lr.make_case("typical", T, N, H, seed=1))
+        dh = tr.make_dh(T, N, H, seed=1).to(dev)
+        h, saved = rnn.lstm_forward(x, w_ih, w_hh, bias, reverse)
+        row = {"h": sha(h)}
+        for need_bias in (True, False):
+            out = rnn.lstm_backward(x, w_ih, w_hh, h, saved, dh, reverse, need_bias=need_bias)
+            assert (out[3] is None) == (not need_bias)
+            row.update({name + ("" if need_bias else "/no_db"): sha(t) for name, t in zip(("dx", "dw_ih", "dw_hh", "db"), out) if t is not None})
+        res["lstm T=%d N=%d H=%d %s" % (T, N, H, "rev" if reverse else "fwd")] = row
+    for i in CONV_ROWS:
+        case = tl.CONV_CASES[i]
+        x, w, b, dy, pad = tl.conv_inputs(case)
+        x = x[:, :, 0].contiguous() if case[1] == 1 else x
+        x, w, b, dy = x.to(dev), w.to(dev), b.to(dev), dy.to(dev)
+        for clamp in (None, tl.CLAMP):
+            y = train_ops.conv1d_forward(x, w, b, case[4], pad, "swish", clamp)
+            dx, dw, db = train_ops.conv1d_backward(x, w, b, y, dy, case[4], pad, "swish", clamp)
+            res["conv row %d %s" % (i, "clamped" if clamp else "free")] = {"y": sha(y), "dx": sha(dx), "dw": sha(dw), "db": sha(db)}
+    for i in LINEAR_ROWS:
+        case = tl.LINEAR_CASES[i]
+        act, scale, clamp = case[4:7]
+        x, w, b, dy = (None if t is None else t.to(dev) for t in tl.linear_inputs(case))
+        for batch_major in (False, True):
+            y = train_ops.linear_forward(x, w, b, act, scale, clamp, batch_major)
+            dyd = dy.permute(1, 0, 2).contiguous() if batch_major else dy
+            dx, dw, db = train_ops.linear_backward(x, w, y, dyd, act, scale, clamp, batch_major)
+            res["linear row %d %s" % (i, "ntc" if batch_major else "tnc")] = {"y": sha(y), "dx": sha(dx), "dw": sha(dw), "db": sha(db)}
+    torch.cuda.synchronize()
+    line = json.dumps(res, sort_keys=True)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
