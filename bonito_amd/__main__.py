@@ -3,9 +3,9 @@ import sys
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
 from bonito_amd import __version__
-from bonito_amd.cli import basecaller, duplex, evaluate
+from bonito_amd.cli import basecaller, duplex, evaluate, train
 
-modules = ["basecaller", "duplex", "evaluate"]
+modules = ["basecaller", "duplex", "evaluate", "train"]
 
 
 def main(argv=None):

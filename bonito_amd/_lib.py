@@ -35,7 +35,7 @@ BH_LAYER_CONV, BH_LAYER_LSTM, BH_LAYER_LINEAR_CRF, BH_LAYER_CLAMP = 1, 2, 3, 4
 BH_LAYER_TRANSFORMER, BH_LAYER_UPSAMPLE, BH_LAYER_TCS_BLOCK, BH_LAYER_CTC_DECODER = 5, 6, 7, 8
 BH_LAYER_DWCONV, BH_LAYER_RESIDUAL_PROJ, BH_LAYER_LINEAR = 9, 10, 11
 
-_vp, _i, _f, _l, _sz = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t
+_vp, _i, _f, _l, _sz, _d = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes).  Every symbol include/bonito_hip.h declares must be listed here
 # (tests/test_abi.py cross-checks the header against this table and against the built library).
@@ -141,6 +141,11 @@ SIGNATURES = {
     "bh_lstm_q8_layer_split": (_i, [_vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "bh_lstm_layer_family": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "bh_lstm_launch_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i]),
+    "bh_optim_chunk": (_i, []),
+    "bh_optim_workspace": (_sz, [_vp, _i]),
+    "bh_optim_norm": (_i, [_vp, _vp, _i, _vp, _d, _i, _d, _d, _i, _d, _d, _vp, _sz, _vp]),
+    "bh_optim_update": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _d, _d, _d, _d, _d, _vp]),
+    "bh_optim_last_kernel": (_i, []),
     "bh_encoder_debug_read": (_i, [_vp, _vp, _sz, _sz]),
     "bh_encoder_set_option": (_i, [_vp, C.c_char_p, _i]),
 }

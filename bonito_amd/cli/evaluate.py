@@ -16,27 +16,11 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from bonito_amd.util import init, load_model
+from bonito_amd.data import load_numpy_datasets
+from bonito_amd.util import decode_ref, init, load_model
 
 SUMM_COLUMNS = ("accuracy", "num_correct", "num_mismatches", "num_insertions", "num_deletions", "ref_len", "seq_len",
                 "align_ref_start", "align_ref_end", "align_seq_start", "align_seq_end")
-
-
-def load_numpy_datasets(limit=None, directory=None):
-    """chunks, references, reference_lengths of a directory (reference bonito/data.py:122-144)."""
-    chunks = np.load(os.path.join(directory, "chunks.npy"), mmap_mode="r")
-    targets = np.load(os.path.join(directory, "references.npy"), mmap_mode="r")
-    lengths = np.load(os.path.join(directory, "reference_lengths.npy"), mmap_mode="r")
-    indices = os.path.join(directory, "indices.npy")
-    if os.path.exists(indices):
-        idx = np.load(indices, mmap_mode="r")
-        idx = idx[idx < lengths.shape[0]]
-        if limit:
-            idx = idx[:limit]
-        return chunks[idx, :], targets[idx, :], lengths[idx]
-    if limit:
-        chunks, targets, lengths = chunks[:limit], targets[:limit], lengths[:limit]
-    return np.array(chunks), np.array(targets), np.array(lengths)
 
 
 def load_chunks(directory, dataset="valid", chunks=512):
@@ -54,11 +38,6 @@ def load_chunks(directory, dataset="valid", chunks=512):
         return data
     split = max(0, len(data[0]) - chunks)
     return tuple(x[split:] if dataset == "valid" else x[:split] for x in data)
-
-
-def decode_ref(encoded, labels):
-    """Integer-encoded reference -> string (reference util.py decode_ref)."""
-    return "".join(labels[int(e)] for e in encoded if e)
 
 
 def report_lines(table, seq_len, ref_len, losses):

@@ -7,6 +7,7 @@ SAM tags follow documentation/SAM.md:39-55: ``mv:B:c,<stride>,<moves...>``, ``qs
 ``ns:i`` (samples incl. trimmed), ``ts:i`` (trimmed samples), ``RG:Z``.
 """
 import csv
+import os
 import sys
 from threading import Thread
 
@@ -211,6 +212,46 @@ class Writer(Thread):
                 summary.close()
         except BaseException as exc:       # surfaced by the caller after join()
             self.error = exc
+
+
+class CSVLogger:
+    """Appends dict rows to a CSV file (losses_N.csv, training.csv of a training run; the reference's bonito/io.py CSVLogger). The
+    first row ever written fixes the columns and writes the header; a file that exists already keeps its header, and its columns
+    choose what later rows contribute ('-' where a row lacks one)."""
+
+    def __init__(self, filename, sep=","):
+        self.filename = str(filename)
+        self.columns = None
+        if os.path.exists(self.filename):
+            with open(self.filename, newline="") as fh:
+                self.columns = csv.DictReader(fh, delimiter=sep).fieldnames
+        self.fh = open(self.filename, "a", newline="")
+        self.writer = csv.writer(self.fh, delimiter=sep)
+        self.unflushed = 0
+
+    def set_columns(self, columns):
+        if self.columns:
+            raise ValueError("CSVLogger: the columns of %s are set already" % self.filename)
+        self.columns = list(columns)
+        self.writer.writerow(self.columns)
+
+    def append(self, row):
+        if self.columns is None:
+            self.set_columns(row.keys())
+        self.writer.writerow([row.get(k, "-") for k in self.columns])
+        self.unflushed += 1
+        if self.unflushed > 100:
+            self.unflushed = 0
+            self.fh.flush()
+
+    def close(self):
+        self.fh.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class RejectCounter(dict):

@@ -334,3 +334,67 @@ def accuracy(ref, seq, balanced=False, min_coverage=0.0, result=None):
     if balanced:
         return (counts["="] - counts["I"]) / (counts["="] + counts["X"] + counts["D"]) * 100
     return counts["="] / (counts["="] + counts["I"] + counts["X"] + counts["D"]) * 100
+
+
+def decode_ref(encoded, labels):
+    """Integer-encoded reference -> string (reference util.py decode_ref)."""
+    return "".join(labels[int(e)] for e in encoded if e)
+
+
+def _toml_value(value, what):
+    if isinstance(value, bool):
+        return "true" if value else "false"
+    if isinstance(value, (int, np.integer)):
+        return "%d" % value
+    if isinstance(value, (float, np.floating)):
+        if value != value:
+            return "nan"
+        if value in (float("inf"), float("-inf")):
+            return "inf" if value > 0 else "-inf"
+        text = repr(float(value))
+        return text if any(c in text for c in ".en") else text + ".0"
+    if isinstance(value, (str, Path)):
+        text = str(value).replace("\\", "\\\\").replace('"', '\\"')
+        for raw, escaped in (("\n", "\\n"), ("\t", "\\t"), ("\r", "\\r"), ("\b", "\\b"), ("\f", "\\f")):
+            text = text.replace(raw, escaped)
+        return '"%s"' % "".join(c if ord(c) >= 0x20 and ord(c) != 0x7F else "\\u%04x" % ord(c) for c in text)
+    if isinstance(value, (list, tuple)):
+        return "[" + ", ".join(_toml_value(v, what) for v in value) + "]"
+    if isinstance(value, dict):                  # a table inside a list of values: inline
+        return "{" + ", ".join("%s = %s" % (_toml_key(k), _toml_value(v, what)) for k, v in value.items()) + "}"
+    raise TypeError("dump_toml: %s holds a %s, which has no TOML form here" % (what, type(value).__name__))
+
+
+def _toml_key(key):
+    key = str(key)
+    return key if re.fullmatch(r"[A-Za-z0-9_-]+", key) else _toml_value(key, key)
+
+
+def dump_toml(config, fh=None):
+    """TOML text of a nested dict of str / int / float / bool / lists (a config.toml: tables, and lists of tables such as an encoder's
+    ``sublayers``); written to `fh` when given. None values are left out (TOML has none). Read back by ``load_toml``."""
+    lines = []
+
+    def is_tables(v):
+        return isinstance(v, (list, tuple)) and len(v) > 0 and all(isinstance(x, dict) for x in v)
+
+    def table(d, path):
+        for k, v in d.items():
+            if v is not None and not isinstance(v, dict) and not is_tables(v):
+                lines.append("%s = %s" % (_toml_key(k), _toml_value(v, ".".join(path + [str(k)]))))
+        for k, v in d.items():
+            sub = path + [str(k)]
+            name = ".".join(_toml_key(p) for p in sub)
+            if isinstance(v, dict):
+                lines.extend(["", "[%s]" % name])
+                table(v, sub)
+            elif is_tables(v):
+                for item in v:
+                    lines.extend(["", "[[%s]]" % name])
+                    table(item, sub)
+
+    table(config, [])
+    text = "\n".join(lines).lstrip("\n") + "\n"
+    if fh is not None:
+        fh.write(text)
+    return text

@@ -825,6 +825,44 @@ size_t bh_lstm_workspace(int N, int H);
 int bh_lstm_layer(const void* gates_in, const void* whh_packed, void* h_out, int T, int N, int H,
                   int reverse, void* workspace, int* err_flag, int flags, void* stream);
 
+/* ---- the optimizer step behind backward(): unscale, gradient norm, overflow check, clip, AdamW, loss scale (csrc/optim.hip) ----------
+ * Per tensor i of n[i] elements: p, m, v (fp32, updated in place) and g (fp32, never written), DEVICE pointers in HOST arrays; they
+ * travel to the kernels by value, at most 32 tensors per launch, so there is no per-step copy and no table in device memory.
+ * ctl: DEVICE double [BH_OPTIM_CTL_WORDS], the control block. The caller initialises SCALE (the loss scale), GROWTH_TRACKER = 0,
+ *   STEP = 0, BETA1_POW = BETA2_POW = 1; the other words are written by every bh_optim_norm call.
+ * bh_optim_norm (once per step, over every tensor of every parameter group):
+ *   partial sums: one workgroup of 256 threads per chunk of BH_OPTIM_CHUNK elements writes the fp32 sum of g^2 of its chunk to slot
+ *     (launch, workgroup) of the workspace; the split and the order of the additions depend on the sizes alone.
+ *   finalise, one wave: sum = the slots added in fp64 (lane l the slots l, l + 64, ..; then the lanes in order);
+ *     scale = use_scale ? ctl[SCALE] : 1;  GRAD_NORM = sqrt(sum) / scale;  SKIPPED = !isfinite(sum);  SCALE_USED = scale;
+ *     not skipped: STEP += 1, BETA1_POW *= beta1, BETA2_POW *= beta2, CLIP_COEF = max_norm > 0 ? min(1, max_norm / (GRAD_NORM + 1e-6)) : 1,
+ *       GRAD_MUL = CLIP_COEF / scale, BIAS1 = 1 - BETA1_POW, BIAS2_SQRT = sqrt(1 - BETA2_POW);   skipped: CLIP_COEF = GRAD_MUL = 0;
+ *     use_scale (torch's GradScaler): skipped -> SCALE *= backoff, GROWTH_TRACKER = 0; otherwise ++GROWTH_TRACKER == growth_interval
+ *       -> SCALE *= growth, GROWTH_TRACKER = 0.
+ * bh_optim_update (once per parameter group, behind bh_optim_norm on the same stream), elementwise and operation by operation in fp32,
+ *   the scalars rounded to fp32 once:  gs = g * (float)GRAD_MUL;  p = p * (float)(1 - lr * weight_decay);  m = beta1 * m + (1 - beta1) * gs;
+ *   v = beta2 * v + ((1 - beta2) * gs) * gs;  denom = sqrt(v) / (float)BIAS2_SQRT + eps;  p = p - (float)(lr / BIAS1) * (m / denom),
+ *   divide and square root correctly rounded. With SKIPPED set the kernel returns in front of its first store.
+ *   float4 accesses where p, g, m and v of a tensor are all 16-byte aligned, scalar ones otherwise (same arithmetic).
+ * workspace: bh_optim_workspace(n, n_tensors) bytes (0 = bad sizes), the caller's, 4-byte aligned.
+ * Bad arguments (null pointers, n < 1, lr / eps / weight_decay / betas out of range, a small workspace) return nonzero with
+ * bh_last_error() set and launch nothing. Stream-ordered; nothing is allocated and nothing synchronises inside.
+ * TEST HOOK bh_optim_last_kernel: the access paths the last bh_optim_update of this thread used, BH_OPTIM_K_VECTOR | BH_OPTIM_K_SCALAR. */
+#define BH_OPTIM_CHUNK 8192
+enum bh_optim_ctl {
+    BH_OPTIM_SCALE = 0, BH_OPTIM_GROWTH_TRACKER = 1, BH_OPTIM_STEP = 2, BH_OPTIM_BETA1_POW = 3, BH_OPTIM_BETA2_POW = 4,
+    BH_OPTIM_GRAD_NORM = 5, BH_OPTIM_CLIP_COEF = 6, BH_OPTIM_SKIPPED = 7, BH_OPTIM_SCALE_USED = 8, BH_OPTIM_GRAD_MUL = 9,
+    BH_OPTIM_BIAS1 = 10, BH_OPTIM_BIAS2_SQRT = 11, BH_OPTIM_CTL_WORDS = 16
+};
+enum bh_optim_kernel { BH_OPTIM_K_VECTOR = 1, BH_OPTIM_K_SCALAR = 2 };
+int bh_optim_chunk(void);
+size_t bh_optim_workspace(const long* n, int n_tensors);
+int bh_optim_norm(const float* const* g, const long* n, int n_tensors, double* ctl, double max_norm, int use_scale, double growth,
+                  double backoff, int growth_interval, double beta1, double beta2, void* workspace, size_t workspace_bytes, void* stream);
+int bh_optim_update(float* const* p, const float* const* g, float* const* m, float* const* v, const long* n, int n_tensors,
+                    const double* ctl, double lr, double beta1, double beta2, double eps, double weight_decay, void* stream);
+int bh_optim_last_kernel(void);
+
 #ifdef __cplusplus
 }
 #endif
