@@ -79,6 +79,10 @@ SIGNATURES = {
     "bh_lstm_train_workgroups": (_i, [_i]),
     "bh_lstm_train_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "bh_lstm_train_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "bh_attention_train_saved_bytes": (_sz, [_i, _i, _i]),
+    "bh_attention_train_backward_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "bh_attention_train_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "bh_attention_train_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "bh_conv1d_train_workspace": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "bh_conv1d_train_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _l, _l, _vp, _vp, _sz, _vp]),
     "bh_conv1d_train_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _l, _l, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -390,6 +390,20 @@ extern "C" int bh_lstm_train_backward(const void* x, const float* w_ih, const fl
     return bh_k_lstm_train_backward(x, w_ih, w_hh, h, saved, dh, T, N, H, reverse, dx, dw_ih, dw_hh, dbias, workspace, workspace_bytes,
                                     (hipStream_t)stream);
 }
+extern "C" size_t bh_attention_train_saved_bytes(int N, int T, int nhead) { return bh_k_attention_train_saved_bytes(N, T, nhead); }
+extern "C" size_t bh_attention_train_backward_workspace(int N, int T, int nhead, int win_left, int win_right) {
+    return bh_k_attention_train_backward_workspace(N, T, nhead, win_left, win_right);
+}
+extern "C" int bh_attention_train_forward(const void* qkv, const float* cos_sin, int N, int T, int nhead, int head_dim, int win_left,
+                                          int win_right, void* out, void* saved, size_t saved_bytes, void* stream) {
+    return bh_k_attention_train_forward(qkv, cos_sin, N, T, nhead, head_dim, win_left, win_right, out, saved, saved_bytes, (hipStream_t)stream);
+}
+extern "C" int bh_attention_train_backward(const void* qkv, const float* cos_sin, const void* out, const void* saved, const void* dout, int N,
+                                           int T, int nhead, int head_dim, int win_left, int win_right, void* dqkv, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    return bh_k_attention_train_backward(qkv, cos_sin, out, saved, dout, N, T, nhead, head_dim, win_left, win_right, dqkv, workspace,
+                                         workspace_bytes, (hipStream_t)stream);
+}
 extern "C" size_t bh_conv1d_train_workspace(int N, int Lin, int Cin, int Cout, int K, int stride, int pad) {
     return bh_k_conv_train_workspace(N, Lin, Cin, Cout, K, stride, pad);
 }

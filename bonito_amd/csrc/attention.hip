@@ -29,12 +29,13 @@ struct AttnArgs {
     int N, T, H;         // H heads, D = 64*H
     int wl, wr;          // window: i-wl <= j <= i+wr
     float scale;         // 1/sqrt(64)
+    float* lse;          // [N][H][T] m + ln(sum) of every query's row, for the backward (attention_train.hip); only attention_kernel<NT, true> writes it
 };
 
 constexpr int QB = 128;     // queries per workgroup
 constexpr int HD = 64;
 
-template <int NT>           // key tiles (of 16) per wave, even
+template <int NT, bool LSE>  // key tiles (of 16) per wave, even; LSE: the training forward, which also writes lse
 __global__ __launch_bounds__(512) void attention_kernel(AttnArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int KR = 7 * 16 + NT * 16;          // staged key rows
@@ -176,6 +177,9 @@ __global__ __launch_bounds__(512) void attention_kernel(AttnArgs p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) ov[e] = (half_t)o[mt][e];
             *(half4_t*)(op + mt * 16) = ov;
+        }
+        if constexpr (LSE) {
+            if (g == 0) p.lse[((long)n * p.H + h) * p.T + qi] = m + __logf(sum);      // every query sees itself: sum >= 1, m finite
         }
     }
 }
@@ -704,21 +708,27 @@ __global__ __launch_bounds__(256) void rmsnorm_residual_kernel(NormArgs p) {
 
 }  // namespace bh
 
-int bh_k_attention(const void* qkv, void* out, const float* cos_sin, int N, int T, int nhead, int head_dim,
-                   int win_left, int win_right, hipStream_t stream) {
+// lse == nullptr: inference (attention_kernel<NT, false>); otherwise the training forward, which also writes lse [N][H][T]
+static int attention_launch(const void* qkv, void* out, const float* cos_sin, int N, int T, int nhead, int head_dim,
+                            int win_left, int win_right, float* lse, hipStream_t stream) {
     using namespace bh;
     BH_REQUIRE(head_dim == 64, "attention: only head_dim 64 is implemented (got %d)", head_dim);
     BH_REQUIRE(win_left >= 0 && win_right >= 0, "attention: a finite window (left, right) is required (got (%d, %d))", win_left, win_right);
     BH_REQUIRE(N > 0 && T > 0 && nhead > 0, "attention: empty problem");
     const int need = (16 + win_left + win_right + 15) / 16;      // key tiles one wave can see
-    AttnArgs a{(const half_t*)qkv, (half_t*)out, cos_sin, N, T, nhead, win_left, win_right, 0.125f};
+    AttnArgs a{(const half_t*)qkv, (half_t*)out, cos_sin, N, T, nhead, win_left, win_right, 0.125f, lse};
     dim3 grid((T + QB - 1) / QB, nhead, N);
-#define BH_ATTN(NT)                                                                                   \
+#define BH_ATTN_L(NT, L)                                                                                \
     do {                                                                                              \
         const size_t lds = (size_t)(7 * 16 + NT * 16) * 128 + (size_t)64 * (7 * 16 + NT * 16 + 4) * 2; \
         if (lds > 64 * 1024)                                                                          \
-            BH_CHECK_HIP(bh_max_lds((const void*)attention_kernel<NT>, (int)lds)); \
-        hipLaunchKernelGGL(attention_kernel<NT>, grid, dim3(512), lds, stream, a);                    \
+            BH_CHECK_HIP(bh_max_lds((const void*)attention_kernel<NT, L>, (int)lds)); \
+        hipLaunchKernelGGL((attention_kernel<NT, L>), grid, dim3(512), lds, stream, a);                \
+    } while (0)
+#define BH_ATTN(NT)                        \
+    do {                                   \
+        if (lse != nullptr) BH_ATTN_L(NT, true); \
+        else BH_ATTN_L(NT, false);         \
     } while (0)
     if (need <= 6) BH_ATTN(6);
     else if (need <= 10) BH_ATTN(10);
@@ -726,8 +736,20 @@ int bh_k_attention(const void* qkv, void* out, const float* cos_sin, int N, int 
     else if (need <= 26) BH_ATTN(26);
     else BH_REQUIRE(false, "attention: window %d+%d is too wide for the LDS-resident kernel", win_left, win_right);
 #undef BH_ATTN
+#undef BH_ATTN_L
     BH_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+int bh_k_attention(const void* qkv, void* out, const float* cos_sin, int N, int T, int nhead, int head_dim,
+                   int win_left, int win_right, hipStream_t stream) {
+    return attention_launch(qkv, out, cos_sin, N, T, nhead, head_dim, win_left, win_right, nullptr, stream);
+}
+
+int bh_k_attention_lse(const void* qkv, void* out, const float* cos_sin, int N, int T, int nhead, int head_dim,
+                       int win_left, int win_right, float* lse, hipStream_t stream) {
+    BH_REQUIRE(lse != nullptr, "attention: null lse");
+    return attention_launch(qkv, out, cos_sin, N, T, nhead, head_dim, win_left, win_right, lse, stream);
 }
 
 // q (already rotated and scaled) | k (already rotated) | v  ->  attention output; see attention_ring_kernel.

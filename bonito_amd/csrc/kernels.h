@@ -227,6 +227,22 @@ int bh_k_attention(const void* qkv, void* out, const float* cos_sin, int N, int 
                    int win_left, int win_right, hipStream_t stream);
 int bh_k_rmsnorm_residual(const void* a, const void* x, const float* w, void* out, long M, int D, float alpha,
                           float eps, hipStream_t stream);
+// the same kernel, also writing lse = m + ln(sum) of every query's softmax row, fp32 [N][nhead][T]: the training forward's launch
+int bh_k_attention_lse(const void* qkv, void* out, const float* cos_sin, int N, int T, int nhead, int head_dim,
+                       int win_left, int win_right, float* lse, hipStream_t stream);
+// The windows bh_k_attention serves: a wave's key tiles (of 16) must number at most 26 (attention_kernel<26>)
+inline bool bh_k_attention_serves(int win_left, int win_right) {
+    return win_left >= 0 && win_right >= 0 && (16 + (long)win_left + win_right + 15) / 16 <= 26;
+}
+
+// attention_train.hip (rotary + sliding-window attention for training: the forward that keeps lse, and the backward; device pointers)
+size_t bh_k_attention_train_saved_bytes(int N, int T, int nhead);
+size_t bh_k_attention_train_backward_workspace(int N, int T, int nhead, int win_left, int win_right);
+int bh_k_attention_train_forward(const void* qkv, const float* cos_sin, int N, int T, int nhead, int head_dim, int win_left, int win_right,
+                                 void* out, void* saved, size_t saved_bytes, hipStream_t stream);
+int bh_k_attention_train_backward(const void* qkv, const float* cos_sin, const void* out, const void* saved, const void* dout, int N, int T,
+                                  int nhead, int head_dim, int win_left, int win_right, void* dqkv, void* workspace, size_t workspace_bytes,
+                                  hipStream_t stream);
 
 // ctc.hip
 int bh_k_dwconv(const void* in, const float* w, void* out, int N, int Lin, int Lout, int C, int K, int stride,

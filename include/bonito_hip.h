@@ -26,6 +26,8 @@
  *                                                                              bonito/ctc/model.py:48-57
  *   bh_lstm_train_forward / bh_lstm_train_backward
  *        torch.nn.LSTM under autocast, and its autograd, as the reference's LSTM layer wraps it   bonito/nn.py:353-397
+ *   bh_attention_train_forward / bh_attention_train_backward
+ *        RotaryEmbedding + flash_attn_qkvpacked_func(qkv, window_size=) and their autograd          bonito/transformer/model.py:58-75
  *   bh_sw_align
  *        parasail.sw_trace_striped_32(seq, ref, 8, 4, parasail.dnafull) behind evaluate's align() and util.accuracy
  *                                                                              bonito/cli/evaluate.py:37-67, bonito/util.py:346-368
@@ -353,6 +355,37 @@ int bh_lstm_train_forward(const void* x, const float* w_ih, const float* w_hh, c
 int bh_lstm_train_backward(const void* x, const float* w_ih, const float* w_hh, const void* h, const void* saved, const void* dh, int T,
                            int N, int H, int reverse, void* dx, float* dw_ih, float* dw_hh, float* dbias, void* workspace,
                            size_t workspace_bytes, void* stream);
+
+/* ---- Rotary embedding + sliding-window attention for training (csrc/attention_train.hip): the forward that keeps lse, and the backward ----
+ * The attention layer of a transformer model on packed qkv (what bonito/transformer/model.py:42-79 delegates to RotaryEmbedding and
+ * flash_attn_qkvpacked_func(qkv, window_size=(win_left, win_right))); key j is visible to query i of the same chunk iff
+ * i - win_left <= j <= i + win_right. Per (chunk, head), rot = rotary by bh_rotary_table's angles of the token's position:
+ *     q~ = fp16(rot(q) / 8)    k~ = fp16(rot(k))    s_ij = q~_i . k~_j (fp32)    lse_i = m_i + ln(sum_j exp(s_ij - m_i)) over the visible j
+ *     O_i = fp16(sum_j fp16(exp(s_ij - m_i) / sum_i) V_j)
+ * - the arithmetic, the kernel and the BYTES of bh_attention; lse (fp32 per chunk, head, query) is what `saved` holds. Backward, with
+ * P_ij = exp(s_ij - lse_i) on the visible pairs (s recomputed by the MFMAs of the forward from the same fp16 operands) and
+ * delta_i = sum_d dO_id O_id (fp32, O the stored fp16 output):
+ *     dV_j = sum_i fp16(P_ij) dO_i      dP_ij = dO_i . V_j      dS_ij = fp16(P_ij (dP_ij - delta_i))
+ *     dq~_i = sum_j dS_ij k~_j          dk~_j = sum_i dS_ij q~_i
+ *     dq = rot^-1(dq~) / 8              dk = rot^-1(dk~)         (rot^-1 = rotation by the negated angle)
+ * q~, k~, P and dS are fp16 MFMA operands; every sum and everything else is fp32; dq, dk, dv are rounded once, at the store. Upstream
+ *   gradients arrive loss-scaled; nothing is scaled or clamped here.
+ * EVERY pointer is a device pointer, 16-byte aligned. qkv, dqkv: fp16 [N*T][3*nhead*64] (q | k | v, head-major inside each); out, dout:
+ *   fp16 [N*T][nhead*64]; cos_sin: device copy of bh_rotary_table(T, 64). dqkv is OVERWRITTEN, every element of it.
+ * No floating-point atomics and no order that depends on scheduling: a query pass owns dq of its 128 queries, a key pass owns dk and dv of
+ *   its 128 keys (the window mirrored), both recompute S as the forward did. Two calls give equal bytes; chunks are independent.
+ * saved (bh_attention_train_saved_bytes): lse, written by the forward, read by the backward of the same N, T, nhead and window.
+ *   workspace (bh_attention_train_backward_workspace): delta. Both are the caller's; a buffer that is too small is an error.
+ * Supported (an error with a message, never a substitute, nothing launched, outputs untouched): head_dim == 64, win_left, win_right >= 0
+ *   with (16 + win_left + win_right + 15) / 16 <= 26 (what bh_attention serves), N, T, nhead >= 1, N, nhead <= 65535.
+ * Stream-ordered; nothing is allocated and nothing synchronises inside. */
+size_t bh_attention_train_saved_bytes(int N, int T, int nhead);                                       /* 0 = unsupported */
+size_t bh_attention_train_backward_workspace(int N, int T, int nhead, int win_left, int win_right);   /* 0 = unsupported window */
+int bh_attention_train_forward(const void* qkv, const float* cos_sin, int N, int T, int nhead, int head_dim, int win_left, int win_right,
+                               void* out, void* saved, size_t saved_bytes, void* stream);
+int bh_attention_train_backward(const void* qkv, const float* cos_sin, const void* out, const void* saved, const void* dout,
+                                int N, int T, int nhead, int head_dim, int win_left, int win_right,
+                                void* dqkv, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- The convolution and the linear / CRF-head layer for training (csrc/train_layers.hip): forward on the rounded master weights, backward ----
  * With bh_lstm_train_* and bh_crf_seq_logz_grad these are all layers of an LSTM-family CRF model (SeqdistModel.forward_train).

@@ -1,0 +1,243 @@
+"""The training attention layer on the device (-m gpu): bh_attention_train_forward / bh_attention_train_backward and bonito_amd.attn.
+
+FORWARD. `out` has the bytes of bh_attention on the same inputs, on every shape.
+
+BACKWARD. exact = the written-out formulas in fp64 (tests/attention_train_ref.py, pinned against fp64 autograd by
+tests/test_attention_train_ref_cpu.py); d16 = the distance of the same formulas with fp16 storage at the kernels' rounding places. With
+dist(a) = max|a - exact| / max|exact|, each of dq, dk, dv must satisfy dist(kernel) <= 4 d16: the project's rule for attention
+(tests/test_gpu_attention.py: fp32 accumulation in another order, hardware exp). A planted defect lies beyond 10 x that bound
+(test_attention_train_ref_cpu.py). Every case prints d16 and the kernel's distance; DESIGN.md section 6 records them.
+
+A window under which every query sees one key has exact dq = dk = 0 (d16 = 0): there out = v and dv = dout bytewise, and dq, dk are held to
+the derived bound of attention_train_ref.single_key_bounds.
+
+The rest is exact: equal bytes from call to call, a chunk's bytes independent of the rest of the batch, untouched guard bytes, refusals
+that launch nothing, autograd that hands on the backward's bytes."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import attention_train_ref as tr
+from bonito_amd import _lib, attn
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+FACTOR = 4.0
+SHAPES = ((2, 40, 2, (3, 5)),            # small
+          (2, 130, 3, (1, 7)),           # crosses a block of 128, T % 16 != 0
+          (2, 290, 2, (40, 40)),         # <6> at its upper edge
+          (1, 150, 2, (40, 41)),         # <10> at its lower edge
+          (1, 300, 1, (127, 128)),       # the product's window, <18>
+          (1, 450, 1, (200, 200)),       # <26>, the widest served
+          (1, 140, 2, (0, 144)),         # one-sided
+          (1, 140, 2, (144, 0)))         # (N, T, H, window)
+KINDS = ("gauss", "peaked")
+
+
+@functools.lru_cache(maxsize=None)
+def _case(N, T, H, kind):
+    return tr.make_case(N, T, H, kind, seed=1)
+
+
+@functools.lru_cache(maxsize=None)
+def _references(N, T, H, window, kind):
+    """(exact, d16) of a case, computed once on the CPU and never modified."""
+    qkv, dout = _case(N, T, H, kind)
+    want = tr.exact(qkv, dout, window)
+    return want, tr.d16(qkv, dout, window, want)
+
+
+def _dev(a):
+    return torch.from_numpy(a).to(DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def _device_run(N, T, H, window, kind):
+    """-> (out, dqkv) of the kernels through bonito_amd.attn, on the device."""
+    qkv, dout = (_dev(a) for a in _case(N, T, H, kind))
+    out, saved = attn.attention_forward(qkv, window)
+    dqkv = attn.attention_backward(qkv, out, saved, dout, window)
+    torch.cuda.synchronize()
+    return out, dqkv
+
+
+def _table(T):
+    tab = np.zeros((T, 32, 2), np.float32)
+    _lib.check(_lib.lib().bh_rotary_table(T, 64, tab.ctypes.data_as(C.c_void_p)), "rotary_table")
+    return torch.from_numpy(tab).to(DEV)
+
+
+def _inference(qkv, N, T, H, window):
+    out = torch.full((N, T, H * 64), float("nan"), dtype=torch.float16, device=DEV)
+    _lib.check(_lib.lib().bh_attention(_lib.ptr(qkv), _lib.ptr(out), _lib.ptr(_table(T)), N, T, H, 64, window[0], window[1], _lib.stream_ptr()),
+               "bh_attention")
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("N,T,H,window", SHAPES, ids=lambda v: str(v))
+def test_forward_has_the_bytes_of_bh_attention(N, T, H, window, kind):
+    out = _device_run(N, T, H, window, kind)[0]
+    assert out.dtype == torch.float16 and tuple(out.shape) == (N, T, H * 64)
+    want = _inference(_dev(_case(N, T, H, kind)[0]), N, T, H, window)
+    assert bool(torch.isfinite(want).all())
+    assert torch.equal(out.view(torch.int16), want.view(torch.int16))
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("N,T,H,window", SHAPES, ids=lambda v: str(v))
+def test_backward_within_four_times_the_cost_of_fp16_storage(N, T, H, window, kind):
+    want, d16 = _references(N, T, H, window, kind)
+    dqkv = _device_run(N, T, H, window, kind)[1]
+    assert dqkv.dtype == torch.float16 and tuple(dqkv.shape) == (N, T, 3, H, 64)
+    failed = []
+    for name, g, w in zip(tr.PARTS, tr.split(dqkv.cpu().numpy()), want[1:]):
+        dk = tr.dist(g, w)
+        print("backward %s %s %s: d16 = %.3e  dist(kernel) = %.3e  ratio = %.2f" % ((N, T, H, window), kind, name, d16[name], dk, dk / d16[name]))
+        if not dk <= FACTOR * d16[name]:
+            failed.append((name, dk, d16[name]))
+    assert not failed, failed
+
+
+@pytest.mark.parametrize("N,T,H,window", [(1, 17, 1, (0, 0)), (1, 1, 1, (3, 5))], ids=lambda v: str(v))
+def test_single_visible_key(N, T, H, window):
+    """P = 1: out = v and dv = dout bytewise; dq and dk (exactly 0 in the reference) within the derived bound."""
+    qkv, dout = _case(N, T, H, "gauss")
+    out, dqkv = _device_run(N, T, H, window, "gauss")
+    assert np.array_equal(out.cpu().numpy().view(np.int16), qkv[:, :, 2].reshape(N, T, H * 64).view(np.int16))
+    dq, dk, dv = tr.split(dqkv.cpu().numpy())
+    assert np.array_equal(dqkv.cpu().numpy()[:, :, 2].reshape(N, T, H * 64).view(np.int16), dout.view(np.int16))
+    bq, bk = tr.single_key_bounds(qkv, dout)
+    print("single key %s: max |dq| / bound = %.3f, max |dk| / bound = %.3f" % ((N, T, H, window), (np.abs(dq) / bq).max(), (np.abs(dk) / bk).max()))
+    assert (np.abs(dq) <= bq).all() and (np.abs(dk) <= bk).all()
+
+
+GUARD = 512
+
+
+class _Guarded:
+    """A device tensor between two guard zones of GUARD bytes of 0xA5 (the payload starts 0xA5 too)."""
+
+    def __init__(self, shape, dtype):
+        n = 1
+        for s in shape:
+            n *= s
+        self.nbytes = n * torch.empty(0, dtype=dtype).element_size()
+        self.raw = torch.full((self.nbytes + 2 * GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
+        self.t = self.raw[GUARD:GUARD + self.nbytes].view(dtype).view(shape)
+
+    def guards_intact(self):
+        return bool((self.raw[:GUARD] == 0xA5).all()) and bool((self.raw[GUARD + self.nbytes:] == 0xA5).all())
+
+    def payload_untouched(self):
+        return bool((self.raw == 0xA5).all())
+
+
+def _buffers(N, T, H, window):
+    lib = _lib.lib()
+    sb, wb = lib.bh_attention_train_saved_bytes(N, T, H), lib.bh_attention_train_backward_workspace(N, T, H, window[0], window[1])
+    assert sb >= N * T * H * 4 and wb >= N * T * H * 4
+    return {"out": _Guarded((N, T, H * 64), torch.float16), "saved": _Guarded((sb,), torch.uint8),
+            "dqkv": _Guarded((N, T, 3, H, 64), torch.float16), "ws": _Guarded((wb,), torch.uint8)}
+
+
+def _raw_call(qkv, dout, N, T, H, window):
+    """Both entry points on buffers of this test's own -> dict of _Guarded (out, saved, dqkv, ws)."""
+    lib, o, tab, s = _lib.lib(), _buffers(N, T, H, window), _table(T), _lib.stream_ptr()
+    _lib.check(lib.bh_attention_train_forward(_lib.ptr(qkv), _lib.ptr(tab), N, T, H, 64, window[0], window[1], _lib.ptr(o["out"].t),
+                                              _lib.ptr(o["saved"].t), o["saved"].nbytes, s), "forward")
+    _lib.check(lib.bh_attention_train_backward(_lib.ptr(qkv), _lib.ptr(tab), _lib.ptr(o["out"].t), _lib.ptr(o["saved"].t), _lib.ptr(dout), N, T, H,
+                                               64, window[0], window[1], _lib.ptr(o["dqkv"].t), _lib.ptr(o["ws"].t), o["ws"].nbytes, s), "backward")
+    torch.cuda.synchronize()
+    return o
+
+
+@pytest.mark.parametrize("N,T,H,window", [(2, 130, 3, (1, 7)), (1, 300, 1, (127, 128)), (1, 450, 1, (200, 200))], ids=lambda v: str(v))
+def test_two_calls_give_equal_bytes_and_guard_bytes_are_untouched(N, T, H, window):
+    qkv, dout = (_dev(a) for a in _case(N, T, H, "gauss"))
+    a, b = _raw_call(qkv, dout, N, T, H, window), _raw_call(qkv, dout, N, T, H, window)
+    for name in a:
+        assert a[name].guards_intact() and b[name].guards_intact(), name
+    for name in ("out", "dqkv"):
+        assert torch.equal(a[name].t.view(torch.int16), b[name].t.view(torch.int16)), name
+        assert bool(torch.isfinite(a[name].t).all()), name
+    words = N * T * H                                     # lse and delta: fp32 per (chunk, head, query); the rest is alignment nobody writes
+    for name in ("saved", "ws"):
+        fa, fb = (x[name].t[:words * 4].view(torch.float32) for x in (a, b))
+        assert torch.equal(fa.view(torch.int32), fb.view(torch.int32)) and bool(torch.isfinite(fa).all()), name
+    # ... and they are the bytes the public wrappers return
+    out, dqkv = _device_run(N, T, H, window, "gauss")
+    assert torch.equal(a["out"].t, out) and torch.equal(a["dqkv"].t, dqkv)
+
+
+def test_a_chunk_has_the_bytes_it_has_alone():
+    N, T, H, window = 3, 150, 2, (40, 41)
+    qkv, dout = (_dev(a) for a in _case(N, T, H, "peaked"))
+    out, saved = attn.attention_forward(qkv, window)
+    dqkv = attn.attention_backward(qkv, out, saved, dout, window)
+    q1, d1 = qkv[1:2].contiguous(), dout[1:2].contiguous()
+    out1, saved1 = attn.attention_forward(q1, window)
+    dqkv1 = attn.attention_backward(q1, out1, saved1, d1, window)
+    assert torch.equal(out1.view(torch.int16), out[1:2].view(torch.int16))
+    assert torch.equal(dqkv1.view(torch.int16), dqkv[1:2].view(torch.int16))
+    assert int(torch.count_nonzero(dqkv1)) > 0
+
+
+def test_refused_calls_leave_the_outputs_untouched():
+    N, T, H, window = 2, 40, 2, (3, 5)
+    qkv, dout = (_dev(a) for a in _case(N, T, H, "gauss"))
+    lib, tab, s = _lib.lib(), _table(T), _lib.stream_ptr()
+    o = _buffers(N, T, H, window)
+
+    def fwd(hd=64, wl=3, wr=5, saved_bytes=None):
+        return lib.bh_attention_train_forward(_lib.ptr(qkv), _lib.ptr(tab), N, T, H, hd, wl, wr, _lib.ptr(o["out"].t), _lib.ptr(o["saved"].t),
+                                              o["saved"].nbytes if saved_bytes is None else saved_bytes, s)
+
+    def bwd(hd=64, wl=3, wr=5, ws_bytes=None):
+        return lib.bh_attention_train_backward(_lib.ptr(qkv), _lib.ptr(tab), _lib.ptr(dout), _lib.ptr(o["saved"].t), _lib.ptr(dout), N, T, H, hd,
+                                               wl, wr, _lib.ptr(o["dqkv"].t), _lib.ptr(o["ws"].t), o["ws"].nbytes if ws_bytes is None else ws_bytes, s)
+
+    for call in (fwd, bwd):
+        assert call(hd=32) != 0 and "head_dim 64" in _lib.last_error()
+        assert call(wl=-1, wr=-1) != 0 and "finite window" in _lib.last_error()
+        assert call(wl=200, wr=201) != 0 and "too wide" in _lib.last_error()
+    assert fwd(saved_bytes=o["saved"].nbytes - 256) != 0 and "saved buffer" in _lib.last_error()
+    assert bwd(ws_bytes=o["ws"].nbytes - 256) != 0 and "workspace of" in _lib.last_error()
+    torch.cuda.synchronize()
+    for name in o:
+        assert o[name].payload_untouched(), name
+    # the wrappers refuse before any launch as well
+    with pytest.raises(ValueError, match="too wide"):
+        attn.attention_forward(qkv, (200, 201))
+    with pytest.raises(ValueError, match="finite window"):
+        attn.attention(qkv, (-1, -1))
+    out, saved = attn.attention_forward(qkv, window)
+    with pytest.raises(ValueError, match="`saved` is not"):
+        attn.attention_backward(qkv, out, saved[:-256], dout, window)
+    with pytest.raises(ValueError, match="`saved` is not"):
+        attn.attention_backward(qkv, out, attn.attention_forward(qkv[:1].contiguous(), window)[1], dout, window)
+    with pytest.raises(ValueError, match="dout must be float16"):
+        attn.attention_backward(qkv, out, saved, dout.float(), window)
+
+
+@pytest.mark.parametrize("N,T,H,window", [(2, 130, 3, (1, 7)), (1, 150, 2, (40, 41))], ids=lambda v: str(v))
+def test_autograd_hands_on_the_bytes_of_the_backward(N, T, H, window):
+    qkv, dout = (_dev(a) for a in _case(N, T, H, "gauss"))
+    out_want, dqkv_want = _device_run(N, T, H, window, "gauss")
+    leaf = qkv.clone().requires_grad_()
+    out = attn.attention(leaf, window)
+    assert torch.equal(out.detach(), out_want)
+    out.backward(dout)
+    assert leaf.grad.dtype == torch.float16 and torch.equal(leaf.grad.view(torch.int16), dqkv_want.view(torch.int16))
+    # an fp32 leaf (and the flat [N][T][3*H*64] layout): the same values, handed back as fp32
+    leaf32 = qkv.float().reshape(N, T, 3 * H * 64).requires_grad_()
+    out32 = attn.attention(leaf32, window)
+    assert out32.dtype == torch.float16 and torch.equal(out32.detach(), out_want)
+    out32.backward(dout)
+    assert leaf32.grad.dtype == torch.float32 and tuple(leaf32.grad.shape) == (N, T, 3 * H * 64)
+    assert torch.equal(leaf32.grad, dqkv_want.float().reshape(N, T, 3 * H * 64))
