@@ -5,6 +5,7 @@ import torch
 
 from bonito_amd import decode
 from conftest import assert_qstrings_agree
+from decode_cases import planted_scores
 from oracle import crf_ref
 
 pytestmark = pytest.mark.gpu
@@ -278,16 +279,7 @@ def test_posterior_viterbi_confident_scores_exact_and_model_api():
     rng = np.random.default_rng(9)
     model = make_model("fast")
     state_len, N, T = model.seqdist.state_len, 6, 400
-    S = 4 ** state_len
-    sc = (rng.standard_normal((N, T, 4 * S)) * 0.5 - 3.0)
-    for n in range(N):
-        st = int(rng.integers(S))
-        for t in range(T):
-            if rng.random() < 0.45:
-                new = (st * 4 + int(rng.integers(4))) % S
-                sc[n, t, new * 4 + st // (S // 4)] = 4.5
-                st = new
-    sc = np.clip(sc, -5, 5).astype(np.float16)
+    sc = planted_scores(rng, N, T, state_len)          # (the generator lives with the plane sweep's cases: same draws, same scores)
     moves, path = decode.posterior_viterbi(torch.from_numpy(sc).cuda())
     om, op = crf_ref.posterior_viterbi(sc, state_len)
     assert np.array_equal(path.numpy(), op)
