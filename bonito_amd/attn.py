@@ -26,7 +26,8 @@ _tables = {}      # (device, T) -> the device copy of bh_rotary_table(T, 64)
 
 
 def supported_window(window):
-    """A finite window the kernels serve: left, right >= 0 and at most 26 key tiles of 16 per wave."""
+    """A finite window the kernels serve: left, right >= 0 and at most 26 key tiles of 16 per wave.
+    The 26 must equal BH_ATTN_MAX_TILES of csrc/kernels.h (bh_k_attention_serves)."""
     try:
         wl, wr = (int(w) for w in window)
     except (TypeError, ValueError):

@@ -16,6 +16,7 @@
 //   The whole visible key range is in registers (<= NT tiles), so the softmax is exact, not online.
 #include <type_traits>
 
+#include "attn_block.h"
 #include "common.h"
 #include "kernels.h"
 #include "options.h"
@@ -28,69 +29,36 @@ struct AttnArgs {
     const float* cs;     // [T][32][2]  (cos, sin) of position * inv_freq
     int N, T, H;         // H heads, D = 64*H
     int wl, wr;          // window: i-wl <= j <= i+wr
-    float scale;         // 1/sqrt(64)
+    float scale;         // QK_SCALE
     float* lse;          // [N][H][T] m + ln(sum) of every query's row, for the backward (attention_train.hip); only attention_kernel<NT, true> writes it
 };
 
-constexpr int QB = 128;     // queries per workgroup
-constexpr int HD = 64;
-
+// the staging and the two tile products are attn_block.h's, shared with the backward passes (attention_train.hip); the softmax between them is this kernel's own
 template <int NT, bool LSE>  // key tiles (of 16) per wave, even; LSE: the training forward, which also writes lse
-__global__ __launch_bounds__(512) void attention_kernel(AttnArgs p) {
+__global__ __launch_bounds__(THREADS) void attention_kernel(AttnArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int KR = 7 * 16 + NT * 16;          // staged key rows
-    constexpr int VS = KR + 4;                    // V^T row stride (halves)
+    constexpr int KR = staged_rows(NT);           // staged key rows
+    constexpr int VS = t_stride(NT);              // V^T row stride (halves)
     char* kl = smem;                              // [KR][128 B] swizzled
-    half_t* vt = (half_t*)(smem + KR * 128);      // [64][VS]
+    half_t* vt = (half_t*)(smem + rows_bytes(NT));      // [64][VS]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int D = p.H * HD;
     const int qb = blockIdx.x, h = blockIdx.y, n = blockIdx.z;
     const int i0 = qb * QB;
     const int jbase = i0 - p.wl;                  // staged row r <-> key jbase + r
-    const half_t* base = p.qkv + (long)n * p.T * 3 * D;
-
-    // ---- stage K (rotary) : task = (row r, pair chunk c in 0..3) ---------------------------------
-    for (int task = tid; task < KR * 4; task += 512) {
-        const int r = task >> 2, c = task & 3;
-        const int j = jbase + r;
-        half8_t lo = {0, 0, 0, 0, 0, 0, 0, 0}, hi = lo;
-        if (j >= 0 && j < p.T) {
-            const half_t* kp = base + (long)j * 3 * D + D + h * HD;
-            const half8_t x1 = *(const half8_t*)(kp + c * 8);
-            const half8_t x2 = *(const half8_t*)(kp + 32 + c * 8);
-            const float* cs = p.cs + ((long)j * 32 + c * 8) * 2;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float co = cs[2 * e], si = cs[2 * e + 1];
-                const float a = (float)x1[e], b = (float)x2[e];
-                lo[e] = (half_t)(a * co - b * si);
-                hi[e] = (half_t)(a * si + b * co);
-            }
-        }
-        *(half8_t*)(kl + r * 128 + ((c ^ (r & 7)) << 4)) = lo;
-        *(half8_t*)(kl + r * 128 + (((c + 4) ^ (r & 7)) << 4)) = hi;
-    }
-    // ---- stage V transposed: task = (key pair kp, d chunk c in 0..7) -----------------------------
-    for (int task = tid; task < (KR / 2) * 8; task += 512) {
-        const int kp2 = task >> 3, c = task & 7;
-        const int r = kp2 * 2;
-        half8_t v0 = {0, 0, 0, 0, 0, 0, 0, 0}, v1 = v0;
-        const int j = jbase + r;
-        if (j >= 0 && j < p.T) v0 = *(const half8_t*)(base + (long)j * 3 * D + 2 * D + h * HD + c * 8);
-        if (j + 1 >= 0 && j + 1 < p.T) v1 = *(const half8_t*)(base + (long)(j + 1) * 3 * D + 2 * D + h * HD + c * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            half2_t pr = {v0[e], v1[e]};
-            *(half2_t*)(vt + (c * 8 + e) * VS + r) = pr;
-        }
-    }
+    const half_t* base = p.qkv + (long)n * p.T * 3 * D + h * HD;
+    stage_rows<true, false>(kl, base + D, 3 * D, jbase, KR, p.T, p.cs, 1.0f);
+    stage_cols<false, false>(vt, VS, base + 2 * D, 3 * D, jbase, KR, p.T, p.cs, 1.0f);
 
     // ---- this wave's 16 queries: rotated, scaled Q fragments in registers -------------------------
+    // The arithmetic of load_pieces<true, true>, written out: through the shared function the compiler pairs these sixteen values
+    // differently and fuses other products of a*co - b*si, and a few elements of q round the other way (rungs 6 and 10 on gfx950);
+    // the bytes of `out` are pinned (tests/golden/attention_block_parent.json), so this site keeps the form that gave them.
     const int qi = i0 + wave * 16 + (lane & 15);
     const int g = lane >> 4;
     half8_t qf[2] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
     if (qi < p.T) {
-        const half_t* qp = base + (long)qi * 3 * D + h * HD;
+        const half_t* qp = base + (long)qi * 3 * D;
         const half8_t x1 = *(const half8_t*)(qp + g * 8);
         const half8_t x2 = *(const half8_t*)(qp + 32 + g * 8);
         const float* cs = p.cs + ((long)qi * 32 + g * 8) * 2;
@@ -108,16 +76,7 @@ __global__ __launch_bounds__(512) void attention_kernel(AttnArgs p) {
     const int r0 = wave * 16;
     float4_t s[NT];
 #pragma unroll
-    for (int kt = 0; kt < NT; ++kt) {
-        const int row = r0 + kt * 16 + (lane & 15);
-        const char* rp = kl + row * 128;
-        const half8_t a0 = *(const half8_t*)(rp + ((g ^ (row & 7)) << 4));
-        const half8_t a1 = *(const half8_t*)(rp + (((g + 4) ^ (row & 7)) << 4));
-        float4_t acc = {0.f, 0.f, 0.f, 0.f};
-        acc = mfma16(a0, qf[0], acc);
-        acc = mfma16(a1, qf[1], acc);
-        s[kt] = acc;
-    }
+    for (int kt = 0; kt < NT; ++kt) s[kt] = row_tile(kl, r0 + kt * 16 + (lane & 15), g, qf[0], qf[1]);
     // ---- mask + exact softmax over the visible keys -------------------------------------------------
     float m = -INFINITY;
 #pragma unroll
@@ -157,17 +116,7 @@ __global__ __launch_bounds__(512) void attention_kernel(AttnArgs p) {
             pb[e] = (half_t)(s[2 * c][e] * inv);
             pb[4 + e] = (half_t)(s[2 * c + 1][e] * inv);
         }
-        const int kcol = r0 + c * 32 + g * 4;
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            const half_t* vp = vt + (mt * 16 + (lane & 15)) * VS + kcol;
-            const half4_t va = *(const half4_t*)vp;
-            const half4_t vb = *(const half4_t*)(vp + 16);
-            half8_t af;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { af[e] = va[e]; af[4 + e] = vb[e]; }
-            o[mt] = mfma16(af, pb, o[mt]);
-        }
+        col_step(vt, VS, r0 + c * 32 + g * 4, lane, pb, o);
     }
     if (qi < p.T) {
         half_t* op = p.out + ((long)n * p.T + qi) * D + h * HD + g * 4;
@@ -708,48 +657,24 @@ __global__ __launch_bounds__(256) void rmsnorm_residual_kernel(NormArgs p) {
 
 }  // namespace bh
 
-// lse == nullptr: inference (attention_kernel<NT, false>); otherwise the training forward, which also writes lse [N][H][T]
-static int attention_launch(const void* qkv, void* out, const float* cos_sin, int N, int T, int nhead, int head_dim,
-                            int win_left, int win_right, float* lse, hipStream_t stream) {
+int bh_k_attention_block(const void* qkv, void* out, const float* cos_sin, int N, int T, int nhead, int win_left, int win_right, float* lse,
+                         hipStream_t stream) {
     using namespace bh;
-    BH_REQUIRE(head_dim == 64, "attention: only head_dim 64 is implemented (got %d)", head_dim);
-    BH_REQUIRE(win_left >= 0 && win_right >= 0, "attention: a finite window (left, right) is required (got (%d, %d))", win_left, win_right);
-    BH_REQUIRE(N > 0 && T > 0 && nhead > 0, "attention: empty problem");
-    const int need = (16 + win_left + win_right + 15) / 16;      // key tiles one wave can see
-    AttnArgs a{(const half_t*)qkv, (half_t*)out, cos_sin, N, T, nhead, win_left, win_right, 0.125f, lse};
-    dim3 grid((T + QB - 1) / QB, nhead, N);
-#define BH_ATTN_L(NT, L)                                                                                \
-    do {                                                                                              \
-        const size_t lds = (size_t)(7 * 16 + NT * 16) * 128 + (size_t)64 * (7 * 16 + NT * 16 + 4) * 2; \
-        if (lds > 64 * 1024)                                                                          \
-            BH_CHECK_HIP(bh_max_lds((const void*)attention_kernel<NT, L>, (int)lds)); \
-        hipLaunchKernelGGL((attention_kernel<NT, L>), grid, dim3(512), lds, stream, a);                \
-    } while (0)
-#define BH_ATTN(NT)                        \
-    do {                                   \
-        if (lse != nullptr) BH_ATTN_L(NT, true); \
-        else BH_ATTN_L(NT, false);         \
-    } while (0)
-    if (need <= 6) BH_ATTN(6);
-    else if (need <= 10) BH_ATTN(10);
-    else if (need <= 18) BH_ATTN(18);
-    else if (need <= 26) BH_ATTN(26);
-    else BH_REQUIRE(false, "attention: window %d+%d is too wide for the LDS-resident kernel", win_left, win_right);
-#undef BH_ATTN
-#undef BH_ATTN_L
+    AttnArgs a{(const half_t*)qkv, (half_t*)out, cos_sin, N, T, nhead, win_left, win_right, QK_SCALE, lse};
+    const dim3 grid((T + QB - 1) / QB, nhead, N);
+    const int rc = attn_for_rung(win_left, win_right, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        return attn_block_launch(lse != nullptr ? attention_kernel<NT, true> : attention_kernel<NT, false>, lds_forward(NT), grid, stream, a);
+    });
+    if (rc != 0) return rc;
     BH_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
 int bh_k_attention(const void* qkv, void* out, const float* cos_sin, int N, int T, int nhead, int head_dim,
                    int win_left, int win_right, hipStream_t stream) {
-    return attention_launch(qkv, out, cos_sin, N, T, nhead, head_dim, win_left, win_right, nullptr, stream);
-}
-
-int bh_k_attention_lse(const void* qkv, void* out, const float* cos_sin, int N, int T, int nhead, int head_dim,
-                       int win_left, int win_right, float* lse, hipStream_t stream) {
-    BH_REQUIRE(lse != nullptr, "attention: null lse");
-    return attention_launch(qkv, out, cos_sin, N, T, nhead, head_dim, win_left, win_right, lse, stream);
+    if (const int rc = bh::attn_block_check("attention", N, T, nhead, head_dim, win_left, win_right)) return rc;
+    return bh_k_attention_block(qkv, out, cos_sin, N, T, nhead, win_left, win_right, nullptr, stream);
 }
 
 // q (already rotated and scaled) | k (already rotated) | v  ->  attention output; see attention_ring_kernel.

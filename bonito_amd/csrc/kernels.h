@@ -227,12 +227,15 @@ int bh_k_attention(const void* qkv, void* out, const float* cos_sin, int N, int 
                    int win_left, int win_right, hipStream_t stream);
 int bh_k_rmsnorm_residual(const void* a, const void* x, const float* w, void* out, long M, int D, float alpha,
                           float eps, hipStream_t stream);
-// the same kernel, also writing lse = m + ln(sum) of every query's softmax row, fp32 [N][nhead][T]: the training forward's launch
-int bh_k_attention_lse(const void* qkv, void* out, const float* cos_sin, int N, int T, int nhead, int head_dim,
-                       int win_left, int win_right, float* lse, hipStream_t stream);
-// The windows bh_k_attention serves: a wave's key tiles (of 16) must number at most 26 (attention_kernel<26>)
+// The block-per-workgroup kernel behind bh_k_attention, behind its checks (attn_block.h: attn_block_check). lse == nullptr: inference;
+// otherwise the training forward (attention_train.hip), which also writes lse = m + ln(sum) of every query's softmax row, fp32 [N][nhead][T]
+int bh_k_attention_block(const void* qkv, void* out, const float* cos_sin, int N, int T, int nhead, int win_left, int win_right, float* lse,
+                         hipStream_t stream);
+// The windows the block kernels serve: the key tiles (of 16) one wave of 16 queries can see must number at most those of the widest instance
+constexpr int BH_ATTN_MAX_TILES = 26;
+inline long bh_k_attention_tiles(int win_left, int win_right) { return (16 + (long)win_left + win_right + 15) / 16; }
 inline bool bh_k_attention_serves(int win_left, int win_right) {
-    return win_left >= 0 && win_right >= 0 && (16 + (long)win_left + win_right + 15) / 16 <= 26;
+    return win_left >= 0 && win_right >= 0 && bh_k_attention_tiles(win_left, win_right) <= BH_ATTN_MAX_TILES;
 }
 
 // attention_train.hip (rotary + sliding-window attention for training: the forward that keeps lse, and the backward; device pointers)

@@ -15,6 +15,9 @@ The rest is exact: equal bytes from call to call, a chunk's bytes independent of
 that launch nothing, autograd that hands on the backward's bytes."""
 import ctypes as C
 import functools
+import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -211,6 +214,8 @@ def test_refused_calls_leave_the_outputs_untouched():
     torch.cuda.synchronize()
     for name in o:
         assert o[name].payload_untouched(), name
+    for win in ((200, 199), (200, 200), (200, 201), (0, 400), (0, 401)):      # the library's widest window is the wrappers'
+        assert (lib.bh_attention_train_backward_workspace(1, 1, 1, win[0], win[1]) != 0) == attn.supported_window(win), win
     # the wrappers refuse before any launch as well
     with pytest.raises(ValueError, match="too wide"):
         attn.attention_forward(qkv, (200, 201))
@@ -223,6 +228,27 @@ def test_refused_calls_leave_the_outputs_untouched():
         attn.attention_backward(qkv, out, attn.attention_forward(qkv[:1].contiguous(), window)[1], dout, window)
     with pytest.raises(ValueError, match="dout must be float16"):
         attn.attention_backward(qkv, out, saved, dout.float(), window)
+
+
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "attention_block_parent.json")) as _fh:
+    PARENT = json.load(_fh)
+
+
+def _sha(t, nbytes=None):
+    raw = t.contiguous().view(torch.uint8).flatten().cpu().numpy().tobytes()
+    return hashlib.sha256(raw if nbytes is None else raw[:nbytes]).hexdigest()
+
+
+@pytest.mark.parametrize("case", PARENT["cases"], ids=lambda c: "%d-%d-%d-%s" % (c["N"], c["T"], c["H"], tuple(c["window"])))
+def test_every_rung_has_the_bytes_of_the_commit_before_the_shared_header(case):
+    """tests/golden/attention_block_parent.json: digests written by tools/attn_block_digests.py against a build of the commit before the block
+    kernels moved onto csrc/attn_block.h, one case per rung of the ladder and the single-key window."""
+    N, T, H, window = case["N"], case["T"], case["H"], tuple(case["window"])
+    qkv, dout = (_dev(a) for a in tr.make_case(N, T, H, PARENT["kind"], seed=PARENT["seed"]))
+    o = _raw_call(qkv, dout, N, T, H, window)
+    got = {"train_out": _sha(o["out"].t), "saved": _sha(o["saved"].t, N * T * H * 4), "inference_out": _sha(_inference(qkv, N, T, H, window)),
+           "dqkv": _sha(o["dqkv"].t)}
+    assert got == {k: case[k] for k in got}
 
 
 @pytest.mark.parametrize("N,T,H,window", [(2, 130, 3, (1, 7)), (1, 150, 2, (40, 41))], ids=lambda v: str(v))

@@ -98,7 +98,12 @@ def bench_shape(N, T, H, win, seconds, repeats, with_torch, dev):
         _lib.check(lib.bh_attention_train_backward(_lib.ptr(qkv), _lib.ptr(tab), _lib.ptr(out), _lib.ptr(saved), _lib.ptr(dout), N, T, H, 64,
                                                    win[0], win[1], _lib.ptr(dqkv), _lib.ptr(ws), wb, st), "bh_attention_train_backward")
 
-    legs = {"forward": forward, "forward_backward": both}
+    out_inf = torch.empty_like(dout)
+
+    def forward_inference():          # bh_attention: the same kernel without lse, what the engine launches for windows the ring kernels do not serve
+        _lib.check(lib.bh_attention(_lib.ptr(qkv), _lib.ptr(out_inf), _lib.ptr(tab), N, T, H, 64, win[0], win[1], st), "bh_attention")
+
+    legs = {"forward": forward, "forward_inference": forward_inference, "forward_backward": both}
     res = {"N": N, "T": T, "H": H, "window": list(win), "saved_bytes": int(sb), "workspace_bytes": int(wb)}
     if with_torch:
         q, k = rotary(qkv[:, :, 0], tab), rotary(qkv[:, :, 1], tab)
