@@ -36,6 +36,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "lstm_cell.h"
+#include "lstm_ring.h"
 #include "options.h"
 
 namespace bh {
@@ -51,47 +52,16 @@ struct LstmArgs {
     unsigned max_spins;
     int* xcc_ws;        // [n_rings][H/16], pre-set to -1: XCD agreement
     int force_slow;     // test hook: always use the placement-independent write-through policy
-    int tune;           // experiment bits: 1 = spin without s_sleep, 2 = single-k-step canary poll before the full read
+    // "lstm_tune" bits: 0 (1) = spin without s_sleep (ring_repoll), 2 (4) = per-wave cycle statistics into xcc_ws' tail (fused, wgx; the
+    // STATS instances of wgx2 and wide), 5 (32) = spread every ring over all XCDs (ring_slice), 6 (64) = wgx2: generic section code throughout
+    int tune;
 };
-
-__device__ __forceinline__ int xcc_id() {
-    return (int)(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 0xF);   // hwreg(HW_REG_XCC_ID, 0, 4)
-}
-
-// XCD agreement of a ring: every member publishes its XCC id and reads the ring's ids; the ring uses plain stores (the lines stay
-// in that XCD's L2, the sc1 polls are L2 hits) iff all members sit on one XCD. A timeout is not an error: the write-through
-// policy is valid for any placement. Every member reads the same published ids, so the choice is identical across the ring.
-__device__ __forceinline__ bool ring_store_policy(const LstmArgs& p, int ring, int slice, int nsl, int lane) {
-    int* slot = p.xcc_ws + (long)ring * nsl;
-    const int mine = xcc_id();
-    if (lane == 0) __hip_atomic_store(slot + slice, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned spins = 0;
-    bool ok = false;
-    while (true) {
-        bool any_unset = false, any_other = false;
-        for (int i = lane; i < nsl; i += 64) {
-            const int v = __hip_atomic_load(slot + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            any_unset |= v < 0;
-            any_other |= v != mine;
-        }
-        if (!__any(any_unset)) { ok = !__any(any_other); break; }
-        if (++spins > p.max_spins) break;
-        __builtin_amdgcn_s_sleep(4);
-    }
-    return ok && !p.force_slow;
-}
-
-constexpr unsigned SENTINEL_MASK = 0x40004000u;
 
 // LDS output transpose: 2-byte writes, 8-byte reads of the same bytes. Plain half_t / unsigned long long accesses are
 // different types for the compiler's alias analysis and were reordered (a wave then published stale LDS contents, which may
 // look like the exchange sentinel): both sides go through may_alias types.
 typedef unsigned short __attribute__((may_alias)) u16_alias_t;
 typedef unsigned long long __attribute__((may_alias)) u64_alias_t;
-
-// Gate-math tanh: the exp form has absolute error ~1e-7 everywhere, which is all the recurrence needs
-// (h and c are consumed at fp16 / additive precision); the relative-accuracy branch of common.h's tanhf_ is skipped.
-__device__ __forceinline__ float tanh_gate(float x) { return __builtin_fmaf(-2.0f, rcpf_(__expf(2.0f * x) + 1.0f), 1.0f); }
 
 // STREAM = false: W_hh fragments of the wave's slice are register-resident, a workgroup serves one slice of FOUR rings.
 // STREAM = true (hidden sizes the register file cannot hold, H > 512: the 768-wide old-style r9.4.1 models, the 1024-wide v4.3
@@ -158,6 +128,8 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_kernel(LstmArgs p) {
             __amdgpu_buffer_rsrc_t rs =
                 __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)row_bytes, 0x00020000);
             uint4_t hf[NKS];
+            // Written out, not ring_repoll: this kernel has no early first round, and with one peeled off in front of the shared loop
+            // <14, true> lost occupancy (2 -> 1) and <30, true>, <32, true> went to scratch (124 / 252 bytes). Same steps, same bound.
             unsigned spins = dead ? p.max_spins : 0u;   // after one timeout never wait again
             unsigned pend = (NKS >= 32) ? 0xffffffffu : ((1u << NKS) - 1u);   // wave-uniform
             while (true) {
@@ -167,10 +139,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_kernel(LstmArgs p) {
                         hf[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + ks * 64, 0, (int)0x80000010 /*sc1 + volatile*/);
 #pragma unroll
                 for (int ks = 0; ks < NKS; ++ks)
-                    if (pend & (1u << ks)) {
-                        unsigned orv = hf[ks].x | hf[ks].y | hf[ks].z | hf[ks].w;
-                        if (!__any((orv & SENTINEL_MASK) != 0)) pend &= ~(1u << ks);
-                    }
+                    if ((pend & (1u << ks)) && !__any(armed_f16(hf[ks]))) pend &= ~(1u << ks);
                 if (pend == 0) break;
                 if (++spins > p.max_spins) {
                     if (lane == 0 && !dead) atomicExch(p.err, 1);
@@ -199,10 +168,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_kernel(LstmArgs p) {
             ho[i] = (half_t)hv;
         }
         unsigned long long packed = __builtin_bit_cast(unsigned long long, ho);
-        unsigned long long* dst =
-            (unsigned long long*)(p.h + ((long)t * p.N + n) * H + hu0);
-        if (fast) *dst = packed;                                                       // stays in this XCD's L2
-        else __hip_atomic_store(dst, packed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1 write-through
+        ring_store((unsigned long long*)(p.h + ((long)t * p.N + n) * H + hu0), packed, fast);
 #pragma unroll
         for (int g = 0; g < 4; ++g) gin[g] = gnx[g];
     }
@@ -342,34 +308,12 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_fused_kernel(LstmFusedArgs 
         // ---- 3. h_{t-1} must be complete: check the first round, re-poll only the k-steps still holding a
         //         sentinel ---------------------------------------------------------------------------------------
         if (step > 0) {
-            unsigned spins = dead ? p.max_spins : 0u;
-            unsigned pend = 0;
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) {
-                unsigned orv = hf[ks].x | hf[ks].y | hf[ks].z | hf[ks].w;
-                if (__any((orv & SENTINEL_MASK) != 0)) pend |= (1u << ks);
-            }
-            unsigned rounds = 1;
+            auto armed = [&](int ks) { return __any(armed_f16(hf[ks])) != 0; };
+            const unsigned pend = ring_pending<NKS>(armed);
             const long long pc2 = (p.tune & 4) ? __builtin_readcyclecounter() : 0;
-            while (pend != 0) {
-                if (++spins > p.max_spins) {
-                    if (lane == 0 && !dead) atomicExch(p.err, 1);
-                    dead = true;
-                    break;
-                }
-                if (!(p.tune & 1)) __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks)
-                    if (pend & (1u << ks))
-                        hf[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + ks * 64, 0, (int)0x80000010);
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks)
-                    if (pend & (1u << ks)) {
-                        unsigned orv = hf[ks].x | hf[ks].y | hf[ks].z | hf[ks].w;
-                        if (!__any((orv & SENTINEL_MASK) != 0)) pend &= ~(1u << ks);
-                    }
-                ++rounds;
-            }
+            const unsigned rounds = ring_repoll<NKS>(p, lane, dead, pend, armed, [&](int ks) {
+                hf[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + ks * 64, 0, (int)0x80000010);
+            });
             if (p.tune & 4) {
                 const long long now = __builtin_readcyclecounter();
                 st_poll += now - pc0; st_rounds += rounds; st_first_ok += (rounds == 1);
@@ -406,13 +350,11 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_fused_kernel(LstmFusedArgs 
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) asm volatile("" : "+v"(xf[ks]));
         unsigned long long packed = __builtin_bit_cast(unsigned long long, ho);
-        unsigned long long* dst = (unsigned long long*)(p.h + ((long)t * p.N + n) * H + hu0);
-        if (fast) *dst = packed;
-        else __hip_atomic_store(dst, packed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ring_store((unsigned long long*)(p.h + ((long)t * p.N + n) * H + hu0), packed, fast);
         if (p.tune & 4) st_rec += __builtin_readcyclecounter() - pc3;
     }
     if ((p.tune & 4) && lane == 0) {
-        long long* st = (long long*)((char*)p.xcc_ws + (((size_t)p.n_rings * NSL * sizeof(int) + 64 + 7) & ~(size_t)7)) + ((long)ring * NSL + slice) * 8;
+        long long* st = lstm_stats_slot<8>(p.xcc_ws, p.n_rings, NSL, ring, slice);
         st[0] = __builtin_readcyclecounter() - st_t0;
         st[1] = st_poll;
         st[2] = st_rounds;
@@ -436,18 +378,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_fused_kernel(LstmFusedArgs 
 // fragments, one workgroup barrier per step publishes them. Compared with lstm_layer_fused_kernel this cuts the
 // L2 read traffic of the exchange and of the x stream by 4x (it was 768 waves x 12 KB x ~2.5 per step at hac
 // size, i.e. L2-bandwidth-bound polling), needs no LDS for weights and keeps all 256 CUs busy at N=512, H=384.
-// XCD agreement and bounded spins as in lstm_layer_fused_kernel.
-__device__ __forceinline__ void mfma16_av(const half8_t& a_agpr, const half8_t& b, float4_t& c) {
-    asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "a"(a_agpr), "v"(b));
-}
-__device__ __forceinline__ void mfma16_vv(const half8_t& a, const half8_t& b, float4_t& c) {
-    asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
-template <int MT>
-__device__ __forceinline__ void mfma_settle_v(float4_t (&c)[MT]) {
-    if constexpr (MT == 3) asm volatile("s_nop 15\n\ts_nop 7" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]));
-    else asm volatile("s_nop 15\n\ts_nop 7" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]));
-}
+// XCD agreement and bounded spins as in lstm_layer_fused_kernel; slice setup, input projection and x stream: lstm_ring.h.
 
 // ---------------------------------------------------------------------------------------------------
 // "wgx": the workgroup-shared structure above with the exchange and the x stream of the 8-bit kernel (lstm_q8.hip). Same
@@ -457,9 +388,8 @@ __device__ __forceinline__ void mfma_settle_v(float4_t (&c)[MT]) {
 //     slots per ring, laid out as ready-made MFMA B fragments ([k-step][lane][16 bytes]: a consumer's poll of a k-step is one
 //     fully coalesced KiB, 8 whole cache lines instead of 16 half lines of a row-major tensor). 4 x 12 KiB per ring, 1.5 MiB for
 //     a 512-chunk batch: it lives in the L2. Sentinel = fp16 0xFFFF as before (|h| <= 1 never has bit 14 set). A producer
-//     re-arms its own bytes of slot (t+2)%4 at step t, behind the workgroup barrier that proves every wave of the ring has
-//     published h_{t-1} (hence finished reading h_{t-2}); its vmcnt(0) ahead of the next barrier completes the re-arm before it
-//     publishes anything newer, so no consumer can find stale bytes. Consequences: no sentinel pre-fill of the output tensor
+//     re-arms its own bytes of slot (t+2)%4 at step t (ring_publish, lstm_ring.h: the protocol and why no consumer can find stale
+//     bytes are stated there). Consequences: no sentinel pre-fill of the output tensor
 //     (the fill kernel, 0.66 GB of writes per layer, is gone), no first-touch fetch of 0.66 GB of polled sentinel lines from
 //     HBM per layer, no third activation buffer;
 //   * the layer output is a second, plain 8-byte store of the same values into [T][N][H] (next layer's input / the linear layer);
@@ -512,34 +442,12 @@ __device__ __forceinline__ void ring_stream_rec(float4_t (&xacc)[MT], float (&cs
                                                 const half8_t (&wih)[MT][NKS], const float4_t (&bias)[MT], unsigned hb) {
     if constexpr (NKS == 12 && MT == 3) ringstep3r_mfma(xacc, cst, hv, whh, wih, bias, hb, 0u);
 }
-__device__ __forceinline__ void dma16_wgx(const char* g, char* lds) {
-    const unsigned l = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(__attribute__((address_space(3))) char*)lds);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(l), "v"(g) : "memory");
-}
 
 struct LstmWgxArgs {
     LstmFusedArgs f;
     char* ex;             // exchange ring buffer [4][R][NKS][64][16], armed with 0xFF
     int R;                // ring stride of `ex` (rings of the whole batch)
 };
-
-// Vector-memory operations of the H = 384 fast path with SCALAR addressing: a wave-uniform 64-bit base in an SGPR pair plus a 32-bit
-// per-lane byte offset that is loop-invariant (the compiler's per-lane 64-bit address arithmetic, the generic -> LDS pointer
-// conversions in front of every M0 write and the spilled scalars behind them were ~55 instructions for the three x-stream DMAs of a
-// ring step alone). IMM: immediate byte offset (13-bit signed) - keep it 0 for LDS-DMA: the hardware adds the instruction offset to
-// the LDS address as well as to the global one. The DMA lands at LDS address lds_a + lane * 16.
-template <int IMM, bool POLL>
-__device__ __forceinline__ void dma16_s(const char* sbase, unsigned voff, unsigned lds_a) {
-    if constexpr (POLL)
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%3 sc0 sc1" ::"s"(lds_a), "v"(voff), "s"(sbase), "i"(IMM) : "memory");
-    else
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%3" ::"s"(lds_a), "v"(voff), "s"(sbase), "i"(IMM) : "memory");
-}
-template <bool SC1>
-__device__ __forceinline__ void store8_s(const char* sbase, unsigned voff, unsigned long long v) {
-    if constexpr (SC1) asm volatile("global_store_dwordx2 %0, %1, %2 sc1" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
-    else asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
-}
 
 template <int NKS, int MT>
 __global__ __launch_bounds__(256, 1) void lstm_layer_wgx_kernel(LstmWgxArgs wp) {
@@ -551,13 +459,8 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx_kernel(LstmWgxArgs wp) 
     static_assert(H % (4 * U) == 0, "four slices per workgroup");
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int xcd = blockIdx.x & 7;
-    const int lwg = blockIdx.x >> 3;
-    const int rl = lwg / WPR;
-    // test hook ("lstm_tune" bit 5): spread the workgroups of every ring over all eight XCDs, so that the placement-independent
-    // (write-through) hand-off really crosses XCDs
-    const int ring = rl * 8 + ((p.tune & 32) ? ((xcd + (lwg - rl * WPR)) & 7) : xcd);
-    const int slice = (lwg - rl * WPR) * 4 + wave;
+    const RingSlice at = ring_slice(WPR, wave, p.tune);
+    const int ring = at.ring, slice = at.slice;
     if (ring >= p.n_rings) return;
 
     char* hbuf = smem;                                  // [2][NKS][64][16]  B fragments of h_{t-1}
@@ -565,23 +468,13 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx_kernel(LstmWgxArgs wp) 
     char* stage = smem + 5 * TILE + wave * (16 * U * 2);
 
     half8_t whh[MT][NKS], wih[MT][NKS];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            const long o = ((((long)slice * MT + m) * NKS + ks) * 64 + lane) * 8;
-            whh[m][ks] = *(const half8_t*)(p.whh + o);
-            wih[m][ks] = *(const half8_t*)(fp.wih + o);
-        }
+    slice_frags(whh, wih, p.whh, fp.wih, slice, lane);
     const int c = lane & 15, q = lane >> 4;
     float cst[MT];
     float4_t bias4[MT];
+    slice_rows(bias4, fp.bias, H, slice * U + q * MT);
 #pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        cst[m] = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) bias4[m][i] = fp.bias[i * H + slice * U + q * MT + m];
-    }
+    for (int m = 0; m < MT; ++m) cst[m] = 0.f;
     bool dead = false;
     const bool fast = ring_store_policy(p, ring, slice, NSL, lane);
 
@@ -595,38 +488,20 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx_kernel(LstmWgxArgs wp) 
     char* exr = wp.ex + (long)ring * TILE;
 
     // lanes that move this wave's U units out: (chunk cc, 4 consecutive units = 8 bytes)
-    constexpr int PARTS = U / 4;
-    const bool mover = lane < 16 * PARTS;
-    const int cc = lane / PARTS, part = lane - cc * PARTS;
-    const int u0 = slice * U + part * 4;
-    const int my_byte = (((u0 >> 5) * 64 + ((u0 >> 3) & 3) * 16 + cc) << 4) + (u0 & 7) * 2;      // inside a ring tile (fragment order)
+    const RingMover mv = ring_mover<U>(lane);
+    const bool mover = mv.mover;
+    const int cc = mv.cc, part = mv.part;
+    const int my_byte = frag_byte<2>(slice * U + part * 4, cc);      // inside a ring tile
 
     uint4_t hq[KQ];
     float4_t xacc[MT];
-    auto x_phase = [&](const char* xb) {
-#pragma unroll
-        for (int m = 0; m < MT; ++m) xacc[m] = bias4[m];
-        half8_t b_cur = *(const half8_t*)(xb + lo), b_nxt = b_cur;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            if (ks + 1 < NKS) b_nxt = *(const half8_t*)(xb + (ks + 1) * 1024 + lo);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                if (m < MT - 1) mfma16_av(wih[m][ks], b_cur, xacc[m]);
-                else mfma16_vv(wih[m][ks], b_cur, xacc[m]);
-            }
-            b_cur = b_nxt;
-        }
-        mfma_settle_v<MT>(xacc);
-    };
-    // x stream: the polls of the exchange go to k-steps w, w+4, ..; the DMA shares are 3-w, 7-w, .. (balanced over the waves).
-    // H = 384: scalar-addressed (a wave-uniform row base + a loop-invariant 32-bit per-lane offset, LDS addresses as integers) - the
+    // x stream (x_dma, lstm_ring.h). H = 384: scalar-addressed (a wave-uniform row base + a loop-invariant 32-bit per-lane offset, LDS addresses as integers) - the
     // per-lane 64-bit address arithmetic and the generic -> LDS pointer conversions were ~18 instructions per DMA
     const unsigned smem_a = lds_addr(smem);
     const unsigned vx_off = (unsigned)(((ring * 16 + c) * H + q * 8) * 2 + (3 - wave) * 64);
     const unsigned vh_off = (unsigned)(((ring * 16 + cc) * H + slice * U + part * 4) * 2);
     const long row_bytes = x_row * 2;
-    auto x_dma = [&](int tt, int slot) {
+    auto x_fetch = [&](int tt, int slot) {
         if constexpr (NKS == 12 && MT == 3) {
             const char* src = (const char*)fp.x + (long)tt * row_bytes;
             const unsigned m0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(smem_a + (2 + slot) * TILE + (3 - wave) * 1024));
@@ -634,19 +509,15 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx_kernel(LstmWgxArgs wp) 
             dma16_s<0, false>(src + 256, vx_off, m0 + 4096);
             dma16_s<0, false>(src + 512, vx_off, m0 + 8192);
         } else {
-#pragma unroll
-            for (int kk = 0; kk < KQ; ++kk) {
-                const int ks = (3 - wave) + 4 * kk;
-                if (EXACT || ks < NKS) dma16_wgx((const char*)(xptr + (long)tt * x_row + ks * 32), xbuf + (slot * NKS + ks) * 1024);
-            }
+            x_dma<NKS>((const char*)(xptr + (long)tt * x_row), 64, xbuf, slot, wave);
         }
     };
 
-    x_dma(t, 0);
-    x_dma(p.T > 1 ? t + dt : t, 1);
+    x_fetch(t, 0);
+    x_fetch(p.T > 1 ? t + dt : t, 1);
     __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): the builtin (unlike inline asm) also clears the compiler's own scoreboard
     __syncthreads();
-    x_phase(xbuf);
+    x_phase<NKS, MT>(xacc, bias4, wih, xbuf, lo);
 #pragma unroll
     for (int kk = 0; kk < KQ; ++kk) hq[kk] = uint4_t{0, 0, 0, 0};
 
@@ -666,36 +537,10 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx_kernel(LstmWgxArgs wp) 
             // wave-uniform descriptor, per-lane offset (a per-lane base would turn every load into a 64-trip readfirstlane loop)
             const char* src = exr + (long)((step - 1) & 3) * slot_stride;
             __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, TILE, 0x00020000);
-            unsigned spins = dead ? p.max_spins : 0u;
-            unsigned pend = 0;
-#pragma unroll
-            for (int kk = 0; kk < KQ; ++kk) {
-                const int ks = wave + 4 * kk;
-                if (EXACT || ks < NKS) {
-                    unsigned orv = hq[kk].x | hq[kk].y | hq[kk].z | hq[kk].w;
-                    if (__any((orv & SENTINEL_MASK) != 0)) pend |= (1u << kk);
-                }
-            }
-            unsigned rounds = 1;
-            while (pend != 0) {
-                if (++spins > p.max_spins) {
-                    if (lane == 0 && !dead) atomicExch(p.err, 1);
-                    dead = true;
-                    break;
-                }
-                if (!(p.tune & 1)) __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-                for (int kk = 0; kk < KQ; ++kk)
-                    if (pend & (1u << kk))
-                        hq[kk] = __builtin_amdgcn_raw_buffer_load_b128(rs, (wave + 4 * kk) * 1024 + lo, 0, (int)0x80000010);
-#pragma unroll
-                for (int kk = 0; kk < KQ; ++kk)
-                    if (pend & (1u << kk)) {
-                        unsigned orv = hq[kk].x | hq[kk].y | hq[kk].z | hq[kk].w;
-                        if (!__any((orv & SENTINEL_MASK) != 0)) pend &= ~(1u << kk);
-                    }
-                ++rounds;
-            }
+            auto armed = [&](int kk) { return (EXACT || wave + 4 * kk < NKS) && __any(armed_f16(hq[kk])); };
+            const unsigned rounds = ring_repoll<KQ>(p, lane, dead, ring_pending<KQ>(armed), armed, [&](int kk) {
+                hq[kk] = __builtin_amdgcn_raw_buffer_load_b128(rs, (wave + 4 * kk) * 1024 + lo, 0, (int)0x80000010);
+            });
             if (p.tune & 4) {
                 st_poll += __builtin_readcyclecounter() - pc0; st_rounds += rounds; st_first_ok += (rounds == 1);
                 st_hist += 1ll << (16 * (rounds > 3 ? 3 : rounds - 1));
@@ -720,7 +565,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx_kernel(LstmWgxArgs wp) 
         if constexpr (STREAM) {
             // ---- X / E. x_{t+2} requested first, then the recurrent MFMAs tile by tile with the gate arithmetic of tile m behind the
             //      MFMAs of tile m + 1 (ringstep3r_mfma, round 3: the bare MFMA phase + the bare gate phase were 1.5 k cycles) ---------
-            if (step + 2 < p.T) x_dma(t + 2 * dt, (step + 2) % 3);
+            if (step + 2 < p.T) x_fetch(t + 2 * dt, (step + 2) % 3);
             float hv[MT];
             ring_stream_rec<NKS, MT>(acc, cst, hv, whh, wih, bias4, lds_addr(hbuf + par * TILE + lo));
 #pragma unroll
@@ -741,7 +586,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx_kernel(LstmWgxArgs wp) 
             }
             pcm = (p.tune & 4) ? __builtin_readcyclecounter() : 0;
             // ---- X. request x_{t+2} into the LDS slot x_{t-1} was consumed from; needed behind the NEXT barrier ----------------
-            if (step + 2 < p.T) x_dma(t + 2 * dt, (step + 2) % 3);
+            if (step + 2 < p.T) x_fetch(t + 2 * dt, (step + 2) % 3);
 #pragma unroll
             for (int m = 0; m < MT; ++m) ho[m] = (half_t)lstm_cell(acc[m][0], acc[m][1], acc[m][2], acc[m][3], cst[m]);
         }
@@ -752,27 +597,11 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx_kernel(LstmWgxArgs wp) 
             for (int m = 0; m < MT; ++m) sg[m] = __builtin_bit_cast(unsigned short, ho[m]);
             if (mover) {
                 const unsigned long long packed = *(const u64_alias_t*)((half_t*)stage + cc * U + part * 4);
-                if constexpr (STREAM) {                    // scalar-addressed stores (uniform slot base + my byte offset)
-                    const char* exs = exr + (long)(step & 3) * slot_stride;
-                    if (fast) store8_s<false>(exs, (unsigned)my_byte, packed); else store8_s<true>(exs, (unsigned)my_byte, packed);
-                    if (step >= 2 && step + 2 < p.T) {     // re-arm my bytes of slot (step+2)&3 (it holds h_{t-2}; see the header)
-                        const char* exa = exr + (long)((step + 2) & 3) * slot_stride;
-                        if (fast) store8_s<false>(exa, (unsigned)my_byte, ~0ull); else store8_s<true>(exa, (unsigned)my_byte, ~0ull);
-                    }
-                    store8_s<false>((const char*)p.h + (long)t * row_bytes, vh_off, packed);
-                } else {
-                unsigned long long* dst = (unsigned long long*)(exr + (long)(step & 3) * slot_stride + my_byte);
-                if (fast) *dst = packed;
-                else __hip_atomic_store(dst, packed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                // re-arm my bytes of slot (step+2)&3 (it holds h_{t-2}; see the header)
-                if (step >= 2 && step + 2 < p.T) {
-                    unsigned long long* ra = (unsigned long long*)(exr + (long)((step + 2) & 3) * slot_stride + my_byte);
-                    if (fast) *ra = ~0ull;
-                    else __hip_atomic_store(ra, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                // H = 384: scalar-addressed stores (uniform slot base + my byte offset)
+                ring_publish<unsigned long long, ~0ull, STREAM>(exr, slot_stride, step, my_byte, packed, fast, step >= 2 && step + 2 < p.T);
                 // the layer output proper (next layer's x rows / the linear layer's input)
-                *(unsigned long long*)(p.h + ((long)t * p.N + ring * 16 + cc) * H + slice * U + part * 4) = packed;
-                }
+                if constexpr (STREAM) store8_s<false>((const char*)p.h + (long)t * row_bytes, vh_off, packed);
+                else *(unsigned long long*)(p.h + ((long)t * p.N + ring * 16 + cc) * H + slice * U + part * 4) = packed;
             }
         }
         // ---- F. first poll round for h_t ----------------------------------------------------------------------------------
@@ -787,7 +616,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx_kernel(LstmWgxArgs wp) 
         }
         const long long pc3 = (p.tune & 4) ? __builtin_readcyclecounter() : 0;
         // ---- G. input projection of step t+1 --------------------------------------------------------------------------------
-        x_phase(xbuf + ((step + 1) % 3) * TILE);
+        x_phase<NKS, MT>(xacc, bias4, wih, xbuf + ((step + 1) % 3) * TILE, lo);
         if (p.tune & 4) {
             const long long now = __builtin_readcyclecounter();
             st_bar += pc2 - pc1; st_rec += pc3 - pc2; st_x += now - pc3;
@@ -795,7 +624,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx_kernel(LstmWgxArgs wp) 
         }
     }
     if ((p.tune & 4) && lane == 0) {
-        long long* st = (long long*)((char*)p.xcc_ws + (((size_t)p.n_rings * NSL * sizeof(int) + 64 + 7) & ~(size_t)7)) + ((long)ring * NSL + slice) * 16;
+        long long* st = lstm_stats_slot(p.xcc_ws, p.n_rings, NSL, ring, slice);
         st[0] = __builtin_readcyclecounter() - st_t0;
         st[1] = st_poll; st[2] = st_rounds; st[3] = st_first_ok; st[4] = st_x; st[5] = st_bar; st[6] = st_rec; st[7] = st_hist;
         st[8] = 0; st[9] = 0; st[10] = st_mf; st[11] = st_gate; st[12] = st_store;
@@ -816,10 +645,6 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx_kernel(LstmWgxArgs wp) 
 //     other ring's x-stream DMA, its three stores, its polls) and waits with exactly that vmcnt - the queue retires in order.
 //   * One workgroup barrier per ring step. LDS: 2 rings x (2 h tiles + 2 x tiles): the x slot consumed by step s is refilled
 //     (x_{s+2}) behind the ring's next barrier, two ring steps before it is needed.
-__device__ __forceinline__ void dma16_poll(const char* g, char* lds) {
-    const unsigned l = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(__attribute__((address_space(3))) char*)lds);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off sc0 sc1" ::"s"(l), "v"(g) : "memory");
-}
 __device__ __forceinline__ void wait_vm(int n) {       // s_waitcnt vmcnt(n), n wave-uniform; a smaller count than necessary is always safe
     switch (n) {
         case 0: __builtin_amdgcn_s_waitcnt(0x0F70); break;
@@ -849,12 +674,9 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx2_kernel(LstmWgxArgs wp)
     static_assert(H % (4 * U) == 0, "four slices per workgroup");
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int xcd = blockIdx.x & 7;
-    const int lwg = blockIdx.x >> 3;
-    const int rl = lwg / WPR;
     const int n_pairs = (p.n_rings + 1) >> 1;
-    const int pair = rl * 8 + ((p.tune & 32) ? ((xcd + (lwg - rl * WPR)) & 7) : xcd);          // bit 5: test hook, see lstm_layer_wgx_kernel
-    const int slice = (lwg - rl * WPR) * 4 + wave;
+    const RingSlice at = ring_slice(WPR, wave, p.tune);         // a pair of rings where the other kernels have a ring
+    const int pair = at.ring, slice = at.slice;
     if (pair >= n_pairs) return;
     const int ring_of[2] = {pair, pair + n_pairs};
     const bool two = ring_of[1] < p.n_rings;            // odd ring count: the last workgroups carry one ring (uniform over the ring)
@@ -864,20 +686,10 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx2_kernel(LstmWgxArgs wp)
     char* stage = smem + 8 * TILE + wave * (16 * U * 2);
 
     half8_t whh[MT][NKS], wih[MT][NKS];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            const long o = ((((long)slice * MT + m) * NKS + ks) * 64 + lane) * 8;
-            whh[m][ks] = *(const half8_t*)(p.whh + o);
-            wih[m][ks] = *(const half8_t*)(fp.wih + o);
-        }
+    slice_frags(whh, wih, p.whh, fp.wih, slice, lane);
     const int c = lane & 15, q = lane >> 4;
     float4_t bias4[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) bias4[m][i] = fp.bias[i * H + slice * U + q * MT + m];
+    slice_rows(bias4, fp.bias, H, slice * U + q * MT);
     bool dead = false;
     const int dt = p.reverse ? -1 : 1;
     const int t0 = p.reverse ? p.T - 1 : 0;
@@ -885,10 +697,9 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx2_kernel(LstmWgxArgs wp)
     const int lo = lane * 16;
     const long slot_stride = (long)wp.R * TILE;
     constexpr int PARTS = U / 4;
-    const int ml = lane < 16 * PARTS ? lane : lane - 16 * PARTS;      // lanes beyond the movers mirror one (see the stores)
-    const int cc = ml / PARTS, part = ml - cc * PARTS;
-    const int u0 = slice * U + part * 4;
-    const int my_byte = (((u0 >> 5) * 64 + ((u0 >> 3) & 3) * 16 + cc) << 4) + (u0 & 7) * 2;      // inside a ring tile (fragment order)
+    const RingMover mv = ring_mover<U>(lane < 16 * PARTS ? lane : lane - 16 * PARTS);      // lanes beyond the movers mirror one (see the stores)
+    const int cc = mv.cc, part = mv.part;
+    const int my_byte = frag_byte<2>(slice * U + part * 4, cc);      // inside a ring tile
     int n_poll = 0, n_dma = 0;                          // instructions of one poll round / one x-stream share of this wave
 #pragma unroll
     for (int kk = 0; kk < KQ; ++kk) {
@@ -935,28 +746,8 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx2_kernel(LstmWgxArgs wp)
     const char* xrow_any = (const char*)fp.x + (long)t0 * row_bytes;
     char* hrow = (char*)p.h + (long)t0 * row_bytes;                                          // row of h_t in the layer output
 
-    auto x_phase = [&](const char* xb, float4_t (&xa)[MT]) {
-#pragma unroll
-        for (int m = 0; m < MT; ++m) xa[m] = bias4[m];
-        half8_t b_cur = *(const half8_t*)(xb + lo), b_nxt = b_cur;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            if (ks + 1 < NKS) b_nxt = *(const half8_t*)(xb + (ks + 1) * 1024 + lo);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                if (m < MT - 1) mfma16_av(wih[m][ks], b_cur, xa[m]);
-                else mfma16_vv(wih[m][ks], b_cur, xa[m]);
-            }
-            b_cur = b_nxt;
-        }
-        mfma_settle_v<MT>(xa);
-    };
-    auto x_dma = [&](const half_t* xp, char* xb, int tt, int slot) {
-#pragma unroll
-        for (int kk = 0; kk < KQ; ++kk) {
-            const int ks = (3 - wave) + 4 * kk;
-            if (EXACT || ks < NKS) dma16_wgx((const char*)(xp + (long)tt * x_row + ks * 32), xb + (slot * NKS + ks) * 1024);
-        }
+    auto x_fetch = [&](const half_t* xp, char* xb, int tt, int slot) {
+        x_dma<NKS>((const char*)(xp + (long)tt * x_row), 64, xb, slot, wave);
     };
     // first poll round of ring r for the h published into exchange slot `slot`: my k-steps, straight into parity `par` of the h tile
     auto poll_dma = [&](const char* exbase, int slot, char* hb, unsigned mask) {
@@ -964,15 +755,15 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx2_kernel(LstmWgxArgs wp)
 #pragma unroll
         for (int kk = 0; kk < KQ; ++kk) {
             const int ks = wave + 4 * kk;
-            if ((EXACT || ks < NKS) && (mask & (1u << kk))) dma16_poll(src + ks * 1024, hb + ks * 1024);
+            if ((EXACT || ks < NKS) && (mask & (1u << kk))) dma16<true>(src + ks * 1024, hb + ks * 1024);
         }
     };
 
 #pragma unroll
     for (int r = 0; r < 2; ++r)
         if (r == 0 || two) {
-            x_dma(xptr[r], xbuf + r * 2 * TILE, t0, 0);
-            x_dma(xptr[r], xbuf + r * 2 * TILE, p.T > 1 ? t0 + dt : t0, 1);
+            x_fetch(xptr[r], xbuf + r * 2 * TILE, t0, 0);
+            x_fetch(xptr[r], xbuf + r * 2 * TILE, p.T > 1 ? t0 + dt : t0, 1);
         }
     if constexpr (NKS == 12 && MT == 3) {              // h_{-1} = 0: step 0 runs the same stream as every other step, on a zero tile
 #pragma unroll
@@ -985,7 +776,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx2_kernel(LstmWgxArgs wp)
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < 2; ++r)
-        if (r == 0 || two) x_phase(xbuf + r * 2 * TILE, xacc[r]);
+        if (r == 0 || two) x_phase<NKS, MT>(xacc[r], bias4, wih, xbuf + r * 2 * TILE, lo);
 
     long long st_poll = 0, st_bar = 0, st_slow = 0, st_sec[6] = {0, 0, 0, 0, 0, 0};      // lstm_tune bit 2: cycles per section (tools/lstm_stats.py)
     const long long st_t0 = __builtin_readcyclecounter();
@@ -1004,29 +795,15 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx2_kernel(LstmWgxArgs wp)
     };
     auto check_end = [&](int rr, int st, uint4_t (&chk)[KQ]) {
         char* hb = hbuf + (rr * 2 + (st & 1)) * TILE;
-        unsigned spins = dead ? p.max_spins : 0u;
-        while (true) {
-            unsigned pend = 0;
-#pragma unroll
-            for (int kk = 0; kk < KQ; ++kk) {
-                const int ks = wave + 4 * kk;
-                if ((EXACT || ks < NKS) && __any(((chk[kk].x | chk[kk].y | chk[kk].z | chk[kk].w) & SENTINEL_MASK) != 0)) pend |= (1u << kk);
-            }
-            if (pend == 0) break;
-            if (++spins > p.max_spins) {
-                if (lane == 0 && !dead) atomicExch(p.err, 1);
-                dead = true;
-                break;
-            }
-            if (!(p.tune & 1)) __builtin_amdgcn_s_sleep(1);
-            poll_dma(exr[rr], (st - 1) & 3, hb, pend);
-            wait_vm(0);
-#pragma unroll
-            for (int kk = 0; kk < KQ; ++kk) {
-                const int ks = wave + 4 * kk;
-                if (EXACT || ks < NKS) chk[kk] = *(const uint4_t*)(hb + ks * 1024 + lo);
-            }
-        }
+        auto armed = [&](int kk) { return (EXACT || wave + 4 * kk < NKS) && __any(armed_f16(chk[kk])); };
+        ring_repoll<KQ>(p, lane, dead, ring_pending<KQ>(armed),
+                        [&](int kk) {       // ring_repoll's contract: called once per re-polled piece behind all DMAs of the round. They must have landed
+                                            // (the wait is a no-op behind the round's first piece), then the piece is read back and tested
+                            wait_vm(0);
+                            chk[kk] = *(const uint4_t*)(hb + (wave + 4 * kk) * 1024 + lo);
+                            return armed(kk);
+                        },
+                        [&](int kk) { poll_dma(exr[rr], (st - 1) & 3, hb, 1u << kk); });
     };
 
     // one time step of ring r (r and TWO are compile-time constants: the per-ring state stays in registers)
@@ -1102,7 +879,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx2_kernel(LstmWgxArgs wp)
         if (p.tune & 4) { st_poll += pc1 - pc0; st_bar += pc2 - pc1; }
         // ---- x_{t+2} into the slot whose x_t the input projection of the previous step consumed -------------------------------
         if (step + 2 < p.T) {
-            x_dma(xptr[r], xb_r, t + 2 * dt, step & 1);
+            x_fetch(xptr[r], xb_r, t + 2 * dt, step & 1);
             since[0] += n_dma; since[1] += n_dma;
         }
         const long long pc3 = (p.tune & 4) ? __builtin_readcyclecounter() : 0;
@@ -1141,13 +918,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx2_kernel(LstmWgxArgs wp)
             // unconditional (before step 2 it re-arms slots that are still armed, in the last two steps slots nobody reads any
             // more): always three stores per section, so the operation count behind a poll round is a constant
             const unsigned long long packed = *(const u64_alias_t*)((half_t*)stage + cc * U + part * 4);
-            unsigned long long* dst = (unsigned long long*)(exr[r] + (long)(step & 3) * slot_stride + my_byte);
-            unsigned long long* ra = (unsigned long long*)(exr[r] + (long)((step + 2) & 3) * slot_stride + my_byte);
-            if (fast[r]) { *dst = packed; *ra = ~0ull; }
-            else {
-                __hip_atomic_store(dst, packed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(ra, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            ring_publish<unsigned long long, ~0ull>(exr[r], slot_stride, step, my_byte, packed, fast[r], true);
             *(unsigned long long*)(p.h + ((long)t * p.N + ring_of[r] * 16 + cc) * H + slice * U + part * 4) = packed;
             since[0] += 3; since[1] += 3;
         }
@@ -1159,7 +930,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx2_kernel(LstmWgxArgs wp)
         const bool chk_o = TWO && step_o >= 1 && step_o < p.T;
         uint4_t chk[KQ];
         if (chk_o) check_begin(o, step_o, chk);
-        if constexpr (!WOVEN) x_phase(xb_r + ((step + 1) & 1) * TILE, xacc[r]);
+        if constexpr (!WOVEN) x_phase<NKS, MT>(xacc[r], bias4, wih, xb_r + ((step + 1) & 1) * TILE, lo);
         if (chk_o) check_end(o, step_o, chk);
         const long long pc7 = (p.tune & 4) ? __builtin_readcyclecounter() : 0;
         // ---- first poll round for h_t, last in the section: the publishes of the other workgroups are visible by now, and it is
@@ -1256,7 +1027,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wgx2_kernel(LstmWgxArgs wp)
     else run(std::false_type{});
     wait_vm(0);                                         // (the unconditional x-stream DMA of the last steps must have landed before the LDS is released)
     if ((p.tune & 4) && lane == 0) {
-        long long* st = (long long*)((char*)p.xcc_ws + (((size_t)p.n_rings * NSL * sizeof(int) + 64 + 7) & ~(size_t)7)) + ((long)ring_of[0] * NSL + slice) * 16;
+        long long* st = lstm_stats_slot(p.xcc_ws, p.n_rings, NSL, ring_of[0], slice);
         st[0] = __builtin_readcyclecounter() - st_t0;
         st[1] = st_poll; st[2] = st_slow; st[3] = 0; st[4] = 0; st[5] = st_bar; st[6] = 0; st[7] = st_sec[5];
         st[8] = st_sec[0]; st[9] = st_sec[1]; st[10] = st_sec[2]; st[11] = st_sec[3]; st[12] = st_sec[4];
@@ -1284,26 +1055,17 @@ __global__ __launch_bounds__(64 * (NKS * 32 / (4 * MT)), 1) void lstm_layer_cta_
     char* xbuf = smem + 2 * NKS * 1024;         // [2][NKS][64][16 B]
 
     half8_t whh[MT][NKS], wih[MT][NKS];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            const long o = ((((long)slice * MT + m) * NKS + ks) * 64 + lane) * 8;
-            whh[m][ks] = *(const half8_t*)(p.whh + o);
-            wih[m][ks] = *(const half8_t*)(fp.wih + o);
-        }
+    slice_frags(whh, wih, p.whh, fp.wih, slice, lane);
     const int c = lane & 15, q = lane >> 4;
     const int lo = lane * 16;
     float cst[MT];
     float4_t bias4[MT];
+    slice_rows(bias4, fp.bias, H, slice * U + q * MT);
     int hoff[MT];                               // where this lane's units live inside a B-fragment tile
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
         cst[m] = 0.f;
-        const int u = slice * U + q * MT + m;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) bias4[m][i] = fp.bias[i * H + u];
-        hoff[m] = (((u >> 5) * 64 + ((u >> 3) & 3) * 16 + c) * 16) + (u & 7) * 2;
+        hoff[m] = frag_byte<2>(slice * U + q * MT + m, c);
     }
     int t = p.reverse ? p.T - 1 : 0;
     const int dt = p.reverse ? -1 : 1;
@@ -1314,7 +1076,7 @@ __global__ __launch_bounds__(64 * (NKS * 32 / (4 * MT)), 1) void lstm_layer_cta_
 
     uint4_t xq = {0, 0, 0, 0}, xr = {0, 0, 0, 0};
     float4_t xacc[MT];
-    auto x_phase = [&](const char* xb) {
+    auto x_phase = [&](const char* xb) {      // (not lstm_ring.h's: plain mfma16, no read-ahead - the compiler schedules this one)
 #pragma unroll
         for (int m = 0; m < MT; ++m) xacc[m] = bias4[m];
 #pragma unroll
@@ -1397,7 +1159,7 @@ struct LstmWideArgs {
 };
 
 // RX (round 2, default): hand-off through an L2-resident ring buffer in fragment order, exactly as lstm_layer_wgx_kernel (the
-// protocol and its argument are stated there): a workgroup's poll of its ring tile (64 KiB at H = 1024) becomes 64 coalesced KiB
+// protocol and its argument: ring_publish, lstm_ring.h): a workgroup's poll of its ring tile (64 KiB at H = 1024) becomes 64 coalesced KiB
 // instead of 1024 half-line pieces of a row-major tensor, the sentinel fill of the output tensor disappears, and the output
 // tensor is written by a second plain store. Same arithmetic -> same bytes as RX = false (tested).
 template <int NKS, bool RX, bool STATS = false>
@@ -1408,24 +1170,15 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wide_kernel(LstmWideArgs wp
     constexpr int NF = NB * NKS;                 // B fragments of a ring's h tile
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int xcd = blockIdx.x & 7;
-    const int lwg = blockIdx.x >> 3;
-    const int rl = lwg / WPR;
-    // test hook ("lstm_tune" bit 5): spread the workgroups of every ring over all eight XCDs, so that the placement-independent
-    // (write-through) hand-off really crosses XCDs
-    const int ring = rl * 8 + ((p.tune & 32) ? ((xcd + (lwg - rl * WPR)) & 7) : xcd);
-    const int slice = (lwg - rl * WPR) * 4 + wave;
+    const RingSlice at = ring_slice(WPR, wave, p.tune);
+    const int ring = at.ring, slice = at.slice;
     if (ring >= p.n_rings) return;
 
     char* hbuf = smem;                                          // [2][NB][NKS][64 lanes][16 B]
     char* stage = smem + 2 * NF * 1024 + wave * (16 * U * 2);   // per-wave [16 chunks][U] output transpose
 
     half8_t whh[MT][NKS];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks)
-            whh[m][ks] = *(const half8_t*)(p.whh + ((((long)slice * MT + m) * NKS + ks) * 64 + lane) * 8);
+    slice_frags(whh, p.whh, slice, lane);
 
     const int c = lane & 15, q = lane >> 4;
     const int lo = lane * 16;
@@ -1487,35 +1240,12 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wide_kernel(LstmWideArgs wp
             if (step > 0) {
                 const char* base = RX ? exr + (long)((step - 1) & 3) * slot_stride : (const char*)p.h + (long)(t - dt) * row_bytes;
                 __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, RX ? TILE : (int)row_bytes, 0x00020000);
-                unsigned spins = dead ? p.max_spins : 0u;
-                unsigned pend = 0;
-#pragma unroll
-                for (int kk = 0; kk < KH; ++kk) {
-                    if (EXH || wave + 4 * kk < NKS) {
-                        unsigned orv = hq[nb][kk].x | hq[nb][kk].y | hq[nb][kk].z | hq[nb][kk].w;
-                        if (__any((orv & SENTINEL_MASK) != 0)) pend |= (1u << kk);
-                    }
-                }
+                auto armed = [&](int kk) { return (EXH || wave + 4 * kk < NKS) && __any(armed_f16(hq[nb][kk])); };
+                const unsigned pend = ring_pending<KH>(armed);
                 if (stats) st_wait += __builtin_readcyclecounter() - c0;
-                while (pend != 0) {
-                    if (++spins > p.max_spins) {
-                        if (lane == 0 && !dead) atomicExch(p.err, 1);
-                        dead = true;
-                        break;
-                    }
-                    ++st_rounds;
-                    if (!(p.tune & 1)) __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-                    for (int kk = 0; kk < KH; ++kk)
-                        if (pend & (1u << kk))
-                            hq[nb][kk] = __builtin_amdgcn_raw_buffer_load_b128(rs, frag_voff(nb * NKS + wave + 4 * kk), 0, (int)0x80000010);
-#pragma unroll
-                    for (int kk = 0; kk < KH; ++kk)
-                        if (pend & (1u << kk)) {
-                            unsigned orv = hq[nb][kk].x | hq[nb][kk].y | hq[nb][kk].z | hq[nb][kk].w;
-                            if (!__any((orv & SENTINEL_MASK) != 0)) pend &= ~(1u << kk);
-                        }
-                }
+                st_rounds += ring_repoll<KH>(p, lane, dead, pend, armed, [&](int kk) {
+                    hq[nb][kk] = __builtin_amdgcn_raw_buffer_load_b128(rs, frag_voff(nb * NKS + wave + 4 * kk), 0, (int)0x80000010);
+                }) - 1;                                  // (re-poll rounds)
 #pragma unroll
                 for (int kk = 0; kk < KH; ++kk) {
                     const int ks = wave + 4 * kk;
@@ -1582,29 +1312,20 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wide_kernel(LstmWideArgs wp
 #pragma unroll
                 for (int m = 0; m < MT; ++m)
                     sg[m] = __builtin_bit_cast(unsigned short, (half_t)lstm_cell(acc[m][0], acc[m][1], acc[m][2], acc[m][3], cst[m][nb]));
-                if (lane < 32) {                    // 16 chunks x 2 parts of 4 units: 8-byte stores
-                    const int cc = lane >> 1, part = lane & 1;
+                if (const RingMover mv = ring_mover<U>(lane); mv.mover) {      // 16 chunks x 2 parts of 4 units: 8-byte stores
+                    const int cc = mv.cc, part = mv.part;
                     const unsigned long long packed = *(const u64_alias_t*)((half_t*)stage + cc * U + part * 4);
                     unsigned long long* dst =
                         (unsigned long long*)(p.h + ((long)t * p.N + (ring * NB + nb) * 16 + cc) * H + slice * U + part * 4);
                     if constexpr (RX) {
-                        const int u0 = slice * U + part * 4;
-                        const int my_byte = (((nb * NKS + (u0 >> 5)) * 64 + ((u0 >> 3) & 3) * 16 + cc) << 4) + (u0 & 7) * 2;
+                        const int my_byte = nb * NKS * 1024 + frag_byte<2>(slice * U + part * 4, cc);
                         // the re-arm store of this tile's previous step must be complete before anything newer of it is published
-                        // (lstm_layer_wgx_kernel); what else is in flight - the other tile's polls - went out a half-step ago
+                        // (ring_publish); what else is in flight - the other tile's polls - went out a half-step ago
                         __builtin_amdgcn_s_waitcnt(0x0F70);
-                        unsigned long long* xd = (unsigned long long*)(exr + (long)(step & 3) * slot_stride + my_byte);
-                        if (fast) *xd = packed;
-                        else __hip_atomic_store(xd, packed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (step >= 2 && step + 2 < p.T) {
-                            unsigned long long* ra = (unsigned long long*)(exr + (long)((step + 2) & 3) * slot_stride + my_byte);
-                            if (fast) *ra = ~0ull;
-                            else __hip_atomic_store(ra, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
+                        ring_publish<unsigned long long, ~0ull>(exr, slot_stride, step, my_byte, packed, fast, step >= 2 && step + 2 < p.T);
                         *dst = packed;              // the layer output proper
                     } else {
-                        if (fast) *dst = packed;
-                        else __hip_atomic_store(dst, packed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        ring_store(dst, packed, fast);
                     }
                 }
             }
@@ -1612,7 +1333,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_wide_kernel(LstmWideArgs wp
         }
     }
     if (stats && lane == 0) {
-        long long* st = (long long*)((char*)p.xcc_ws + (((size_t)p.n_rings * NSL * sizeof(int) + 64 + 7) & ~(size_t)7)) + ((long)ring * NSL + slice) * 16;
+        long long* st = lstm_stats_slot(p.xcc_ws, p.n_rings, NSL, ring, slice);
         st[0] = __builtin_readcyclecounter() - st_t0;
         st[1] = st_poll; st[2] = st_bar; st[3] = st_mf; st[4] = st_gate; st[5] = st_rounds;
         st[6] = (long long)__builtin_amdgcn_s_memrealtime() - st_r0; st[7] = st_wait;
@@ -1641,9 +1362,9 @@ __global__ void fill_u16_kernel(uint16_t* dst, uint16_t v, size_t count) {
 static unsigned max_spins() { return (unsigned)bh::g_opt.lstm_max_spins; }
 
 size_t bh_k_lstm_ws_bytes(int N, int H) {
-    // XCD agreement slots + (tune bit 4) per-wave statistics: up to 16 x int64 per (ring, slice)
+    // XCD agreement slots + ("lstm_tune" bit 2) per-wave statistics: up to 16 x int64 per (ring, slice)
     const size_t waves = (size_t)((N + 15) / 16) * ((H + 7) / 8);        // up to H/8 slices per ring (wide variant)
-    return waves * sizeof(int) + 64 + waves * 16 * sizeof(long long) + 64;
+    return waves * sizeof(int) + bh::LSTM_STATS_GAP + waves * bh::LSTM_STATS_WORDS * sizeof(long long) + 64;      // lstm_stats_slot
 }
 
 int bh_k_fill_u16(void* dst, uint16_t value, size_t count, hipStream_t stream) {

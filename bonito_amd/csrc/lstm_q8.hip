@@ -17,9 +17,8 @@
 //     ([k-step][lane][16 bytes]: what a consumer lane needs is one aligned 16-byte piece, a k-step of a ring is one
 //     contiguous KiB), and the hand-off uses a small RING BUFFER of four time slots per ring (4 x H x 16 bytes; 768 KiB for
 //     a 512-chunk batch: it never leaves the L2). Bytes are valid when they differ from the sentinel 0x80 (-128 is not a
-//     quantised value). A producer re-arms its own bytes of slot (t+2)%4 at step t: every wave of the ring has published
-//     h_{t-1} by then, so nobody reads h_{t-2} any more, and the re-arm store is two steps ahead of the data store that
-//     replaces it. No sentinel pre-fill of the output tensor (the fp16 path's fill kernel and the first-touch fetch of the
+//     quantised value). A producer re-arms its own bytes of slot (t+2)%4 at step t (ring_publish, lstm_ring.h: the protocol
+//     and its argument). No sentinel pre-fill of the output tensor (the fp16 path's fill kernel and the first-touch fetch of the
 //     polled lines from HBM are gone), no flags, no fences; every byte is validated on its own;
 //   * the layer output for the next layer is a second, plain store of the same bytes (fragment order, [T][ring][k-step]);
 //     only the last recurrent layer also writes fp16 rows for the CRF head.
@@ -29,6 +28,8 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lstm_cell.h"
+#include "lstm_ring.h"
 
 namespace bh {
 
@@ -59,44 +60,6 @@ struct LstmQ8Args {
     int* dbg;              // test hook: int32 sums [T][N][4H][2] (x part, h part); null in the product path
 };
 
-__device__ __forceinline__ int xcc_id_q8() { return (int)(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 0xF); }
-
-// any byte of the four words equal to 0x80?  (x ^ 0x80 has a zero byte)
-__device__ __forceinline__ bool has_sentinel(const uint4_t& v) {
-    unsigned r = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned y = v[i] ^ 0x80808080u;
-        r |= (y - 0x01010101u) & ~y & 0x80808080u;
-    }
-    return r != 0;
-}
-
-// same cell as the fp16 kernels (lstm.hip: lstm_cell), duplicated here because that one is file-local there
-__device__ __forceinline__ float q8_cell(float ai, float af, float ag, float ao, float& c) {
-    const float ei = __expf(-__builtin_amdgcn_fmed3f(ai, -25.0f, 25.0f));
-    const float ef = __expf(-__builtin_amdgcn_fmed3f(af, -25.0f, 25.0f));
-    const float eg = __expf(-2.0f * __builtin_amdgcn_fmed3f(ag, -12.5f, 12.5f));
-    const float eo = __expf(-__builtin_amdgcn_fmed3f(ao, -25.0f, 25.0f));
-    const float didg = __fmul_rn(1.0f + ei, 1.0f + eg);
-    const float df = 1.0f + ef;
-    const float num = __builtin_fmaf(c, didg, __fmul_rn(1.0f - eg, df));
-    c = __fmul_rn(num, rcpf_(__fmul_rn(df, didg)));
-    const float ec = __expf(-2.0f * __builtin_amdgcn_fmed3f(c, -12.5f, 12.5f));
-    const float hv = __fmul_rn(1.0f - ec, rcpf_(__fmul_rn(1.0f + ec, 1.0f + eo)));
-    return (fabsf(hv) <= 1.0f) ? hv : 0.0f;
-}
-
-// One 1 KiB global -> LDS DMA: lane l moves 16 bytes from g (per lane) to lds + 16 l (lds is wave-uniform). The compiler
-// neither counts nor waits for it: the issuing wave covers it with its own s_waitcnt vmcnt(0) before a barrier publishes it.
-__device__ __forceinline__ void dma16_q8(const char* g, char* lds) {
-    const unsigned l = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(__attribute__((address_space(3))) char*)lds);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(l), "v"(g) : "memory");
-}
-
-// byte offset of unit u (0 .. 64*NK8) of chunk c inside a ring tile in fragment order
-__device__ __forceinline__ int frag_byte(int u, int c) { return (((u >> 6) * 64 + ((u >> 4) & 3) * 16 + c) << 4) + (u & 15); }
-
 // LAST: this layer also writes fp16 rows (the layer after it is not an 8-bit recurrent layer); DBG: dump the integer sums.
 // Template parameters rather than run-time tests so that the gate arithmetic of a wave's MT units is ONE basic block (the
 // compiler interleaves the transcendentals of the three cells; behind per-unit branches they ran one after the other).
@@ -109,13 +72,8 @@ __global__ __launch_bounds__(256, WPS) void lstm_layer_q8_kernel(LstmQ8Args p) {
     const int NSL = H / U, WPR = NSL / 4;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int xcd = blockIdx.x & 7;
-    const int lwg = blockIdx.x >> 3;
-    const int rl = lwg / WPR;
-    // test hook ("lstm_tune" bit 5): spread the workgroups of every ring over all eight XCDs, so that the placement-independent
-    // (write-through) hand-off really crosses XCDs
-    const int ring = rl * 8 + ((p.tune & 32) ? ((xcd + (lwg - rl * WPR)) & 7) : xcd);
-    const int slice = (lwg - rl * WPR) * 4 + wave;
+    const RingSlice at = ring_slice(WPR, wave, p.tune);
+    const int ring = at.ring, slice = at.slice;
     if (ring >= p.n_rings) return;                      // whole workgroup (same ring) leaves together
 
     char* hbuf = smem;                                  // [2][NK8][64][16]  B fragments of h_{t-1}
@@ -123,46 +81,17 @@ __global__ __launch_bounds__(256, WPS) void lstm_layer_q8_kernel(LstmQ8Args p) {
     char* stage = smem + 5 * TILE + wave * (16 * U * 3);   // per wave: [16 chunks][U] bytes + [16][U] halves
 
     int4_t whh[MT][NK8], wih[MT][NK8];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int ks = 0; ks < NK8; ++ks) {
-            const long o = ((((long)slice * MT + m) * NK8 + ks) * 64 + lane) * 16;
-            whh[m][ks] = *(const int4_t*)(p.whh + o);
-            wih[m][ks] = *(const int4_t*)(p.wih + o);
-        }
+    slice_frags(whh, wih, p.whh, p.wih, slice, lane);
     const int c = lane & 15, q = lane >> 4;
     float cst[MT];
     float4_t sx4[MT], sh4[MT], b4[MT];
+    slice_rows(sx4, p.sx, H, slice * U + q * MT);
+    slice_rows(sh4, p.sh, H, slice * U + q * MT);
+    slice_rows(b4, p.bias, H, slice * U + q * MT);
 #pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        cst[m] = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = i * H + slice * U + q * MT + m;
-            sx4[m][i] = p.sx[r]; sh4[m][i] = p.sh[r]; b4[m][i] = p.bias[r];
-        }
-    }
+    for (int m = 0; m < MT; ++m) cst[m] = 0.f;
     bool dead = false;
-    bool fast = false;
-    {
-        int* slot = p.xcc_ws + (long)ring * NSL;
-        const int mine = xcc_id_q8();
-        if (lane == 0) __hip_atomic_store(slot + slice, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        unsigned spins = 0;
-        bool ok = false;
-        while (true) {
-            bool unset = false, other = false;
-            for (int i = lane; i < NSL; i += 64) {
-                const int v = __hip_atomic_load(slot + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                unset |= v < 0; other |= v != mine;
-            }
-            if (!__any(unset)) { ok = !__any(other); break; }
-            if (++spins > p.max_spins) break;          // not an error: the write-through policy is valid for any placement
-            __builtin_amdgcn_s_sleep(4);
-        }
-        fast = ok && !p.force_slow;
-    }
+    const bool fast = ring_store_policy(p, ring, slice, NSL, lane);
 
     int t = p.reverse ? p.T - 1 : 0;
     const int dt = p.reverse ? -1 : 1;
@@ -173,10 +102,10 @@ __global__ __launch_bounds__(256, WPS) void lstm_layer_q8_kernel(LstmQ8Args p) {
     const int lo = lane * 16;
 
     // the lanes that move this wave's U units out: lane -> (chunk cc, dword part): 4 consecutive units of one chunk
-    constexpr int PARTS = U / 4;
-    const bool mover = lane < 16 * PARTS;
-    const int cc = lane / PARTS, part = lane - cc * PARTS;
-    const int my_byte = frag_byte(slice * U + part * 4, cc);          // inside a ring tile
+    const RingMover mv = ring_mover<U>(lane);
+    const bool mover = mv.mover;
+    const int cc = mv.cc, part = mv.part;
+    const int my_byte = frag_byte<1>(slice * U + part * 4, cc);       // inside a ring tile
 
     uint4_t hq[KQ];
     int4_t xacc[MT];
@@ -204,17 +133,11 @@ __global__ __launch_bounds__(256, WPS) void lstm_layer_q8_kernel(LstmQ8Args p) {
     // wait for and cannot put the fetch on the critical path. A wave's DMAs are covered by its own vmcnt(0) ahead of the
     // barrier that publishes the tile. Shares: the polls of the exchange go w, w+4; the x stream goes 3-w, 7-w, so every
     // wave moves three KiB per step at H = 384.
-    auto x_dma = [&](int tt, int slot) {
-#pragma unroll
-        for (int kk = 0; kk < KQ; ++kk) {
-            const int ks = (3 - wave) + 4 * kk;
-            if (EXACT || ks < NK8) dma16_q8((const char*)(xptr + (long)tt * t_stride + ks * 1024), xbuf + (slot * NK8 + ks) * 1024);
-        }
-    };
+    auto x_fetch = [&](int tt, int slot) { x_dma<NK8>((const char*)(xptr + (long)tt * t_stride), 1024, xbuf, slot, wave); };
 
     // ---- prologue: x_0 and x_1 -> LDS, input projection of step 0 -------------------------------------------------------
-    x_dma(t, 0);
-    x_dma(p.T > 1 ? t + dt : t, 1);
+    x_fetch(t, 0);
+    x_fetch(p.T > 1 ? t + dt : t, 1);
     __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): the builtin (unlike inline asm) also clears the compiler's own scoreboard
     __syncthreads();
     x_phase(xbuf);
@@ -233,30 +156,10 @@ __global__ __launch_bounds__(256, WPS) void lstm_layer_q8_kernel(LstmQ8Args p) {
             // every load in a 64-trip readfirstlane loop
             const char* src = exr + (long)((step - 1) & 3) * slot_stride;
             __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, TILE, 0x00020000);
-            unsigned spins = dead ? p.max_spins : 0u;
-            unsigned pend = 0;
-#pragma unroll
-            for (int kk = 0; kk < KQ; ++kk) {
-                const int ks = wave + 4 * kk;
-                if ((EXACT || ks < NK8) && __any(has_sentinel(hq[kk]))) pend |= (1u << kk);
-            }
-            unsigned rounds = 1;
-            while (pend != 0) {
-                if (++spins > p.max_spins) {
-                    if (lane == 0 && !dead) atomicExch(p.err, 1);
-                    dead = true;
-                    break;
-                }
-                if (!(p.tune & 1)) __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-                for (int kk = 0; kk < KQ; ++kk)
-                    if (pend & (1u << kk))
-                        hq[kk] = __builtin_amdgcn_raw_buffer_load_b128(rs, (wave + 4 * kk) * 1024 + lo, 0, (int)0x80000010);
-#pragma unroll
-                for (int kk = 0; kk < KQ; ++kk)
-                    if ((pend & (1u << kk)) && !__any(has_sentinel(hq[kk]))) pend &= ~(1u << kk);
-                ++rounds;
-            }
+            auto armed = [&](int kk) { return (EXACT || wave + 4 * kk < NK8) && __any(has_sentinel(hq[kk])); };
+            const unsigned rounds = ring_repoll<KQ>(p, lane, dead, ring_pending<KQ>(armed), armed, [&](int kk) {
+                hq[kk] = __builtin_amdgcn_raw_buffer_load_b128(rs, (wave + 4 * kk) * 1024 + lo, 0, (int)0x80000010);
+            });
 #pragma unroll
             for (int kk = 0; kk < KQ; ++kk) {
                 const int ks = wave + 4 * kk;
@@ -289,7 +192,7 @@ __global__ __launch_bounds__(256, WPS) void lstm_layer_q8_kernel(LstmQ8Args p) {
         // ---- X. request x_{t+2} into the slot x_{t-1} was consumed from; it is needed behind the NEXT barrier. Issued between
         //         the MFMAs and the gates: older than this step's stores and polls in the memory queue, and behind the
         //         compiler's own vmcnt(0) at the head of this phase (which would otherwise wait for it) ---------------------
-        if (step + 2 < p.T) x_dma(t + 2 * dt, (step + 2) % 3);
+        if (step + 2 < p.T) x_fetch(t + 2 * dt, (step + 2) % 3);
         if constexpr (DBG) {
 #pragma unroll
             for (int m = 0; m < MT; ++m)
@@ -309,7 +212,7 @@ __global__ __launch_bounds__(256, WPS) void lstm_layer_q8_kernel(LstmQ8Args p) {
             for (int i = 0; i < 4; ++i)
                 pre[i] = __fadd_rn(DBG ? __fadd_rn(__fmul_rn((float)xacc[m][i], sx4[m][i]), b4[m][i]) : xpre[m][i],
                                    __fmul_rn((float)acc[m][i], sh4[m][i]));
-            const float hv = q8_cell(pre[0], pre[1], pre[2], pre[3], cst[m]);
+            const float hv = lstm_cell(pre[0], pre[1], pre[2], pre[3], cst[m]);
             const half_t h16 = (half_t)hv;
             const float hq_f = __builtin_rintf(__fmul_rn((float)h16, 127.0f));       // |h16| <= 1 -> |hq| <= 127, never the sentinel
             sg8[m] = (unsigned char)(signed char)(int)hq_f;
@@ -318,20 +221,9 @@ __global__ __launch_bounds__(256, WPS) void lstm_layer_q8_kernel(LstmQ8Args p) {
         const long long pcg = (p.tune & 4) ? __builtin_readcyclecounter() : 0;
         if (mover) {
             const unsigned packed = *(const u32a_t*)((const char*)stage + cc * U + part * 4);
-            unsigned* dst = (unsigned*)(exr + (long)(step & 3) * slot_stride + my_byte);
-            if (fast) *dst = packed;                                                                    // stays in this XCD's L2
-            else __hip_atomic_store(dst, packed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);               // sc1 write-through
-            // ---- R. re-arm my bytes of slot (step+2)&3. It holds h_{t-2}; behind this step's barrier the workgroup has seen
-            //         every k-step of h_{t-1}, i.e. EVERY wave of the ring has published h_{t-1} and so finished reading
-            //         h_{t-2} (a wave publishes only after its workgroup's barrier, which follows all four quarter polls). The
-            //         data store into this slot follows two steps from now; the vmcnt(0) ahead of the next barrier completes
-            //         the re-arm before this wave publishes h_{t+1}, and nobody polls the slot for h_{t+2} before having seen
-            //         everybody's h_{t+1}: no consumer can find the old bytes -------------------------------------------
-            if (step >= 2 && step + 2 < p.T) {
-                unsigned* ra = (unsigned*)(exr + (long)((step + 2) & 3) * slot_stride + my_byte);
-                if (fast) *ra = 0x80808080u;
-                else __hip_atomic_store(ra, 0x80808080u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            // publish h_t, re-arm my bytes of slot (step+2)&3 (it holds h_{t-2}): the vmcnt(0) ahead of the next barrier completes the
+            // re-arm before this wave publishes h_{t+1}
+            ring_publish<unsigned, 0x80808080u>(exr, slot_stride, step, my_byte, packed, fast, step >= 2 && step + 2 < p.T);
             if (!LAST || p.hq_out != nullptr) *(unsigned*)(p.hq_out + (long)t * t_stride + (long)ring * TILE + my_byte) = packed;
             if constexpr (LAST) {
                 const unsigned long long h4 = *(const u64a_t*)((const char*)stage + 16 * U + (cc * U + part * 4) * 2);
@@ -357,7 +249,7 @@ __global__ __launch_bounds__(256, WPS) void lstm_layer_q8_kernel(LstmQ8Args p) {
         }
     }
     if ((p.tune & 4) && lane == 0) {
-        long long* st = (long long*)((char*)p.xcc_ws + (((size_t)p.n_rings * NSL * sizeof(int) + 64 + 7) & ~(size_t)7)) + ((long)ring * NSL + slice) * 16;
+        long long* st = lstm_stats_slot(p.xcc_ws, p.n_rings, NSL, ring, slice);
         st[0] = __builtin_readcyclecounter() - st_t0;
         st[1] = st_poll; st[2] = st_rounds; st[3] = st_first_ok; st[4] = st_x; st[5] = st_bar; st[6] = st_rec;
         st[7] = st_mf; st[8] = st_gate;

@@ -16,7 +16,7 @@ The integer products are taken in float64 (|sum| <= 512 * 127 * 127 < 2^53: exac
 A failed exact check raises AssertionError naming the step.
 
 `saturating_case` is the data of the saturation test: biases of +-30 in eight sign patterns by unit (u % 8) so that i, f, g, o sit
-beyond the +-25 / +-12.5 clamps of q8_cell in both signs (pattern 0 lets c climb by one per step and drives h to +1, pattern 1 to -1),
+beyond the +-25 / +-12.5 clamps of lstm_cell in both signs (pattern 0 lets c climb by one per step and drives h to +1, pattern 1 to -1),
 weight rows that are all zero (scale 1.0), and inputs at +-10 * bound and +-65504.
 """
 import numpy as np
@@ -37,7 +37,7 @@ def nk8(H):
 
 
 def frag_byte(u, c):
-    """Byte of unit u of chunk c (0..15) inside a ring tile: frag_byte() of csrc/lstm_q8.hip."""
+    """Byte of unit u of chunk c (0..15) inside a ring tile: frag_byte<1>() of csrc/lstm_ring.h."""
     return ((((u >> 6) * 64 + ((u >> 4) & 3) * 16 + c) << 4) + (u & 15))
 
 

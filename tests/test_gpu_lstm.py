@@ -4,11 +4,14 @@ bound (derived there, pinned by tests/test_lstm_ref_cpu.py; nothing is tuned her
 and behind h_out, the timeout flag (an error return of the entry) and that a second run gives the same bytes; the exchange policies
 (flags bit 0) must agree bit for bit. The references run on the device in fp64."""
 import ctypes as C
+import json
+import os
 
 import numpy as np
 import pytest
 import torch
 
+import lstm_digests as ld
 import lstm_ref as lr
 from bonito_amd import _lib
 
@@ -16,18 +19,9 @@ pytestmark = pytest.mark.gpu
 
 FAM = _lib.LSTM_FAMILIES
 GEMM_FIRST = ("wave", "stream", "wide")                 # G = fp16(x W_ih^T + b) is part of the operation
-HAS_POLICY = ("wave", "fused", "stream", "wgx", "wgx2", "wide")      # (cta exchanges through LDS only)
+HAS_POLICY = ld.HAS_POLICY
 GUARD, FRONT, BACK = 0x7E5A, 64, 4096                   # an fp16 NaN payload no result can equal (|h| <= 1; the kernels' own sentinel is 0xFFFF)
-WIDTHS = {
-    "wave": [32 * k for k in range(1, 17)],
-    "fused": [32 * k for k in range(1, 17)],
-    "stream": [64 * k for k in range(1, 17)],
-    "wgx": [96, 192, 288, 384, 64, 128, 256],
-    "wgx2": [96, 192, 288, 384, 64, 128, 256],
-    "cta": [64, 96, 128],
-    "wide": [640, 768, 896, 1024],
-}
-MAIN = {"wave": 384, "fused": 384, "wgx": 384, "wgx2": 384, "cta": 96, "wide": 1024, "stream": 1024}
+WIDTHS, MAIN = ld.WIDTHS, ld.MAIN       # (family -> widths with an instance, the width the longer tests use): tests/lstm_digests.py
 T_SET = (1, 2, 3, 5, 9, 10, 13, 17)     # the paired kernel's unrolled loop runs for 4 <= step, step + 4 <= T - 2: none, one pass, every tail
 WORST = {}                              # (family, class) -> largest err / bound seen
 
@@ -170,6 +164,29 @@ def test_every_wide_width_runs_or_is_refused_at_create(H):
         ref = nn_ref.forward(model, x.float(), expand_blanks=False).permute(1, 0, 2)
     d = (got.cpu().float() - ref).abs()
     assert torch.isfinite(got.float()).all() and d.max().item() < 2.4e-2 and d.mean().item() < 8e-3, (H, d.max().item(), d.mean().item())
+
+
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lstm_kernels_parent.json")) as _fh:
+    PARENT = json.load(_fh)
+
+
+@pytest.mark.parametrize("family", list(WIDTHS))
+def test_every_family_has_the_bytes_of_the_commit_before_the_shared_header(family):
+    """tests/golden/lstm_kernels_parent.json: digests written by tools/lstm_kernel_digests.py against a build of the commit before the
+    recurrent kernels moved their shared parts into csrc/lstm_ring.h. Cases: tests/lstm_digests.py."""
+    assert PARENT["seed"] == ld.SEED
+    want = PARENT["fp16"][family]
+    got = {ld.fp16_key(*c): ld.fp16_digest(family, *c) for c in ld.fp16_cases(family)}
+    assert sorted(got) == sorted(want)
+    assert [k for k in got if got[k] != want[k]] == []
+
+
+@pytest.mark.parametrize("name", [n for n in ld.ENGINE_CASES if not n.startswith("q8")])
+def test_tune_bits_have_the_bytes_of_the_commit_before_the_shared_header(name):
+    """The "lstm_tune" bits only an encoder passes on: the bit-5 spread over the XCDs (wgx, wgx2, wide) and wgx2's generic section code.
+    The digest is of a whole encoder's scores (tests/lstm_digests.py, engine_digest): a change on purpose to the convolutions, the linear
+    layer, the CRF head or the model builder moves it too, and the golden is then rewritten from the commit before that change."""
+    assert ld.engine_digest(name) == PARENT["engine"][name]
 
 
 def test_zz_worst_ratio_per_family_and_class():

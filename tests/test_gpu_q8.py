@@ -32,6 +32,8 @@ also runs one ring past the device's own launch size ("dbg" and "last"). The thr
 rounded fp32 operations in the same order (lstm_q8.hip is compiled without contraction).
 """
 import ctypes as C
+import json
+import os
 
 import numpy as np
 import pytest
@@ -41,6 +43,7 @@ from bonito_amd import _lib, decode, synthetic
 from bonito_amd.engine import HipEncoder
 from oracle import crf_ref, lstm_q8_ref, nn_ref
 
+import lstm_digests as ld
 import q8_ref
 
 pytestmark = pytest.mark.gpu
@@ -174,6 +177,26 @@ def test_q8_forced_launch_split(H):
     assert _same_bytes(last[:2], whole[:2]) and np.array_equal(inner[1], whole[1])
 
 
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lstm_kernels_parent.json")) as _fh:
+    PARENT = json.load(_fh)
+
+
+def test_q8_kernels_have_the_bytes_of_the_commit_before_the_shared_header():
+    """tests/golden/lstm_kernels_parent.json (tools/lstm_kernel_digests.py, cases of tests/lstm_digests.py): every instance in its three
+    LAST / DBG forms at T = 5, both directions, and H = 384 at T = 1, 2, 3, 11, 14 - h16, the int8 fragments and the int32 sums."""
+    assert PARENT["seed"] == ld.SEED
+    want = PARENT["q8"]
+    got = {ld.q8_key(*c): ld.q8_digest(*c) for c in ld.q8_cases()}
+    assert sorted(got) == sorted(want)
+    assert [k for k in got if got[k] != want[k]] == []
+
+
+@pytest.mark.parametrize("name", [n for n in ld.ENGINE_CASES if n.startswith("q8")])
+def test_q8_options_have_the_bytes_of_the_commit_before_the_shared_header(name):
+    """What only an encoder passes on to the 8-bit kernel: the "lstm_tune" bit-5 spread over the XCDs and the write-through policy."""
+    assert ld.engine_digest(name) == PARENT["engine"][name]
+
+
 def _rings_per_launch(H, variant=0):
     out = (C.c_int32 * 17)()
     cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -212,7 +235,7 @@ SAT_TOL = 4.9e-4 + 2 * SAT_FAST
 @pytest.mark.parametrize("bound", BOUNDS)
 @pytest.mark.parametrize("H", [96, 384])
 def test_q8_saturation(H, bound):
-    """Gates beyond the clamps of q8_cell in both signs (biases of +-30 in eight patterns by unit), all-zero weight rows, inputs at
+    """Gates beyond the clamps of lstm_cell in both signs (biases of +-30 in eight patterns by unit), all-zero weight rows, inputs at
     +-10 bound and +-65504. Sums exact; xq saturates at +-127; hq reaches +127 and -127 and never -128; h16 finite; the cell within
     SAT_TOL = 4.9e-4 (fp16 half-ulp as the project counts it) + 2 x the measured fast-exp / rcp error. Measured on MI355X: worst
     |h16 - fp64 cell| over the six cases 1.824e-4, 2.377e-4, 2.294e-4 (H = 96; bound 1, 3.5, 4) and 2.416e-4, 2.440007e-4, 2.428e-4
