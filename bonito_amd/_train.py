@@ -49,3 +49,24 @@ class HalfLayer(torch.autograd.Function):
         need = ctx.needs_input_grad[2:]
         dx, *rest = ctx.backward_fn(ctx.saved_tensors, dy.to(torch.float16), need)
         return (None, None, dx.to(ctx.x_dtype) if need[0] else None) + tuple(g if n else None for g, n in zip(rest, need[1:]))
+
+
+class HalfLayer2(torch.autograd.Function):
+    """HalfLayer with two activations (a sublayer's output a and the residual x beside it): each is cast to fp16 on entry and gets its
+    gradient in its own dtype. forward(a16, x16, *params) -> (y, the tensors to keep); backward(kept, dy fp16, need) -> (da, dx, a
+    gradient or None per parameter), `need` being needs_input_grad of (a, x, *params)."""
+
+    @staticmethod
+    def forward(ctx, forward, backward, a, x, *params):
+        a16, x16 = (t if t.dtype == torch.float16 else t.to(torch.float16) for t in (a, x))
+        y, keep = forward(a16, x16, *params)
+        ctx.save_for_backward(*keep)
+        ctx.backward_fn, ctx.dtypes = backward, (a.dtype, x.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        need = ctx.needs_input_grad[2:]
+        da, dx, *rest = ctx.backward_fn(ctx.saved_tensors, dy.to(torch.float16), need)
+        return (None, None, da.to(ctx.dtypes[0]) if need[0] else None, dx.to(ctx.dtypes[1]) if need[1] else None) \
+            + tuple(g if n else None for g, n in zip(rest, need[2:]))

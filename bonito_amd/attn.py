@@ -7,6 +7,8 @@ include/bonito_hip.h under bh_attention_train_forward).
     dqkv       = attention_backward(qkv, out, saved, dout, window)
     out        = attention(qkv, window)                    # differentiable with respect to qkv (fp16 or fp32)
     y          = mha_module(layer, x)                      # a transformer.model.MultiHeadAttention container, x [N][T][D]
+    y          = encoder_layer(layer, x)                   # a transformer.model.TransformerEncoderLayer container: attention, the two
+                                                           # DeepNorm residual RMSNorms and the gated MLP (bonito_amd.train_ops)
 
 window = (left, right): key j is visible to query i of the same chunk iff i - left <= j <= i + right. torch allocates and orders the
 streams; every number is computed by libbonito_hip.so. There is no PyTorch fallback: CPU tensors raise NoTorchCompute, an unsupported
@@ -19,7 +21,8 @@ from bonito_amd import _lib
 from bonito_amd._train import HalfLayer, devices, half, tensors
 from bonito_amd.nn import NoTorchCompute
 
-__all__ = ["attention_forward", "attention_backward", "attention", "mha_module", "supported_window", "HEAD_DIM"]
+__all__ = ["attention_forward", "attention_backward", "attention", "mha_module", "encoder_layer", "encoder_layer_check", "supported_window",
+           "HEAD_DIM"]
 
 HEAD_DIM = 64
 _tables = {}      # (device, T) -> the device copy of bh_rotary_table(T, 64)
@@ -153,17 +156,64 @@ def mha_module(module, x):
     """A bonito_amd.transformer.model.MultiHeadAttention container applied to x [N][T][D]: Wqkv, rotary + windowed attention, out_proj.
     Gradients land on the container's fp32 parameters (Wqkv.weight, Wqkv.bias if any, out_proj.weight, out_proj.bias if any)."""
     from bonito_amd import train_ops
-    from bonito_amd.transformer.model import MultiHeadAttention
-    if not isinstance(module, MultiHeadAttention):
-        raise ValueError("mha_module: expected a bonito_amd.transformer.model.MultiHeadAttention container, got %s" % type(module).__name__)
-    if module.head_dim != HEAD_DIM:
-        raise ValueError("mha_module: only head_dim %d is served, got %d" % (HEAD_DIM, module.head_dim))
-    if module.rotary_dim != module.head_dim:
-        raise ValueError("mha_module: rotary_dim must equal head_dim (got %d and %d)" % (module.rotary_dim, module.head_dim))
-    window = _window(module.attn_window, "mha_module")
-    tensors([("x", x)], "mha_module")
-    if x.dim() != 3 or x.shape[2] != module.d_model:
-        raise ValueError("mha_module: x must be [N][T][%d], got %s" % (module.d_model, tuple(x.shape)))
+    window = _mha_check(module, "mha_module")
+    _activations(x, module.d_model, "mha_module")
     qkv = train_ops.linear(x, module.Wqkv.weight, module.Wqkv.bias)
     out = attention(qkv, window)
     return train_ops.linear(out, module.out_proj.weight, module.out_proj.bias)
+
+
+def _mha_check(module, what):
+    """What mha_module refuses about the container itself -> its window."""
+    from bonito_amd.transformer.model import MultiHeadAttention
+    if not isinstance(module, MultiHeadAttention):
+        raise ValueError("%s: expected a bonito_amd.transformer.model.MultiHeadAttention container, got %s" % (what, type(module).__name__))
+    if module.head_dim != HEAD_DIM:
+        raise ValueError("%s: only head_dim %d is served, got %d" % (what, HEAD_DIM, module.head_dim))
+    if module.rotary_dim != module.head_dim:
+        raise ValueError("%s: rotary_dim must equal head_dim (got %d and %d)" % (what, module.rotary_dim, module.head_dim))
+    return _window(module.attn_window, what)
+
+
+def _activations(x, d_model, what):
+    tensors([("x", x)], what)
+    if x.dim() != 3 or x.shape[2] != d_model:
+        raise ValueError("%s: x must be [N][T][%d], got %s" % (what, d_model, tuple(x.shape)))
+
+
+def encoder_layer_check(layer, what="encoder_layer"):
+    """What encoder_layer refuses about the container itself, in front of any launch: mha_module's refusals, and a dim_feedforward that is
+    no multiple of 8. SeqdistModel.forward_train calls it for every layer before its first launch."""
+    from bonito_amd.transformer.model import TransformerEncoderLayer
+    if not isinstance(layer, TransformerEncoderLayer):
+        raise ValueError("%s: expected a bonito_amd.transformer.model.TransformerEncoderLayer container, got %s" % (what, type(layer).__name__))
+    _mha_check(layer.self_attn, what)
+    F2, D = layer.ff.fc1.weight.shape
+    if F2 % 16 != 0 or tuple(layer.ff.fc2.weight.shape) != (layer.self_attn.d_model, F2 // 2) or D != layer.self_attn.d_model:
+        raise ValueError("%s: dim_feedforward must be a multiple of 8 (fc1 %s, fc2 %s)"
+                         % (what, tuple(layer.ff.fc1.weight.shape), tuple(layer.ff.fc2.weight.shape)))
+
+
+def _alpha(layer):
+    """deepnorm_alpha as a number. It is a buffer (a checkpoint may carry its own value), so it is read from the tensor - once per value:
+    reading a device tensor waits for the stream."""
+    buf = layer.deepnorm_alpha
+    key = (buf._version, buf.data_ptr(), buf.device)
+    cached = layer.__dict__.get("_alpha_read")
+    if cached is None or cached[0] != key:
+        cached = layer.__dict__["_alpha_read"] = (key, float(buf))
+    return cached[1]
+
+
+def encoder_layer(layer, x):
+    """A bonito_amd.transformer.model.TransformerEncoderLayer container applied to x [N][T][D] (fp16 or fp32) -> fp16 [N][T][D]:
+        x1  = rmsnorm(self_attn(x) + deepnorm_alpha x) norm1.weight
+        out = rmsnorm(fc2(swiglu(fc1(x1))) + deepnorm_alpha x1) norm2.weight
+    Gradients land on the container's fp32 parameters; deepnorm_alpha is a buffer and gets none."""
+    from bonito_amd import train_ops
+    encoder_layer_check(layer)
+    _activations(x, layer.self_attn.d_model, "encoder_layer")
+    alpha = _alpha(layer)
+    x1 = train_ops.rmsnorm_residual(mha_module(layer.self_attn, x), x, layer.norm1.weight, alpha, layer.norm1.eps)
+    f = train_ops.linear(train_ops.gated_linear(x1, layer.ff.fc1.weight), layer.ff.fc2.weight)
+    return train_ops.rmsnorm_residual(f, x1, layer.norm2.weight, alpha, layer.norm2.eps)

@@ -1,5 +1,5 @@
 """
-``python -m bonito_amd train``: train an LSTM-family CRF model on labelled chunks (chunks.npy, references.npy, reference_lengths.npy,
+``python -m bonito_amd train``: train a CRF model of the LSTM or the transformer family on labelled chunks (chunks.npy, references.npy, reference_lengths.npy,
 what ``basecaller --save-ctc`` writes) on one HIP device -- the arguments of the reference's bonito/cli/train.py.
 
 The training directory receives config.toml (the model's config, the arguments under [training]), per epoch weights_N.tar,
@@ -59,7 +59,7 @@ def main(args):
     else:
         model = load_symbol(config, "Model")(config)
     if not hasattr(model, "forward_train"):
-        _refuse("%s.%s has no forward_train: the LSTM family of CRF models trains on the device" % (type(model).__module__, type(model).__name__))
+        _refuse("%s.%s has no forward_train: the LSTM and transformer families of CRF models train on the device" % (type(model).__module__, type(model).__name__))
     model = model.to(device)
 
     print("[loading data]")
@@ -94,7 +94,7 @@ def argparser():
     parser = ArgumentParser(
         formatter_class=ArgumentDefaultsHelpFormatter,
         add_help=False,
-        description="Train an LSTM-family CRF model on labelled chunks on one HIP device; the training directory receives config.toml, "
+        description="Train a CRF model of the LSTM or the transformer family on labelled chunks on one HIP device; the training directory receives config.toml, "
                     "weights_N.tar, optim_N.tar, losses_N.csv and training.csv.",
     )
     parser.add_argument("training_directory")

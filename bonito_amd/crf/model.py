@@ -286,12 +286,17 @@ class SeqdistModel(Module):
         """The forward of a training step: x cuda fp16 [N,1,L] -> scores in the shape, layout and dtype of ``forward(x)``, INSIDE
         autograd, so that ``self.loss(self.forward_train(x), targets, lengths).backward()`` leaves a gradient on every trainable
         parameter. The parameters are the fp32 master weights on x's device; every layer rounds them to fp16 on the device in every
-        call (autocast's arithmetic: bonito_amd.train_ops, bonito_amd.rnn). Serves the LSTM family - conv x3 -> permute -> LSTM x n ->
-        [linear] -> linearcrfencoder [-> clamp] - with the folding rules of ``engine.lower``: a Clamp after a Convolution or the head
-        is fused into it, Permute([2,0,1]) is folded into the producing convolution's store, Permute([1,0,2]) after the head is a
-        no-op. Anything else is refused with a ValueError that names the layer. The inference engine is neither built nor dropped."""
-        from bonito_amd import nn as bnn, rnn, train_ops
+        call (autocast's arithmetic: bonito_amd.train_ops, bonito_amd.rnn, bonito_amd.attn). Serves the LSTM family - conv x3 ->
+        permute -> LSTM x n -> [linear] -> linearcrfencoder [-> clamp] - and the transformer family - conv x n (no norm) ->
+        permute [0,2,1] -> TransformerEncoderLayer x depth -> LinearUpsample -> linearcrfencoder [-> clamp] - with the folding rules of
+        ``engine.lower``: a Clamp after a Convolution or the head is fused into it, Permute([2,0,1]) is folded into the producing
+        convolution's store, Permute([0,2,1]) is the layout the convolutions store anyway, Permute([1,0,2]) after the head is a no-op
+        (batch-major rows are the scores' layout already), a batch-first LinearUpsample is a linear layer whose [N][T][s D] output is
+        read as [N][s T][D]. Anything else is refused with a ValueError that names the layer. The inference engine is neither built
+        nor dropped."""
+        from bonito_amd import attn, nn as bnn, rnn, train_ops
         from bonito_amd.engine import _flatten
+        from bonito_amd.transformer.model import TransformerEncoderLayer
         if getattr(self, "_quantize", False):
             raise ValueError("forward_train: quantize (the 8-bit recurrent path) has no training forward; call use_hip(quantize=False)")
         if not isinstance(x, torch.Tensor) or x.dtype != torch.float16 or x.dim() != 3 or x.shape[1] != 1:
@@ -311,9 +316,24 @@ class SeqdistModel(Module):
             return None, tm
 
         # every refusal comes before the first launch; what is wrong on any device is judged first
+        time_major, width = False, None          # are the activations [T][N][C] here, and how many channels (None: not followed)
         for i, m in enumerate(mods):
             name = "layer %d (%s)" % (i, type(m).__name__)
-            if isinstance(m, bnn.Convolution):
+            if isinstance(m, TransformerEncoderLayer):
+                attn.encoder_layer_check(m, "forward_train: %s" % name)
+                if time_major:
+                    raise ValueError("forward_train: %s follows the permute to time-major activations; a transformer layer needs "
+                                     "[N][T][C] (permute [0,2,1])" % name)
+                if width is not None and width != m.self_attn.d_model:
+                    raise ValueError("forward_train: %s has d_model %d and follows %d channels" % (name, m.self_attn.d_model, width))
+            elif isinstance(m, bnn.LinearUpsample) and not time_major:
+                if not m.batch_first:
+                    raise ValueError("forward_train: %s with batch_first=False has no training forward" % name)
+                if m.d_model % 8 != 0 or (width is not None and width != m.d_model):
+                    raise ValueError("forward_train: %s needs d_model %% 8 == 0 and as many input channels (d_model %d, %s channels)"
+                                     % (name, m.d_model, width))
+            elif isinstance(m, bnn.Convolution):
+                width = m.conv.out_channels
                 if m.norm is not None:
                     raise ValueError("forward_train: %s carries a norm (%s); a normalised convolution has no training backward yet"
                                      % (name, getattr(m.norm, "name", type(m.norm).__name__)))
@@ -334,9 +354,13 @@ class SeqdistModel(Module):
             elif isinstance(m, bnn.Permute):
                 if list(m.dims) not in ([2, 0, 1], [0, 2, 1], [1, 0, 2]):
                     raise ValueError("forward_train: %s with dims %s cannot be folded" % (name, list(m.dims)))
+                time_major = time_major or list(m.dims) == [2, 0, 1]
             elif not isinstance(m, (bnn.LinearCRFEncoder, bnn.Linear, bnn.Clamp, bnn.MakeContiguous)) or isinstance(m, bnn.LinearUpsample):
-                raise ValueError("forward_train: %s has no training forward (the LSTM family of CRF models is served: convolutions, "
-                                 "LSTMs, linear, linearcrfencoder, clamp)" % name)
+                raise ValueError("forward_train: %s has no training forward (the LSTM and transformer families of CRF models are served: "
+                                 "convolutions, LSTMs, transformer encoder layers, linear, batch-major linearupsample, linearcrfencoder, "
+                                 "clamp)" % name)
+            elif isinstance(m, bnn.Linear):
+                width = m.linear.out_features
             for pname, p in m.named_parameters():
                 if p.dtype != torch.float32:
                     raise ValueError("forward_train: %s holds %s parameters (%s); training needs the fp32 master weights - call "
@@ -380,13 +404,25 @@ class SeqdistModel(Module):
                     raise ValueError("forward_train: %s must follow permute [2,0,1]" % name)
                 h = rnn.lstm_module(m, h)
                 i += 1
+            elif isinstance(m, TransformerEncoderLayer):
+                if layout != "nlc":
+                    raise ValueError("forward_train: %s needs the [N][T][C] output of the convolutions" % name)
+                h = attn.encoder_layer(m, h)
+                i += 1
+            elif isinstance(m, bnn.LinearUpsample):        # [N][T][D] -> [N][T][s D], which is [N][s T][D]
+                if layout != "nlc":
+                    raise ValueError("forward_train: %s needs [N][T][C] activations" % name)
+                h = train_ops.linear(h, m.linear.weight, m.linear.bias)
+                h = h.view(h.shape[0], h.shape[1] * m.scale_factor, m.d_model)
+                i += 1
             elif isinstance(m, (bnn.LinearCRFEncoder, bnn.Linear)):
-                if layout != "tnc":
-                    raise ValueError("forward_train: %s needs the time-major output of the LSTM stack" % name)
+                if layout not in ("tnc", "nlc") or h.dim() != 3:
+                    raise ValueError("forward_train: %s needs the time-major output of the LSTM stack or [N][T][C] activations" % name)
                 head = isinstance(m, bnn.LinearCRFEncoder)
                 clamp = clamp_after(i)
+                # batch-major rows ([N][T][C], the transformer family) are stored as they are: that is the scores' layout already
                 h = train_ops.linear(h, m.linear.weight, m.linear.bias, m.activation if head else None,
-                                     (m.scale if m.scale else None) if head else None, clamp, head)
+                                     (m.scale if m.scale else None) if head else None, clamp, head and layout == "tnc")
                 if head:
                     layout = "ntc"
                 i += 2 if clamp is not None else 1

@@ -432,6 +432,20 @@ extern "C" int bh_linear_train_backward(const void* x, const float* w, const voi
     return bh_k_linear_train_backward(x, w, y, dy, T, N, K, C, act, scale, clamp_lo, clamp_hi, batch_major, dx, dw, db, workspace,
                                       workspace_bytes, (hipStream_t)stream);
 }
+extern "C" size_t bh_rmsnorm_train_workspace(long M, int D) { return bh_k_rmsnorm_train_workspace(M, D); }
+extern "C" int bh_rmsnorm_train_backward(const void* a, const void* x, const float* w, const void* dy, long M, int D, float alpha, float eps,
+                                         void* da, void* dx, float* dw, void* workspace, size_t workspace_bytes, void* stream) {
+    return bh_k_rmsnorm_train_backward(a, x, w, dy, M, D, alpha, eps, da, dx, dw, workspace, workspace_bytes, (hipStream_t)stream);
+}
+extern "C" size_t bh_gated_linear_train_workspace(long M, int D, int F) { return bh_k_gated_linear_train_workspace(M, D, F); }
+extern "C" int bh_gated_linear_train_forward(const void* x, const float* w, long M, int D, int F, void* h, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+    return bh_k_gated_linear_train_forward(x, w, M, D, F, h, workspace, workspace_bytes, (hipStream_t)stream);
+}
+extern "C" int bh_gated_linear_train_backward(const void* x, const float* w, const void* dh, long M, int D, int F, void* dx, float* dw,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
+    return bh_k_gated_linear_train_backward(x, w, dh, M, D, F, dx, dw, workspace, workspace_bytes, (hipStream_t)stream);
+}
 extern "C" size_t bh_sw_workspace(int n, int max_seq, int max_ref) { return bh_k_sw_workspace(n, max_seq, max_ref); }
 extern "C" int bh_sw_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, const void* refs, long ref_stride,
                            const int32_t* ref_lengths, int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace,

@@ -174,6 +174,16 @@ int bh_k_linear_train_backward(const void* x, const float* w, const void* y, con
                                float clamp_lo, float clamp_hi, int batch_major, void* dx, float* dw, float* db, void* workspace,
                                size_t workspace_bytes, hipStream_t stream);
 
+// transformer_train.hip (what a transformer encoder layer adds to training: the backward of bh_k_rmsnorm_residual, and fc1 + SwiGLU)
+size_t bh_k_rmsnorm_train_workspace(long M, int D);
+int bh_k_rmsnorm_train_backward(const void* a, const void* x, const float* w, const void* dy, long M, int D, float alpha, float eps, void* da,
+                                void* dx, float* dw, void* workspace, size_t workspace_bytes, hipStream_t stream);
+size_t bh_k_gated_linear_train_workspace(long M, int D, int F);
+int bh_k_gated_linear_train_forward(const void* x, const float* w, long M, int D, int F, void* h, void* workspace, size_t workspace_bytes,
+                                    hipStream_t stream);
+int bh_k_gated_linear_train_backward(const void* x, const float* w, const void* dh, long M, int D, int F, void* dx, float* dw, void* workspace,
+                                     size_t workspace_bytes, hipStream_t stream);
+
 // align.hip (Smith-Waterman, affine gaps, traceback; the lengths are host arrays)
 size_t bh_k_sw_workspace(int n, int max_seq, int max_ref);
 int bh_k_sw_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,

@@ -292,7 +292,7 @@ int bh_k_lstm_train_forward(const void* x, const float* w_ih, const float* w_hh,
     hipLaunchKernelGGL(lstm_train_weights_kernel, dim3(grid), dim3(256), 0, stream, w_hh, whh16, (int)W_FWD, H);
     BH_CHECK_HIP(hipGetLastError());
     // G = x W_ih^T + b over all T N rows, fp16
-    if (int rc = linear_rows((const half_t*)x, wih16, bias, (half_t*)(sv + L.gates), T, N, H, 4 * H, ACT_NONE, 1.0f, -INFINITY, INFINITY, false, stream))
+    if (int rc = linear_rows((const half_t*)x, wih16, bias, (half_t*)(sv + L.gates), T, N, H, 4 * H, ACT_NONE, 1.0f, -INFINITY, INFINITY, false, false, stream))
         return rc;
     FwdArgs a{whh16, (half_t*)(sv + L.hfrag), (half_t*)(sv + L.gates), (float*)(sv + L.c), (half_t*)h_out, T, N, H, reverse};
     hipLaunchKernelGGL(lstm_train_fwd_kernel, dim3((N + TILE_N - 1) / TILE_N), dim3(recurrent_threads(H)), 0, stream, a);
@@ -325,7 +325,7 @@ int bh_k_lstm_train_backward(const void* x, const float* w_ih, const float* w_hh
     hipLaunchKernelGGL(lstm_train_bwd_kernel, dim3((N + TILE_N - 1) / TILE_N), dim3(recurrent_threads(H)), 0, stream, a);
     BH_CHECK_HIP(hipGetLastError());
     // dx = dA W_ih over all T N rows, fp16
-    if (int rc = linear_rows(da, wihT, nullptr, (half_t*)dx, T, N, 4 * H, H, ACT_NONE, 1.0f, -INFINITY, INFINITY, false, stream)) return rc;
+    if (int rc = linear_rows(da, wihT, nullptr, (half_t*)dx, T, N, 4 * H, H, ACT_NONE, 1.0f, -INFINITY, INFINITY, false, false, stream)) return rc;
     // dW_ih, dW_hh = dA^T [X | H_prev] and db = the column sums of dA, over all T N rows
     const RowRule rule{(const half_t*)x, ROWS_LSTM, H, 0, 0, 0, 0, 0, (const half_t*)h, T, N, reverse};
     return reduce_rows(da, rule, (long)T * N, 4 * H, 2 * H, (float*)(ws + W.dw_part), (float*)(ws + W.db_part), dw_ih, dw_hh, dbias, stream);

@@ -1,6 +1,7 @@
-// What the training units share (lstm_train.hip, train_layers.hip): the small host helpers, the split of a reduction over rows, and
-// the two entries of train_common.hip - reduce_rows (the weight and bias gradients of every layer) and linear_rows (a GEMM over all
-// T N rows through bh_k_linear). Each exists once; the kernels are compiled in train_common.hip only.
+// What the training units share (lstm_train.hip, train_layers.hip, transformer_train.hip): the small host helpers, the split of a
+// reduction over rows, and the three entries of train_common.hip - reduce_rows (the weight and bias gradients of every layer),
+// round_weights (a linear layer's fp32 master weights as the fp16 operand of a launch) and linear_rows (a GEMM over all T N rows
+// through bh_k_linear). Each exists once; the kernels are compiled in train_common.hip only.
 #pragma once
 #include <math.h>
 
@@ -63,6 +64,16 @@ struct RowRule {
 int reduce_rows(const half_t* a, const RowRule& b, long M, int R, int Cc, float* dw_part, float* db_part, float* dw, float* dw_hi, float* db,
                 hipStream_t stream);
 
+// ---- the master weights of a linear layer, rounded ------------------------------------------------------------------------------------------
+enum WeightForm : int {
+    WEIGHTS_ROWS = 0,         // fp16 [C][K], the rows as they are
+    WEIGHTS_TRANSPOSED = 1,   // fp16 [K][C]
+    WEIGHTS_GATED_PAIRS = 2   // fp16 [C][K] with row j of the first half at 2 j and row j of the second half at 2 j + 1: (y_j, gate_j), what
+                        // bh_k_linear's SwiGLU epilogue reads (C even)
+};
+// fp32 w [C][K] (a device tensor, torch's layout) -> its round-to-nearest fp16 values in `form`; one launch
+int round_weights(const float* w, half_t* out, int C, int K, int form, hipStream_t stream);
+
 // ---- a GEMM over all rows ----------------------------------------------------------------------------------------------------------------
 // rows of one bh_k_linear call: its kernels may index an operand with 32-bit offsets, so both stay below 2^30 halves; the rows of a GEMM
 // are independent, the blocks change no byte. With the batch-major row map a block is whole time steps (a multiple of N rows).
@@ -73,8 +84,9 @@ inline long gemm_rows(int K, int C, int N, bool whole_steps) {
     return rows;
 }
 // Y = clamp(act(X W^T + b) scale, lo, hi) over the T N rows m = t N + n of x [T][N][K], block by block; y [T][N][C], or batch-major
-// [N][T][C]. The first non-zero return code of bh_k_linear is passed up.
+// [N][T][C]. gated: w's C rows are pairs (y_j, gate_j) and y has C / 2 columns y_j gate_j sigmoid(gate_j), bh_k_linear's SwiGLU epilogue
+// (act none, no bias). The first non-zero return code of bh_k_linear is passed up.
 int linear_rows(const half_t* x, const half_t* w, const float* bias, half_t* y, int T, int N, int K, int C, int act, float scale, float lo,
-                float hi, bool batch_major, hipStream_t stream);
+                float hi, bool batch_major, bool gated, hipStream_t stream);
 
 }  // namespace bh

@@ -1,5 +1,5 @@
-// The two pieces every training layer needs (train_common.h), on gfx950: the reduction over rows that gives the weight and bias
-// gradients, and the loop that walks bh_k_linear over blocks of rows.
+// The pieces the training layers share (train_common.h), on gfx950: the reduction over rows that gives the weight and bias
+// gradients, the rounding of a linear layer's master weights, and the loop that walks bh_k_linear over blocks of rows.
 //     dW = dz^T B over the M rows and db = sum of dz are ONE kernel family for every layer (atb_kernel + colsum_kernel + reduce_kernel).
 //     B's row m (RowRule) is X[m] for the linear layer; for the convolution the window of K Cin contiguous halves at x[n][t s - p], zero
 //     where it hangs over an edge; for the LSTM layer [x[m] | h of the step processed before m's], zero at the first processed step.
@@ -157,7 +157,24 @@ int reduce_rows_of(const half_t* a, const RowRule& b, long M, int R, int Cc, flo
     return 0;
 }
 
+__global__ __launch_bounds__(256) void round_weights_kernel(const float* __restrict__ w, half_t* __restrict__ out, int C, int K, int form) {
+    const long total = (long)C * K;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const long c = e / K, k = e - c * K;
+        long to = e;
+        if (form == WEIGHTS_TRANSPOSED) to = k * C + c;
+        else if (form == WEIGHTS_GATED_PAIRS) to = (c < C / 2 ? 2 * c : 2 * (c - C / 2) + 1) * K + k;
+        out[to] = (half_t)w[e];
+    }
+}
+
 }  // namespace
+
+int round_weights(const float* w, half_t* out, int C, int K, int form, hipStream_t stream) {
+    hipLaunchKernelGGL(round_weights_kernel, dim3(cvt_grid((long)C * K)), dim3(256), 0, stream, w, out, C, K, form);
+    BH_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 
 int reduce_rows(const half_t* a, const RowRule& b, long M, int R, int Cc, float* dw_part, float* db_part, float* dw, float* dw_hi, float* db,
                 hipStream_t stream) {
@@ -171,15 +188,16 @@ int reduce_rows(const half_t* a, const RowRule& b, long M, int R, int Cc, float*
 }
 
 int linear_rows(const half_t* x, const half_t* w, const float* bias, half_t* y, int T, int N, int K, int C, int act, float scale, float lo,
-                float hi, bool batch_major, hipStream_t stream) {
+                float hi, bool batch_major, bool gated, hipStream_t stream) {
     const long rows = (long)T * N, step = gemm_rows(K, C, N, batch_major);
+    const int ldo = gated ? C / 2 : C;      // the SwiGLU epilogue stores one column per (y_j, gate_j) pair of W's rows
     for (long m0 = 0; m0 < rows; m0 += step) {
         const int m = (int)(rows - m0 < step ? rows - m0 : step);
         int rc;
         if (batch_major)      // rows are (t, n): the engine's remap to [N][T][C]; the block starts at time step m0 / N
-            rc = bh_k_linear(x + m0 * K, w, bias, y + m0 / N * C, m, C, K, K, K, C, act, scale, lo, hi, 0, N, 1, T, N, stream);
+            rc = bh_k_linear(x + m0 * K, w, bias, y + m0 / N * ldo, m, C, K, K, K, ldo, act, scale, lo, hi, gated, N, 1, T, N, stream);
         else
-            rc = bh_k_linear(x + m0 * K, w, bias, y + m0 * C, m, C, K, K, K, C, act, scale, lo, hi, 0, 0, 0, 0, 0, stream);
+            rc = bh_k_linear(x + m0 * K, w, bias, y + m0 * ldo, m, C, K, K, K, ldo, act, scale, lo, hi, gated, 0, 0, 0, 0, stream);
         if (rc) return rc;
     }
     return 0;

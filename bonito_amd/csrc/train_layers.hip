@@ -21,7 +21,7 @@
 //     training layer: B's row m is X[m] for the linear layer (ROWS_PLAIN) and, for the convolution, the window of K Cin contiguous
 //     halves at x[n][t s - p], zero where it hangs over an edge (ROWS_CONV). The rows are split into blocks whose partial sums are
 //     added in block order: no floating-point atomics, equal bytes from call to call.
-//     dx: linear through linear_rows on W^T (fp16 copy made by linear_weights_kernel); convolution in conv_dx_kernel, one thread per 8
+//     dx: linear through linear_rows on W^T (fp16 copy made by round_weights, train_common.hip); convolution in conv_dx_kernel, one thread per 8
 //     input channels of one input position, taps with (l + p - k) mod s == 0 only, fp32 sums in a fixed order.
 // Every kernel of this file indexes with 64 bits. bh_k_linear is called through linear_rows (train_common.hip), on blocks of rows whose
 // operands stay below 2^30 halves.
@@ -52,14 +52,6 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void round_kernel(const float* __restrict__ in, float* __restrict__ out, long n) {
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x)
         out[e] = in ? (float)(half_t)in[e] : 0.0f;
-}
-// fp32 [C][K] -> fp16 [C][K], or transposed [K][C]
-__global__ __launch_bounds__(256) void linear_weights_kernel(const float* __restrict__ w, half_t* __restrict__ out, int C, int K, int transpose) {
-    const long total = (long)C * K;
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const long c = e / K, k = e - c * K;
-        out[transpose ? k * C + c : e] = (half_t)w[e];
-    }
 }
 
 // ---- activation derivative and the clamp's mask ---------------------------------------------------------------------------------------
@@ -400,10 +392,10 @@ int bh_k_linear_train_forward(const void* x, const float* w, const float* bias, 
     char* ws = (char*)workspace;
     half_t* w16 = (half_t*)(ws + L.w);
     float* b16 = bias ? (float*)(ws + L.bias) : nullptr;
-    hipLaunchKernelGGL(linear_weights_kernel, dim3(cvt_grid((long)C * K)), dim3(256), 0, stream, w, w16, C, K, 0);
+    if (int rc = round_weights(w, w16, C, K, WEIGHTS_ROWS, stream)) return rc;
     if (bias) hipLaunchKernelGGL(round_kernel, dim3(cvt_grid(C)), dim3(256), 0, stream, bias, b16, (long)C);
     BH_CHECK_HIP(hipGetLastError());
-    return linear_rows((const half_t*)x, w16, b16, (half_t*)y, T, N, K, C, act, scale, clamp_lo, clamp_hi, batch_major != 0, stream);
+    return linear_rows((const half_t*)x, w16, b16, (half_t*)y, T, N, K, C, act, scale, clamp_lo, clamp_hi, batch_major != 0, false, stream);
 }
 
 int bh_k_linear_train_backward(const void* x, const float* w, const void* y, const void* dy, int T, int N, int K, int C, int act, float scale,
@@ -424,9 +416,8 @@ int bh_k_linear_train_backward(const void* x, const float* w, const void* y, con
     hipLaunchKernelGGL(linear_dz_kernel, dim3((unsigned)((items + 255) / 256 < 65536 ? (items + 255) / 256 : 65536)), dim3(256), 0, stream, a);
     BH_CHECK_HIP(hipGetLastError());
     if (dx) {      // dx = dz W over all rows, fp16
-        hipLaunchKernelGGL(linear_weights_kernel, dim3(cvt_grid((long)C * K)), dim3(256), 0, stream, w, wT, C, K, 1);
-        BH_CHECK_HIP(hipGetLastError());
-        if (int rc = linear_rows(dz, wT, nullptr, (half_t*)dx, T, N, C, K, ACT_NONE, 1.0f, -INFINITY, INFINITY, false, stream)) return rc;
+        if (int rc = round_weights(w, wT, C, K, WEIGHTS_TRANSPOSED, stream)) return rc;
+        if (int rc = linear_rows(dz, wT, nullptr, (half_t*)dx, T, N, C, K, ACT_NONE, 1.0f, -INFINITY, INFINITY, false, false, stream)) return rc;
     }
     const RowRule rule{(const half_t*)x, ROWS_PLAIN, K};
     return reduce_rows(dz, rule, rows, C, K, (float*)(ws + L.dw_part), (float*)(ws + L.db_part), dw, nullptr, db, stream);

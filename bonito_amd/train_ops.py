@@ -1,6 +1,8 @@
 """
 The convolution and the linear / CRF-head layer for training on the device: forward on the rounded master weights, backward, and their
-autograd (csrc/train_layers.hip; the arithmetic is stated in include/bonito_hip.h under bh_conv1d_train_forward).
+autograd (csrc/train_layers.hip; the arithmetic is stated in include/bonito_hip.h under bh_conv1d_train_forward) - and the two layers a
+transformer encoder layer adds, the DeepNorm residual RMSNorm and the gated input layer of the MLP (csrc/transformer_train.hip; under
+bh_rmsnorm_train_backward).
 
     y = conv1d_forward(x, weight, bias, stride, padding, activation, clamp, time_major)     # x fp16 [N][Lin][Cin] ([N][Lin] for Cin == 1)
     dx, dw, db = conv1d_backward(x, weight, bias, y, dy, stride, padding, activation, clamp, time_major)
@@ -8,6 +10,12 @@ autograd (csrc/train_layers.hip; the arithmetic is stated in include/bonito_hip.
     y = linear_forward(x, weight, bias, activation, scale, clamp, batch_major_out)          # x fp16 [T][N][K]
     dx, dw, db = linear_backward(x, weight, y, dy, activation, scale, clamp, batch_major_out)
     y = linear(x, weight, bias, activation, scale, clamp, batch_major_out)                  # differentiable
+    out = rmsnorm_residual_forward(a, x, weight, alpha, eps)                                # a, x fp16 [...][D]: rmsnorm(a + alpha x) weight
+    da, dx, dw = rmsnorm_residual_backward(a, x, weight, dy, alpha, eps)
+    out = rmsnorm_residual(a, x, weight, alpha, eps)                                        # differentiable
+    h = gated_linear_forward(x, weight)                                                     # x fp16 [...][D], weight [2F][D] -> [...][F]
+    dx, dw = gated_linear_backward(x, weight, dh)
+    h = gated_linear(x, weight)                                                             # differentiable
 
 Activations are channel-minor: a convolution returns [N][Lout][Cout], or time-major [Lout][N][Cout] (the permute in front of the LSTM
 stack, folded into the store). weight and bias are the fp32 master tensors in torch's layout ([Cout][Cin][K], [C][K]).
@@ -20,9 +28,11 @@ import math
 import torch
 
 from bonito_amd import _lib
-from bonito_amd._train import HalfLayer, devices as _devices, half as _half, master as _master, tensors as _tensors
+from bonito_amd._train import HalfLayer, HalfLayer2, devices as _devices, half as _half, master as _master, tensors as _tensors
 
-__all__ = ["conv1d_forward", "conv1d_backward", "conv1d", "linear_forward", "linear_backward", "linear", "conv_out_len"]
+__all__ = ["conv1d_forward", "conv1d_backward", "conv1d", "linear_forward", "linear_backward", "linear", "conv_out_len",
+           "rmsnorm_residual_forward", "rmsnorm_residual_backward", "rmsnorm_residual",
+           "gated_linear_forward", "gated_linear_backward", "gated_linear"]
 
 _INF = float("inf")
 
@@ -245,3 +255,157 @@ def linear(x, weight, bias=None, activation=None, scale=None, clamp=None, batch_
         return linear_backward(*kept, dy, *args, need_dx=need[0], need_db=bias is not None and need[2])
 
     return HalfLayer.apply(forward, backward, x, weight, bias)
+
+
+# ---- DeepNorm residual RMSNorm --------------------------------------------------------------------------------------------------------------
+_BOTH = (torch.float16, torch.float32)
+
+
+def _dtype_names(dtypes):
+    return " or ".join(str(d).replace("torch.", "") for d in dtypes)
+
+
+def _norm_check(a, x, weight, alpha, eps, what, dtypes=(torch.float16,), devices=True):
+    named = [("a", a), ("x", x), ("weight", weight)]
+    _tensors(named, what)
+    for name, t in named[:2]:
+        if t.dtype not in dtypes:
+            raise ValueError("%s: %s must be %s, got %s" % (what, name, _dtype_names(dtypes), t.dtype))
+    if a.dim() < 2 or a.numel() == 0 or a.shape != x.shape:
+        raise ValueError("%s: a and x must be [...][D] of one shape, got %s and %s" % (what, tuple(a.shape), tuple(x.shape)))
+    D = int(a.shape[-1])
+    _master(weight, (D,), "weight", what)
+    if isinstance(alpha, torch.Tensor) and alpha.numel() != 1:
+        raise ValueError("%s: alpha must be one number, got a tensor %s" % (what, tuple(alpha.shape)))
+    alpha, eps = float(alpha), float(eps)
+    if not math.isfinite(alpha) or not math.isfinite(eps) or eps < 0.0:
+        raise ValueError("%s: alpha must be finite and eps finite and >= 0, got %r and %r" % (what, alpha, eps))
+    if D % 8 != 0 or not 8 <= D <= 1024:
+        raise ValueError("%s: D must be a multiple of 8 in 8..1024, got %d" % (what, D))
+    if devices:
+        _devices(named, what)
+    return a.numel() // D, D, alpha, eps
+
+
+def rmsnorm_residual_forward(a, x, weight, alpha, eps=1e-5):
+    """-> out fp16 in the shape of a: rmsnorm(a + alpha x) weight, the bytes of bh_rmsnorm_residual (a, x fp16 [...][D], weight fp32 [D])."""
+    M, D, alpha, eps = _norm_check(a, x, weight, alpha, eps, "rmsnorm_residual_forward")
+    a, x, weight = a.contiguous(), x.contiguous(), weight.detach().contiguous()
+    with torch.cuda.device(a.device):
+        out = torch.empty_like(a)
+        _lib.check(_lib.lib().bh_rmsnorm_residual(_lib.ptr(a), _lib.ptr(x), _lib.ptr(weight), _lib.ptr(out), M, D, alpha, eps,
+                                                  _lib.stream_ptr(a.device)), "bh_rmsnorm_residual")
+    return out
+
+
+def rmsnorm_residual_backward(a, x, weight, dy, alpha, eps=1e-5, need_da=True, need_dx=True):
+    """-> (da fp16 or None, dx fp16 or None, dw fp32 [D]) from the upstream gradient dy (fp16, in the shape of a); nothing of the forward
+    is needed: z and r are recomputed from a and x."""
+    what = "rmsnorm_residual_backward"
+    M, D, alpha, eps = _norm_check(a, x, weight, alpha, eps, what, devices=False)
+    _tensors([("dy", dy)], what)
+    _half(dy, a.shape, "dy", what)
+    _devices([("a", a), ("x", x), ("weight", weight), ("dy", dy)], what)
+    a, x, weight, dy = a.contiguous(), x.contiguous(), weight.detach().contiguous(), dy.contiguous()
+    lib = _lib.lib()
+    nbytes = lib.bh_rmsnorm_train_workspace(M, D)
+    if nbytes == 0:
+        raise ValueError("%s: shape M=%d D=%d is not supported" % (what, M, D))
+    with torch.cuda.device(a.device):
+        da = torch.empty_like(a) if need_da else None
+        dx = torch.empty_like(a) if need_dx else None
+        dw = torch.empty(D, dtype=torch.float32, device=a.device)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+        _lib.check(lib.bh_rmsnorm_train_backward(_lib.ptr(a), _lib.ptr(x), _lib.ptr(weight), _lib.ptr(dy), M, D, alpha, eps, _lib.ptr(da),
+                                                 _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(ws), nbytes, _lib.stream_ptr(a.device)),
+                   "bh_rmsnorm_train_backward")
+    return da, dx, dw
+
+
+def rmsnorm_residual(a, x, weight, alpha, eps=1e-5):
+    """out fp16 = rmsnorm(a + alpha x) weight, differentiable with respect to a, x (each fp16 or fp32; fp32 is cast to fp16 and its
+    gradient comes back as fp32) and weight, each where requires_grad is set. alpha (a number or a one-element tensor) gets no gradient."""
+    _, _, alpha, eps = _norm_check(a, x, weight, alpha, eps, "rmsnorm_residual", dtypes=_BOTH)
+
+    def forward(a16, x16, weight):
+        return rmsnorm_residual_forward(a16, x16, weight, alpha, eps), (a16, x16, weight)
+
+    def backward(kept, dy, need):
+        return rmsnorm_residual_backward(*kept, dy.contiguous(), alpha, eps, need_da=need[0], need_dx=need[1])
+
+    return HalfLayer2.apply(forward, backward, a, x, weight)
+
+
+# ---- gated input layer of the MLP (fc1 + SwiGLU) ----------------------------------------------------------------------------------------------
+def _gated_check(x, weight, what, dtypes=(torch.float16,), devices=True):
+    named = [("x", x), ("weight", weight)]
+    _tensors(named, what)
+    if weight.dim() != 2 or weight.shape[0] % 2 != 0:
+        raise ValueError("%s: weight must be [2F][D] (y rows, then gate rows), got %s" % (what, tuple(weight.shape)))
+    F, D = int(weight.shape[0]) // 2, int(weight.shape[1])
+    if x.dtype not in dtypes:
+        raise ValueError("%s: x must be %s, got %s" % (what, _dtype_names(dtypes), x.dtype))
+    if x.dim() < 2 or x.shape[-1] != D or x.numel() == 0:
+        raise ValueError("%s: x must be [...][%d], got %s" % (what, D, tuple(x.shape)))
+    _master(weight, (2 * F, D), "weight", what)
+    if D % 8 != 0 or F % 8 != 0 or F < 8:
+        raise ValueError("%s: D and F must be multiples of 8 (D=%d F=%d)" % (what, D, F))
+    if devices:
+        _devices(named, what)
+    return x.numel() // D, D, F
+
+
+def _gated_workspace(M, D, F, what):
+    nbytes = _lib.lib().bh_gated_linear_train_workspace(M, D, F)
+    if nbytes == 0:
+        raise ValueError("%s: shape M=%d D=%d F=%d is not supported" % (what, M, D, F))
+    return nbytes
+
+
+def gated_linear_forward(x, weight):
+    """-> h fp16 [...][F] = y gate sigmoid(gate), [y | gate] = x weight^T (x fp16 [...][D], weight fp32 [2F][D]): the bytes of bh_linear with
+    gated = 1 on the rounded, row-interleaved weights, which is the engine's fc1."""
+    what = "gated_linear_forward"
+    M, D, F = _gated_check(x, weight, what)
+    x, weight = x.contiguous(), weight.detach().contiguous()
+    nbytes = _gated_workspace(M, D, F, what)
+    with torch.cuda.device(x.device):
+        h = torch.empty(tuple(x.shape[:-1]) + (F,), dtype=torch.float16, device=x.device)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _lib.check(_lib.lib().bh_gated_linear_train_forward(_lib.ptr(x), _lib.ptr(weight), M, D, F, _lib.ptr(h), _lib.ptr(ws), nbytes,
+                                                            _lib.stream_ptr(x.device)), "bh_gated_linear_train_forward")
+    return h
+
+
+def gated_linear_backward(x, weight, dh, need_dx=True):
+    """-> (dx fp16 in the shape of x or None, dw fp32 [2F][D] in torch's row order) from the upstream gradient dh (fp16 [...][F]); y and gate
+    are recomputed."""
+    what = "gated_linear_backward"
+    M, D, F = _gated_check(x, weight, what, devices=False)
+    _tensors([("dh", dh)], what)
+    _half(dh, tuple(x.shape[:-1]) + (F,), "dh", what)
+    _devices([("x", x), ("weight", weight), ("dh", dh)], what)
+    x, weight, dh = x.contiguous(), weight.detach().contiguous(), dh.contiguous()
+    nbytes = _gated_workspace(M, D, F, what)
+    with torch.cuda.device(x.device):
+        dx = torch.empty_like(x) if need_dx else None
+        dw = torch.empty((2 * F, D), dtype=torch.float32, device=x.device)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _lib.check(_lib.lib().bh_gated_linear_train_backward(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(dh), M, D, F, _lib.ptr(dx), _lib.ptr(dw),
+                                                             _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device)), "bh_gated_linear_train_backward")
+    return dx, dw
+
+
+def gated_linear(x, weight):
+    """h fp16 [...][F] of the gated input layer, differentiable with respect to x (fp16 or fp32; fp32 is cast to fp16 and its gradient
+    comes back as fp32) and weight, each where requires_grad is set."""
+    _gated_check(x, weight, "gated_linear", dtypes=_BOTH)
+
+    def forward(x16, weight):
+        x16 = x16.contiguous()
+        return gated_linear_forward(x16, weight), (x16, weight)
+
+    def backward(kept, dh, need):
+        return gated_linear_backward(*kept, dh.contiguous(), need_dx=need[0])
+
+    return HalfLayer.apply(forward, backward, x, weight)

@@ -10,7 +10,8 @@ The training loop of ``python -m bonito_amd train`` (the reference's bonito/trai
 of kernel launch. The host reads the step's scalars (``optimizer.last()``) once per step, for the log and for the quantile clip.
 
 The inference engine snapshots the weights when it is built and the update kernel changes them behind the module's back, so the engine
-is dropped before every validation pass (and only there: forward_train does not use it).
+is dropped before every validation pass (and only there: forward_train does not use it). The model is any SeqdistModel whose
+forward_train serves it: the LSTM family and the transformer family (convolutions without a norm).
 """
 import math
 import os
@@ -87,7 +88,7 @@ class Trainer:
         if not use_amp:
             raise ValueError("Trainer: use_amp=False is not served: forward_train computes in fp16 and there is no fp32 path")
         if not hasattr(model, "forward_train"):
-            raise ValueError("Trainer: %s has no forward_train (the LSTM family of CRF models trains on the device)" % type(model).__name__)
+            raise ValueError("Trainer: %s has no forward_train (the LSTM and transformer families of CRF models train on the device)" % type(model).__name__)
         self.model = model.to(device)
         self.device = device
         self.train_loader, self.valid_loader = train_loader, valid_loader

@@ -28,6 +28,8 @@
  *        torch.nn.LSTM under autocast, and its autograd, as the reference's LSTM layer wraps it   bonito/nn.py:353-397
  *   bh_attention_train_forward / bh_attention_train_backward
  *        RotaryEmbedding + flash_attn_qkvpacked_func(qkv, window_size=) and their autograd          bonito/transformer/model.py:58-75
+ *   bh_rmsnorm_train_backward / bh_gated_linear_train_forward / bh_gated_linear_train_backward
+ *        the autograd of RMSNorm(attn / ff + deepnorm_alpha * x) and of GatedMlp's fc1 + SwiGLU         bonito/transformer/model.py:83-133
  *   bh_sw_align
  *        parasail.sw_trace_striped_32(seq, ref, 8, 4, parasail.dnafull) behind evaluate's align() and util.accuracy
  *                                                                              bonito/cli/evaluate.py:37-67, bonito/util.py:346-368
@@ -424,6 +426,40 @@ int bh_linear_train_forward(const void* x, const float* w, const float* bias, in
 int bh_linear_train_backward(const void* x, const float* w, const void* y, const void* dy, int T, int N, int K, int C, int act, float scale,
                              float clamp_lo, float clamp_hi, int batch_major, void* dx, float* dw, float* db, void* workspace,
                              size_t workspace_bytes, void* stream);
+
+/* ---- What a transformer encoder layer adds to training (csrc/transformer_train.hip): the norm's backward, and fc1 + SwiGLU ----------
+ * With bh_attention_train_* and bh_linear_train_* these are all pieces of a TransformerEncoderLayer (bonito/transformer/model.py:83-133:
+ * x1 = norm1(attn(x) + alpha x), out = norm2(ff(x1) + alpha x1); bonito_amd.attn.encoder_layer chains them).
+ * DeepNorm residual RMSNorm, a, x, dy fp16 [M][D], w fp32 [D] (used as it is, as bh_rmsnorm_residual does):
+ *     z = a + alpha x      r = rsqrt(mean_d z^2 + eps)      out = fp16(z r w)             - the forward IS bh_rmsnorm_residual; nothing is saved
+ *   backward, z and r recomputed from a and x:
+ *     g = dy w      c = (1/D) sum_d g_d z_d      dz = r g - r^3 c z
+ *     da = fp16(dz)      dx = fp16(alpha dz)      dw[d] = sum_m dy[m][d] z[m][d] r[m]   (fp32, OVERWRITTEN)
+ *   Every sum and every intermediate is fp32; da and dx are rounded once, at the store. dy arrives loss-scaled; nothing is scaled or
+ *   clamped. da or dx may be NULL = not written. One wave per row; dw: a workgroup sums a block of rows (the block a function of M
+ *   alone) into the workspace and a second launch adds the blocks in block order (eight runs of consecutive blocks, each added in block
+ *   order, then the runs in order) - no floating-point atomics, two calls give equal bytes.
+ *   Supported: D a multiple of 8 in 8..1024, M >= 1.
+ * Gated input layer of the MLP, x fp16 [M][D], w fp32 [2F][D] in torch's layout (y rows first, then gate rows: flash-attn's GatedMlp):
+ *     [y | gate] = x fp16(w)^T      h = fp16(y gate sigmoid(gate))     fp16 [M][F]
+ *   forward: the weights are rounded and their rows interleaved (y_j, gate_j) on the device, then bh_linear's gated epilogue runs: h has
+ *   the bytes of bh_linear(gated = 1) on those weights, which is what bh_encoder_forward computes.
+ *   backward, from dh fp16 [M][F]: u = [y | gate] is RECOMPUTED by the plain GEMM and stored as fp16 (the forward keeps nothing), then
+ *     s = sigmoid(gate)      dy = dh gate s      dgate = dh y s (1 + gate (1 - s))      du = fp16([dy | dgate])   (fp32, one rounding)
+ *     dx = du fp16(w) (fp16, through bh_linear on the transposed rounded weights)      dw = du^T x (fp32 [2F][D], torch's row order, OVERWRITTEN)
+ *   dx may be NULL. dw's reduction over rows is that of bh_linear_train_backward: equal bytes from call to call.
+ *   Supported: D % 8 == 0, F % 8 == 0, M < 2^31; M * 2F may pass 2^31 elements (64-bit offsets throughout).
+ * EVERY pointer is a device pointer, 16-byte aligned. workspace (bh_*_train_workspace; 0 = unsupported shape): the caller's.
+ * Anything unsupported returns nonzero with bh_last_error() set, launches nothing and leaves every output untouched.
+ * Stream-ordered; nothing is allocated and nothing synchronises inside. */
+size_t bh_rmsnorm_train_workspace(long M, int D);
+int bh_rmsnorm_train_backward(const void* a, const void* x, const float* w, const void* dy, long M, int D, float alpha, float eps,
+                              void* da, void* dx, float* dw, void* workspace, size_t workspace_bytes, void* stream);
+size_t bh_gated_linear_train_workspace(long M, int D, int F);
+int bh_gated_linear_train_forward(const void* x, const float* w, long M, int D, int F, void* h, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+int bh_gated_linear_train_backward(const void* x, const float* w, const void* dh, long M, int D, int F, void* dx, float* dw,
+                                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Smith-Waterman local alignment with affine gaps and a traceback (csrc/align.hip) ----------------------------------
  * n pairs of a called sequence `seq` (the query, index i) and a known sequence `ref` (index j). seqs / refs: DEVICE int8 planes

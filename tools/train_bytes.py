@@ -12,6 +12,9 @@ tests/train_layers_ref.py; fixed seeds).
                                 exists), both directions; h, dx, dw_ih, dw_hh, db with a bias gradient and dx, dw_ih, dw_hh without
     convolution                 CONV_CASES rows 0, 3, 4, 7, clamp on and off: y, dx, dw, db
     linear                      LINEAR_CASES rows 1, 3, 4, both row maps: y, dx, dw, db
+    norm (M, D)                 the DeepNorm residual RMSNorm (tests/transformer_train_ref.py): a tail of rows, a second vector per lane, more
+                                than one dw block; out, da, dx, dw
+    gated (M, D, F)             fc1 + SwiGLU: h, dx, dw
 
 Prints one JSON line {case: {tensor: sha256}}."""
 import argparse
@@ -35,6 +38,9 @@ LSTM_CASES = ((150, 20, 64, False), (600, 5, 32, False), (37, 5, 32, True), (3, 
               (24, 16, 384, False))
 CONV_ROWS = (0, 3, 4, 7)
 LINEAR_ROWS = (1, 3, 4)
+NORM_CASES = ((5, 64), (257, 520), (130, 1024))          # (M, D)
+NORM_ALPHA = 2.4494897
+GATED_CASES = ((17, 64, 72), (1030, 128, 256), (33, 512, 2048))      # (M, D, F)
 
 
 def sha(t):
@@ -77,6 +83,18 @@ def main():
             dyd = dy.permute(1, 0, 2).contiguous() if batch_major else dy
             dx, dw, db = train_ops.linear_backward(x, w, y, dyd, act, scale, clamp, batch_major)
             res["linear row %d %s" % (i, "ntc" if batch_major else "tnc")] = {"y": sha(y), "dx": sha(dx), "dw": sha(dw), "db": sha(db)}
+    if hasattr(train_ops, "rmsnorm_residual_backward"):        # a checkout from before the transformer family's layers has neither
+        import transformer_train_ref as tt
+        for M, D in NORM_CASES:
+            c = {k: v.to(dev) for k, v in tt.norm_case(M, D).items()}
+            out = train_ops.rmsnorm_residual_forward(c["a"], c["x"], c["w"], NORM_ALPHA)
+            da, dx, dw = train_ops.rmsnorm_residual_backward(c["a"], c["x"], c["w"], c["dy"], NORM_ALPHA)
+            res["norm M=%d D=%d" % (M, D)] = {"out": sha(out), "da": sha(da), "dx": sha(dx), "dw": sha(dw)}
+        for M, D, F in GATED_CASES:
+            c = {k: v.to(dev) for k, v in tt.gated_case(M, D, F).items()}
+            h = train_ops.gated_linear_forward(c["x"], c["w"])
+            dx, dw = train_ops.gated_linear_backward(c["x"], c["w"], c["dh"])
+            res["gated M=%d D=%d F=%d" % (M, D, F)] = {"h": sha(h), "dx": sha(dx), "dw": sha(dw)}
     torch.cuda.synchronize()
     line = json.dumps(res, sort_keys=True)
     print(line)
