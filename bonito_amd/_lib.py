@@ -94,6 +94,9 @@ SIGNATURES = {
     "bh_gated_linear_train_workspace": (_sz, [_l, _i, _i]),
     "bh_gated_linear_train_forward": (_i, [_vp, _vp, _l, _i, _i, _vp, _vp, _sz, _vp]),
     "bh_gated_linear_train_backward": (_i, [_vp, _vp, _vp, _l, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "bh_batchnorm_train_workspace": (_sz, [_i, _i, _i]),
+    "bh_batchnorm_train_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _f, _f, _l, _l, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "bh_batchnorm_train_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _l, _l, _vp, _vp, _vp, _vp, _sz, _vp]),
     "bh_sw_workspace": (_sz, [_i, _i, _i]),
     "bh_sw_align": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _l, _vp, _vp]),
     "bh_sg_align": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _l, _vp, _vp]),

@@ -6,6 +6,7 @@ The training directory receives config.toml (the model's config, the arguments u
 losses_N.csv (chunks, time, grad_norm, lr, scale, loss per step) and every --save-optim-every epochs optim_N.tar, and training.csv
 (one row per epoch); ``basecaller`` and ``evaluate`` load it. The step is bonito_amd.training.Trainer's: forward_train, the CTC-CRF loss,
 backward and bonito_amd.optim.AdamW, all on the device in fp16 with fp32 master weights; --no-amp has nothing to select and is refused.
+``--norm batch`` trains a model whose convolutions carry a BatchNorm (every published configuration) with batch statistics.
 """
 import os
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
@@ -67,11 +68,24 @@ def main(args):
     chunks_per_epoch = args.chunks or len(train_loader.lengths)
     if chunks_per_epoch < args.batch:
         _refuse("%d training chunks are fewer than one batch of %d" % (chunks_per_epoch, args.batch))
-    try:                                       # what forward_train refuses, it refuses in front of its first launch
+    norm_kwargs = {} if args.norm is None else {"norm": args.norm}
+    # what forward_train refuses, it refuses in front of its first launch. With --norm batch the probe runs in train mode (load_model
+    # returns eval mode) and would rewrite the running statistics: they are put back, byte for byte.
+    buffers = {name: b.clone() for name, b in model.named_buffers()} if norm_kwargs else {}
+    was_training = model.training
+    try:
+        if norm_kwargs:
+            model.train()
         with torch.no_grad():
-            model.forward_train(next(iter(valid_loader))[0][:1].to(torch.float16).to(device))
+            model.forward_train(next(iter(valid_loader))[0][:1].to(torch.float16).to(device), **norm_kwargs)
     except ValueError as exc:
         _refuse(str(exc))
+    finally:
+        model.train(was_training)
+        with torch.no_grad():
+            for name, b in model.named_buffers():
+                if name in buffers:
+                    b.copy_(buffers[name])
 
     with open(os.path.join(workdir, "config.toml"), "w") as fh:
         dump_toml({**config, **argsdict}, fh)
@@ -84,7 +98,7 @@ def main(args):
 
     trainer = Trainer(model, device, train_loader, valid_loader, use_amp=True, lr_scheduler_fn=lr_scheduler_fn, restore_optim=args.restore_optim,
                       save_optim_every=args.save_optim_every, grad_accum_split=args.grad_accum_split,
-                      quantile_grad_clip=args.quantile_grad_clip, chunks_per_epoch=chunks_per_epoch, batch_size=args.batch)
+                      quantile_grad_clip=args.quantile_grad_clip, chunks_per_epoch=chunks_per_epoch, batch_size=args.batch, **norm_kwargs)
     lr = [float(x) for x in args.lr.split(",")] if "," in args.lr else float(args.lr)
     trainer.fit(workdir, args.epochs, lr, **config.get("optim", {}))
     return 0
@@ -120,4 +134,7 @@ def argparser():
     quantile.add_argument("--no-quantile-grad-clip", dest="quantile_grad_clip", action="store_false")
     quantile.set_defaults(quantile_grad_clip=True)
     parser.add_argument("--num-workers", default=4, type=int)
+    parser.add_argument("--norm", default=None, choices=["batch"],
+                        help="how a convolution's BatchNorm trains: batch = with batch statistics, updating the running ones; "
+                             "without the option a model with norms is refused")
     return parser

@@ -282,7 +282,7 @@ class SeqdistModel(Module):
             raise NoTorchCompute("bonito_amd models only run on a HIP device; got a %s tensor" % x.device)
         return self._engine(x)(x)
 
-    def forward_train(self, x):
+    def forward_train(self, x, norm=None):
         """The forward of a training step: x cuda fp16 [N,1,L] -> scores in the shape, layout and dtype of ``forward(x)``, INSIDE
         autograd, so that ``self.loss(self.forward_train(x), targets, lengths).backward()`` leaves a gradient on every trainable
         parameter. The parameters are the fp32 master weights on x's device; every layer rounds them to fp16 on the device in every
@@ -293,7 +293,14 @@ class SeqdistModel(Module):
         convolution's store, Permute([0,2,1]) is the layout the convolutions store anyway, Permute([1,0,2]) after the head is a no-op
         (batch-major rows are the scores' layout already), a batch-first LinearUpsample is a linear layer whose [N][T][s D] output is
         read as [N][s T][D]. Anything else is refused with a ValueError that names the layer. The inference engine is neither built
-        nor dropped."""
+        nor dropped.
+
+        ``norm`` says what a Convolution that carries a norm gets. None: it is refused, and forward_train has no side effect.
+        ``"batch"``: a ``bonito_amd.nn.BatchNorm`` in train mode normalises with the statistics of this batch, as the reference's
+        training does (conv with no activation -> ``train_ops.batchnorm`` with the layer's activation, the fused clamp and the
+        time-major store) - and every call REWRITES the module's ``running_mean`` / ``running_var`` buffers and adds one to
+        ``num_batches_tracked``, under ``torch.no_grad()`` too. The inference engine holds the statistics of the moment it was built:
+        drop it (``_drop_engine``) before inference is to see the new ones. A BatchNorm in eval mode (frozen statistics) is refused."""
         from bonito_amd import attn, nn as bnn, rnn, train_ops
         from bonito_amd.engine import _flatten
         from bonito_amd.transformer.model import TransformerEncoderLayer
@@ -317,6 +324,7 @@ class SeqdistModel(Module):
 
         # every refusal comes before the first launch; what is wrong on any device is judged first
         time_major, width = False, None          # are the activations [T][N][C] here, and how many channels (None: not followed)
+        length = x.shape[2]                      # positions per chunk behind the convolutions so far
         for i, m in enumerate(mods):
             name = "layer %d (%s)" % (i, type(m).__name__)
             if isinstance(m, TransformerEncoderLayer):
@@ -334,12 +342,33 @@ class SeqdistModel(Module):
                                      % (name, m.d_model, width))
             elif isinstance(m, bnn.Convolution):
                 width = m.conv.out_channels
-                if m.norm is not None:
+                if m.norm is not None and norm is None:
                     raise ValueError("forward_train: %s carries a norm (%s); a normalised convolution has no training backward yet"
                                      % (name, getattr(m.norm, "name", type(m.norm).__name__)))
                 if m.conv.groups != 1 or m.conv.dilation[0] != 1:
                     raise ValueError("forward_train: %s is a grouped / dilated (depthwise, QuartzNet) convolution, which has no training "
                                      "backward" % name)
+                length = train_ops.conv_out_len(length, m.conv.kernel_size[0], m.conv.stride[0], m.conv.padding[0])
+                if m.norm is not None:
+                    norm_name = getattr(m.norm, "name", type(m.norm).__name__)
+                    if norm != "batch":
+                        raise ValueError("forward_train: %s carries a norm (%s) and norm=%r is not served (None, or \"batch\" for batch "
+                                         "statistics)" % (name, norm_name, norm))
+                    if not isinstance(m.norm, bnn.BatchNorm):
+                        raise ValueError("forward_train: %s carries a norm (%s) that is no BatchNorm; norm=\"batch\" serves batchnorm only"
+                                         % (name, norm_name))
+                    if not m.norm.bn.training:
+                        raise ValueError("forward_train: %s has its BatchNorm in eval mode; norm=\"batch\" trains with batch statistics "
+                                         "(call model.train()), frozen statistics are not built" % name)
+                    if m.norm.bn.track_running_stats and m.norm.bn.momentum is None:
+                        raise ValueError("forward_train: %s has a BatchNorm with momentum=None (the cumulative average), which is not "
+                                         "served" % name)
+                    if (m.conv.out_channels % 8 and not isinstance(next_compute(i)[0], bnn.Convolution)) or m.conv.out_channels > 2048:
+                        raise ValueError("forward_train: %s normalises %d channels; a multiple of 8 up to 2048 is served (zero padding "
+                                         "only in front of another convolution)" % (name, m.conv.out_channels))
+                    if x.shape[0] * length < 2:
+                        raise ValueError("forward_train: %s normalises %d value per channel; batch statistics need more than one"
+                                         % (name, x.shape[0] * max(length, 0)))
                 clamp = clamp_after(i)
                 if isinstance(next_compute(i)[0], bnn.Convolution) and m.conv.out_channels % 8 and clamp is not None \
                         and not clamp[0] <= 0.0 <= clamp[1]:
@@ -365,6 +394,8 @@ class SeqdistModel(Module):
                 if p.dtype != torch.float32:
                     raise ValueError("forward_train: %s holds %s parameters (%s); training needs the fp32 master weights - call "
                                      "model.float()" % (name, str(p.dtype).replace("torch.", ""), pname))
+        if norm not in (None, "batch"):
+            raise ValueError("forward_train: norm=%r is not served (None, or \"batch\" for batch statistics)" % (norm,))
         if not x.is_cuda:
             raise NoTorchCompute("forward_train runs on a HIP device only; x is a %s tensor" % x.device)
         for i, m in enumerate(mods):
@@ -396,7 +427,18 @@ class SeqdistModel(Module):
                     b = None if b is None else torch.nn.functional.pad(b, (0, pad_in))
                 if tm and not isinstance(nxt, bnn.LSTM):
                     raise ValueError("forward_train: %s stores time-major for a layer that is no LSTM" % name)
-                h = train_ops.conv1d(h, w, b, c.stride[0], c.padding[0], m.activation, clamp, tm)
+                if m.norm is None:
+                    h = train_ops.conv1d(h, w, b, c.stride[0], c.padding[0], m.activation, clamp, tm)
+                else:                   # z = conv(x) as it is, then norm, activation, clamp and the store in one layer
+                    bn = m.norm.bn
+                    gamma, beta = bn.weight, bn.bias
+                    if pad_in and bn.affine:
+                        gamma, beta = torch.nn.functional.pad(gamma, (0, pad_in)), torch.nn.functional.pad(beta, (0, pad_in))
+                    h = train_ops.conv1d(h, w, b, c.stride[0], c.padding[0], None, None, False)
+                    h = train_ops.batchnorm(h, gamma, beta, bn.running_mean, bn.running_var, bn.momentum, bn.eps, m.activation, clamp, tm,
+                                            channels=c.out_channels)
+                    if bn.num_batches_tracked is not None:
+                        bn.num_batches_tracked.add_(1)
                 layout = "tnc" if tm else "nlc"
                 i += 2 if clamp is not None else 1
             elif isinstance(m, bnn.LSTM):

@@ -446,6 +446,21 @@ extern "C" int bh_gated_linear_train_backward(const void* x, const float* w, con
                                               void* workspace, size_t workspace_bytes, void* stream) {
     return bh_k_gated_linear_train_backward(x, w, dh, M, D, F, dx, dw, workspace, workspace_bytes, (hipStream_t)stream);
 }
+extern "C" size_t bh_batchnorm_train_workspace(int N, int L, int C) { return bh_k_batchnorm_train_workspace(N, L, C); }
+extern "C" int bh_batchnorm_train_forward(const void* z, const float* gamma, const float* beta, float* running_mean, float* running_var, int N,
+                                          int L, int C, int C_param, float eps, float momentum, int act, float clamp_lo, float clamp_hi,
+                                          long os_n, long os_t, void* y, float* mean, float* rstd, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+    return bh_k_batchnorm_train_forward(z, gamma, beta, running_mean, running_var, N, L, C, C_param, eps, momentum, act, clamp_lo, clamp_hi,
+                                        os_n, os_t, y, mean, rstd, workspace, workspace_bytes, (hipStream_t)stream);
+}
+extern "C" int bh_batchnorm_train_backward(const void* z, const float* gamma, const float* beta, const float* mean, const float* rstd,
+                                           const void* y, const void* dy, int N, int L, int C, int C_param, int act, float clamp_lo,
+                                           float clamp_hi, long os_n, long os_t, void* dz, float* dgamma, float* dbeta, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    return bh_k_batchnorm_train_backward(z, gamma, beta, mean, rstd, y, dy, N, L, C, C_param, act, clamp_lo, clamp_hi, os_n, os_t, dz, dgamma,
+                                         dbeta, workspace, workspace_bytes, (hipStream_t)stream);
+}
 extern "C" size_t bh_sw_workspace(int n, int max_seq, int max_ref) { return bh_k_sw_workspace(n, max_seq, max_ref); }
 extern "C" int bh_sw_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, const void* refs, long ref_stride,
                            const int32_t* ref_lengths, int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace,

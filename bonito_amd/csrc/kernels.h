@@ -175,6 +175,13 @@ int bh_k_linear_train_backward(const void* x, const float* w, const void* y, con
                                size_t workspace_bytes, hipStream_t stream);
 
 // transformer_train.hip (what a transformer encoder layer adds to training: the backward of bh_k_rmsnorm_residual, and fc1 + SwiGLU)
+size_t bh_k_batchnorm_train_workspace(int N, int L, int C);
+int bh_k_batchnorm_train_forward(const void* z, const float* gamma, const float* beta, float* running_mean, float* running_var, int N, int L,
+                                 int C, int C_param, float eps, float momentum, int act, float clamp_lo, float clamp_hi, long os_n, long os_t,
+                                 void* y, float* mean, float* rstd, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int bh_k_batchnorm_train_backward(const void* z, const float* gamma, const float* beta, const float* mean, const float* rstd, const void* y,
+                                  const void* dy, int N, int L, int C, int C_param, int act, float clamp_lo, float clamp_hi, long os_n, long os_t,
+                                  void* dz, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, hipStream_t stream);
 size_t bh_k_rmsnorm_train_workspace(long M, int D);
 int bh_k_rmsnorm_train_backward(const void* a, const void* x, const float* w, const void* dy, long M, int D, float alpha, float eps, void* da,
                                 void* dx, float* dw, void* workspace, size_t workspace_bytes, hipStream_t stream);

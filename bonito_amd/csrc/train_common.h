@@ -18,6 +18,50 @@ inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 // grid of a grid-stride conversion kernel of 256 threads over n elements
 inline int cvt_grid(long n) { return (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024); }
 
+// ---- activation, its derivative and the clamp's mask ------------------------------------------------------------------------------------
+inline bool act_ok(int act) { return act == ACT_NONE || act == ACT_SWISH || act == ACT_TANH || act == ACT_RELU; }
+inline bool is_clamped(float lo, float hi) { return !(lo == -INFINITY && hi == INFINITY); }
+__device__ __forceinline__ float act_grad(float z, int act) {
+    switch (act) {
+        case ACT_SWISH: { const float s = sigmoidf_(z); return s * (1.0f + z * (1.0f - s)); }
+        case ACT_TANH: { const float t = tanhf_(z); return 1.0f - t * t; }
+        case ACT_RELU: return z > 0.0f ? 1.0f : 0.0f;
+        default: return 1.0f;
+    }
+}
+
+// One column of partial sums [blocks][C], added in block order by a workgroup of BS_COLS x BS_RUNS threads (thread = column
+// threadIdx.x % BS_COLS, run threadIdx.x / BS_COLS): the blocks are cut into BS_RUNS runs of consecutive blocks (a function of their
+// number alone), a thread adds one run of its column in block order - eight loads in flight, the additions in order - and the runs are
+// added in run order. -> the sum, in the threads of run 0 (the others get their run's sum). run: LDS, free again after the call.
+constexpr int BS_COLS = 32, BS_RUNS = 8;
+__device__ __forceinline__ float block_order_sum(const float* __restrict__ part, long blocks, int C, int c, float (*run)[BS_COLS]) {
+    const int col = threadIdx.x % BS_COLS, g = threadIdx.x / BS_COLS;
+    const long per = (blocks + BS_RUNS - 1) / BS_RUNS;
+    const long b_lo = g * per, b_hi = b_lo + per < blocks ? b_lo + per : blocks;
+    float s = 0.0f;
+    if (c < C) {
+        long b = b_lo;
+        for (; b + 8 <= b_hi; b += 8) {
+            float t[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) t[i] = part[(b + i) * C + c];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) s += t[i];
+        }
+        for (; b < b_hi; ++b) s += part[b * C + c];
+    }
+    __syncthreads();
+    run[g][col] = s;
+    __syncthreads();
+    if (g == 0) {
+        s = run[0][col];
+#pragma unroll
+        for (int q = 1; q < BS_RUNS; ++q) s += run[q][col];
+    }
+    return s;
+}
+
 // ---- the reduction over rows: dw = A^T B, db = column sums of A ------------------------------------------------------------------------
 constexpr int RT_TILE = 64;            // atb kernel: 64 x 64 outputs per workgroup
 constexpr int RT_KSTEP = 32;           // rows of M per MFMA

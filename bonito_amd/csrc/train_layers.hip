@@ -54,16 +54,6 @@ __global__ __launch_bounds__(256) void round_kernel(const float* __restrict__ in
         out[e] = in ? (float)(half_t)in[e] : 0.0f;
 }
 
-// ---- activation derivative and the clamp's mask ---------------------------------------------------------------------------------------
-__device__ __forceinline__ float act_grad(float z, int act) {
-    switch (act) {
-        case ACT_SWISH: { const float s = sigmoidf_(z); return s * (1.0f + z * (1.0f - s)); }
-        case ACT_TANH: { const float t = tanhf_(z); return 1.0f - t * t; }
-        case ACT_RELU: return z > 0.0f ? 1.0f : 0.0f;
-        default: return 1.0f;
-    }
-}
-
 // ---- convolution: dz ----------------------------------------------------------------------------------------------------------------
 struct ConvBwdArgs {
     const half_t* x;        // [N][Lin][Cin]
@@ -288,9 +278,6 @@ __global__ __launch_bounds__(256) void linear_dz_kernel(LinearDzArgs p) {
         *(half8_t*)(p.dz + m * p.C + c) = o;
     }
 }
-
-inline bool act_ok(int act) { return act == ACT_NONE || act == ACT_SWISH || act == ACT_TANH || act == ACT_RELU; }
-inline bool is_clamped(float lo, float hi) { return !(lo == -INFINITY && hi == INFINITY); }
 
 }  // namespace
 }  // namespace bh

@@ -134,35 +134,13 @@ __global__ __launch_bounds__(64 * NORM_WAVES) void rmsnorm_bwd_kernel(NormBwdArg
     }
 }
 
-// dw[c] = the blocks' partial sums in block order: the blocks are cut into DW_RUNS runs of consecutive blocks (a function of their
-// number alone), a thread adds one run of one column in block order - eight loads in flight, the additions in order - and the runs are
-// added in run order. (One thread per column over all blocks is a chain of as many dependent loads: DESIGN.md section 6 has both times.)
-constexpr int DW_COLS = 32, DW_RUNS = 8;
-__global__ __launch_bounds__(DW_COLS * DW_RUNS) void rmsnorm_dw_kernel(const float* __restrict__ part, long blocks, int D, float* __restrict__ dw) {
-    __shared__ float run[DW_RUNS][DW_COLS];
-    const int col = threadIdx.x % DW_COLS, g = threadIdx.x / DW_COLS;
-    const int c = blockIdx.x * DW_COLS + col;
-    const long per = (blocks + DW_RUNS - 1) / DW_RUNS;
-    const long b_lo = g * per, b_hi = b_lo + per < blocks ? b_lo + per : blocks;
-    float s = 0.0f;
-    if (c < D) {
-        long b = b_lo;
-        for (; b + 8 <= b_hi; b += 8) {
-            float t[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) t[i] = part[(b + i) * D + c];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) s += t[i];
-        }
-        for (; b < b_hi; ++b) s += part[b * D + c];
-    }
-    run[g][col] = s;
-    __syncthreads();
-    if (g != 0 || c >= D) return;
-    float t = run[0][col];
-#pragma unroll
-    for (int q = 1; q < DW_RUNS; ++q) t += run[q][col];
-    dw[c] = t;
+// dw[c] = the blocks' partial sums in block order (block_order_sum, train_common.h; one thread per column over all blocks is a chain of
+// as many dependent loads: DESIGN.md section 6 has both times)
+__global__ __launch_bounds__(BS_COLS * BS_RUNS) void rmsnorm_dw_kernel(const float* __restrict__ part, long blocks, int D, float* __restrict__ dw) {
+    __shared__ float run[BS_RUNS][BS_COLS];
+    const int c = blockIdx.x * BS_COLS + threadIdx.x % BS_COLS;
+    const float s = block_order_sum(part, blocks, D, c, run);
+    if (threadIdx.x < BS_COLS && c < D) dw[c] = s;
 }
 
 // ---- gated layer --------------------------------------------------------------------------------------------------------------------------
@@ -227,7 +205,7 @@ int bh_k_rmsnorm_train_backward(const void* a, const void* x, const float* w, co
     NormBwdArgs p{(const half_t*)a, (const half_t*)x, w, (const half_t*)dy, (half_t*)da, (half_t*)dx, (float*)workspace, M, norm_block_rows(M),
                   D, alpha, eps};
     hipLaunchKernelGGL(rmsnorm_bwd_kernel, dim3((unsigned)blocks), dim3(64 * NORM_WAVES), 0, stream, p);
-    hipLaunchKernelGGL(rmsnorm_dw_kernel, dim3((D + DW_COLS - 1) / DW_COLS), dim3(DW_COLS * DW_RUNS), 0, stream, (const float*)workspace, blocks,
+    hipLaunchKernelGGL(rmsnorm_dw_kernel, dim3((D + BS_COLS - 1) / BS_COLS), dim3(BS_COLS * BS_RUNS), 0, stream, (const float*)workspace, blocks,
                        D, dw);
     BH_CHECK_HIP(hipGetLastError());
     return 0;

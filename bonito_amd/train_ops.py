@@ -1,8 +1,9 @@
 """
 The convolution and the linear / CRF-head layer for training on the device: forward on the rounded master weights, backward, and their
-autograd (csrc/train_layers.hip; the arithmetic is stated in include/bonito_hip.h under bh_conv1d_train_forward) - and the two layers a
+autograd (csrc/train_layers.hip; the arithmetic is stated in include/bonito_hip.h under bh_conv1d_train_forward) - the two layers a
 transformer encoder layer adds, the DeepNorm residual RMSNorm and the gated input layer of the MLP (csrc/transformer_train.hip; under
-bh_rmsnorm_train_backward).
+bh_rmsnorm_train_backward) - and the batch-statistics BatchNorm behind a convolution (csrc/batchnorm_train.hip; under
+bh_batchnorm_train_forward).
 
     y = conv1d_forward(x, weight, bias, stride, padding, activation, clamp, time_major)     # x fp16 [N][Lin][Cin] ([N][Lin] for Cin == 1)
     dx, dw, db = conv1d_backward(x, weight, bias, y, dy, stride, padding, activation, clamp, time_major)
@@ -16,6 +17,9 @@ bh_rmsnorm_train_backward).
     h = gated_linear_forward(x, weight)                                                     # x fp16 [...][D], weight [2F][D] -> [...][F]
     dx, dw = gated_linear_backward(x, weight, dh)
     h = gated_linear(x, weight)                                                             # differentiable
+    y, mean, rstd = batchnorm_forward(z, weight, bias, running_mean, running_var, momentum, eps, activation, clamp, time_major, channels)
+    dz, dw, db = batchnorm_backward(z, weight, bias, mean, rstd, y, dy, activation, clamp, time_major, channels)
+    y = batchnorm(z, weight, bias, running_mean, running_var, momentum, eps, activation, clamp, time_major, channels)    # differentiable
 
 Activations are channel-minor: a convolution returns [N][Lout][Cout], or time-major [Lout][N][Cout] (the permute in front of the LSTM
 stack, folded into the store). weight and bias are the fp32 master tensors in torch's layout ([Cout][Cin][K], [C][K]).
@@ -32,7 +36,8 @@ from bonito_amd._train import HalfLayer, HalfLayer2, devices as _devices, half a
 
 __all__ = ["conv1d_forward", "conv1d_backward", "conv1d", "linear_forward", "linear_backward", "linear", "conv_out_len",
            "rmsnorm_residual_forward", "rmsnorm_residual_backward", "rmsnorm_residual",
-           "gated_linear_forward", "gated_linear_backward", "gated_linear"]
+           "gated_linear_forward", "gated_linear_backward", "gated_linear",
+           "batchnorm_forward", "batchnorm_backward", "batchnorm"]
 
 _INF = float("inf")
 
@@ -409,3 +414,135 @@ def gated_linear(x, weight):
         return gated_linear_backward(*kept, dh.contiguous(), need_dx=need[0])
 
     return HalfLayer.apply(forward, backward, x, weight)
+
+
+# ---- batch-statistics BatchNorm behind a convolution ------------------------------------------------------------------------------------------
+def _bn_check(z, weight, bias, activation, clamp, channels, what, dtypes=(torch.float16,), devices=True):
+    named = [("z", z)] + [(n, t) for n, t in (("weight", weight), ("bias", bias)) if t is not None]
+    _tensors(named, what)
+    if z.dtype not in dtypes:
+        raise ValueError("%s: z must be %s, got %s" % (what, _dtype_names(dtypes), z.dtype))
+    if z.dim() != 3 or z.numel() == 0:
+        raise ValueError("%s: z must be [N][L][C], got %s" % (what, tuple(z.shape)))
+    N, L, C = (int(v) for v in z.shape)
+    if (weight is None) != (bias is None):
+        raise ValueError("%s: weight and bias come together or not at all (affine)" % what)
+    if weight is not None:
+        _master(weight, (C,), "weight", what)
+        _master(bias, (C,), "bias", what)
+    act = _act(activation, (None, "none", "swish", "tanh", "relu"), what)
+    lo, hi = _clamp(clamp, what)
+    if C % 8 != 0 or C > 2048:
+        raise ValueError("%s: C must be a multiple of 8 up to 2048, got %d" % (what, C))
+    Cp = C if channels is None else int(channels)
+    if not 1 <= Cp <= C:
+        raise ValueError("%s: channels must be in 1..%d, got %d" % (what, C, Cp))
+    if N * L < 2:
+        raise ValueError("%s: more than one value per channel is needed, got z %s" % (what, tuple(z.shape)))
+    if devices:
+        _devices(named, what)
+    return N, L, C, Cp, act, lo, hi
+
+
+def _bn_strides(N, L, C, time_major):
+    return (C, N * C) if time_major else (L * C, C)
+
+
+def _bn_workspace(N, L, C, what):
+    nbytes = _lib.lib().bh_batchnorm_train_workspace(N, L, C)
+    if nbytes == 0:
+        raise ValueError("%s: shape N=%d L=%d C=%d is not supported" % (what, N, L, C))
+    return nbytes
+
+
+def batchnorm_forward(z, weight, bias, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, activation=None, clamp=None,
+                      time_major=False, channels=None):
+    """-> (y fp16 [N][L][C], or [L][N][C] with time_major; mean fp32 [C]; rstd fp32 [C]) of torch.nn.BatchNorm1d in training mode on
+    z fp16 [N][L][C] (channel-minor), with the activation and the clamp: y = clamp(act(weight (z - mean) rstd + bias)). weight and bias
+    are fp32 [C], or both None (affine=False). running_mean / running_var (fp32 [channels], or both None) are UPDATED IN PLACE with
+    `momentum` and the unbiased variance, as torch does. channels < C: the channels behind are zero padding - y is 0 there, mean and rstd
+    stay 0, and weight and bias are not read there."""
+    what = "batchnorm_forward"
+    N, L, C, Cp, act, lo, hi = _bn_check(z, weight, bias, activation, clamp, channels, what, devices=False)
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("%s: running_mean and running_var come together or not at all (track_running_stats)" % what)
+    named = [("z", z)] + [(n, t) for n, t in (("weight", weight), ("bias", bias), ("running_mean", running_mean),
+                                              ("running_var", running_var)) if t is not None]
+    _tensors(named, what)
+    if running_mean is not None:
+        for name, t in named[-2:]:
+            _master(t, (Cp,), name, what)
+            if not t.is_contiguous():
+                raise ValueError("%s: %s must be contiguous (it is updated in place)" % (what, name))
+        if momentum is None:
+            raise ValueError("%s: momentum=None (the cumulative average) is not served" % what)
+    momentum, eps = 0.0 if momentum is None else float(momentum), float(eps)
+    if not 0.0 <= momentum <= 1.0:
+        raise ValueError("%s: momentum must be in 0..1, got %r" % (what, momentum))
+    if not (math.isfinite(eps) and eps > 0.0):
+        raise ValueError("%s: eps must be finite and > 0, got %r" % (what, eps))
+    _devices(named, what)
+    z = z.contiguous()
+    weight, bias = (None, None) if weight is None else (weight.detach().contiguous(), bias.detach().contiguous())
+    nbytes = _bn_workspace(N, L, C, what)
+    os_n, os_t = _bn_strides(N, L, C, time_major)
+    with torch.cuda.device(z.device):
+        y = torch.empty((L, N, C) if time_major else (N, L, C), dtype=torch.float16, device=z.device)
+        mean = torch.zeros(C, dtype=torch.float32, device=z.device)
+        rstd = torch.zeros(C, dtype=torch.float32, device=z.device)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=z.device)
+        _lib.check(_lib.lib().bh_batchnorm_train_forward(_lib.ptr(z), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(running_mean),
+                                                         _lib.ptr(running_var), N, L, C, Cp, eps, momentum, act, lo, hi, os_n, os_t, _lib.ptr(y),
+                                                         _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(ws), nbytes, _lib.stream_ptr(z.device)),
+                   "bh_batchnorm_train_forward")
+    return y, mean, rstd
+
+
+def batchnorm_backward(z, weight, bias, mean, rstd, y, dy, activation=None, clamp=None, time_major=False, channels=None, need_dw=True,
+                       need_db=True):
+    """-> (dz fp16 [N][L][C], dw fp32 [C] or None, db fp32 [C] or None) from what batchnorm_forward returned and the upstream gradient
+    dy (fp16, in y's layout). Padded channels get zeros."""
+    what = "batchnorm_backward"
+    N, L, C, Cp, act, lo, hi = _bn_check(z, weight, bias, activation, clamp, channels, what, devices=False)
+    _tensors([("mean", mean), ("rstd", rstd), ("y", y), ("dy", dy)], what)
+    _master(mean, (C,), "mean", what)
+    _master(rstd, (C,), "rstd", what)
+    shape = (L, N, C) if time_major else (N, L, C)
+    _half(y, shape, "y", what)
+    _half(dy, shape, "dy", what)
+    _devices([("z", z), ("mean", mean), ("rstd", rstd), ("y", y), ("dy", dy)]
+             + ([("weight", weight), ("bias", bias)] if weight is not None else []), what)
+    z, mean, rstd, y, dy = z.contiguous(), mean.contiguous(), rstd.contiguous(), y.contiguous(), dy.contiguous()
+    weight, bias = (None, None) if weight is None else (weight.detach().contiguous(), bias.detach().contiguous())
+    nbytes = _bn_workspace(N, L, C, what)
+    os_n, os_t = _bn_strides(N, L, C, time_major)
+    with torch.cuda.device(z.device):
+        dz = torch.empty((N, L, C), dtype=torch.float16, device=z.device)
+        dw = torch.zeros(C, dtype=torch.float32, device=z.device) if need_dw else None
+        db = torch.zeros(C, dtype=torch.float32, device=z.device) if need_db else None
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=z.device)
+        _lib.check(_lib.lib().bh_batchnorm_train_backward(_lib.ptr(z), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(mean), _lib.ptr(rstd),
+                                                          _lib.ptr(y), _lib.ptr(dy), N, L, C, Cp, act, lo, hi, os_n, os_t, _lib.ptr(dz),
+                                                          _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), nbytes, _lib.stream_ptr(z.device)),
+                   "bh_batchnorm_train_backward")
+    return dz, dw, db
+
+
+def batchnorm(z, weight, bias, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, activation=None, clamp=None, time_major=False,
+              channels=None):
+    """y fp16 of batch-statistics BatchNorm with its activation and clamp, differentiable with respect to z (fp16 or fp32; fp32 is cast
+    to fp16 and its gradient comes back as fp32), weight and bias, each where requires_grad is set. The forward - and only the forward -
+    updates running_mean / running_var in place, under torch.no_grad() too, as torch.nn.BatchNorm1d in training mode does."""
+    _bn_check(z, weight, bias, activation, clamp, channels, "batchnorm", dtypes=_BOTH)
+    args = (activation, clamp, bool(time_major), channels)
+
+    def forward(z16, weight, bias):
+        z16 = z16.contiguous()
+        y, mean, rstd = batchnorm_forward(z16, weight, bias, running_mean, running_var, momentum, eps, *args)
+        return y, (z16, weight, bias, mean, rstd, y)
+
+    def backward(kept, dy, need):
+        affine = kept[1] is not None
+        return batchnorm_backward(*kept, dy.contiguous(), *args, need_dw=affine and need[1], need_db=affine and need[2])
+
+    return HalfLayer.apply(forward, backward, z, weight, bias)

@@ -11,7 +11,9 @@ of kernel launch. The host reads the step's scalars (``optimizer.last()``) once 
 
 The inference engine snapshots the weights when it is built and the update kernel changes them behind the module's back, so the engine
 is dropped before every validation pass (and only there: forward_train does not use it). The model is any SeqdistModel whose
-forward_train serves it: the LSTM family and the transformer family (convolutions without a norm).
+forward_train serves it: the LSTM family and the transformer family. ``Trainer(norm="batch")`` trains convolutions that carry a
+BatchNorm with batch statistics (forward_train's keyword): every sub-batch of a step rewrites the running statistics, as in the
+reference, and the validation pass, which drops the engine, folds the new ones.
 """
 import math
 import os
@@ -84,7 +86,7 @@ class _FixedClip:
 
 class Trainer:
     def __init__(self, model, device, train_loader, valid_loader, criterion=None, use_amp=True, lr_scheduler_fn=None, restore_optim=False,
-                 save_optim_every=10, grad_accum_split=1, quantile_grad_clip=False, chunks_per_epoch=None, batch_size=None):
+                 save_optim_every=10, grad_accum_split=1, quantile_grad_clip=False, chunks_per_epoch=None, batch_size=None, norm=None):
         if not use_amp:
             raise ValueError("Trainer: use_amp=False is not served: forward_train computes in fp16 and there is no fp32 path")
         if not hasattr(model, "forward_train"):
@@ -98,6 +100,7 @@ class Trainer:
         self.optimizer = None
         self.clip_grad = ClipGrad() if quantile_grad_clip else _FixedClip(2.0)
         self.batch_size, self.chunks_per_epoch = batch_size, chunks_per_epoch
+        self.norm_kwargs = {} if norm is None else {"norm": norm}       # forward_train's keyword, passed only where it was asked for
         self.steps_per_epoch = chunks_per_epoch // batch_size
 
     def train_one_step(self, batch):
@@ -106,7 +109,7 @@ class Trainer:
         self.optimizer.zero_grad(set_to_none=True)
         losses = None
         for data, targets, lengths in zip(*(t.chunk(self.grad_accum_split, dim=0) for t in batch)):
-            scores = self.model.forward_train(data.to(torch.float16).to(self.device))
+            scores = self.model.forward_train(data.to(torch.float16).to(self.device), **self.norm_kwargs)
             losses_ = self.criterion(scores, targets, lengths)
             if not isinstance(losses_, dict):
                 losses_ = {"loss": losses_}

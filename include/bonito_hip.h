@@ -30,6 +30,8 @@
  *        RotaryEmbedding + flash_attn_qkvpacked_func(qkv, window_size=) and their autograd          bonito/transformer/model.py:58-75
  *   bh_rmsnorm_train_backward / bh_gated_linear_train_forward / bh_gated_linear_train_backward
  *        the autograd of RMSNorm(attn / ff + deepnorm_alpha * x) and of GatedMlp's fc1 + SwiGLU         bonito/transformer/model.py:83-133
+ *   bh_batchnorm_train_forward / bh_batchnorm_train_backward
+ *        torch.nn.BatchNorm1d in training mode behind a Convolution (activation(norm(conv(x)))) and its autograd   bonito/nn.py:222-241
  *   bh_sw_align
  *        parasail.sw_trace_striped_32(seq, ref, 8, 4, parasail.dnafull) behind evaluate's align() and util.accuracy
  *                                                                              bonito/cli/evaluate.py:37-67, bonito/util.py:346-368
@@ -460,6 +462,37 @@ int bh_gated_linear_train_forward(const void* x, const float* w, long M, int D, 
                                   void* stream);
 int bh_gated_linear_train_backward(const void* x, const float* w, const void* dh, long M, int D, int F, void* dx, float* dw,
                                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Batch-statistics BatchNorm for training (csrc/batchnorm_train.hip): what follows conv(x) in a normalised convolution ------------
+ * torch.nn.BatchNorm1d in training mode with the activation and the clamp of the convolution (bonito/nn.py Convolution.forward:
+ * activation(norm(conv(x)))); bh_conv1d_train_forward with act none and no clamp yields z. M = N L rows per channel:
+ *     mean_c = (1/M) sum z      var_c = (1/M) sum (z - mean_c)^2 (biased)      rstd_c = 1 / sqrt(var_c + eps)
+ *     xh = (z - mean_c) rstd_c      u = gamma_c xh + beta_c      y = fp16(clamp(act(u), lo, hi))
+ *   z fp16 [N][L][C] channel-minor; y written at n * os_n + t * os_t + c (os_n = C, os_t = N * C stores time-major [L][N][C]).
+ *   gamma, beta fp32 [C_param], used unrounded; both NULL = affine off (1 and 0). mean and rstd: fp32 [C_param] outputs, the
+ *   backward's inputs. running_mean / running_var fp32 [C_param], updated in place by the finishing kernel (no host synchronisation):
+ *     rm <- (1 - momentum) rm + momentum mean      rv <- (1 - momentum) rv + momentum var M / (M - 1);     both NULL = not tracked.
+ *   C_param <= C counts the real channels: channels c >= C_param (zero padding up to a multiple of 8) get y = 0 and dz = 0 exactly, and
+ *   no statistic, parameter or gradient is read or written for them.
+ *   Every sum is fp32. A workgroup sums a block of rows (the block a function of M alone), a thread every k-th row of it in row order;
+ *   the threads of a workgroup are added in a fixed order through LDS and the blocks in block order by a second launch - no
+ *   floating-point atomics, two calls give equal bytes. The variance is the CENTRED sum of a second pass over z, never E[z^2] - E[z]^2.
+ *   backward, dy in the layout of y, dz fp16 [N][L][C] in z's row order:
+ *     du = dy [lo < y < hi] act'(u)   (u recomputed in fp32 from z, mean, rstd; the mask from the STORED y, strictly inside)
+ *     dbeta_c = sum du      dgamma_c = sum du xh      dz = fp16(gamma_c rstd_c (du - dbeta_c / M - xh dgamma_c / M))
+ *   dgamma and dbeta fp32 [C_param], OVERWRITTEN; either may be NULL = not written.
+ *   Supported: N L >= 2 (more than one value per channel), C a multiple of 8 up to 2048, 1 <= C_param <= C, act none / swish / tanh /
+ *   relu, os_n and os_t multiples of 8, eps > 0, 0 <= momentum <= 1; N L C may pass 2^31 elements (64-bit offsets throughout).
+ * z, y, dy, dz and the workspace are 16-byte aligned device pointers. workspace (bh_batchnorm_train_workspace, one size for forward and
+ * backward; 0 = unsupported shape): the caller's. Anything unsupported returns nonzero with bh_last_error() set, launches nothing and
+ * leaves every output untouched. Stream-ordered; nothing is allocated and nothing synchronises inside. */
+size_t bh_batchnorm_train_workspace(int N, int L, int C);
+int bh_batchnorm_train_forward(const void* z, const float* gamma, const float* beta, float* running_mean, float* running_var, int N, int L,
+                               int C, int C_param, float eps, float momentum, int act, float clamp_lo, float clamp_hi, long os_n, long os_t,
+                               void* y, float* mean, float* rstd, void* workspace, size_t workspace_bytes, void* stream);
+int bh_batchnorm_train_backward(const void* z, const float* gamma, const float* beta, const float* mean, const float* rstd, const void* y,
+                                const void* dy, int N, int L, int C, int C_param, int act, float clamp_lo, float clamp_hi, long os_n,
+                                long os_t, void* dz, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Smith-Waterman local alignment with affine gaps and a traceback (csrc/align.hip) ----------------------------------
  * n pairs of a called sequence `seq` (the query, index i) and a known sequence `ref` (index j). seqs / refs: DEVICE int8 planes

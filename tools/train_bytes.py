@@ -15,6 +15,9 @@ tests/train_layers_ref.py; fixed seeds).
     norm (M, D)                 the DeepNorm residual RMSNorm (tests/transformer_train_ref.py): a tail of rows, a second vector per lane, more
                                 than one dw block; out, da, dx, dw
     gated (M, D, F)             fc1 + SwiGLU: h, dx, dw
+    batchnorm (N, L, C, pad)    batch-statistics BatchNorm behind a convolution (tests/batchnorm_train_ref.py), swish: one block of rows and
+                                several with a short last one, 65 vectors per row, zero-padded channels, clamp on and off, the time-major
+                                store; y, mean, rstd, running_mean, running_var, dz, dgamma, dbeta
 
 Prints one JSON line {case: {tensor: sha256}}."""
 import argparse
@@ -41,6 +44,7 @@ LINEAR_ROWS = (1, 3, 4)
 NORM_CASES = ((5, 64), (257, 520), (130, 1024))          # (M, D)
 NORM_ALPHA = 2.4494897
 GATED_CASES = ((17, 64, 72), (1030, 128, 256), (33, 512, 2048))      # (M, D, F)
+BATCHNORM_CASES = ((3, 5, 16, 4), (2, 257, 64, 0), (5, 1000, 520, 0))       # (N, L, C, zero-padded channels)
 
 
 def sha(t):
@@ -95,6 +99,19 @@ def main():
             h = train_ops.gated_linear_forward(c["x"], c["w"])
             dx, dw = train_ops.gated_linear_backward(c["x"], c["w"], c["dh"])
             res["gated M=%d D=%d F=%d" % (M, D, F)] = {"h": sha(h), "dx": sha(dx), "dw": sha(dw)}
+    if hasattr(train_ops, "batchnorm_backward"):               # new keys: a checkout from before the layer has none of them
+        import batchnorm_train_ref as bn
+        for N, L, C, pad in BATCHNORM_CASES:
+            c = {k: v.to(dev) for k, v in bn.bn_case(N, L, C - pad).items()}
+            z, dy, gamma, beta = (torch.nn.functional.pad(c[k], (0, pad)) for k in ("z", "dy", "gamma", "beta"))
+            for clamp, time_major in ((None, False), (bn.CLAMP, True)):
+                rm, rv = c["running_mean"].clone(), c["running_var"].clone()
+                y, mean, rstd = train_ops.batchnorm_forward(z, gamma, beta, rm, rv, bn.MOMENTUM, bn.EPS, "swish", clamp, time_major, C - pad)
+                dyd = dy.permute(1, 0, 2).contiguous() if time_major else dy
+                dz, dgamma, dbeta = train_ops.batchnorm_backward(z, gamma, beta, mean, rstd, y, dyd, "swish", clamp, time_major, C - pad)
+                res["batchnorm N=%d L=%d C=%d-%d %s" % (N, L, C, pad, "clamped tm" if clamp else "free")] = {
+                    "y": sha(y), "mean": sha(mean), "rstd": sha(rstd), "running_mean": sha(rm), "running_var": sha(rv), "dz": sha(dz),
+                    "dgamma": sha(dgamma), "dbeta": sha(dbeta)}
     torch.cuda.synchronize()
     line = json.dumps(res, sort_keys=True)
     print(line)
