@@ -97,6 +97,12 @@ SIGNATURES = {
     "bh_batchnorm_train_workspace": (_sz, [_i, _i, _i]),
     "bh_batchnorm_train_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _f, _f, _l, _l, _vp, _vp, _vp, _vp, _sz, _vp]),
     "bh_batchnorm_train_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _l, _l, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "bh_dwconv1d_train_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "bh_dwconv1d_train_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "bh_residual_act_train_forward": (_i, [_vp, _vp, _l, _i, _i, C.c_uint32, _f, C.c_uint64, C.c_uint64, _vp, _vp]),
+    "bh_residual_act_train_backward": (_i, [_vp, _vp, _vp, _l, _i, _i, C.c_uint32, _f, C.c_uint64, C.c_uint64, _vp, _vp]),
+    "bh_ctc_head_train_workspace": (_sz, [_l, _i, _i]),
+    "bh_ctc_head_train_backward": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "bh_sw_workspace": (_sz, [_i, _i, _i]),
     "bh_sw_align": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _l, _vp, _vp]),
     "bh_sg_align": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _l, _vp, _vp]),

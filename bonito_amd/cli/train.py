@@ -1,5 +1,5 @@
 """
-``python -m bonito_amd train``: train a CRF model of the LSTM or the transformer family on labelled chunks (chunks.npy, references.npy, reference_lengths.npy,
+``python -m bonito_amd train``: train a CRF model of the LSTM or the transformer family, or with --norm batch a QuartzNet CTC model, on labelled chunks (chunks.npy, references.npy, reference_lengths.npy,
 what ``basecaller --save-ctc`` writes) on one HIP device -- the arguments of the reference's bonito/cli/train.py.
 
 The training directory receives config.toml (the model's config, the arguments under [training]), per epoch weights_N.tar,
@@ -60,7 +60,7 @@ def main(args):
     else:
         model = load_symbol(config, "Model")(config)
     if not hasattr(model, "forward_train"):
-        _refuse("%s.%s has no forward_train: the LSTM and transformer families of CRF models train on the device" % (type(model).__module__, type(model).__name__))
+        _refuse("%s.%s has no forward_train: the LSTM and transformer families of CRF models and the QuartzNet CTC models train on the device" % (type(model).__module__, type(model).__name__))
     model = model.to(device)
 
     print("[loading data]")
@@ -108,7 +108,7 @@ def argparser():
     parser = ArgumentParser(
         formatter_class=ArgumentDefaultsHelpFormatter,
         add_help=False,
-        description="Train a CRF model of the LSTM or the transformer family on labelled chunks on one HIP device; the training directory receives config.toml, "
+        description="Train a CRF model of the LSTM or the transformer family, or with --norm batch a QuartzNet CTC model, on labelled chunks on one HIP device; the training directory receives config.toml, "
                     "weights_N.tar, optim_N.tar, losses_N.csv and training.csv.",
     )
     parser.add_argument("training_directory")
@@ -136,5 +136,5 @@ def argparser():
     parser.add_argument("--num-workers", default=4, type=int)
     parser.add_argument("--norm", default=None, choices=["batch"],
                         help="how a convolution's BatchNorm trains: batch = with batch statistics, updating the running ones; "
-                             "without the option a model with norms is refused")
+                             "without the option a model with norms (every QuartzNet CTC model among them) is refused")
     return parser

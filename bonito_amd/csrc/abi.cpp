@@ -461,6 +461,25 @@ extern "C" int bh_batchnorm_train_backward(const void* z, const float* gamma, co
     return bh_k_batchnorm_train_backward(z, gamma, beta, mean, rstd, y, dy, N, L, C, C_param, act, clamp_lo, clamp_hi, os_n, os_t, dz, dgamma,
                                          dbeta, workspace, workspace_bytes, (hipStream_t)stream);
 }
+extern "C" size_t bh_dwconv1d_train_workspace(int N, int L, int C, int K, int pad) { return bh_k_dwconv_train_workspace(N, L, C, K, pad); }
+extern "C" int bh_dwconv1d_train_backward(const void* x, const float* w, const void* dy, int N, int L, int C, int K, int pad, void* dx,
+                                          float* dw, void* workspace, size_t workspace_bytes, void* stream) {
+    return bh_k_dwconv_train_backward(x, w, dy, N, L, C, K, pad, dx, dw, workspace, workspace_bytes, (hipStream_t)stream);
+}
+extern "C" int bh_residual_act_train_forward(const void* a, const void* b, long M, int C, int act, unsigned int p_threshold, float inv_keep,
+                                             unsigned long long seed, unsigned long long stream_id, void* y, void* stream) {
+    return bh_k_residual_act_train_forward(a, b, M, C, act, p_threshold, inv_keep, seed, stream_id, y, (hipStream_t)stream);
+}
+extern "C" int bh_residual_act_train_backward(const void* a, const void* b, const void* dy, long M, int C, int act, unsigned int p_threshold,
+                                              float inv_keep, unsigned long long seed, unsigned long long stream_id, void* da,
+                                              void* stream) {
+    return bh_k_residual_act_train_backward(a, b, dy, M, C, act, p_threshold, inv_keep, seed, stream_id, da, (hipStream_t)stream);
+}
+extern "C" size_t bh_ctc_head_train_workspace(long M, int F, int classes) { return bh_k_ctc_head_train_workspace(M, F, classes); }
+extern "C" int bh_ctc_head_train_backward(const void* x, const float* w, const float* bias, const void* dlp, long M, int F, int classes,
+                                          void* dx, float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream) {
+    return bh_k_ctc_head_train_backward(x, w, bias, dlp, M, F, classes, dx, dw, db, workspace, workspace_bytes, (hipStream_t)stream);
+}
 extern "C" size_t bh_sw_workspace(int n, int max_seq, int max_ref) { return bh_k_sw_workspace(n, max_seq, max_ref); }
 extern "C" int bh_sw_align(const void* seqs, long seq_stride, const int32_t* seq_lengths, const void* refs, long ref_stride,
                            const int32_t* ref_lengths, int n, int match, int mismatch, int gap_open, int gap_extend, void* workspace,

@@ -191,6 +191,18 @@ int bh_k_gated_linear_train_forward(const void* x, const float* w, long M, int D
 int bh_k_gated_linear_train_backward(const void* x, const float* w, const void* dh, long M, int D, int F, void* dx, float* dw, void* workspace,
                                      size_t workspace_bytes, hipStream_t stream);
 
+// quartznet_train.hip (what training a bonito.ctc model adds: the depthwise backward, residual + activation + dropout, the head backward)
+size_t bh_k_dwconv_train_workspace(int N, int L, int C, int K, int pad);
+int bh_k_dwconv_train_backward(const void* x, const float* w, const void* dy, int N, int L, int C, int K, int pad, void* dx, float* dw,
+                               void* workspace, size_t workspace_bytes, hipStream_t stream);
+int bh_k_residual_act_train_forward(const void* a, const void* b, long M, int C, int act, unsigned int p_threshold, float inv_keep,
+                                    unsigned long long seed, unsigned long long stream_id, void* y, hipStream_t stream);
+int bh_k_residual_act_train_backward(const void* a, const void* b, const void* dy, long M, int C, int act, unsigned int p_threshold,
+                                     float inv_keep, unsigned long long seed, unsigned long long stream_id, void* da, hipStream_t stream);
+size_t bh_k_ctc_head_train_workspace(long M, int F, int classes);
+int bh_k_ctc_head_train_backward(const void* x, const float* w, const float* bias, const void* dlp, long M, int F, int classes, void* dx,
+                                 float* dw, float* db, void* workspace, size_t workspace_bytes, hipStream_t stream);
+
 // align.hip (Smith-Waterman, affine gaps, traceback; the lengths are host arrays)
 size_t bh_k_sw_workspace(int n, int max_seq, int max_ref);
 int bh_k_sw_align(const void* seqs, long seq_stride, const int* seq_lens, const void* refs, long ref_stride, const int* ref_lens,

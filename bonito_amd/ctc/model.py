@@ -9,6 +9,11 @@ identical ``state_dict()`` keys (``encoder.encoder.<i>.conv.<j>.{depthwise,point
 residual add fused, 1x1 decoder + log_softmax) and returns log-probabilities in the reference's TNC layout.
 The CPU Rust decoders of fast_ctc_decode (:11,39-46) are replaced by bonito_amd.ctc.decode (HIP), and
 ``torch.nn.functional.ctc_loss`` behind ``ctc_label_smoothing_loss`` / ``loss`` (:48-57) by csrc/ctc_loss.hip.
+
+``model.forward_train(x, norm="batch")`` is the same network inside autograd, layer by layer on the device (bonito_amd.train_ops:
+depthwise and pointwise convolution, batch-statistics BatchNorm, residual add with activation and dropout, decoder with log-softmax),
+so that ``model.loss(model.forward_train(x, norm="batch"), targets, lengths)["total_loss"].backward()`` leaves a gradient on every
+parameter.
 """
 import torch
 from torch.nn import BatchNorm1d, Conv1d, Dropout, Module, ModuleList, Sequential
@@ -167,6 +172,170 @@ class Model(Module):
             bs, cs = self._hip_args if self._hip_args is not None else (None, None)
             self._hip = HipEncoder(self, max(int(bs or 0), N), max(int(cs or 0), L), device=x.device, lowering=lower_ctc)
         return self._hip(x).permute(1, 0, 2)
+
+    def _train_plan(self, x, norm):
+        """Every check of forward_train, in front of its first launch and its first side effect. -> the blocks as lists of
+        (TCSConv1d, BatchNorm1d) with their Dropout modules."""
+        from bonito_amd import train_ops
+        what = "forward_train"
+        if norm is None:
+            raise ValueError("forward_train: a bonito.ctc model has no forward_train without batch statistics: every block carries a "
+                             "BatchNorm; pass norm=\"batch\" / --norm batch")
+        if norm != "batch":
+            raise ValueError("forward_train: norm=%r is not served (\"batch\" for batch statistics)" % (norm,))
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float16 or x.dim() != 3 or x.shape[1] != 1 or x.shape[0] < 1:
+            raise ValueError("forward_train: x must be a float16 tensor [N,1,L], got %s"
+                             % ("%s %s" % (x.dtype, tuple(x.shape)) if isinstance(x, torch.Tensor) else type(x).__name__))
+        N, L, C = int(x.shape[0]), int(x.shape[2]), 1
+        plan = []
+
+        def tcs_check(name, tcs, bn, Lin, Cin):
+            convs = [("depthwise", tcs.depthwise), ("pointwise", tcs.pointwise)] if tcs.separable else [("conv", tcs.conv)]
+            for cname, c in convs:
+                if c.dilation[0] != 1:
+                    raise ValueError("%s: %s.%s has dilation %d; only dilation 1 has a training backward" % (what, name, cname, c.dilation[0]))
+                for pname, t in (("weight", c.weight), ("bias", c.bias)):
+                    if t is not None and t.dtype != torch.float32:
+                        raise ValueError("%s: %s.%s holds %s parameters (%s); training needs the fp32 master weights"
+                                         % (what, name, cname, t.dtype, pname))
+            if convs[0][1].in_channels != Cin:
+                raise ValueError("%s: %s expects %d input channels and follows %d" % (what, name, convs[0][1].in_channels, Cin))
+            Cout = convs[-1][1].out_channels
+            if Cout % 8 != 0 or (Cin != 1 and Cin % 8 != 0):
+                raise ValueError("%s: %s has %d -> %d channels; multiples of 8 are served" % (what, name, Cin, Cout))
+            if tcs.separable:
+                dw, pw = tcs.depthwise, tcs.pointwise
+                K, pad = dw.kernel_size[0], dw.padding[0]
+                if dw.stride[0] != 1 or K > 127:
+                    raise ValueError("%s: %s is a separable convolution with stride %d and K = %d; stride 1 and K <= 127 are served"
+                                     % (what, name, dw.stride[0], K))
+                if Cin % 8 != 0 or dw.groups != Cin or dw.bias is not None or pw.bias is not None:
+                    raise ValueError("%s: %s is not a bias-free depthwise + pointwise pair over a multiple of 8 channels" % (what, name))
+                train_ops._dw_check(torch.empty((N, Lin, Cin), dtype=torch.float16, device="meta"), dw.weight, pad,
+                                    "%s: %s.depthwise" % (what, name), devices=False)
+                Lout = train_ops.conv_out_len(Lin, K, 1, pad)
+            else:
+                c = tcs.conv
+                wide = Cin == 1 and Cout > 256          # the single-channel kernel serves 256 filters: seven zero channels ride beside the signal
+                shape = (N, Lin) if Cin == 1 and not wide else (N, Lin, 8 if wide else Cin)
+                weight = torch.empty((Cout, 8, c.kernel_size[0]), dtype=c.weight.dtype, device="meta") if wide else c.weight
+                train_ops._conv_check(torch.empty(shape, dtype=torch.float16, device="meta"), weight, c.bias, c.stride[0], c.padding[0], None,
+                                      None, "%s: %s.conv" % (what, name), devices=False)
+                from bonito_amd import _lib
+                if _lib.lib().bh_conv1d_train_workspace(N, Lin, 8 if wide else Cin, Cout, c.kernel_size[0], c.stride[0], c.padding[0]) == 0:
+                    raise ValueError("%s: %s.conv: shape N=%d Lin=%d Cin=%d Cout=%d K=%d stride=%d padding=%d is not supported"
+                                     % (what, name, N, Lin, Cin, Cout, c.kernel_size[0], c.stride[0], c.padding[0]))
+                Lout = train_ops.conv_out_len(Lin, c.kernel_size[0], c.stride[0], c.padding[0])
+            if not isinstance(bn, BatchNorm1d) or bn.num_features != Cout:
+                raise ValueError("%s: %s is not followed by a BatchNorm1d over its %d channels" % (what, name, Cout))
+            if not bn.training:
+                raise ValueError("%s: %s has its BatchNorm in eval mode; norm=\"batch\" trains with batch statistics (call model.train())"
+                                 % (what, name))
+            if bn.track_running_stats and bn.momentum is None:
+                raise ValueError("%s: %s has a BatchNorm with momentum=None (the cumulative average), which is not served" % (what, name))
+            for pname, t in bn.named_parameters():
+                if t.dtype != torch.float32:
+                    raise ValueError("%s: %s holds %s parameters (BatchNorm %s); training needs the fp32 master weights"
+                                     % (what, name, t.dtype, pname))
+            if Cout > 2048 or N * Lout < 2:
+                raise ValueError("%s: %s normalises %d channels over %d values; up to 2048 channels and more than one value are served"
+                                 % (what, name, Cout, N * Lout))
+            return Lout, Cout
+
+        for bi, block in enumerate(self.encoder.encoder):
+            bname = "encoder.encoder.%d" % bi
+            mods = list(block.conv)
+            steps, i = [], 0
+            Lb, Cb = L, C
+            while i < len(mods):
+                if not isinstance(mods[i], TCSConv1d) or i + 1 >= len(mods):
+                    raise ValueError("%s: %s.conv.%d (%s) is no TCSConv1d followed by a BatchNorm1d" % (what, bname, i, type(mods[i]).__name__))
+                Lb, Cb = tcs_check("%s.conv.%d" % (bname, i), mods[i], mods[i + 1], Lb, Cb)
+                drop = None
+                if i + 2 < len(mods):
+                    if i + 3 >= len(mods) or not isinstance(mods[i + 3], Dropout):
+                        raise ValueError("%s: %s.conv.%d is not followed by an activation and a Dropout" % (what, bname, i + 1))
+                    train_ops._act(mods[i + 2], (None, "none", "swish", "tanh", "relu"), "%s: %s" % (what, bname))
+                    drop = mods[i + 3]
+                steps.append((mods[i], mods[i + 1], drop))
+                i += 4
+            act, drop = block.activation[0], block.activation[1]
+            train_ops._act(act, (None, "none", "swish", "tanh", "relu"), "%s: %s" % (what, bname))
+            for d in [s[2] for s in steps[:-1]] + [drop]:
+                if not isinstance(d, Dropout) or not 0.0 <= d.p < 1.0:
+                    raise ValueError("%s: %s has a dropout probability outside 0 <= p < 1" % (what, bname))
+            res = None
+            if block.use_res:
+                res = (block.residual[0], block.residual[1])
+                Lr, Cr = tcs_check("%s.residual" % bname, res[0], res[1], L, C)
+                if (Lr, Cr) != (Lb, Cb):
+                    raise ValueError("%s: %s adds a residual of %d steps x %d channels to %d x %d" % (what, bname, Lr, Cr, Lb, Cb))
+            plan.append((steps, res, act, drop))
+            L, C = Lb, Cb
+        head = self.decoder.layers[0]
+        train_ops._head_check(torch.empty((N, L, C), dtype=torch.float16, device="meta"), head.weight, head.bias, "%s: decoder" % what,
+                              devices=False)
+        if not x.is_cuda:
+            raise NoTorchCompute("forward_train runs on a HIP device only; x is a %s tensor" % x.device)
+        for pname, t in list(self.named_parameters()) + list(self.named_buffers()):
+            if t.device != x.device:
+                raise ValueError("forward_train: %s is on %s, x is on %s" % (pname, t.device, x.device))
+        return plan
+
+    def forward_train(self, x, norm=None, seed=None):
+        """x: cuda fp16 [N,1,L] -> log-probabilities fp16 [T, N, n_labels] (the layout of ``forward``, a view of batch-major rows),
+        inside autograd: every layer is a device layer of bonito_amd.train_ops with its own backward.
+
+        ``norm`` must be ``"batch"``: every block carries a BatchNorm, which normalises with the statistics of this batch and updates
+        its running statistics and ``num_batches_tracked``, as the reference's training does. ``norm=None`` is refused, like every
+        other refusal (eval-mode BatchNorm, dilation, a separable convolution with a stride or K > 127, channel counts that are no
+        multiples of 8, parameters that are not fp32, what train_ops.conv1d refuses in a plain convolution - K > 32, which is
+        dna_r9.4.1@v1's first layer) in front of the first launch and the first side effect. A single-channel first convolution with
+        more than 256 filters (dna_r9.4.1@v2: 344) gets seven zero channels beside the signal, which is what that layer serves.
+
+        Dropout is not stored: site i of the model (every Dropout module, in model order) keeps an element iff a counter-based hash
+        of (seed, i, element index) reaches p 2^32 (include/bonito_hip.h). ``seed``: one 64-bit number per call; None draws it from
+        torch's default CPU generator, so torch.manual_seed reproduces a run. A Dropout module in eval mode drops nothing."""
+        from bonito_amd import train_ops
+        plan = self._train_plan(x, norm)
+        if seed is None:
+            seed = int(torch.randint(-(1 << 63), (1 << 63) - 1, (1,), dtype=torch.int64).item())
+        seed = int(seed) & ((1 << 64) - 1)
+        site = [0]
+
+        def dropped(drop):
+            site[0] += 1
+            return (drop.p if drop.training else 0.0), site[0] - 1
+
+        def tcs_bn(tcs, bn, h, activation):
+            if tcs.separable:
+                h = train_ops.depthwise_conv1d(h, tcs.depthwise.weight, tcs.depthwise.padding[0])
+                h = train_ops.linear(h, tcs.pointwise.weight[:, :, 0])
+            else:
+                w = tcs.conv.weight
+                if w.shape[1] == 1 and w.shape[0] > 256:          # seven zero channels beside the signal (see _train_plan)
+                    h, w = torch.nn.functional.pad(h.unsqueeze(-1), (0, 7)), torch.nn.functional.pad(w, (0, 0, 0, 7))
+                h = train_ops.conv1d(h, w, tcs.conv.bias, tcs.conv.stride[0], tcs.conv.padding[0])
+            h = train_ops.batchnorm(h, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, activation)
+            if bn.num_batches_tracked is not None:
+                bn.num_batches_tracked.add_(1)
+            return h
+
+        h = x[:, 0, :].contiguous()
+        for steps, res, act, drop in plan:
+            inp = h
+            for tcs, bn, between in steps[:-1]:
+                h = tcs_bn(tcs, bn, h, act)
+                p, sid = dropped(between)
+                if p > 0.0:
+                    h = train_ops.residual_act(h, None, "none", p, seed, sid)
+            p, sid = dropped(drop)
+            fused = res is None and p == 0.0
+            h = tcs_bn(steps[-1][0], steps[-1][1], h, act if fused else None)
+            if not fused:
+                h = train_ops.residual_act(h, None if res is None else tcs_bn(res[0], res[1], inp, None), act, p, seed, sid)
+        head = self.decoder.layers[0]
+        return train_ops.ctc_head(h, head.weight, head.bias).permute(1, 0, 2)
 
     def decode(self, x, beamsize=5, threshold=1e-3, qscores=False, return_path=False):
         """x: log-probabilities [T, n_labels] of ONE read (any device). Greedy when beamsize == 1 or

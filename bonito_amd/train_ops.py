@@ -3,7 +3,8 @@ The convolution and the linear / CRF-head layer for training on the device: forw
 autograd (csrc/train_layers.hip; the arithmetic is stated in include/bonito_hip.h under bh_conv1d_train_forward) - the two layers a
 transformer encoder layer adds, the DeepNorm residual RMSNorm and the gated input layer of the MLP (csrc/transformer_train.hip; under
 bh_rmsnorm_train_backward) - and the batch-statistics BatchNorm behind a convolution (csrc/batchnorm_train.hip; under
-bh_batchnorm_train_forward).
+bh_batchnorm_train_forward) - and what a QuartzNet CTC model adds: the depthwise convolution, the residual add with activation and
+dropout, and the 1x1 decoder with its log-softmax (csrc/quartznet_train.hip; under bh_dwconv1d_train_backward).
 
     y = conv1d_forward(x, weight, bias, stride, padding, activation, clamp, time_major)     # x fp16 [N][Lin][Cin] ([N][Lin] for Cin == 1)
     dx, dw, db = conv1d_backward(x, weight, bias, y, dy, stride, padding, activation, clamp, time_major)
@@ -20,6 +21,15 @@ bh_batchnorm_train_forward).
     y, mean, rstd = batchnorm_forward(z, weight, bias, running_mean, running_var, momentum, eps, activation, clamp, time_major, channels)
     dz, dw, db = batchnorm_backward(z, weight, bias, mean, rstd, y, dy, activation, clamp, time_major, channels)
     y = batchnorm(z, weight, bias, running_mean, running_var, momentum, eps, activation, clamp, time_major, channels)    # differentiable
+    y = depthwise_conv1d_forward(x, weight, padding)                                        # x fp16 [N][L][C], weight fp32 [C][1][K]
+    dx, dw = depthwise_conv1d_backward(x, weight, dy, padding)
+    y = depthwise_conv1d(x, weight, padding)                                                # differentiable
+    y = residual_act_forward(a, b, activation, p, seed, stream_id)                          # a, b fp16 [...][C]; b may be None
+    da = residual_act_backward(a, b, dy, activation, p, seed, stream_id)                    # the gradient of a and of b
+    y = residual_act(a, b, activation, p, seed, stream_id)                                  # differentiable
+    lp = ctc_head_forward(x, weight, bias)                                                  # x fp16 [N][T][F] -> fp16 [N][T][classes]
+    dx, dw, db = ctc_head_backward(x, weight, bias, dlp)
+    lp = ctc_head(x, weight, bias)                                                          # differentiable
 
 Activations are channel-minor: a convolution returns [N][Lout][Cout], or time-major [Lout][N][Cout] (the permute in front of the LSTM
 stack, folded into the store). weight and bias are the fp32 master tensors in torch's layout ([Cout][Cin][K], [C][K]).
@@ -37,7 +47,10 @@ from bonito_amd._train import HalfLayer, HalfLayer2, devices as _devices, half a
 __all__ = ["conv1d_forward", "conv1d_backward", "conv1d", "linear_forward", "linear_backward", "linear", "conv_out_len",
            "rmsnorm_residual_forward", "rmsnorm_residual_backward", "rmsnorm_residual",
            "gated_linear_forward", "gated_linear_backward", "gated_linear",
-           "batchnorm_forward", "batchnorm_backward", "batchnorm"]
+           "batchnorm_forward", "batchnorm_backward", "batchnorm",
+           "depthwise_conv1d_forward", "depthwise_conv1d_backward", "depthwise_conv1d",
+           "residual_act_forward", "residual_act_backward", "residual_act", "keep_threshold",
+           "ctc_head_forward", "ctc_head_backward", "ctc_head"]
 
 _INF = float("inf")
 
@@ -546,3 +559,231 @@ def batchnorm(z, weight, bias, running_mean=None, running_var=None, momentum=0.1
         return batchnorm_backward(*kept, dy.contiguous(), *args, need_dw=affine and need[1], need_db=affine and need[2])
 
     return HalfLayer.apply(forward, backward, z, weight, bias)
+
+
+# ---- depthwise convolution (QuartzNet's TCSConv1d.depthwise) --------------------------------------------------------------------------------
+def _dw_check(x, weight, padding, what, dtypes=(torch.float16,), devices=True):
+    named = [("x", x), ("weight", weight)]
+    _tensors(named, what)
+    if weight.dim() != 3 or weight.shape[1] != 1:
+        raise ValueError("%s: weight must be [C][1][K] (groups = C), got %s" % (what, tuple(weight.shape)))
+    C, K = int(weight.shape[0]), int(weight.shape[2])
+    if x.dtype not in dtypes:
+        raise ValueError("%s: x must be %s, got %s" % (what, _dtype_names(dtypes), x.dtype))
+    if x.dim() != 3 or x.shape[2] != C or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("%s: x must be [N][L][%d], got %s" % (what, C, tuple(x.shape)))
+    _master(weight, (C, 1, K), "weight", what)
+    N, L, padding = int(x.shape[0]), int(x.shape[1]), int(padding)
+    if C % 8 != 0:
+        raise ValueError("%s: C must be a multiple of 8, got %d" % (what, C))
+    if not (1 <= K <= 127 and 0 <= padding < K and L + 2 * padding >= K):
+        raise ValueError("%s: K <= 127, padding < K and one whole window are needed (K=%d padding=%d L=%d)" % (what, K, padding, L))
+    if devices:
+        _devices(named, what)
+    return N, L, C, K, padding
+
+
+def depthwise_conv1d_forward(x, weight, padding=0):
+    """-> y fp16 [N][Lout][C]: the bytes of bh_dwconv1d (stride 1) on the fp32 weights, used unrounded."""
+    N, L, C, K, padding = _dw_check(x, weight, padding, "depthwise_conv1d_forward")
+    x, weight = x.contiguous(), weight.detach().contiguous()
+    with torch.cuda.device(x.device):
+        y = torch.empty((N, conv_out_len(L, K, 1, padding), C), dtype=torch.float16, device=x.device)
+        _lib.check(_lib.lib().bh_dwconv1d(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(y), N, L, C, K, 1, padding, _lib.stream_ptr(x.device)),
+                   "bh_dwconv1d")
+    return y
+
+
+def depthwise_conv1d_backward(x, weight, dy, padding=0, need_dx=True, need_dw=True):
+    """-> (dx fp16 in the shape of x or None, dw fp32 [C][1][K] or None) from the upstream gradient dy (fp16 [N][Lout][C])."""
+    what = "depthwise_conv1d_backward"
+    N, L, C, K, padding = _dw_check(x, weight, padding, what, devices=False)
+    _tensors([("dy", dy)], what)
+    _half(dy, (N, conv_out_len(L, K, 1, padding), C), "dy", what)
+    _devices([("x", x), ("weight", weight), ("dy", dy)], what)
+    x, weight, dy = x.contiguous(), weight.detach().contiguous(), dy.contiguous()
+    lib = _lib.lib()
+    nbytes = lib.bh_dwconv1d_train_workspace(N, L, C, K, padding)
+    if nbytes == 0:
+        raise ValueError("%s: shape N=%d L=%d C=%d K=%d padding=%d is not supported" % (what, N, L, C, K, padding))
+    with torch.cuda.device(x.device):
+        dx = torch.empty_like(x) if need_dx else None
+        dw = torch.empty((C, 1, K), dtype=torch.float32, device=x.device) if need_dw else None
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _lib.check(lib.bh_dwconv1d_train_backward(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(dy), N, L, C, K, padding, _lib.ptr(dx), _lib.ptr(dw),
+                                                  _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device)), "bh_dwconv1d_train_backward")
+    return dx, dw
+
+
+def depthwise_conv1d(x, weight, padding=0):
+    """y fp16 [N][Lout][C] of a depthwise convolution (stride 1, dilation 1, no bias), differentiable with respect to x (fp16 or fp32;
+    fp32 is cast to fp16 and its gradient comes back as fp32) and weight, each where requires_grad is set."""
+    _dw_check(x, weight, padding, "depthwise_conv1d", dtypes=_BOTH)
+    padding = int(padding)
+
+    def forward(x16, weight):
+        x16 = x16.contiguous()
+        return depthwise_conv1d_forward(x16, weight, padding), (x16, weight)
+
+    def backward(kept, dy, need):
+        return depthwise_conv1d_backward(*kept, dy.contiguous(), padding, need_dx=need[0], need_dw=need[1])
+
+    return HalfLayer.apply(forward, backward, x, weight)
+
+
+# ---- residual add + activation + dropout -----------------------------------------------------------------------------------------------------
+def keep_threshold(p):
+    """-> (p_threshold, inv_keep) of a dropout probability: floor(p 2^32) in double and 1 / (1 - p); an element is kept iff the top 32
+    bits of its counter-based hash reach p_threshold (include/bonito_hip.h)."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout probability must be in 0 <= p < 1, got %r" % p)
+    return int(math.floor(p * 4294967296.0)), 1.0 / (1.0 - p)
+
+
+def _res_check(a, b, activation, p, seed, stream_id, what, dtypes=(torch.float16,), devices=True):
+    named = [("a", a)] + ([("b", b)] if b is not None else [])
+    _tensors(named, what)
+    for name, t in named:
+        if t.dtype not in dtypes:
+            raise ValueError("%s: %s must be %s, got %s" % (what, name, _dtype_names(dtypes), t.dtype))
+    if a.dim() < 2 or a.numel() == 0 or (b is not None and b.shape != a.shape):
+        raise ValueError("%s: a and b must be [...][C] of one shape, got %s%s" % (what, tuple(a.shape), "" if b is None else " and %s" % (tuple(b.shape),)))
+    C = int(a.shape[-1])
+    act = _act(activation, (None, "none", "swish", "tanh", "relu"), what)
+    try:
+        threshold, inv_keep = keep_threshold(p)
+    except ValueError as exc:
+        raise ValueError("%s: %s" % (what, exc)) from None
+    seed, stream_id = int(seed), int(stream_id)
+    if not (0 <= seed < 1 << 64 and 0 <= stream_id < 1 << 64):
+        raise ValueError("%s: seed and stream_id must be in 0..2^64-1, got %d and %d" % (what, seed, stream_id))
+    if C % 8 != 0:
+        raise ValueError("%s: C must be a multiple of 8, got %d" % (what, C))
+    if devices:
+        _devices(named, what)
+    return a.numel() // C, C, act, threshold, inv_keep, seed, stream_id
+
+
+def residual_act_forward(a, b, activation=None, p=0.0, seed=0, stream_id=0):
+    """-> y fp16 in the shape of a: dropout(act(a + b)), b may be None. The mask is a function of (seed, stream_id, element index)."""
+    M, C, act, threshold, inv_keep, seed, stream_id = _res_check(a, b, activation, p, seed, stream_id, "residual_act_forward")
+    a, b = a.contiguous(), None if b is None else b.contiguous()
+    with torch.cuda.device(a.device):
+        y = torch.empty_like(a)
+        _lib.check(_lib.lib().bh_residual_act_train_forward(_lib.ptr(a), _lib.ptr(b), M, C, act, threshold, inv_keep, seed, stream_id,
+                                                            _lib.ptr(y), _lib.stream_ptr(a.device)), "bh_residual_act_train_forward")
+    return y
+
+
+def residual_act_backward(a, b, dy, activation=None, p=0.0, seed=0, stream_id=0):
+    """-> da fp16 in the shape of a, which is the gradient of b too, from the upstream gradient dy; a + b and the mask are recomputed."""
+    what = "residual_act_backward"
+    M, C, act, threshold, inv_keep, seed, stream_id = _res_check(a, b, activation, p, seed, stream_id, what, devices=False)
+    _tensors([("dy", dy)], what)
+    _half(dy, a.shape, "dy", what)
+    _devices([("a", a), ("dy", dy)] + ([("b", b)] if b is not None else []), what)
+    a, b, dy = a.contiguous(), None if b is None else b.contiguous(), dy.contiguous()
+    with torch.cuda.device(a.device):
+        da = torch.empty_like(a)
+        _lib.check(_lib.lib().bh_residual_act_train_backward(_lib.ptr(a), _lib.ptr(b), _lib.ptr(dy), M, C, act, threshold, inv_keep, seed,
+                                                             stream_id, _lib.ptr(da), _lib.stream_ptr(a.device)),
+                   "bh_residual_act_train_backward")
+    return da
+
+
+def residual_act(a, b=None, activation=None, p=0.0, seed=0, stream_id=0):
+    """y fp16 = dropout_p(act(a + b)) (b may be None), differentiable with respect to a and b (each fp16 or fp32; fp32 is cast to fp16 and
+    its gradient comes back as fp32). Nothing of the mask is stored: forward and backward compute it from (seed, stream_id, index)."""
+    _res_check(a, b, activation, p, seed, stream_id, "residual_act", dtypes=_BOTH)
+    args = (activation, float(p), int(seed), int(stream_id))
+    if b is None:
+        def forward(a16):
+            a16 = a16.contiguous()
+            return residual_act_forward(a16, None, *args), (a16,)
+
+        def backward(kept, dy, need):
+            return (residual_act_backward(kept[0], None, dy.contiguous(), *args),)
+
+        return HalfLayer.apply(forward, backward, a)
+
+    def forward2(a16, b16):
+        a16, b16 = a16.contiguous(), b16.contiguous()
+        return residual_act_forward(a16, b16, *args), (a16, b16)
+
+    def backward2(kept, dy, need):
+        da = residual_act_backward(*kept, dy.contiguous(), *args)
+        return da, da
+
+    return HalfLayer2.apply(forward2, backward2, a, b)
+
+
+# ---- the 1x1 decoder with its log-softmax (QuartzNet's Decoder) ---------------------------------------------------------------------------------
+def _head_check(x, weight, bias, what, dtypes=(torch.float16,), devices=True):
+    named = [("x", x), ("weight", weight), ("bias", bias)]
+    _tensors(named, what)
+    if weight.dim() != 3 or weight.shape[2] != 1:
+        raise ValueError("%s: weight must be [classes][F][1], got %s" % (what, tuple(weight.shape)))
+    classes, F = int(weight.shape[0]), int(weight.shape[1])
+    if x.dtype not in dtypes:
+        raise ValueError("%s: x must be %s, got %s" % (what, _dtype_names(dtypes), x.dtype))
+    if x.dim() != 3 or x.shape[2] != F or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("%s: x must be [N][T][%d], got %s" % (what, F, tuple(x.shape)))
+    _master(weight, (classes, F, 1), "weight", what)
+    _master(bias, (classes,), "bias", what)
+    if not 1 <= classes <= 8 or F % 8 != 0 or classes * F * 4 > 65536:
+        raise ValueError("%s: classes <= 8, F %% 8 == 0 and classes F fp32 weights within 64 KiB are needed (classes=%d F=%d)"
+                         % (what, classes, F))
+    if devices:
+        _devices(named, what)
+    return int(x.shape[0]), int(x.shape[1]), F, classes
+
+
+def ctc_head_forward(x, weight, bias):
+    """-> log-probabilities fp16 [N][T][classes]: the bytes of bh_ctc_head on the fp32 weights."""
+    N, T, F, classes = _head_check(x, weight, bias, "ctc_head_forward")
+    x, weight, bias = x.contiguous(), weight.detach().contiguous(), bias.detach().contiguous()
+    with torch.cuda.device(x.device):
+        lp = torch.empty((N, T, classes), dtype=torch.float16, device=x.device)
+        _lib.check(_lib.lib().bh_ctc_head(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(lp), N * T, F, classes,
+                                          _lib.stream_ptr(x.device)), "bh_ctc_head")
+    return lp
+
+
+def ctc_head_backward(x, weight, bias, dlp, need_dx=True, need_dw=True, need_db=True):
+    """-> (dx fp16 [N][T][F] or None, dw fp32 [classes][F][1] or None, db fp32 [classes] or None) from dlp, the gradient of the
+    log-probabilities (fp16 [N][T][classes]); the logits and their softmax are recomputed in fp32."""
+    what = "ctc_head_backward"
+    N, T, F, classes = _head_check(x, weight, bias, what, devices=False)
+    _tensors([("dlp", dlp)], what)
+    _half(dlp, (N, T, classes), "dlp", what)
+    _devices([("x", x), ("weight", weight), ("bias", bias), ("dlp", dlp)], what)
+    x, weight, bias, dlp = x.contiguous(), weight.detach().contiguous(), bias.detach().contiguous(), dlp.contiguous()
+    lib = _lib.lib()
+    nbytes = lib.bh_ctc_head_train_workspace(N * T, F, classes)
+    if nbytes == 0:
+        raise ValueError("%s: shape M=%d F=%d classes=%d is not supported" % (what, N * T, F, classes))
+    with torch.cuda.device(x.device):
+        dx = torch.empty_like(x) if need_dx else None
+        dw = torch.empty((classes, F, 1), dtype=torch.float32, device=x.device) if need_dw else None
+        db = torch.empty(classes, dtype=torch.float32, device=x.device) if need_db else None
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        _lib.check(lib.bh_ctc_head_train_backward(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(dlp), N * T, F, classes, _lib.ptr(dx),
+                                                  _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device)),
+                   "bh_ctc_head_train_backward")
+    return dx, dw, db
+
+
+def ctc_head(x, weight, bias):
+    """Log-probabilities fp16 [N][T][classes] of the 1x1 decoder, differentiable with respect to x (fp16 or fp32; fp32 is cast to fp16 and
+    its gradient comes back as fp32), weight and bias, each where requires_grad is set."""
+    _head_check(x, weight, bias, "ctc_head", dtypes=_BOTH)
+
+    def forward(x16, weight, bias):
+        x16 = x16.contiguous()
+        return ctc_head_forward(x16, weight, bias), (x16, weight, bias)
+
+    def backward(kept, dlp, need):
+        return ctc_head_backward(*kept, dlp.contiguous(), need_dx=need[0], need_dw=need[1], need_db=need[2])
+
+    return HalfLayer.apply(forward, backward, x, weight, bias)

@@ -10,8 +10,8 @@ The training loop of ``python -m bonito_amd train`` (the reference's bonito/trai
 of kernel launch. The host reads the step's scalars (``optimizer.last()``) once per step, for the log and for the quantile clip.
 
 The inference engine snapshots the weights when it is built and the update kernel changes them behind the module's back, so the engine
-is dropped before every validation pass (and only there: forward_train does not use it). The model is any SeqdistModel whose
-forward_train serves it: the LSTM family and the transformer family. ``Trainer(norm="batch")`` trains convolutions that carry a
+is dropped before every validation pass (and only there: forward_train does not use it). The model is any model whose forward_train
+serves it: the LSTM and the transformer family of CRF models, and with norm="batch" the QuartzNet CTC models (bonito_amd.ctc). ``Trainer(norm="batch")`` trains convolutions that carry a
 BatchNorm with batch statistics (forward_train's keyword): every sub-batch of a step rewrites the running statistics, as in the
 reference, and the validation pass, which drops the engine, folds the new ones.
 """
@@ -90,7 +90,7 @@ class Trainer:
         if not use_amp:
             raise ValueError("Trainer: use_amp=False is not served: forward_train computes in fp16 and there is no fp32 path")
         if not hasattr(model, "forward_train"):
-            raise ValueError("Trainer: %s has no forward_train (the LSTM and transformer families of CRF models train on the device)" % type(model).__name__)
+            raise ValueError("Trainer: %s has no forward_train (the LSTM and transformer families of CRF models and the QuartzNet CTC models train on the device)" % type(model).__name__)
         self.model = model.to(device)
         self.device = device
         self.train_loader, self.valid_loader = train_loader, valid_loader
@@ -141,7 +141,11 @@ class Trainer:
         scores = self.model(data.to(torch.float16).to(self.device))
         losses = self.criterion(scores, targets, lengths)
         losses = {k: v.item() for k, v in losses.items()} if isinstance(losses, dict) else losses.item()
-        seqs = self.model.decode_batch(scores)
+        if hasattr(self.model, "decode_batch"):
+            seqs = self.model.decode_batch(scores)
+        else:                                 # bonito.ctc: the prefix beam search `evaluate` scores such a model with
+            from bonito_amd.cli.evaluate import decode_batch
+            seqs = decode_batch(self.model, scores)
         refs = [decode_ref(target, self.model.alphabet) for target in targets]
         n_pre, n_post = getattr(self.model, "n_pre_context_bases", 0), getattr(self.model, "n_post_context_bases", 0)
         if n_pre > 0 or n_post > 0:

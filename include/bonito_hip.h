@@ -32,6 +32,9 @@
  *        the autograd of RMSNorm(attn / ff + deepnorm_alpha * x) and of GatedMlp's fc1 + SwiGLU         bonito/transformer/model.py:83-133
  *   bh_batchnorm_train_forward / bh_batchnorm_train_backward
  *        torch.nn.BatchNorm1d in training mode behind a Convolution (activation(norm(conv(x)))) and its autograd   bonito/nn.py:222-241
+ *   bh_dwconv1d_train_backward / bh_residual_act_train_forward / bh_residual_act_train_backward / bh_ctc_head_train_backward
+ *        the autograd of a QuartzNet Block and Decoder: Conv1d(groups=C), the residual add with activation and Dropout, and
+ *        log_softmax(Conv1d(kernel_size=1))                                     bonito/ctc/model.py:90-207
  *   bh_sw_align
  *        parasail.sw_trace_striped_32(seq, ref, 8, 4, parasail.dnafull) behind evaluate's align() and util.accuracy
  *                                                                              bonito/cli/evaluate.py:37-67, bonito/util.py:346-368
@@ -493,6 +496,46 @@ int bh_batchnorm_train_forward(const void* z, const float* gamma, const float* b
 int bh_batchnorm_train_backward(const void* z, const float* gamma, const float* beta, const float* mean, const float* rstd, const void* y,
                                 const void* dy, int N, int L, int C, int C_param, int act, float clamp_lo, float clamp_hi, long os_n,
                                 long os_t, void* dz, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Training a QuartzNet CTC model (csrc/quartznet_train.hip): depthwise backward, residual + activation + dropout, head backward ---
+ * Depthwise convolution, stride 1, dilation 1. The forward is bh_dwconv1d as it stands (fp32 weights unrounded, fmaf over the taps in tap
+ * order, one rounding at the store). x fp16 [N][L][C] channel-minor, w fp32 [C][K], dy fp16 [N][Lout][C], Lout = L + 2 pad - K + 1:
+ *     dx[n][p][c] = fp16(sum_k w[c][k] dy[n][p + pad - k][c])      over the k with 0 <= p + pad - k < Lout, fp32 fmaf in tap order
+ *     dw[c][k]    = sum_{n,t} dy[n][t][c] x[n][t + k - pad][c]      fp32 [C][K], OVERWRITTEN; terms with the x index outside 0..L-1 are 0
+ *   dx or dw may be NULL = not written. dw: a workgroup owns 64 channels and a block of consecutive units of 64 rows (the block a function
+ *   of the shape alone), a thread fixed (channel, tap) accumulators added to in row order; the [block][C][K] planes lie in the workspace
+ *   and a second launch adds them in block order (eight runs of consecutive blocks, each in block order, then the runs in order) - no
+ *   floating-point atomics, two calls give equal bytes.
+ *   Supported: C % 8 == 0, 1 <= K <= 127, 0 <= pad < K, Lout >= 1, N L < 2^30 rows; N L C may pass 2^31 elements (64-bit offsets).
+ * Residual add + activation + dropout, a, b, y, dy, da fp16 [M][C] (M = N L rows, C % 8 == 0), b may be NULL (u = a):
+ *     u = a + b (fp32)      y = fp16(keep ? act(u) inv_keep : 0)      da = fp16(keep ? dy inv_keep act'(u) : 0)   (u recomputed)
+ *   da is the gradient of b as well. act: none / swish / tanh / relu, the functions of the other training layers. keep is NOT stored: with
+ *   64-bit unsigned arithmetic (mod 2^64), G = 0x9E3779B97F4A7C15 and the splitmix64 finaliser
+ *     mix(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *     keep(i) = (mix(mix(seed + G (stream_id + 1)) + G (i + 1)) >> 32) >= p_threshold          i = m C + c, the flat element index
+ *   The host computes p_threshold = floor(p 2^32) in double and inv_keep = (float)(1 / (1 - p)), 0 <= p < 1. p = 0: p_threshold = 0 keeps
+ *   every element and inv_keep = 1, the bytes are those of fp16(act(a + b)). M C < 2^35 elements.
+ * CTC head, x fp16 [M][F], w fp32 [classes][F], bias fp32 [classes]. The forward is bh_ctc_head as it stands. Backward from dlp fp16
+ * [M][classes], the gradient of the log-probabilities:
+ *     logit, s = softmax(logit): RECOMPUTED in fp32 from x, w, bias exactly as the forward forms them (never from the rounded output)
+ *     dlogit_c = dlp_c - s_c sum_{c' < classes} dlp_c'      dx = fp16(sum_c dlogit_c w[c][.])  (fmaf in class order)
+ *     dw[c][f] = sum_m dlogit[m][c] x[m][f]      db[c] = sum_m dlogit[m][c]      fp32, OVERWRITTEN
+ *   dx, dw, db may each be NULL = not written. dlogit is kept as fp32 [M][8] in the workspace; dw and db: a workgroup sums a block of rows
+ *   (a function of M alone) in row order, the blocks are added in block order - equal bytes from call to call.
+ *   Supported: 1 <= classes <= 8, F % 8 == 0, classes F fp32 weights within 64 KiB of LDS, M < 2^32.
+ * x, dy, dx, a, b, y, da and the workspace are 16-byte aligned device pointers. workspace (bh_*_train_workspace; 0 = unsupported shape):
+ * the caller's. Anything unsupported returns nonzero with bh_last_error() set, launches nothing and leaves every output untouched.
+ * Stream-ordered; nothing is allocated and nothing synchronises inside. */
+size_t bh_dwconv1d_train_workspace(int N, int L, int C, int K, int pad);
+int bh_dwconv1d_train_backward(const void* x, const float* w, const void* dy, int N, int L, int C, int K, int pad, void* dx, float* dw,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int bh_residual_act_train_forward(const void* a, const void* b, long M, int C, int act, unsigned int p_threshold, float inv_keep,
+                                  unsigned long long seed, unsigned long long stream_id, void* y, void* stream);
+int bh_residual_act_train_backward(const void* a, const void* b, const void* dy, long M, int C, int act, unsigned int p_threshold,
+                                   float inv_keep, unsigned long long seed, unsigned long long stream_id, void* da, void* stream);
+size_t bh_ctc_head_train_workspace(long M, int F, int classes);
+int bh_ctc_head_train_backward(const void* x, const float* w, const float* bias, const void* dlp, long M, int F, int classes, void* dx,
+                               float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Smith-Waterman local alignment with affine gaps and a traceback (csrc/align.hip) ----------------------------------
  * n pairs of a called sequence `seq` (the query, index i) and a known sequence `ref` (index j). seqs / refs: DEVICE int8 planes
