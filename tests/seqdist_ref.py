@@ -8,7 +8,7 @@
   them to the reference's own class; run in fp32 they are the "reference-order fp32 scan" the GPU tolerance is measured from.
   ``torch_log_scan_gather`` is the same recurrence with the gather done per step (full-size inputs do not fit as [T, N, L]).
 * ``enumerate_alignments``: brute force over every monotone alignment (T <= 8).
-* ``free_start_logz``: fp64 sum over every alignment AND start state, on the full (emitted, state) lattice.
+* ``free_start_logz``: sum over every alignment AND start state, on the full (emitted, state) lattice, any float dtype.
 
 Layouts: ``scores`` is always indexed [n, t, c] here (pass ``x.transpose(1, 0, 2)`` views of [T, N, C] tensors)."""
 import itertools
@@ -141,26 +141,28 @@ def enumerate_alignments(scores_tc, target_row, length, state_len, layout_5s, bl
     return np.logaddexp.reduce(totals), best, np.array(best_al, np.int32)
 
 
-def free_start_logz(scores_tc, seq, state_len, blank):
+def free_start_logz(scores_tc, seq, state_len, blank, dtype=np.float64):
     """ln sum over every start state and every alignment emitting exactly `seq` (base indices 0..3) of exp(path score), one chunk of
-    koi-layout scores [T, 4S], fp64, on the full lattice A[emitted][state]."""
-    sc = np.asarray(scores_tc, np.float64)
+    koi-layout scores [T, 4S], on the full lattice A[emitted][state], every level in one numpy step. In `dtype`: fp64 is the yardstick;
+    run in fp32 it is the fp32 scan of rows that have no fixed-start chain (shorter than k). -inf, never NaN, where len(seq) > T."""
+    sc = np.asarray(scores_tc).astype(dtype)
+    seq = np.asarray(seq, np.int64).reshape(-1)
     T, S, L = sc.shape[0], 4 ** state_len, len(seq)
     q = S // 4
     states = np.arange(S)
     pred = np.stack([r * q + states // 4 for r in range(4)], axis=1)          # [S, 4]
-    A = np.full((L + 1, S), -np.inf)
-    A[0] = 0.0
+    enters = states[None, :] % 4 == seq[:, None]                              # [L, S]: level i is entered by emitting seq[i - 1]
+    A = np.full((L + 1, S), -np.inf, dtype)
+    A[0] = 0
     with np.errstate(invalid="ignore"):
         for t in range(T):
             row = sc[t].reshape(S, 4)
-            new = A + blank
-            for i in range(1, L + 1):
-                inc = np.logaddexp.reduce(A[i - 1][pred] + row, axis=1)
-                inc = np.where(states % 4 == seq[i - 1], inc, -np.inf)
-                new[i] = np.logaddexp(new[i], inc)
-            A = new
-    return np.logaddexp.reduce(A[L])
+            new = (A + dtype(blank)).astype(dtype)
+            if L:
+                inc = np.logaddexp.reduce(A[:-1][:, pred] + row[None], axis=2)
+                new[1:] = np.logaddexp(new[1:], np.where(enters, inc, dtype(-np.inf)))
+            A = new.astype(dtype)
+        return np.logaddexp.reduce(A[L])
 
 
 # ---- torch restatement of koi.ctc.logZ_cu / viterbi_alignments (the reference-order scan) ----------------------------------------

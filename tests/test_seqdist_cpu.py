@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, ROOT
+import seqdist_cases as sc_cases
 import seqdist_ref as sr
 
 ALPHABET = ["N", "A", "C", "G", "T"]
@@ -150,6 +151,106 @@ def test_free_start_restatement_equals_the_oracle(sl):
     seq = rng.integers(0, 4, size=10)
     fixed = sr.log_scan(sc[None], (seq + 1)[None], np.array([10]), sl, False, 2.0)[0]
     assert sr.free_start_logz(sc, seq, sl, 2.0) > fixed
+
+
+@pytest.mark.parametrize("sl", [4, 5])
+def test_free_start_restatement_equals_the_oracle_at_long_state_lengths(sl):
+    """State_len 4 and 5 on a short lattice, lengths on both sides of k: the sequence ends inside the dense levels, at the first chain
+    position, and beyond; in both dtypes a sequence longer than T is -inf, not NaN."""
+    from oracle import crf_ref
+    rng = np.random.default_rng(70 + sl)
+    T, S = 8, 4 ** sl
+    sc = sc_cases.host_scores((T, 4 * S), 80 + sl)
+    for length in list(range(sl + 3)) + [T, T + 1]:
+        seq = rng.integers(0, 4, size=length)
+        lp, _ = crf_ref.seq_logprob(sc, sl, "".join("ACGT"[b] for b in seq), blank=2.0)
+        mine = sr.free_start_logz(sc, seq, sl, 2.0)
+        if length > T:
+            assert np.isneginf(lp) and np.isneginf(mine) and np.isneginf(sr.free_start_logz(sc, seq, sl, 2.0, dtype=np.float32))
+            continue
+        assert abs(mine - lp) < 1e-9 * max(1.0, abs(lp)), (length, mine, lp)
+    assert abs(sr.free_start_logz(sc, [], sl, 2.0) - (T * 2.0 + sl * np.log(4.0))) < 1e-12       # the closed form of the empty sequence
+
+
+def _free_short_rows(sl, T, scores, dtype):
+    targets, lengths = sc_cases.free_short_case(sl, T)
+    return np.array([sr.free_start_logz(scores, sc_cases.bases(targets, lengths, n), sl, sc_cases.BLANK, dtype=dtype)
+                     for n in range(len(lengths))], np.float64)
+
+
+@pytest.mark.parametrize("sl", sc_cases.FREE_STATE_LENS)
+def test_free_start_fp32_run_agrees_with_fp64_on_the_short_cases(sl):
+    """The fp32 run of the restatement is the yardstick of rows without a fixed-start chain: same finite / -inf pattern as fp64, and a
+    distance of fp32 accumulation (measured 3.8e-9 .. 1.4e-5 over the 25 cases, the largest at state_len 5, T = 24, |logz| <= 65)."""
+    for T in sc_cases.FREE_SHORT_T:
+        scores = sc_cases.host_scores((T, 4 * 4 ** sl), 8000 + 100 * sl + T)
+        _, lengths = sc_cases.free_short_case(sl, T)
+        w64, w32 = _free_short_rows(sl, T, scores, np.float64), _free_short_rows(sl, T, scores, np.float32)
+        assert not np.isnan(w64).any() and not np.isnan(w32).any()
+        assert (np.isfinite(w64) == (lengths <= T)).all() and (np.isneginf(w64) == (lengths > T)).all()
+        assert (np.isfinite(w32) == np.isfinite(w64)).all() and (np.isneginf(w32) == np.isneginf(w64)).all()
+        fin = np.isfinite(w64)
+        d = float(np.abs(w32[fin] - w64[fin]).max())
+        print("sl %d T %d: fp32 run vs fp64 %.3e (|logz| <= %.1f)" % (sl, T, d, np.abs(w64[fin]).max()))
+        # worst case of the roundings on the way to one result: per step two adds, the log-sum over four predecessors and the one with
+        # the stay (six), then the running log-sum over the 4^k states; each within a spacing of the largest value
+        assert d <= (6 * T + 4 ** sl) * np.spacing(np.float32(np.abs(w64[fin]).max()))
+        assert abs(w64[0] - (T * sc_cases.BLANK + sl * np.log(4.0))) < 1e-12 and lengths[0] == 0
+
+
+def _instance_from_workspace(handle, N, T, Lmax, k):
+    """The instance row a launch selects, read from the host-only workspace query: its traceback words per step are waves x positions
+    per thread, which differs from row to row."""
+    words = (handle.bh_crf_seq_workspace(N, T, Lmax, k) - 512) // (N * T * 8)
+    return [threads // 64 * per for threads, per in sc_cases.GEOMETRY].index(words)
+
+
+def test_edge_cases_hold_every_row_class_and_reach_every_instance():
+    """What tests/test_gpu_seqdist.py runs on the device, checked here without one: every class of row is in every free-start launch,
+    the widened launch takes the 256 x 4 instance, and the instance sweeps select all seven rows of the list."""
+    from bonito_amd import _lib
+    handle = _lib.lib()
+    assert len(sc_cases.GEOMETRY) == 7 and len({t // 64 * p for t, p in sc_cases.GEOMETRY}) == 7
+    for sl in sc_cases.FREE_STATE_LENS:
+        for T in sc_cases.FREE_SHORT_T:
+            targets, lengths = sc_cases.free_short_case(sl, T)
+            assert targets.dtype == (np.int32 if T % 2 else np.int8)
+            have = set(lengths.tolist())
+            assert have >= set(range(sl)) | {sl, T, T + 1}, (sl, T, have)           # 0, each of 1 .. k-1, k, just fits, cannot fit
+            assert targets.shape[1] == lengths.max() == max(sl + 1, T + 1)
+            assert ((targets != 0) == (np.arange(targets.shape[1])[None, :] < lengths[:, None])).all()
+            assert lengths[-1] == min(sl + 1, T) and (targets[-1, :lengths[-1]] == targets[-1, 0]).all()
+            row = _instance_from_workspace(handle, len(lengths), T, targets.shape[1], sl)
+            assert row == sc_cases.chain_instance(targets.shape[1], sl) and sc_cases.GEOMETRY[row][0] == 64      # one wave
+            wide = sc_cases.widen(targets)
+            assert wide.shape[1] == sc_cases.WIDE and (wide[:, :targets.shape[1]] == targets).all() and not wide[:, targets.shape[1]:].any()
+            row = _instance_from_workspace(handle, len(lengths), T, sc_cases.WIDE, sl)
+            assert row == sc_cases.chain_instance(sc_cases.WIDE, sl) and sc_cases.GEOMETRY[row] == (256, 4)
+            # ... so the four-wave launch mixes rows the prefix kernel finishes with rows the chain kernel finishes
+            assert (lengths < sl).any() and (lengths >= sl).any()
+    rows = set()
+    for npos in sc_cases.NPOS:
+        scores, targets, lengths = sc_cases.free_instance_case(npos)
+        sl, (N, T) = sc_cases.FREE_INSTANCE_SL, scores.shape[:2]
+        assert targets.shape == (3, npos + 1) and T == npos + 4 and lengths.tolist() == [npos + 1, npos + 1, max(2, npos - 1)]
+        assert (targets[0] == targets[0, 0]).all() and (lengths >= sl).all() and (lengths <= T).all()          # every row finite
+        assert ((targets != 0) == (np.arange(npos + 1)[None, :] < lengths[:, None])).all()
+        row = _instance_from_workspace(handle, N, T, targets.shape[1], sl)
+        assert row == sc_cases.chain_instance(targets.shape[1], sl)
+        threads, per = sc_cases.GEOMETRY[row]
+        assert npos <= threads * per and (row == 0 or npos > np.prod(sc_cases.GEOMETRY[row - 1]))
+        rows.add(row)
+        # the plain Log scan's sweep at state_len 1 (Lmax = npos) selects the same row
+        assert _instance_from_workspace(handle, 2, npos + 67, npos, 1) == row
+    assert rows == set(range(7))
+    assert sc_cases.chain_instance(4097, 1) == -1 and handle.bh_crf_seq_workspace(2, 10, 4097, 1) == 0
+    for T in sc_cases.TINY_T:
+        for five in (False, True):
+            raw, ntc, targets, lengths = sc_cases.tiny_log_case(T, five)
+            k = sc_cases.TINY_SL
+            assert lengths.tolist() == [k, k + 1, k + T, k + T + 1] and ntc.shape == (4, T, (5 if five else 4) * 4 ** k)
+            want = sr.log_scan(ntc, targets, lengths, k, five, sc_cases.BLANK)
+            assert np.isfinite(want[:3]).all() and np.isneginf(want[3])
 
 
 def test_new_symbols_are_declared_bound_and_exported():
