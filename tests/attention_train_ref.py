@@ -13,7 +13,31 @@ lse_i = ln sum_j exp(s_ij), P_ij = exp(s_ij - lse_i), O = P V and delta_i = sum_
                                                   q~ and k~ (MFMA operands), the normalised probabilities of the forward's PV product and the
                                                   forward's output (attention_ref's general kernel), P as the operand of dV, dS as the operand
                                                   of dq~ and dk~, and dq, dk, dv once at the store; delta from the rounded O. Everything else fp64.
-    exact(..., defect=NAME)                       a planted defect (DEFECTS), for the test that the bound would catch it
+    exact(..., storage_fp16=True, fp32_places=True)
+                                                  additionally the two places where the kernels' fp32 arithmetic is not small beside their fp16
+                                                  storage. Both show where a query puts all its weight on one key: P = 1 and dP - delta = 0 (a single
+                                                  visible key) or nearly so (the probes of tests/attention_train_cases.py that must not be seen)
+                                                  whatever q~ and k~ round to, so the fp16 roundings above cost nothing, d16 would be 0 and 4 d16
+                                                  unattainable for a correct kernel.
+                                                  (1) dS = P (dP - delta) is the difference of two fp32 sums of 64 products taken in different
+                                                  orders, dP by the MFMA chain and delta sequentially (attn_delta_kernel): here dP is the fp64 sum
+                                                  rounded once to fp32 and delta the kernel's own sequential fp32 sum (feature 0 first; a product
+                                                  of two fp16 values is exact in fp32).
+                                                  (2) q~ and k~ are rounded to fp16 TWICE, by the forward (which leaves lse and out) and again by
+                                                  the backward passes (which recompute s), from fp32 rotations a co - b si that the compiler fuses
+                                                  into one multiply-add at some sites and elements and not at others (csrc/attn_block.h says so,
+                                                  and the forward's bytes are pinned): the two fp32 values differ in their last bit, and about one
+                                                  element in 2^13 rounds to the other fp16 neighbour. exp(s - lse) is then the forward's
+                                                  probability times exp(ulp16(q~) k~): 1 - 2^-11 instead of 1 once |q~| reaches 4. Here the
+                                                  forward's q~, k~ come from the unfused fp32 rotation and the backward's from the fused one
+                                                  (cos and sin rounded to fp32, as in the kernels' table).
+                                                  The probe sweep measures its d16 with this; the Gaussian cases keep the plain form.
+    exact(..., stats=True)                        appends lse and delta [N, H, T] (the layout of the kernels' planes) to the result
+    exact(..., defect=NAME)                       a planted defect (DEFECTS, WINDOW_DEFECTS), for the test that the bound would catch it.
+                                                  WINDOW_DEFECTS are wrong decisions about single (query, key) pairs: drop_left (both passes lose
+                                                  the key at -wl), unmirrored (the key pass walks j - wl .. j + wr), drop_right_key_pass (the key
+                                                  pass loses the query at j - wr), seam_leak (the query pass ignores the chunk bounds and meets the
+                                                  rows of the chunks stored in front of and behind its own)
     autograd(qkv, dout, window)                   fp64 torch autograd through rotary + masked softmax attention
     dist(a, e) = max|a - e| / max|e|;  d16 of a case = dist(exact(storage_fp16=True), exact()) per part: what fp16 storage costs a
     correct kernel. The device test requires dist(kernel, exact) <= 4 d16 per part (the project's rule for attention,
@@ -30,6 +54,7 @@ import attention_ref as ar
 HEAD_DIM = ar.HEAD_DIM
 PARTS = ("dq", "dk", "dv")
 DEFECTS = ("no_delta", "no_scale", "rot_forward", "unmirrored", "drop_left")
+WINDOW_DEFECTS = ("drop_left", "unmirrored", "drop_right_key_pass", "seam_leak")          # wrong decisions about one (query, key) pair
 
 
 def make_case(N, T, H, kind="gauss", seed=0):
@@ -49,32 +74,61 @@ def _rot(x, inverse=False):
     return ar.rotate(x[None, :, None, :], inverse)[0, :, 0]
 
 
-def _one(q, k, v, do, window, s16, defect):
-    """One (chunk, head): q, k, v, do [T, 64] float64 -> (out, dq, dk, dv) [T, 64]."""
+def _delta32(do, out):
+    """attn_delta_kernel's sum: fp32, sequential over the 64 features; do, out [T, 64] hold fp16 values, so every product is exact in fp32."""
+    acc = np.zeros(do.shape[0], np.float32)
+    for d in range(do.shape[1]):
+        acc = acc + (do[:, d] * out[:, d]).astype(np.float32)
+    assert acc.dtype == np.float32
+    return acc.astype(np.float64)[:, None]
+
+
+def _rot32(x, fused):
+    """x [T, 64] fp16 values -> the rotation as the kernels form it in fp32 from the fp32 table: a co - b si and a si + b co with the first
+    product fused into the subtraction / addition (one rounding) or not (two). float64 holding fp32 values."""
+    ang = ar.rotary_angles(x.shape[0], x.shape[1])
+    co, si = np.cos(ang).astype(np.float32).astype(np.float64), np.sin(ang).astype(np.float32).astype(np.float64)
+    f32 = lambda a: a.astype(np.float32).astype(np.float64)
+    a, b = x[:, :x.shape[1] // 2], x[:, x.shape[1] // 2:]
+    first = (lambda p: p) if fused else f32                   # a fp16 value times a fp32 value is exact in fp64
+    return np.concatenate([f32(first(a * co) - f32(b * si)), f32(first(a * si) + f32(b * co))], axis=1)
+
+
+def _one(q, k, v, do, window, s16, defect, fp32_places=False, stats=False):
+    """One (chunk, head): q, k, v, do [T, 64] float64 -> (out, dq, dk, dv) [T, 64]; stats: also (lse, delta) [T]."""
     T = q.shape[0]
     wl, wr = window
     rnd = ar.r16 if s16 else (lambda a: a)
     mask = ar.visible(T, window)
     qt, kt = rnd(_rot(q) * 0.125), rnd(_rot(k))
+    if fp32_places:
+        assert s16, "the fp32 places belong to the fp16-storage form"
+        qt, kt = rnd(_rot32(q, False) * 0.125), rnd(_rot32(k, False))          # the forward's
     out = ar.attend_one(qt, kt, v, mask, False, "normalised" if s16 else None, s16)
     s = np.where(mask, qt @ kt.T, -np.inf)
     m = s.max(axis=1, keepdims=True)
     lse = m + np.log(np.exp(s - m).sum(axis=1, keepdims=True))
+    if fp32_places:
+        qt, kt = rnd(_rot32(q, True) * 0.125), rnd(_rot32(k, True))            # the backward's
     delta = (do * out).sum(axis=1, keepdims=True)
+    dp = do @ v.T
+    if fp32_places:
+        delta, dp = _delta32(do, out), dp.astype(np.float32).astype(np.float64)
     if defect == "no_delta":
         delta = np.zeros_like(delta)
-    dp = do @ v.T
 
     def p_ds(msk):
         p = np.where(msk, np.exp(np.where(msk, qt @ kt.T, 0.0) - lse), 0.0)
         return p, p * (dp - delta)
 
     mq = mk = mask
+    i, j = np.arange(T)[:, None], np.arange(T)[None, :]
     if defect == "drop_left":                     # the key at offset -wl is lost by both passes
-        i, j = np.arange(T)[:, None], np.arange(T)[None, :]
         mq = mk = mask & (j != i - wl)
     if defect == "unmirrored":                    # the key pass walks the queries j - wl .. j + wr instead of j - wr .. j + wl
         mk = ar.visible(T, (wr, wl))
+    if defect == "drop_right_key_pass":           # the key pass loses the query at j - wr
+        mk = mask & (i != j - wr)
     _, ds_q = p_ds(mq)
     p_k, ds_k = p_ds(mk)
     dqt = rnd(ds_q) @ kt
@@ -83,23 +137,49 @@ def _one(q, k, v, do, window, s16, defect):
     back = defect != "rot_forward"
     dq = _rot(dqt, inverse=back) * (1.0 if defect == "no_scale" else 0.125)
     dk = _rot(dkt, inverse=back)
-    return out, rnd(dq), rnd(dk), rnd(dv)
+    res = (out, rnd(dq), rnd(dk), rnd(dv))
+    return res + (lse[:, 0], delta[:, 0]) if stats else res
 
 
-def exact(qkv, dout, window, storage_fp16=False, defect=None):
-    """qkv [N, T, 3, H, 64], dout [N, T, H*64] (the fp16 values the kernels are given) -> (out [N, T, H*64], dq, dk, dv [N, T, H, 64]) float64."""
-    assert defect is None or defect in DEFECTS
+def _leaky_query_pass(q, k, v, do, lse, delta, window, s16):
+    """The planted defect `seam_leak`: the query pass of one head with the chunk bounds ignored. The rows of all chunks are contiguous in
+    memory, so query i of chunk n then also meets the rows of chunk n - 1 and n + 1 that lie at the memory positions i - wl .. i + wr (each
+    rotated by its own position in its own chunk, as it is stored). lse and delta are the correct forward's. q, k, v, do [N, T, 64],
+    lse, delta [N, T] -> dq [N, T, 64]."""
+    N, T, d = q.shape
+    rnd = ar.r16 if s16 else (lambda a: a)
+    qt = np.stack([rnd(_rot(q[n]) * 0.125) for n in range(N)]).reshape(N * T, d)
+    kt = np.stack([rnd(_rot(k[n])) for n in range(N)]).reshape(N * T, d)
+    band = ar.visible(N * T, window)
+    p = np.where(band, np.exp(np.where(band, qt @ kt.T, 0.0) - lse.reshape(-1, 1)), 0.0)
+    ds = p * (do.reshape(N * T, d) @ v.reshape(N * T, d).T - delta.reshape(-1, 1))
+    dqt = (rnd(ds) @ kt).reshape(N, T, d)
+    return np.stack([rnd(_rot(dqt[n], inverse=True) * 0.125) for n in range(N)])
+
+
+def exact(qkv, dout, window, storage_fp16=False, defect=None, fp32_places=False, stats=False):
+    """qkv [N, T, 3, H, 64], dout [N, T, H*64] (the fp16 values the kernels are given) -> (out [N, T, H*64], dq, dk, dv [N, T, H, 64]) float64;
+    stats: also (lse, delta) [N, H, T]."""
+    assert defect is None or defect in DEFECTS + WINDOW_DEFECTS
     qkv = np.asarray(qkv, np.float64)
     N, T, three, H, d = qkv.shape
     assert three == 3 and d == HEAD_DIM
     do = np.asarray(dout, np.float64).reshape(N, T, H, d)
     res = [np.zeros((N, T, H, d)) for _ in range(4)]
+    planes = [np.zeros((N, H, T)) for _ in range(2)]
     for n in range(N):
         for h in range(H):
-            parts = _one(qkv[n, :, 0, h], qkv[n, :, 1, h], qkv[n, :, 2, h], do[n, :, h], window, storage_fp16, defect)
+            parts = _one(qkv[n, :, 0, h], qkv[n, :, 1, h], qkv[n, :, 2, h], do[n, :, h], window, storage_fp16,
+                         None if defect == "seam_leak" else defect, fp32_places, True)
             for r, p in zip(res, parts):
                 r[n, :, h] = p
-    return (res[0].reshape(N, T, H * d),) + tuple(res[1:])
+            for r, p in zip(planes, parts[4:]):
+                r[n, h] = p
+    if defect == "seam_leak":
+        for h in range(H):
+            res[1][:, :, h] = _leaky_query_pass(qkv[:, :, 0, h], qkv[:, :, 1, h], qkv[:, :, 2, h], do[:, :, h], planes[0][:, h], planes[1][:, h],
+                                                window, storage_fp16)
+    return (res[0].reshape(N, T, H * d),) + tuple(res[1:]) + (tuple(planes) if stats else ())
 
 
 def dist(a, e):

@@ -1,5 +1,6 @@
 """tests/attention_train_ref.py pinned on the CPU - the written-out backward against fp64 autograd and central differences, the bound
-4 d16 against planted defects - and the host side of the training attention layer: what bonito_amd.attn and the library refuse without
+4 d16 against planted defects, the probe sweep of tests/attention_train_cases.py (decisive for every case, and the four window defects
+rejected at the widest windows) - and the host side of the training attention layer: what bonito_amd.attn and the library refuse without
 a device, and that header, binding and library agree on the bh_attention_train_* entries."""
 import ctypes as C
 import functools
@@ -12,6 +13,7 @@ import torch
 
 from conftest import ROOT
 import attention_ref as ar
+import attention_train_cases as tc
 import attention_train_ref as tr
 from bonito_amd import _lib, attn
 from bonito_amd.nn import NoTorchCompute
@@ -78,6 +80,84 @@ def test_fp16_storage_is_small_and_every_planted_defect_lies_far_beyond_the_boun
         ratios = {name: tr.dist(g, w) / (4 * d16[name]) for name, g, w in zip(tr.PARTS, got[1:], want[1:])}
         print("  defect %-11s: dist / (4 d16) = %s" % (defect, " ".join("%s %.0f" % kv for kv in ratios.items())))
         assert max(ratios.values()) > 10, (defect, ratios)
+
+
+@pytest.mark.parametrize("case", tc.CASES, ids=tc.case_id)
+def test_probe_sweep_is_decisive_for_every_case(case):
+    """What the device sweep asserts in front of every launch, without a device: 4 d16 < smallest probe effect / 10 per part; and that the
+    case probes what it is there for."""
+    N, T, H, window, need = case
+    ref = tc.references(case)
+    pr = ref["probes"]
+    print("%s: %s" % (tc.case_id(case), "  ".join("%s d16 %.2e effect %.2e (%.1f x 40 d16)" % (
+        p, ref["d16"][p], ref["effects"][p], ref["effects"][p] / (40 * ref["d16"][p]) if ref["d16"][p] else np.inf) for p in tr.PARTS)))
+    assert tc.need_tiles(window) == need
+    tc.check_decisive(tc.case_id(case), ref["d16"], ref["effects"])
+    own = np.broadcast_to(np.arange(N)[:, None, None], pr["pn"].shape)
+    unseen_here, unseen_there = pr["pair"] & ~pr["seen"] & (pr["pn"] == own), pr["pair"] & (pr["pn"] != own)
+    assert not (pr["seen"] & (pr["pn"] != own)).any()         # a row of another chunk must never be seen
+    assert unseen_here.any() or unseen_there.any()
+    if case in tc.RUNG_CASES:
+        t0 = tc.sweep_length(window)
+        assert t0 <= T <= t0 + 15 and pr["seen"].any() and unseen_here.any()
+        i, j = np.nonzero(pr["seen"])[1], pr["pt"][pr["seen"]]          # seen pairs that cross a block seam of 128, in either direction
+        assert (i // 128 < j // 128).any() or window[1] == 0
+        assert (i // 128 > j // 128).any() or window[0] == 0
+    if case in tc.SEAM_CASES or (case in tc.EDGE_CASES and T < max(window)):
+        assert N >= 3 and (pr["pn"][unseen_there] < own[unseen_there]).any() and (pr["pn"][unseen_there] > own[unseen_there]).any()
+
+
+def test_probe_sweep_launches_every_rung_at_both_needs_in_every_direction():
+    got = {}
+    for N, T, H, (wl, wr), need in tc.RUNG_CASES:
+        got.setdefault(need, set()).add("symmetric" if abs(wl - wr) <= 1 else "left" if wr == 0 else "right" if wl == 0 else "other")
+    assert got == {6: {"symmetric", "left", "right"}, 7: {"symmetric", "left", "right"}, 10: {"symmetric", "left", "right"},
+                   11: {"symmetric", "right"}, 18: {"symmetric", "left", "right"}, 19: {"symmetric", "left"},
+                   26: {"symmetric", "left", "right"}}
+    odd = sum(T % 16 != 0 for _, T, _, _, _ in tc.RUNG_CASES)
+    assert len(tc.RUNG_CASES) // 3 <= odd <= 2 * len(tc.RUNG_CASES) // 3 + 1
+    edges = {(T, w) for N, T, H, w, need in tc.EDGE_CASES}
+    assert edges >= {(T, w) for T in (1, 17, 127, 128, 129, 257) for w in ((40, 41), (136, 137))} | {(130, (0, 0)), (130, (1, 7))}
+    assert {(N, T, H, w) for N, T, H, w, need in tc.SEAM_CASES} == {(3, 129, 2, (40, 41)), (3, 144, 2, (200, 200)), (3, 130, 3, (1, 7))}
+    assert all(c in tc.CASES for c in tc.PLANE_CASES)
+
+
+WIDE = {(200, 200): 585, (0, 400): 1041, (400, 0): 1056}          # the widest windows, each at its length in the sweep
+
+
+@pytest.mark.parametrize("window", list(WIDE), ids=lambda v: str(v))
+def test_window_defects_at_the_widest_windows_fail_on_probes(window):
+    """drop_left, unmirrored, drop_right_key_pass (one long chunk) and seam_leak (three chunks shorter than the window) each move a part
+    beyond 10 x (4 d16) on probe inputs, in absolute terms as the device sweep judges. On Gaussian inputs the old criterion
+    (max|a - exact| / max|exact| <= 4 d16 over the tensor) is printed beside it, not asserted: that figure is why the probes exist."""
+    for defects, (N, T, H) in ((("drop_left", "unmirrored", "drop_right_key_pass"), (1, WIDE[window], 1)), (("seam_leak",), (3, 144, 1))):
+        case = (N, T, H, window, tc.need_tiles(window))
+        ref = tc.references(case)
+        tc.check_decisive(tc.case_id(case), ref["d16"], ref["effects"])
+        gq, gd = tr.make_case(N, T, H, "gauss", seed=1)
+        gwant = tr.exact(gq, gd, window)
+        gd16 = tr.d16(gq, gd, window, gwant)
+        for defect in defects:
+            got = tr.exact(ref["qkv"], ref["dout"], window, defect=defect)
+            err = tc.errors(got[1:], ref["want"])
+            ratios = {p: err[p] / (4 * ref["d16"][p]) for p in tr.PARTS}
+            old = {p: tr.dist(g, w) / (4 * gd16[p]) for p, g, w in zip(tr.PARTS, tr.exact(gq, gd, window, defect=defect)[1:], gwant[1:])}
+            print("%s N%d T%d %-19s probes: error / (4 d16) = %s | gauss, old criterion: dist / (4 d16) = %s -> %s" % (
+                window, N, T, defect, " ".join("%s %.0f" % kv for kv in ratios.items()), " ".join("%s %.2f" % kv for kv in old.items()),
+                "caught" if max(old.values()) > 1 else "NOT caught"))
+            if defect == "drop_left":                         # ONE wrong pair on the Gaussian inputs (the key at -wl of one query) under the old criterion
+                i = np.arange(window[0], T)
+                pairs = {"pair": np.zeros((N, T, H), bool), "pn": np.zeros((N, T, H), int), "pt": np.zeros((N, T, H), int)}
+                pairs["pair"][0, i, 0], pairs["pt"][0, i, 0] = True, i - window[0]
+                stats = tr.exact(gq, gd, window, stats=True)
+                for label, fn in (("median", np.median), ("largest", np.max)):
+                    eff = tc.probe_effects(gq, gd, pairs, stats[4], stats[5], reduce=fn)
+                    print("%s N%d T%d one pair at -wl, gauss, old criterion: %s effect / (4 d16 max|exact|) = %s" % (window, N, T, label, " ".join(
+                        "%s %.3f" % (p, eff[p] / (4 * gd16[p] * np.abs(w).max())) for p, w in zip(tr.PARTS, gwant[1:]))))
+            if defect == "unmirrored" and window[0] == window[1]:
+                assert max(err.values()) == 0.0               # a symmetric window is its own mirror: nothing to catch
+            else:
+                assert max(ratios.values()) > 10, (defect, ratios)
 
 
 def test_single_key_reference_and_bound():

@@ -11,6 +11,13 @@ dist(a) = max|a - exact| / max|exact|, each of dq, dk, dv must satisfy dist(kern
 A window under which every query sees one key has exact dq = dk = 0 (d16 = 0): there out = v and dv = dout bytewise, and dq, dk are held to
 the derived bound of attention_train_ref.single_key_bounds.
 
+WINDOW EDGES. On Gaussian inputs under a wide window one wrong (query, key) pair is not safely above 4 d16 in a max-norm. The probe sweep
+(tests/attention_train_cases.py: inputs, case list, the effect of a wrong decision) launches every rung's backward instance on both sides of
+its boundary - symmetric, left-only and right-only windows, the T edges, chunk seams - on inputs whose gradients hang on one pair per query,
+and holds each part to max|kernel - exact| <= 4 d16 in absolute terms after asserting, from the reference alone, that 4 d16 lies below a
+tenth of the smallest effect. The saved planes: lse against the fp64 lse by the same rule, delta against the fp64 sum over the kernel's own
+fp16 out within the derived bound of a sequential fp32 sum.
+
 The rest is exact: equal bytes from call to call, a chunk's bytes independent of the rest of the batch, untouched guard bytes, refusals
 that launch nothing, autograd that hands on the backward's bytes."""
 import ctypes as C
@@ -23,6 +30,7 @@ import numpy as np
 import pytest
 import torch
 
+import attention_train_cases as tc
 import attention_train_ref as tr
 from bonito_amd import _lib, attn
 
@@ -228,6 +236,87 @@ def test_refused_calls_leave_the_outputs_untouched():
         attn.attention_backward(qkv, out, attn.attention_forward(qkv[:1].contiguous(), window)[1], dout, window)
     with pytest.raises(ValueError, match="dout must be float16"):
         attn.attention_backward(qkv, out, saved, dout.float(), window)
+
+
+@functools.lru_cache(maxsize=None)
+def _probe_references(case):
+    """tc.references of a sweep case, computed once on the CPU and never modified."""
+    return tc.references(case)
+
+
+def _probe_call(case, ref):
+    N, T, H, window, _ = case
+    qkv, dout = _dev(ref["qkv"]), _dev(ref["dout"])
+    o = _raw_call(qkv, dout, N, T, H, window)
+    for name in o:
+        assert o[name].guards_intact(), name
+    return o
+
+
+def _planes(o, N, T, H):
+    """-> (lse, delta) [N, H, T] float64 of a raw call: the first N T H floats of `saved` and of the workspace."""
+    return tuple(o[name].t[:N * T * H * 4].view(torch.float32).cpu().numpy().astype(np.float64).reshape(N, H, T) for name in ("saved", "ws"))
+
+
+@pytest.mark.parametrize("case", tc.CASES, ids=tc.case_id)
+def test_backward_window_edges_on_probes(case):
+    """attn_bwd_q_kernel / attn_bwd_kv_kernel <6 | 10 | 18 | 26> at need = 6 | 7, 10 | 11, 18 | 19, 26 and below, on probe inputs. Flipping
+    one probed pair in one pass moves a part by more than 10 x the tolerance (asserted first), so a dropped or admitted key, an unmirrored
+    key pass or a row read across a chunk seam cannot pass. d16 includes the kernels' two fp32 places (attention_train_ref, fp32_places):
+    without them d16 is 0 wherever every query sees one key, and the first run of this sweep on an MI355X had dv off by one fp16 ulp
+    (2.0e-3) at (1, 130, 2, (0, 0)) - the backward's q~ differs from the forward's by an fp16 ulp in a few elements, so its P is
+    1 - 2^-11, not 1, once |q~| reaches 4. Measured on MI355X: DESIGN.md, "Training attention layer"."""
+    N, T, H, window, need = case
+    ref = _probe_references(case)
+    name = "probes N%d T%d H%d %s need %d" % (N, T, H, window, need)
+    tc.check_decisive(name, ref["d16"], ref["effects"])
+    o = _probe_call(case, ref)
+    err = tc.errors(tr.split(o["dqkv"].t.cpu().numpy()), ref["want"])
+    failed = []
+    for part in tr.PARTS:
+        print("%s %s: d16 %.3e kernel %.3e (smallest probe effect %.3e)" % (name, part, ref["d16"][part], err[part], ref["effects"][part]))
+        if not err[part] <= tc.FACTOR * ref["d16"][part]:
+            failed.append((part, err[part], ref["d16"][part]))
+    assert not failed, (name, failed)
+
+
+@functools.lru_cache(maxsize=None)
+def _gauss_lse(N, T, H, window):
+    """(fp64 lse [N, H, T], d16 of lse) of a Gaussian shape."""
+    qkv, dout = _case(N, T, H, "gauss")
+    want = tr.exact(qkv, dout, window, stats=True)[4]
+    return want, float(np.abs(tr.exact(qkv, dout, window, storage_fp16=True, stats=True)[4] - want).max())
+
+
+def _check_planes(name, o, N, T, H, dout, lse_want, lse_d16):
+    lse, delta = _planes(o, N, T, H)
+    d = float(np.abs(lse - lse_want).max())
+    print("%s lse: d16 %.3e kernel %.3e" % (name, lse_d16, d))
+    assert np.isfinite(lse).all() and d <= tc.FACTOR * lse_d16, (name, d, lse_d16)
+    # delta: a sequential fp32 sum of 64 products, each exact in fp32, of dO and the kernel's OWN fp16 out
+    prod = (dout.cpu().numpy().astype(np.float64) * o["out"].t.cpu().numpy().astype(np.float64)).reshape(N, T, H, 64)
+    want = prod.sum(axis=-1).transpose(0, 2, 1)
+    bound = 64 * 2.0 ** -24 * np.abs(prod).sum(axis=-1).transpose(0, 2, 1)
+    dd = np.abs(delta - want)
+    print("%s delta: largest |delta - fp64| %.3e, largest share of its bound %.3f" % (name, dd.max(), (dd / np.maximum(bound, 1e-300)).max()))
+    assert np.isfinite(delta).all() and (dd <= bound).all(), name
+
+
+@pytest.mark.parametrize("N,T,H,window", SHAPES, ids=lambda v: str(v))
+def test_saved_planes_on_gaussian_inputs(N, T, H, window):
+    """lse (the head of `saved`) within 4 d16 of the fp64 lse, d16 = what rounding q~ and k~ to fp16 costs it; delta (the head of the
+    workspace) within 64 2^-24 sum_d |dO_id O_id| of the fp64 sum over the kernel's own out."""
+    qkv, dout = (_dev(a) for a in _case(N, T, H, "gauss"))
+    o = _raw_call(qkv, dout, N, T, H, window)
+    _check_planes("planes gauss %s" % ((N, T, H, window),), o, N, T, H, dout, *_gauss_lse(N, T, H, window))
+
+
+@pytest.mark.parametrize("case", tc.PLANE_CASES, ids=tc.case_id)
+def test_saved_planes_on_probes(case):
+    N, T, H, window, _ = case
+    ref = _probe_references(case)
+    o = _probe_call(case, ref)
+    _check_planes("planes probes %s" % (case,), o, N, T, H, _dev(ref["dout"]), ref["want"][4], ref["d16"]["lse"])
 
 
 with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "attention_block_parent.json")) as _fh:
