@@ -6,6 +6,9 @@ cases on the device, tests/test_seqdist_cpu.py proves without one that they hold
   labels, plus a homopolymer; ``widen`` pads the same rows with zero columns so that the launch takes a four-wave instance.
 * ``free_instance_case``: the free start at state_len 2 with `npos` chain positions, both edges of every instance row.
 * ``tiny_log_case``: the plain Log scan at T below the prefetch depth, lengths k, k + 1, k + T (a move at every step), k + T + 1.
+* ``grad_instance_case``: the chain gradient at state_len 2 with `npos` chain positions, either layout, per-row weights; next to the
+  full-length rows of free_instance_case it holds a row of k and one of k + 1 labels, which run in whatever instance Lmax selects.
+* ``grad_wide_case``: the chain gradient's short rows (k, k + 1, half way, a move at every step, cannot fit) widened to four waves.
 * ``chain_instance``: the row of the (threads, positions per thread) list a launch selects - the arithmetic of csrc/seq_chain.h."""
 import numpy as np
 
@@ -17,6 +20,12 @@ NPOS = (1, 64, 65, 128, 129, 256, 257, 512, 513, 1024, 1025, 2048, 2049, 4096)  
 FREE_INSTANCE_SL = 2
 TINY_T = (1, 2, 3, 5)
 TINY_SL = 3
+GRAD_INSTANCE_SL = 2
+GRAD_INSTANCE_WEIGHTS = (1.0, -1.0, 0.5, 0.0, 2.0)
+GRAD_FIRST_SIZES = (1, 65, 129, 257, 513, 1025, 2049)                         # the first size of each instance row
+GRAD_WIDE_SL = (1, 3, 5)
+GRAD_WIDE_T = (1, 2, 3, 5, 24)
+GRAD_WIDE_WEIGHTS = (1.0, -1.0, 0.5, 2.0, -0.25)
 
 # (threads, positions per thread) of BH_SEQ_INSTANCES, in its order
 GEOMETRY = ((64, 1), (64, 2), (64, 4), (64, 8), (256, 4), (256, 8), (256, 16))
@@ -85,6 +94,37 @@ def tiny_log_case(T, five):
     targets[np.arange(targets.shape[1])[None, :] >= lengths[:, None]] = 0
     raw = host_scores((T, 4, 5 * S) if five else (4, T, 4 * S), 9800 + 10 * T + five)
     return raw, (raw.transpose(1, 0, 2) if five else raw), targets, lengths
+
+
+def grad_instance_case(npos, five):
+    """(raw, scores indexed [n, t, c], targets int8 [5, Lmax], lengths, weights float64 [5]) at state_len 2: Lmax = npos + 1 and
+    T = Lmax + 3 as in free_instance_case; a homopolymer of Lmax, random labels of Lmax, random labels of max(2, Lmax - 2), a row of
+    exactly k labels (one chain position) and one of k + 1 (of k where Lmax = k: one position overall). raw is [T, 5, 80] for the
+    reference layout and [5, T, 64] (with blank = BLANK) for the koi layout; every row fits."""
+    k = GRAD_INSTANCE_SL
+    rng = np.random.default_rng(9900 + 2 * npos + five)
+    Lmax = npos + 1
+    T = Lmax + 3
+    lengths = np.array([Lmax, Lmax, max(2, Lmax - 2), k, min(k + 1, Lmax)], np.int32)
+    targets = rng.integers(1, 5, size=(5, Lmax)).astype(np.int8)
+    targets[0] = 3
+    targets[np.arange(Lmax)[None, :] >= lengths[:, None]] = 0
+    raw = host_scores((T, 5, 5 * 4 ** k) if five else (5, T, 4 * 4 ** k), 10000 + 2 * npos + five)
+    return raw, (raw.transpose(1, 0, 2) if five else raw), targets, lengths, np.array(GRAD_INSTANCE_WEIGHTS)
+
+
+def grad_wide_case(sl, T, five):
+    """(raw, scores indexed [n, t, c], targets int8 [5, WIDE], lengths, weights float64 [5]): rows of k, k + 1, k + (T + 1) // 2 and
+    k + T labels (a move at every step; a homopolymer) and one of k + T + 1, which cannot fit, zero-padded to WIDE columns so that the
+    launch takes the 256 x 4 instance and almost every thread holds no position of any row."""
+    rng = np.random.default_rng(10500 + 100 * sl + 10 * T + five)
+    lengths = np.array([sl, sl + 1, sl + (T + 1) // 2, sl + T, sl + T + 1], np.int32)
+    targets = rng.integers(1, 5, size=(5, sl + T + 1)).astype(np.int8)
+    targets[3] = targets[3, 0]
+    targets[np.arange(targets.shape[1])[None, :] >= lengths[:, None]] = 0
+    S = 4 ** sl
+    raw = host_scores((T, 5, 5 * S) if five else (5, T, 4 * S), 10600 + 100 * sl + 10 * T + five)
+    return raw, (raw.transpose(1, 0, 2) if five else raw), widen(targets), lengths, np.array(GRAD_WIDE_WEIGHTS)
 
 
 def bases(targets, lengths, n):

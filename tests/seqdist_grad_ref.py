@@ -5,6 +5,7 @@ dense_logz, whose fp32 run is the reference-order scan, and its mirror), is the 
 autograd anywhere: the torch restatement's backward is NaN at unreachable positions (logaddexp(-inf, -inf)).
 
 * ``chain_grad``: posterior edge occupancy of the target chain, scattered onto the score elements the edges gather.
+* ``chain_grad_banded``: the same numbers bit for bit (logz, grad, share), computed row by row over the reachable cells only.
 * ``dense_grad``: posteriors of CTC_CRF.logZ (every edge of every state).
 * ``torch_dense_posteriors``: the reference's own expression for SequenceDist.posteriors - autograd of its logZ scan, as the koi
   stub of tests/golden/make_golden.py computes it (dense: every state is reachable, so autograd is safe there).
@@ -62,6 +63,71 @@ def chain_grad(scores, targets, lengths, state_len, layout_5s, blank=None, dtype
         used.append(move_idx[i, :max(npos[i] - 1, 0)])
         used = np.concatenate(used)
         share[i] = np.bincount(used).max() if used.size else 0
+    return {"logz": logz, "grad": grad, "stay_total": stay_total, "move_total": move_total, "share": share}
+
+
+def chain_grad_banded(scores, targets, lengths, state_len, layout_5s, blank=None, dtype=np.float64, weight=None):
+    """chain_grad, row by row and only over the cells a path can pass: before step t a row of `npos` positions is alive at
+    max(0, npos - 1 - (T - t)) <= j <= min(npos - 1, t) - to the left of that band the end is out of reach (beta = -inf), to the
+    right nothing has arrived (alpha = -inf), and either way chain_grad adds an exact zero there. Inside the band every operation is
+    chain_grad's own, on the same operands, in the same order, so the result is bit for bit chain_grad's in either dtype
+    (tests/test_seqdist_grad_cpu.py asserts that) at a cost of rows x T x band instead of rows x T x Lmax: what makes a 4096-position
+    case with T = Lmax + 3 a matter of a second."""
+    stay_idx, move_idx = sr.edge_indices(targets, state_len, layout_5s)
+    N, T, C = scores.shape
+    lens = np.asarray(lengths).astype(np.int64)
+    w = np.ones(N, dtype) if weight is None else np.asarray(weight).astype(dtype)
+    logz = np.full(N, -np.inf, dtype)
+    grad = np.zeros((N, T, C), dtype)
+    stay_total = np.zeros((N, T), dtype)
+    move_total = np.zeros((N, T), dtype)
+    share = np.zeros(N, np.int64)
+    ninf = np.full(1, -np.inf, dtype)
+    for i in range(N):
+        npos = int(lens[i]) + 1 - state_len
+        si = None if stay_idx is None else stay_idx[i, :npos]
+        mi = move_idx[i, :npos - 1]
+        used = np.concatenate(([] if si is None else [si]) + [mi])
+        share[i] = np.bincount(used).max() if used.size else 0
+        if npos - 1 > T:
+            continue
+        x = np.asarray(scores[i])
+        lo = [max(0, npos - 1 - (T - t)) for t in range(T + 1)]
+        hi = [min(npos - 1, t) for t in range(T + 1)]
+
+        def stays(t, a, b):                                                    # the stay edges of positions a .. b
+            return x[t, si[a:b + 1]].astype(dtype) if si is not None else dtype(blank)
+
+        alpha = np.full(npos, -np.inf, dtype)
+        alpha[0] = 0
+        kept = []
+        for t in range(T):
+            kept.append(alpha[lo[t]:hi[t] + 1].copy())
+            a, b = lo[t + 1], hi[t + 1]                                        # the band after the step
+            stay = stays(t, a, b)
+            first = max(a, 1)                                                  # mi[j - 1] scores the edge into position j >= 1
+            inc = (alpha[first - 1:b] + x[t, mi[first - 1:b]].astype(dtype)).astype(dtype)
+            if a == 0:
+                inc = np.concatenate([ninf, inc])
+            alpha[a:b + 1] = np.logaddexp(alpha[a:b + 1] + stay, inc).astype(dtype)
+        logz[i] = alpha[npos - 1]
+        lz = logz[i]
+        beta = np.full(npos + 1, -np.inf, dtype)                               # (one past the end: no edge leaves the last position)
+        beta[npos - 1] = 0
+        for t in range(T - 1, -1, -1):
+            a, b = lo[t], hi[t]
+            stay = stays(t, a, b)
+            move = x[t, mi[a:b + 1]].astype(dtype)                             # the edges j -> j + 1 for a <= j <= min(b, npos - 2)
+            m = move.shape[0]
+            st = (stay + beta[a:b + 1]).astype(dtype)
+            inn = (move + beta[a + 1:a + 1 + m]).astype(dtype)
+            ps = np.exp(kept[t] + st - lz).astype(dtype)
+            pm = np.exp(kept[t][:m] + inn - lz).astype(dtype)
+            stay_total[i, t], move_total[i, t] = ps.sum(), pm.sum()
+            if si is not None:
+                np.add.at(grad[i, t], si[a:b + 1], ps * w[i])
+            np.add.at(grad[i, t], mi[a:a + m], pm * w[i])
+            beta[a:b + 1] = np.logaddexp(st, np.concatenate([inn, ninf]) if m == b - a else inn).astype(dtype)
     return {"logz": logz, "grad": grad, "stay_total": stay_total, "move_total": move_total, "share": share}
 
 

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+import seqdist_cases as sc_cases
 import seqdist_ref as sr
 import seqdist_grad_ref as gr
 from bonito_amd import decode
@@ -152,10 +153,12 @@ def _geometry_case(npos):
     return x, targets, np.array([npos, npos], np.int32)
 
 
-@pytest.mark.parametrize("npos", [1, 64, 65, 128, 129, 512, 513, 1024, 1025, 2048, 4096])
+@pytest.mark.parametrize("npos", sc_cases.NPOS)
 def test_geometry_every_positions_per_thread(npos):
     """C = 20, so repeated elements are everywhere: every single-wave P (1, 2, 4, 8) and every four-wave P (4, 8, 16) is hit, each at
-    its first and last size."""
+    its first and last size - the sizes of seqdist_cases.NPOS, which the forward scans sweep too (an earlier list of its own left
+    out 256, 257 and 2049: the last size of 64 x 4 and the first of 64 x 8 and of 256 x 16). State_len 1, the [T, N, 5S] layout, equal
+    lengths and unit weights only: test_instance_sweep... below takes the other layout, k-mers, short rows and the flags there."""
     x, targets, lengths = _geometry_case(npos)
     ntc = _ntc(x, True)
     r64 = gr.chain_grad(ntc, targets, lengths, 1, True)
@@ -351,3 +354,198 @@ def test_gradient_steps_lower_the_fp64_loss():
         trace.append(_loss64(x.detach().half(), c))
     print("fp64 loss over ten steps: " + " ".join("%.4f" % v for v in trace))
     assert all(b < a for a, b in zip(trace, trace[1:])), trace
+
+
+# ---- every instance, layout and row class (cases of tests/seqdist_cases.py; tests/test_seqdist_grad_cpu.py proves what they reach) ------
+def _chain_refs(ntc, targets, lengths, sl, five, wt):
+    """fp64 truth and g32 of one case through the banded restatement (bit for bit chain_grad, see its CPU test)."""
+    args = (ntc, targets, lengths, sl, five, None if five else sc_cases.BLANK)
+    r64 = gr.chain_grad_banded(*args, weight=wt)
+    r32 = gr.chain_grad_banded(*args, weight=wt, dtype=np.float32)
+    return r64, float(np.abs(r32["grad"].astype(np.float64) - r64["grad"]).max())
+
+
+def _chain_bound(r64, g32, wt, want, dtype):
+    return 4 * g32 + 2.0 ** -30 * (r64["share"] * np.abs(wt))[:, None, None] + _rounding(want, dtype)
+
+
+@pytest.mark.parametrize("five", [False, True], ids=["koi", "5S"])
+@pytest.mark.parametrize("npos", sc_cases.NPOS)
+def test_instance_sweep_layouts_short_rows_and_flags(npos, five):
+    """grad_instance_case: state_len 2 (real k-mer gather offsets; C = 80 / 64, so most elements have no owner at small sizes and the
+    homopolymer piles every edge on two of them), both layouts, weights 1, -1, 0.5, 0, 2, and next to the full-length rows one of k
+    and one of k + 1 labels, which run in whatever instance Lmax selects. logz bit-equal to the forward scan, the weight-0 row exactly
+    zero, in the 5S layout every step's gradient sums to the row's weight. At the first size of each instance: fp32 output, int32
+    targets, a NaN-filled `out` that comes back finite with exact zeros where the fp64 gradient is zero, and accumulate into a strided
+    `out` with guard elements. At 257 and 2049 positions (the first sizes of 64 x 8 and of 256 x 16, the one instance with a prefetch
+    depth of 2): equal bytes from two calls. Measured on MI355X: see DESIGN.md section 6."""
+    sl, blank = sc_cases.GRAD_INSTANCE_SL, None if five else sc_cases.BLANK
+    raw, ntc, targets, lengths, wt = sc_cases.grad_instance_case(npos, five)
+    row = sc_cases.chain_instance(targets.shape[1], sl)
+    assert npos <= np.prod(sc_cases.GEOMETRY[row]) and (row == 0 or npos > np.prod(sc_cases.GEOMETRY[row - 1]))
+    r64, g32 = _chain_refs(ntc, targets, lengths, sl, five, wt)
+    want = r64["grad"]
+    assert np.isfinite(r64["logz"]).all()
+    x = torch.from_numpy(raw).cuda()
+    tg, ln, w = torch.from_numpy(targets), torch.from_numpy(lengths), torch.from_numpy(wt)
+    plain = decode.seq_logz(x, tg, ln, sl, blank)
+    logz, g = decode.seq_logz_grad(x, tg, ln, sl, blank, weight=w)
+    assert torch.equal(logz, plain) and bool(torch.isfinite(logz).all())               # bit for bit the forward scan
+    got = _ntc(g, five).astype(np.float64)
+    dk = float(np.abs(got - want).max())
+    print("npos %d %s %s: g32 %.3e kernel %.3e (share %s)" % (npos, "5S" if five else "koi", sc_cases.GEOMETRY[row], g32, dk, r64["share"].tolist()))
+    assert wt[3] == 0.0 and not got[3].any()                                            # the weight-0 row: exactly zero
+    assert (np.abs(got - want) <= _chain_bound(r64, g32, wt, want, torch.float16)).all(), (dk, g32)
+    if five:                                                                            # a path takes one edge per step
+        total = _chain_bound(r64, g32, wt, want, torch.float16).sum(axis=2)              # the per-element bound, summed over the step
+        ds = np.abs(got.sum(axis=2) - wt[:, None])
+        print("    a step's gradient against the row's weight: %.3e (allowed %.3e .. %.3e)" % (ds.max(), total.min(), total.max()))
+        assert (ds <= total).all()
+    if npos in sc_cases.GRAD_FIRST_SIZES:
+        zero = want == 0
+        assert zero.any() and (not zero.all() or (npos == 1 and not five))               # (one position, koi layout: no edge has an element)
+        # fp32 output into a NaN-filled tensor; then fp16 with int32 targets
+        out = torch.full(x.shape, float("nan"), dtype=torch.float32, device="cuda")
+        lz, g2 = decode.seq_logz_grad(x, tg, ln, sl, blank, weight=w, out=out)
+        assert g2 is out and torch.equal(lz, plain)
+        got32 = _ntc(out, five).astype(np.float64)
+        assert np.isfinite(got32).all() and not got32[zero].any() and not got32[3].any()
+        d32 = float(np.abs(got32 - want).max())
+        assert (np.abs(got32 - want) <= _chain_bound(r64, g32, wt, want, torch.float32)).all(), (d32, g32)
+        out = torch.full(x.shape, float("nan"), dtype=torch.float16, device="cuda")
+        lz, _ = decode.seq_logz_grad(x, tg.to(torch.int32), ln, sl, blank, weight=w, out=out)
+        assert torch.equal(lz, plain) and torch.equal(out, g)                            # int32 rows: the same bits; every element written
+        assert not _ntc(out, five)[zero].any()
+        worst = 0.0
+        for dtype in (torch.float16, torch.float32):
+            fill = 3.0
+            buf, view, mask = _guarded_out(x.shape, dtype, fill)
+            lz, g3 = decode.seq_logz_grad(x, tg, ln, sl, blank, weight=w, out=view, accumulate=True)
+            assert g3 is view and torch.equal(lz, plain)
+            assert bool((buf[~mask] == fill).all()), "guard elements around the strided gradient were written"
+            acc = _ntc(view, five).astype(np.float64)
+            assert (acc[zero] == fill).all() and (acc[3] == fill).all()                  # nothing gathered, weight 0: the fill itself
+            worst = max(worst, float(np.abs(acc - (want + fill)).max()))
+            assert (np.abs(acc - (want + fill)) <= _chain_bound(r64, g32, wt, want + fill, dtype)).all(), (dtype, worst)
+        print("    first size: fp32 output %.3e, accumulate %.3e" % (d32, worst))
+    if npos in (257, 2049):                                                              # determinism: bit-identical from call to call
+        assert torch.equal(g, decode.seq_logz_grad(x, tg, ln, sl, blank, weight=w)[1])
+        f32 = torch.zeros(x.shape, dtype=torch.float32, device="cuda")
+        a = decode.seq_logz_grad(x, tg, ln, sl, blank, weight=w, out=f32)[1].clone()
+        assert torch.equal(a, decode.seq_logz_grad(x, tg, ln, sl, blank, weight=w, out=f32)[1])
+
+
+@pytest.mark.parametrize("five", [False, True], ids=["koi", "5S"])
+@pytest.mark.parametrize("T", sc_cases.GRAD_WIDE_T)
+@pytest.mark.parametrize("sl", sc_cases.GRAD_WIDE_SL)
+def test_short_rows_in_a_four_wave_launch(sl, T, five):
+    """grad_wide_case: rows of k, k + 1, k + (T + 1) // 2 and k + T labels and one that cannot fit, zero-padded to 600 columns: the
+    launch takes the 256 x 4 instance, where all but one or a few threads hold no position of the row, most store no alpha, and thread 0
+    picks logz. T = 1, 2, 3 lie below the prefetch depth. Both output types, overwrite and accumulate, guard elements."""
+    blank = None if five else sc_cases.BLANK
+    raw, ntc, targets, lengths, wt = sc_cases.grad_wide_case(sl, T, five)
+    row = sc_cases.chain_instance(targets.shape[1], sl)
+    assert sc_cases.GEOMETRY[row] == (256, 4) and targets.shape[1] == sc_cases.WIDE       # a four-wave row
+    r64, g32 = _chain_refs(ntc, targets, lengths, sl, five, wt)
+    fin = np.isfinite(r64["logz"])
+    assert fin.tolist() == [True, True, True, True, False] and np.isneginf(r64["logz"][4])
+    x = torch.from_numpy(raw).cuda()
+    tg = torch.from_numpy(targets).to(torch.int32 if T % 2 else torch.int8)
+    ln, w = torch.from_numpy(lengths), torch.from_numpy(wt)
+    plain = decode.seq_logz(x, tg, ln, sl, blank)
+    assert np.isneginf(plain.cpu().numpy()[4]) and np.isfinite(plain.cpu().numpy()[:4]).all()
+    worst = {torch.float16: 0.0, torch.float32: 0.0}
+    for dtype in (torch.float16, torch.float32):
+        for accumulate in (False, True):
+            fill = 3.0
+            buf, out, mask = _guarded_out(x.shape, dtype, fill)
+            logz, g = decode.seq_logz_grad(x, tg, ln, sl, blank, weight=w, out=out, accumulate=accumulate)
+            assert g is out and torch.equal(logz, plain)
+            assert bool((buf[~mask] == fill).all()), "guard elements around the strided gradient were written"
+            base = fill if accumulate else 0.0
+            want = r64["grad"] + base
+            got = _ntc(out, five).astype(np.float64)
+            assert (got[4] == base).all()                                                # does not fit: nothing added / zeros
+            assert (got[r64["grad"] == 0] == base).all()
+            worst[dtype] = max(worst[dtype], float(np.abs(got - want).max()))
+            assert (np.abs(got - want) <= _chain_bound(r64, g32, wt, want, dtype)).all(), (dtype, accumulate, worst, g32)
+    print("wide sl %d T %d %s: g32 %.3e kernel fp32 %.3e fp16 %.3e (share %s)"
+          % (sl, T, "5S" if five else "koi", g32, worst[torch.float32], worst[torch.float16], r64["share"].tolist()))
+
+
+@pytest.mark.parametrize("five", [False, True], ids=["koi", "5S"])
+@pytest.mark.parametrize("sl", [1, 2, 3, 4, 5])
+def test_dense_gradient_below_the_prefetch_depth(sl, five):
+    """T = 1, 2, 3 (below the prefetch depth 4 in both directions) and 5, every state_len - at 1 and 2 the workgroup of 64 threads is
+    mostly inactive - N = 3 with weights 1, -0.5, 0: against dense_grad in fp64 within 4 x g32 + the output rounding; the weight-0 row
+    exactly zero."""
+    blank = None if five else sc_cases.BLANK
+    wt = np.array([1.0, -0.5, 0.0])
+    C = (5 if five else 4) * 4 ** sl
+    for T in sc_cases.TINY_T:
+        raw = sc_cases.host_scores((T, 3, C) if five else (3, T, C), 11000 + 100 * sl + 10 * T + five)
+        ntc = raw.transpose(1, 0, 2) if five else raw
+        _, d64 = gr.dense_grad(ntc, sl, five, blank, weight=wt)
+        _, d32 = gr.dense_grad(ntc, sl, five, blank, weight=wt, dtype=np.float32)
+        gd32 = float(np.abs(d32.astype(np.float64) - d64).max())
+        x = torch.from_numpy(raw).cuda()
+        worst = {}
+        for xin in (x, x.float()):
+            lz, g = decode.logz_grad(xin, sl, blank, weight=torch.from_numpy(wt))
+            assert g.dtype == xin.dtype and g.shape == xin.shape
+            got = _ntc(g, five).astype(np.float64)
+            assert not got[2].any()                                                      # weight 0: exactly zero
+            worst[xin.dtype] = float(np.abs(got - d64).max())
+            assert (np.abs(got - d64) <= 4 * gd32 + _rounding(d64, xin.dtype)).all(), (T, xin.dtype, worst, gd32)
+            assert bool(torch.isfinite(lz).all())
+        print("dense sl %d %s T %d: g32 %.3e kernel fp32 %.3e fp16 %.3e" % (sl, "5S" if five else "koi", T, gd32, worst[torch.float32], worst[torch.float16]))
+
+
+def test_ctc_loss_backward_through_a_four_wave_launch():
+    """ctc_loss(...).backward() at state_len 2 on [T = 640, N = 3, 80] scores with targets of 600, 300 and 2 labels: 599 chain positions
+    take the 256 x 4 instance, the two-label row is one position inside it. normalise_scores on and off, reduction "mean" and "none"
+    with an upstream vector: x.grad against (dense64 - chain64) * w with the bound of test_fixture_ctc_loss_backward; the loss
+    bit-equal to the no-grad path."""
+    sl, T, N, Lmax = 2, 640, 3, 600
+    assert sc_cases.GEOMETRY[sc_cases.chain_instance(Lmax, sl)] == (256, 4)
+    raw = sc_cases.host_scores((T, N, 5 * 4 ** sl), 11900)
+    ntc = raw.transpose(1, 0, 2)
+    lengths = np.array([600, 300, 2], np.int32)
+    targets = np.random.default_rng(11901).integers(1, 5, size=(N, Lmax)).astype(np.int8)
+    targets[np.arange(Lmax)[None, :] >= lengths[:, None]] = 0
+    c64 = gr.chain_grad_banded(ntc, targets, lengths, sl, True)
+    c32 = gr.chain_grad_banded(ntc, targets, lengths, sl, True, dtype=np.float32)
+    _, d64 = gr.dense_grad(ntc, sl, True)
+    _, d32 = gr.dense_grad(ntc, sl, True, dtype=np.float32)
+    g32c = float(np.abs(c32["grad"].astype(np.float64) - c64["grad"]).max())
+    g32d = float(np.abs(d32.astype(np.float64) - d64).max())
+    assert np.isfinite(c64["logz"]).all()
+    lens = lengths.astype(np.float64)
+    share = c64["share"].astype(np.float64)
+    sd = CTC_CRF(sl, ALPHABET)
+    base = torch.from_numpy(raw).cuda()
+    tg, ln = torch.from_numpy(targets), torch.from_numpy(lengths)
+    up = np.array([0.75, -1.25, 2.0])
+    for norm in (True, False):
+        D = (d64 if norm else 0.0) - c64["grad"]
+        mag = (d64 if norm else 0.0) + c64["grad"]
+        err = 4 * g32c + (4 * g32d if norm else 0.0) + 2.0 ** -30 * share[:, None, None] + 2.0 ** -22 * mag
+        for reduction in ("mean", "none"):
+            x = base.clone().requires_grad_(True)
+            kw = dict(reduction=reduction, normalise_scores=norm)
+            loss = sd.ctc_loss(x, tg, ln, **kw)
+            with torch.no_grad():
+                assert torch.equal(loss.detach(), sd.ctc_loss(base, tg, ln, **kw))         # bit-equal to the no-grad path
+            if reduction == "none":
+                loss.backward(torch.from_numpy(up).to(loss))
+                w = up / lens
+            else:
+                loss.backward()
+                w = np.full(N, 1.0 / N) / lens
+            want = D * w[:, None, None]
+            assert x.grad.dtype == torch.float16 and x.grad.shape == x.shape
+            got = _ntc(x.grad, True).astype(np.float64)
+            bound = err * np.abs(w)[:, None, None] + _rounding(want, torch.float16)
+            dk = float(np.abs(got - want).max())
+            print("wide ctc_loss norm=%d %s: g32 chain %.3e dense %.3e, backward vs fp64 %.3e" % (norm, reduction, g32c, g32d, dk))
+            assert (np.abs(got - want) <= bound).all(), dk

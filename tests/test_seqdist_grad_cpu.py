@@ -1,6 +1,8 @@
 """Gradients of the CTC-CRF log-sums without a GPU: the alpha-beta restatement (tests/seqdist_grad_ref.py) against central differences
 of the fp64 scans, against posteriors from exhaustive enumeration, the sum-to-one property the fixed-point combine of the kernel rests
-on, the four new ABI symbols, and the argument errors of the new Python surface."""
+on, the four new ABI symbols, and the argument errors of the new Python surface. The edge cases of tests/seqdist_cases.py that
+tests/test_gpu_seqdist_grad.py runs on the device: they reach all seven instances at both edges and the four-wave row, hold every row
+class, and the banded restatement those tests use is chain_grad bit for bit."""
 import os
 import re
 
@@ -9,6 +11,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+import seqdist_cases as sc_cases
 import seqdist_ref as sr
 import seqdist_grad_ref as gr
 
@@ -179,3 +182,107 @@ def test_gradient_surface_refuses_host_tensors():
         with pytest.raises(NoTorchCompute):                                  # the plain scans return plain tensors
             decode.seq_logz(x, tg, ln, 3)
     assert "forward value only" not in (CTC_CRF.ctc_loss.__doc__ + decode.seq_logz.__doc__)
+
+
+# ---- the cases tests/test_gpu_seqdist_grad.py runs on the device (tests/seqdist_cases.py), proved here without one -----------------------
+def _grad_rows(handle, N, T, Lmax, k):
+    """Positions kept per step by the gradient launch, from its host-only workspace query."""
+    return (handle.bh_crf_seq_grad_workspace(N, T, Lmax, k) - 512) // (N * T * 4)
+
+
+def test_gradient_cases_reach_every_instance_at_both_edges_and_the_four_wave_row():
+    from bonito_amd import _lib
+    handle = _lib.lib()
+    k = sc_cases.GRAD_INSTANCE_SL
+    edges, firsts = set(), []
+    for npos in sc_cases.NPOS:
+        for five in (False, True):
+            raw, ntc, targets, lengths, wt = sc_cases.grad_instance_case(npos, five)
+            Lmax, T = npos + 1, npos + 4
+            assert raw.dtype == np.float16 and raw.shape == ((T, 5, 80) if five else (5, T, 64)) and ntc.shape[:2] == (5, T)
+            assert targets.shape == (5, Lmax) and targets.dtype == np.int8
+            assert lengths.tolist() == [Lmax, Lmax, max(2, Lmax - 2), k, min(k + 1, Lmax)] and (lengths - k <= T).all()
+            assert wt.tolist() == [1.0, -1.0, 0.5, 0.0, 2.0]
+            assert (targets[0] == targets[0, 0]).all() and (np.unique(targets[1]).size > 1 or npos < 64)
+            assert ((targets != 0) == (np.arange(Lmax)[None, :] < lengths[:, None])).all()
+            row = sc_cases.chain_instance(Lmax, k)
+            threads, per = sc_cases.GEOMETRY[row]
+            first = row == 0 and npos == 1 or row > 0 and npos == np.prod(sc_cases.GEOMETRY[row - 1]) + 1
+            last = npos == threads * per
+            assert first != last                                                # every size of NPOS is an edge of its row
+            edges.add((row, "first" if first else "last"))
+            if first and five:
+                firsts.append(npos)
+            # the library selects that row: the forward launch by its traceback words, the gradient by its alpha pitch
+            words = (handle.bh_crf_seq_workspace(5, T, Lmax, k) - 512) // (5 * T * 8)
+            assert [t // 64 * p for t, p in sc_cases.GEOMETRY].index(words) == row
+            assert _grad_rows(handle, 5, T, Lmax, k) == -(-npos // per) * per
+    assert edges == {(r, e) for r in range(7) for e in ("first", "last")}
+    assert tuple(firsts) == sc_cases.GRAD_FIRST_SIZES                          # where the device test adds the flags
+    for sl in sc_cases.GRAD_WIDE_SL:
+        for T in sc_cases.GRAD_WIDE_T:
+            for five in (False, True):
+                raw, ntc, targets, lengths, wt = sc_cases.grad_wide_case(sl, T, five)
+                S = 4 ** sl
+                assert raw.shape == ((T, 5, 5 * S) if five else (5, T, 4 * S)) and targets.shape == (5, sc_cases.WIDE)
+                assert lengths.tolist() == [sl, sl + 1, sl + (T + 1) // 2, sl + T, sl + T + 1]
+                assert ((targets != 0) == (np.arange(sc_cases.WIDE)[None, :] < lengths[:, None])).all()
+                assert (targets[3, :lengths[3]] == targets[3, 0]).all()
+                row = sc_cases.chain_instance(sc_cases.WIDE, sl)
+                assert row == 4 and sc_cases.GEOMETRY[row] == (256, 4)
+                assert _grad_rows(handle, 5, T, sc_cases.WIDE, sl) == -(-(sc_cases.WIDE + 1 - sl) // 4) * 4
+                # all but the first few of the 256 threads hold no position of any row
+                assert (lengths.max() + 1 - sl + 3) // 4 <= 7
+
+
+@pytest.mark.parametrize("five", [False, True], ids=["koi", "5S"])
+def test_restatement_on_the_instance_cases(five):
+    """Every row of grad_instance_case fits (finite logz); the homopolymer's share is its number of chain positions (5S: the stay
+    edges of all of them gather one element; koi layout, where the stay edge has no element: its npos - 1 move edges do); in the 5S
+    layout every step's posteriors sum to the row's weight."""
+    k, blank = sc_cases.GRAD_INSTANCE_SL, None if five else sc_cases.BLANK
+    for npos in sc_cases.NPOS:
+        raw, ntc, targets, lengths, wt = sc_cases.grad_instance_case(npos, five)
+        r = gr.chain_grad_banded(ntc, targets, lengths, k, five, blank, weight=wt)
+        assert np.isfinite(r["logz"]).all(), npos
+        assert r["share"][0] == (npos if five else npos - 1)
+        assert np.abs(r["stay_total"] + r["move_total"] - 1.0).max() < 1e-9
+        if five:
+            assert np.abs(r["grad"].sum(axis=2) - wt[:, None]).max() < 1e-9
+        assert not r["grad"][3].any()
+
+
+@pytest.mark.parametrize("five", [False, True], ids=["koi", "5S"])
+@pytest.mark.parametrize("sl", sc_cases.GRAD_WIDE_SL)
+def test_restatement_on_the_widened_cases(sl, five):
+    """-inf for exactly the row meant not to fit, finite for the others; the homopolymer (a move at every step) shares one element
+    among its T + 1 stay edges (koi layout: its T move edges); 5S: a step's posteriors sum to the weight, to zero where nothing fits."""
+    blank = None if five else sc_cases.BLANK
+    for T in sc_cases.GRAD_WIDE_T:
+        raw, ntc, targets, lengths, wt = sc_cases.grad_wide_case(sl, T, five)
+        r = gr.chain_grad(ntc, targets, lengths, sl, five, blank, weight=wt)
+        assert np.isfinite(r["logz"][:4]).all() and np.isneginf(r["logz"][4])
+        assert r["share"][3] == (T + 1 if five else T)
+        assert not r["grad"][4].any()
+        if five:
+            assert np.abs(r["grad"].sum(axis=2) - np.where(np.arange(5) < 4, wt, 0.0)[:, None]).max() < 1e-9
+        for dtype in (np.float64, np.float32):
+            a = gr.chain_grad(ntc, targets, lengths, sl, five, blank, weight=wt, dtype=dtype)
+            b = gr.chain_grad_banded(ntc, targets, lengths, sl, five, blank, weight=wt, dtype=dtype)
+            assert all(np.array_equal(a[key], b[key]) for key in ("logz", "grad", "share"))
+
+
+@pytest.mark.parametrize("five", [False, True], ids=["koi", "5S"])
+def test_banded_restatement_is_chain_grad_bit_for_bit(five):
+    """chain_grad_banded skips only cells where chain_grad adds an exact zero: logz, grad and share equal chain_grad's bit for bit, in
+    fp64 and in fp32, on the instance cases up to 257 positions (rows of Lmax, Lmax - 2, k and k + 1 labels, weights of both signs and
+    zero) - and on every widened case, a row that cannot fit included (the test above)."""
+    k, blank = sc_cases.GRAD_INSTANCE_SL, None if five else sc_cases.BLANK
+    for npos in [n for n in sc_cases.NPOS if n <= 257]:
+        raw, ntc, targets, lengths, wt = sc_cases.grad_instance_case(npos, five)
+        for dtype in (np.float64, np.float32):
+            a = gr.chain_grad(ntc, targets, lengths, k, five, blank, weight=wt, dtype=dtype)
+            b = gr.chain_grad_banded(ntc, targets, lengths, k, five, blank, weight=wt, dtype=dtype)
+            assert all(np.array_equal(a[key], b[key]) for key in ("logz", "grad", "share")), (npos, dtype)
+            assert a["grad"].dtype == b["grad"].dtype == dtype
+            assert np.abs(a["stay_total"] - b["stay_total"]).max() < 1e-6 and np.abs(a["move_total"] - b["move_total"]).max() < 1e-6
