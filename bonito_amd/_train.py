@@ -1,6 +1,11 @@
-"""What the training layers of bonito_amd.rnn and bonito_amd.train_ops share: the argument checks and the autograd wrapper."""
+"""What the training layers of bonito_amd.rnn, bonito_amd.attn and bonito_amd.train_ops share - the argument checks, the workspace query
+and the autograd wrapper - and what the two forward_train plans (crf.model.SeqdistModel, ctc.model.Model) share.
+
+A plan is a list of steps. A step is a callable (h, seed) -> h that applies one device layer with every folding decision already made;
+`run` applies them in order. `seed` is the dropout seed of the call, which is drawn after the plan (a refused call draws nothing)."""
 import torch
 
+from bonito_amd import _lib, nn as bnn
 from bonito_amd.nn import NoTorchCompute
 
 
@@ -20,6 +25,40 @@ def master(t, shape, name, what):
 def half(t, shape, name, what):
     if t.dtype != torch.float16 or tuple(t.shape) != tuple(shape):
         raise ValueError("%s: %s must be float16 %s, got %s %s" % (what, name, tuple(shape), t.dtype, tuple(t.shape)))
+
+
+def half_dev(t, shape, name, what):
+    """A tensor the caller did not make itself (an upstream gradient, a kept output): on the device, fp16, of this shape -> contiguous."""
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise NoTorchCompute("%s runs on a HIP device only; %s is not a device tensor" % (what, name))
+    half(t, shape, name, what)
+    return t.contiguous()
+
+
+def dtype_names(dtypes):
+    return " or ".join(str(d).replace("torch.", "") for d in dtypes)
+
+
+def act_name(activation):
+    """None, a name or an activation module -> the name the library knows it by (None stays None)."""
+    name = activation if activation is None or isinstance(activation, str) else getattr(activation, "name", type(activation).__name__.lower())
+    return "swish" if name == "silu" else name
+
+
+def unsupported_shape(what, **dims):
+    """The refusal of a shape the library returned no workspace size for; a dimension that is a pair (the attention window) reads
+    `window (left, right)`."""
+    return ValueError("%s: shape %s is not supported"
+                      % (what, " ".join(("%s %s" if isinstance(v, tuple) else "%s=%d") % (k, v) for k, v in dims.items())))
+
+
+def workspace(entry, what, window=(), **dims):
+    """The bytes entry point `entry` of the library asks for at these dimensions (its arguments, in order, then the attention window's
+    two); 0 is its refusal of the shape."""
+    nbytes = getattr(_lib.lib(), entry)(*dims.values(), *window)
+    if nbytes == 0:
+        raise unsupported_shape(what, **dims, **({"window": window} if window else {}))
+    return nbytes
 
 
 def devices(named, what):
@@ -70,3 +109,54 @@ class HalfLayer2(torch.autograd.Function):
         da, dx, *rest = ctx.backward_fn(ctx.saved_tensors, dy.to(torch.float16), need)
         return (None, None, da.to(ctx.dtypes[0]) if need[0] else None, dx.to(ctx.dtypes[1]) if need[1] else None) \
             + tuple(g if n else None for g, n in zip(rest, need[2:]))
+
+
+# ---- the plans of forward_train ---------------------------------------------------------------------------------------------------------------
+def run(steps, h, seed=None):
+    for step in steps:
+        h = step(h, seed)
+    return h
+
+
+def clamp_after(mods, i):
+    """The range of a Clamp directly behind layer i, which layer i fuses, or None."""
+    return (float(mods[i + 1].min), float(mods[i + 1].max)) if i + 1 < len(mods) and isinstance(mods[i + 1], bnn.Clamp) else None
+
+
+def next_compute(mods, i):
+    """-> (the layer that consumes layer i's output or None, whether a Permute([2,0,1]) lies between): Permute, Clamp and MakeContiguous
+    are folded."""
+    tm = False
+    for m in mods[i + 1:]:
+        if isinstance(m, bnn.Permute):
+            tm = tm or list(m.dims) == [2, 0, 1]
+        elif not isinstance(m, (bnn.Clamp, bnn.MakeContiguous)):
+            return m, tm
+    return None, tm
+
+
+def pad_channels(weight, bias, pad_in, pad_out):
+    """Zero input and output channels around a convolution's weight [Cout][Cin][K] and bias: the channels a convolution pair carries
+    between them up to a multiple of 8. They stay exactly zero through swish / relu / tanh."""
+    if pad_in:
+        weight = torch.nn.functional.pad(weight, (0, 0, 0, pad_in))
+    if pad_out:
+        weight = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, pad_out))
+        bias = None if bias is None else torch.nn.functional.pad(bias, (0, pad_out))
+    return weight, bias
+
+
+def batchnorm_step(bn, *args, pad=0, **kwargs):
+    """The step of a torch BatchNorm1d in train mode behind a convolution: train_ops.batchnorm(h, weight, bias, the running statistics,
+    momentum, eps, *args, **kwargs) on `pad` zero channels more than bn has, then the batch counter."""
+    from bonito_amd import train_ops
+
+    def step(h, seed):
+        weight, bias = bn.weight, bn.bias
+        if pad:
+            weight, bias = torch.nn.functional.pad(weight, (0, pad)), torch.nn.functional.pad(bias, (0, pad))
+        h = train_ops.batchnorm(h, weight, bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, *args, **kwargs)
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+        return h
+    return step

@@ -18,8 +18,7 @@ import numpy as np
 import torch
 
 from bonito_amd import _lib
-from bonito_amd._train import HalfLayer, devices, half, tensors
-from bonito_amd.nn import NoTorchCompute
+from bonito_amd._train import HalfLayer, devices, dtype_names, half_dev, tensors, workspace
 
 __all__ = ["attention_forward", "attention_backward", "attention", "mha_module", "encoder_layer", "encoder_layer_check", "supported_window",
            "HEAD_DIM"]
@@ -74,7 +73,7 @@ def _shape(qkv, what):
 def _check(qkv, window, what, dtypes=(torch.float16,)):
     tensors([("qkv", qkv)], what)
     if qkv.dtype not in dtypes:
-        raise ValueError("%s: qkv must be %s, got %s" % (what, " or ".join(str(d).replace("torch.", "") for d in dtypes), qkv.dtype))
+        raise ValueError("%s: qkv must be %s, got %s" % (what, dtype_names(dtypes), qkv.dtype))
     N, T, H = _shape(qkv, what)
     wl, wr = _window(window, what)
     devices([("qkv", qkv)], what)
@@ -90,21 +89,12 @@ def _table(device, T):
     return _tables[key]
 
 
-def _half_dev(t, shape, name, what):
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise NoTorchCompute("%s runs on a HIP device only; %s is not a device tensor" % (what, name))
-    half(t, shape, name, what)
-    return t.contiguous()
-
-
 def attention_forward(qkv, window):
     """-> (out fp16 [N][T][H*64] with the bytes of bh_attention, saved): `saved` is the opaque byte buffer attention_backward needs."""
     N, T, H, wl, wr = _check(qkv, window, "attention_forward")
     qkv = qkv.contiguous()
     lib = _lib.lib()
-    nbytes = lib.bh_attention_train_saved_bytes(N, T, H)
-    if nbytes == 0:
-        raise ValueError("attention_forward: shape N=%d T=%d H=%d is not supported" % (N, T, H))
+    nbytes = workspace("bh_attention_train_saved_bytes", "attention_forward", N=N, T=T, H=H)
     with torch.cuda.device(qkv.device):
         tab = _table(qkv.device, T)
         out = torch.empty((N, T, H * HEAD_DIM), dtype=torch.float16, device=qkv.device)
@@ -118,15 +108,13 @@ def attention_backward(qkv, out, saved, dout, window):
     """-> dqkv fp16, shaped like qkv, from the upstream gradient dout fp16 [N][T][H*64]."""
     N, T, H, wl, wr = _check(qkv, window, "attention_backward")
     qkv = qkv.contiguous()
-    out = _half_dev(out, (N, T, H * HEAD_DIM), "out", "attention_backward")
-    dout = _half_dev(dout, (N, T, H * HEAD_DIM), "dout", "attention_backward")
+    out = half_dev(out, (N, T, H * HEAD_DIM), "out", "attention_backward")
+    dout = half_dev(dout, (N, T, H * HEAD_DIM), "dout", "attention_backward")
     lib = _lib.lib()
     if not isinstance(saved, torch.Tensor) or saved.device != qkv.device or saved.dtype != torch.uint8 or saved.dim() != 1 or \
             not saved.is_contiguous() or saved.numel() != lib.bh_attention_train_saved_bytes(N, T, H):
         raise ValueError("attention_backward: `saved` is not what attention_forward returned for N=%d T=%d H=%d" % (N, T, H))
-    nbytes = lib.bh_attention_train_backward_workspace(N, T, H, wl, wr)
-    if nbytes == 0:
-        raise ValueError("attention_backward: shape N=%d T=%d H=%d window (%d, %d) is not supported" % (N, T, H, wl, wr))
+    nbytes = workspace("bh_attention_train_backward_workspace", "attention_backward", N=N, T=T, H=H, window=(wl, wr))
     with torch.cuda.device(qkv.device):
         tab = _table(qkv.device, T)
         dqkv = torch.empty_like(qkv)

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from bonito_amd import decode as hip_decode
-from bonito_amd.engine import HipEncoder
+from bonito_amd.engine import EngineHolder, HipEncoder
 from bonito_amd.nn import (Module, Convolution, LinearCRFEncoder, Serial, Permute, layers, to_dict, from_dict,
                            register, NoTorchCompute)
 
@@ -203,7 +203,7 @@ def rnn_encoder(n_base, state_len, insize=1, first_conv_size=4, stride=5, winlen
 
 
 @register
-class SeqdistModel(Module):
+class SeqdistModel(EngineHolder, Module):
     def __init__(self, encoder, seqdist, n_pre_post_context_bases=None, target_projection=None):
         super().__init__()
         self.seqdist = seqdist
@@ -219,8 +219,6 @@ class SeqdistModel(Module):
             self.target_projection = None
         else:
             self.register_buffer("target_projection", torch.tensor([0] + target_projection), persistent=False)
-        self._hip = None          # HipEncoder (plain object, not a submodule), built lazily
-        self._hip_args = None     # (batchsize, chunksize) requested through use_koi / use_hip
 
     @classmethod
     def from_dict(cls, model_dict, layer_types=None):
@@ -228,47 +226,8 @@ class SeqdistModel(Module):
                       seqdist=CTC_CRF(**model_dict["seqdist"]))
         return cls(**kwargs)
 
-    # ---- accelerator swap point ---------------------------------------------------------------
-    def use_hip(self, batchsize=None, chunksize=None, quantize=None, **_):
-        """Route ``forward`` through the HIP engine. Same keywords as the reference's ``use_koi``.
-        ``quantize=True`` (cli/basecaller.py:186-189, crf/model.py:245) selects the 8-bit recurrent path Q8-1 for every LSTM
-        layer the int8 kernel covers (hidden sizes that are multiples of 48 or 64 up to 512, input size == hidden size);
-        other layers keep the fp16 kernels -- ``model._hip.describe()`` lists what runs where. The default stays fp16."""
-        self._hip_args = (batchsize, chunksize)
-        self._quantize = bool(quantize)
-        self._drop_engine()
-        return self
-
-    use_koi = use_hip
-
-    # The engine snapshots the weights when it is built (first forward). Anything that changes parameters afterwards --
-    # load_state_dict, .half() / .to() / .float() (Module._apply), apply(fuse_bn_) -- drops it, so the next forward lowers
-    # the current weights again instead of silently running stale ones.
-    def _drop_engine(self):
-        eng = self.__dict__.get("_hip")
-        if eng is not None:
-            eng.close()
-        self.__dict__["_hip"] = None
-
-    def load_state_dict(self, *args, **kwargs):
-        self._drop_engine()
-        return super().load_state_dict(*args, **kwargs)
-
-    def _apply(self, fn, *args, **kwargs):
-        self._drop_engine()
-        return super()._apply(fn, *args, **kwargs)
-
-    def _engine(self, x):
-        N, L = x.shape[0], x.shape[-1]
-        if self._hip is not None and (N > self._hip.max_batch or L > self._hip.max_chunk
-                                      or x.device != self._hip.device):
-            self._hip.close()
-            self._hip = None
-        if self._hip is None:
-            bs, cs = self._hip_args if self._hip_args is not None else (None, None)
-            self._hip = HipEncoder(self.encoder, max(int(bs or 0), N), max(int(cs or 0), L), device=x.device,
-                                   quantize=getattr(self, "_quantize", False))
-        return self._hip
+    def _lowering(self):
+        return self.encoder, dict(quantize=getattr(self, "_quantize", False))
 
     def engine_replica(self, x):
         """A second, independent engine over the same weights (own workspace): the basecaller keeps `lanes` batches in flight,
@@ -282,49 +241,22 @@ class SeqdistModel(Module):
             raise NoTorchCompute("bonito_amd models only run on a HIP device; got a %s tensor" % x.device)
         return self._engine(x)(x)
 
-    def forward_train(self, x, norm=None):
-        """The forward of a training step: x cuda fp16 [N,1,L] -> scores in the shape, layout and dtype of ``forward(x)``, INSIDE
-        autograd, so that ``self.loss(self.forward_train(x), targets, lengths).backward()`` leaves a gradient on every trainable
-        parameter. The parameters are the fp32 master weights on x's device; every layer rounds them to fp16 on the device in every
-        call (autocast's arithmetic: bonito_amd.train_ops, bonito_amd.rnn, bonito_amd.attn). Serves the LSTM family - conv x3 ->
-        permute -> LSTM x n -> [linear] -> linearcrfencoder [-> clamp] - and the transformer family - conv x n (no norm) ->
-        permute [0,2,1] -> TransformerEncoderLayer x depth -> LinearUpsample -> linearcrfencoder [-> clamp] - with the folding rules of
-        ``engine.lower``: a Clamp after a Convolution or the head is fused into it, Permute([2,0,1]) is folded into the producing
-        convolution's store, Permute([0,2,1]) is the layout the convolutions store anyway, Permute([1,0,2]) after the head is a no-op
-        (batch-major rows are the scores' layout already), a batch-first LinearUpsample is a linear layer whose [N][T][s D] output is
-        read as [N][s T][D]. Anything else is refused with a ValueError that names the layer. The inference engine is neither built
-        nor dropped.
-
-        ``norm`` says what a Convolution that carries a norm gets. None: it is refused, and forward_train has no side effect.
-        ``"batch"``: a ``bonito_amd.nn.BatchNorm`` in train mode normalises with the statistics of this batch, as the reference's
-        training does (conv with no activation -> ``train_ops.batchnorm`` with the layer's activation, the fused clamp and the
-        time-major store) - and every call REWRITES the module's ``running_mean`` / ``running_var`` buffers and adds one to
-        ``num_batches_tracked``, under ``torch.no_grad()`` too. The inference engine holds the statistics of the moment it was built:
-        drop it (``_drop_engine``) before inference is to see the new ones. A BatchNorm in eval mode (frozen statistics) is refused."""
+    def _train_plan(self, x, norm):
+        """The one walk over the flattened encoder, in front of forward_train's first launch and first side effect: every refusal, and
+        -> the steps to run (bonito_amd._train), each with its folding decisions made: the zero channels that pad a convolution pair to a
+        multiple of 8, the clamp fused into the layer in front of it, the time-major store in front of the LSTM stack, the BatchNorm step
+        behind a normalised convolution and its real channels, batch_major_out of the head, the upsample's view. What is wrong on any
+        device is judged first (structure, shapes, parameter dtypes), then ``norm``, then a CPU x, then parameters on another device."""
         from bonito_amd import attn, nn as bnn, rnn, train_ops
+        from bonito_amd._train import batchnorm_step, clamp_after, next_compute, pad_channels
         from bonito_amd.engine import _flatten
         from bonito_amd.transformer.model import TransformerEncoderLayer
-        if getattr(self, "_quantize", False):
-            raise ValueError("forward_train: quantize (the 8-bit recurrent path) has no training forward; call use_hip(quantize=False)")
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float16 or x.dim() != 3 or x.shape[1] != 1:
-            raise ValueError("forward_train: x must be a float16 tensor [N,1,L], got %s"
-                             % ("%s %s" % (x.dtype, tuple(x.shape)) if isinstance(x, torch.Tensor) else type(x).__name__))
         mods = _flatten(self.encoder)
-        def clamp_after(i):
-            return (float(mods[i + 1].min), float(mods[i + 1].max)) if i + 1 < len(mods) and isinstance(mods[i + 1], bnn.Clamp) else None
-
-        def next_compute(i):            # the layer that consumes layer i's output, and whether a Permute([2,0,1]) lies between
-            tm = False
-            for m in mods[i + 1:]:
-                if isinstance(m, bnn.Permute):
-                    tm = tm or list(m.dims) == [2, 0, 1]
-                elif not isinstance(m, (bnn.Clamp, bnn.MakeContiguous)):
-                    return m, tm
-            return None, tm
-
-        # every refusal comes before the first launch; what is wrong on any device is judged first
-        time_major, width = False, None          # are the activations [T][N][C] here, and how many channels (None: not followed)
+        steps = []
+        layout = "signal"                        # [N][L] -> "nlc" [N][L][C] -> "tnc" [T][N][C] -> "ntc" scores
+        time_major, width = False, None          # has a Permute([2,0,1]) been seen, and how many channels are here (None: not followed)
         length = x.shape[2]                      # positions per chunk behind the convolutions so far
+        pad_in = 0                               # zero channels the convolution in front added to its output
         for i, m in enumerate(mods):
             name = "layer %d (%s)" % (i, type(m).__name__)
             if isinstance(m, TransformerEncoderLayer):
@@ -334,21 +266,35 @@ class SeqdistModel(Module):
                                      "[N][T][C] (permute [0,2,1])" % name)
                 if width is not None and width != m.self_attn.d_model:
                     raise ValueError("forward_train: %s has d_model %d and follows %d channels" % (name, m.self_attn.d_model, width))
+                if layout != "nlc":
+                    raise ValueError("forward_train: %s needs the [N][T][C] output of the convolutions" % name)
+                steps.append(lambda h, seed, m=m: attn.encoder_layer(m, h))
             elif isinstance(m, bnn.LinearUpsample) and not time_major:
                 if not m.batch_first:
                     raise ValueError("forward_train: %s with batch_first=False has no training forward" % name)
                 if m.d_model % 8 != 0 or (width is not None and width != m.d_model):
                     raise ValueError("forward_train: %s needs d_model %% 8 == 0 and as many input channels (d_model %d, %s channels)"
                                      % (name, m.d_model, width))
+                if layout != "nlc":
+                    raise ValueError("forward_train: %s needs [N][T][C] activations" % name)
+                steps.append(lambda h, seed, m=m: train_ops.linear(h, m.linear.weight, m.linear.bias)      # [N][T][s D], which is [N][s T][D]
+                             .view(h.shape[0], h.shape[1] * m.scale_factor, m.d_model))
             elif isinstance(m, bnn.Convolution):
-                width = m.conv.out_channels
+                c, clamp = m.conv, clamp_after(mods, i)
+                nxt, tm = next_compute(mods, i)
+                pad_out = -c.out_channels % 8 if isinstance(nxt, bnn.Convolution) else 0      # zero channels up to a multiple of 8
+                width = c.out_channels
                 if m.norm is not None and norm is None:
                     raise ValueError("forward_train: %s carries a norm (%s); a normalised convolution has no training backward yet"
                                      % (name, getattr(m.norm, "name", type(m.norm).__name__)))
-                if m.conv.groups != 1 or m.conv.dilation[0] != 1:
+                if c.groups != 1 or c.dilation[0] != 1:
                     raise ValueError("forward_train: %s is a grouped / dilated (depthwise, QuartzNet) convolution, which has no training "
                                      "backward" % name)
-                length = train_ops.conv_out_len(length, m.conv.kernel_size[0], m.conv.stride[0], m.conv.padding[0])
+                if layout not in ("signal", "nlc"):
+                    raise ValueError("forward_train: %s follows the permute to time-major activations" % name)
+                if (c.in_channels == 1) != (layout == "signal"):
+                    raise ValueError("forward_train: %s expects %d input channels" % (name, c.in_channels))
+                length = train_ops.conv_out_len(length, c.kernel_size[0], c.stride[0], c.padding[0])
                 if m.norm is not None:
                     norm_name = getattr(m.norm, "name", type(m.norm).__name__)
                     if norm != "batch":
@@ -363,37 +309,62 @@ class SeqdistModel(Module):
                     if m.norm.bn.track_running_stats and m.norm.bn.momentum is None:
                         raise ValueError("forward_train: %s has a BatchNorm with momentum=None (the cumulative average), which is not "
                                          "served" % name)
-                    if (m.conv.out_channels % 8 and not isinstance(next_compute(i)[0], bnn.Convolution)) or m.conv.out_channels > 2048:
+                    if (c.out_channels % 8 and not pad_out) or c.out_channels > 2048:
                         raise ValueError("forward_train: %s normalises %d channels; a multiple of 8 up to 2048 is served (zero padding "
-                                         "only in front of another convolution)" % (name, m.conv.out_channels))
+                                         "only in front of another convolution)" % (name, c.out_channels))
                     if x.shape[0] * length < 2:
                         raise ValueError("forward_train: %s normalises %d value per channel; batch statistics need more than one"
                                          % (name, x.shape[0] * max(length, 0)))
-                clamp = clamp_after(i)
-                if isinstance(next_compute(i)[0], bnn.Convolution) and m.conv.out_channels % 8 and clamp is not None \
-                        and not clamp[0] <= 0.0 <= clamp[1]:
+                if pad_out and clamp is not None and not clamp[0] <= 0.0 <= clamp[1]:
                     raise ValueError("forward_train: %s has %d channels, served by zero padding, and its clamp range %s does not contain 0"
-                                     % (name, m.conv.out_channels, clamp))
+                                     % (name, c.out_channels, clamp))
+                # a convolution, a transformer layer or an upsample behind the permute refuses itself, by its own name
+                if tm and (nxt is None or isinstance(nxt, (bnn.Linear, bnn.LinearCRFEncoder))):
+                    raise ValueError("forward_train: %s stores time-major for a layer that is no LSTM" % name)
+                # a normalised convolution is z = conv(x) as it is; norm, activation, clamp and the store are the BatchNorm step's
+                steps.append(lambda h, seed, c=c, pads=(pad_in, pad_out), args=(m.activation, clamp, tm) if m.norm is None else (None, None, False):
+                             train_ops.conv1d(h, *pad_channels(c.weight, c.bias, *pads), c.stride[0], c.padding[0], *args))
+                if m.norm is not None:
+                    steps.append(batchnorm_step(m.norm.bn, m.activation, clamp, tm, channels=c.out_channels,
+                                                pad=pad_out if m.norm.bn.affine else 0))
+                layout, pad_in = "tnc" if tm else "nlc", pad_out
             elif isinstance(m, bnn.LSTM):
                 r = m.rnn
                 if r.num_layers != 1 or r.bidirectional or r.input_size != r.hidden_size or getattr(r, "proj_size", 0) \
                         or not rnn.supported_hidden_size(r.hidden_size):
                     raise ValueError("forward_train: %s is not an LSTM the device layer serves (one layer, one direction, insize == size, "
                                      "a multiple of 32 in 32..1024)" % name)
-            elif isinstance(m, bnn.Permute):
+                if layout != "tnc":
+                    raise ValueError("forward_train: %s must follow permute [2,0,1]" % name)
+                steps.append(lambda h, seed, m=m: rnn.lstm_module(m, h))
+            elif isinstance(m, bnn.Permute):            # folded: into the store of the convolution in front, or a no-op
                 if list(m.dims) not in ([2, 0, 1], [0, 2, 1], [1, 0, 2]):
                     raise ValueError("forward_train: %s with dims %s cannot be folded" % (name, list(m.dims)))
                 time_major = time_major or list(m.dims) == [2, 0, 1]
-            elif not isinstance(m, (bnn.LinearCRFEncoder, bnn.Linear, bnn.Clamp, bnn.MakeContiguous)) or isinstance(m, bnn.LinearUpsample):
+            elif isinstance(m, (bnn.LinearCRFEncoder, bnn.Linear)):
+                if layout not in ("tnc", "nlc"):
+                    raise ValueError("forward_train: %s needs the time-major output of the LSTM stack or [N][T][C] activations" % name)
+                # batch-major rows ([N][T][C], the transformer family) are stored as they are: that is the scores' layout already
+                if isinstance(m, bnn.LinearCRFEncoder):
+                    args = (m.activation, m.scale if m.scale else None, clamp_after(mods, i), layout == "tnc")
+                    layout = "ntc"
+                else:
+                    args = (None, None, clamp_after(mods, i), False)
+                    width = m.linear.out_features
+                steps.append(lambda h, seed, m=m, args=args: train_ops.linear(h, m.linear.weight, m.linear.bias, *args))
+            elif isinstance(m, bnn.Clamp):
+                if i == 0 or not isinstance(mods[i - 1], (bnn.Convolution, bnn.Linear, bnn.LinearCRFEncoder)):
+                    raise ValueError("forward_train: %s follows no convolution, linear or head to be fused into" % name)
+            elif not isinstance(m, bnn.MakeContiguous):
                 raise ValueError("forward_train: %s has no training forward (the LSTM and transformer families of CRF models are served: "
                                  "convolutions, LSTMs, transformer encoder layers, linear, batch-major linearupsample, linearcrfencoder, "
                                  "clamp)" % name)
-            elif isinstance(m, bnn.Linear):
-                width = m.linear.out_features
             for pname, p in m.named_parameters():
                 if p.dtype != torch.float32:
                     raise ValueError("forward_train: %s holds %s parameters (%s); training needs the fp32 master weights - call "
                                      "model.float()" % (name, str(p.dtype).replace("torch.", ""), pname))
+        if layout != "ntc":
+            raise ValueError("forward_train: the encoder does not end in a linearcrfencoder")
         if norm not in (None, "batch"):
             raise ValueError("forward_train: norm=%r is not served (None, or \"batch\" for batch statistics)" % (norm,))
         if not x.is_cuda:
@@ -402,79 +373,35 @@ class SeqdistModel(Module):
             for pname, p in m.named_parameters():
                 if p.device != x.device:
                     raise ValueError("forward_train: layer %d (%s) has %s on %s, x is on %s" % (i, type(m).__name__, pname, p.device, x.device))
+        return steps
 
-        h = x.reshape(x.shape[0], x.shape[2])       # [N][L]: one input channel
-        layout = "signal"                           # -> "nlc" [N][L][C] -> "tnc" [T][N][C] -> "ntc" scores
-        pad_in = 0                                  # zero channels the convolution in front added to its output
-        i = 0
-        while i < len(mods):
-            m = mods[i]
-            name = "layer %d (%s)" % (i, type(m).__name__)
-            if isinstance(m, bnn.Convolution):
-                if layout not in ("signal", "nlc"):
-                    raise ValueError("forward_train: %s follows the permute to time-major activations" % name)
-                c = m.conv
-                if (c.in_channels == 1) != (layout == "signal"):
-                    raise ValueError("forward_train: %s expects %d input channels" % (name, c.in_channels))
-                clamp = clamp_after(i)
-                nxt, tm = next_compute(i)
-                w, b = c.weight, c.bias
-                if pad_in:
-                    w = torch.nn.functional.pad(w, (0, 0, 0, pad_in))
-                pad_in = -c.out_channels % 8 if isinstance(nxt, bnn.Convolution) else 0
-                if pad_in:              # zero output channels up to a multiple of 8: they stay exactly zero through swish / relu / tanh
-                    w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, pad_in))
-                    b = None if b is None else torch.nn.functional.pad(b, (0, pad_in))
-                if tm and not isinstance(nxt, bnn.LSTM):
-                    raise ValueError("forward_train: %s stores time-major for a layer that is no LSTM" % name)
-                if m.norm is None:
-                    h = train_ops.conv1d(h, w, b, c.stride[0], c.padding[0], m.activation, clamp, tm)
-                else:                   # z = conv(x) as it is, then norm, activation, clamp and the store in one layer
-                    bn = m.norm.bn
-                    gamma, beta = bn.weight, bn.bias
-                    if pad_in and bn.affine:
-                        gamma, beta = torch.nn.functional.pad(gamma, (0, pad_in)), torch.nn.functional.pad(beta, (0, pad_in))
-                    h = train_ops.conv1d(h, w, b, c.stride[0], c.padding[0], None, None, False)
-                    h = train_ops.batchnorm(h, gamma, beta, bn.running_mean, bn.running_var, bn.momentum, bn.eps, m.activation, clamp, tm,
-                                            channels=c.out_channels)
-                    if bn.num_batches_tracked is not None:
-                        bn.num_batches_tracked.add_(1)
-                layout = "tnc" if tm else "nlc"
-                i += 2 if clamp is not None else 1
-            elif isinstance(m, bnn.LSTM):
-                if layout != "tnc":
-                    raise ValueError("forward_train: %s must follow permute [2,0,1]" % name)
-                h = rnn.lstm_module(m, h)
-                i += 1
-            elif isinstance(m, TransformerEncoderLayer):
-                if layout != "nlc":
-                    raise ValueError("forward_train: %s needs the [N][T][C] output of the convolutions" % name)
-                h = attn.encoder_layer(m, h)
-                i += 1
-            elif isinstance(m, bnn.LinearUpsample):        # [N][T][D] -> [N][T][s D], which is [N][s T][D]
-                if layout != "nlc":
-                    raise ValueError("forward_train: %s needs [N][T][C] activations" % name)
-                h = train_ops.linear(h, m.linear.weight, m.linear.bias)
-                h = h.view(h.shape[0], h.shape[1] * m.scale_factor, m.d_model)
-                i += 1
-            elif isinstance(m, (bnn.LinearCRFEncoder, bnn.Linear)):
-                if layout not in ("tnc", "nlc") or h.dim() != 3:
-                    raise ValueError("forward_train: %s needs the time-major output of the LSTM stack or [N][T][C] activations" % name)
-                head = isinstance(m, bnn.LinearCRFEncoder)
-                clamp = clamp_after(i)
-                # batch-major rows ([N][T][C], the transformer family) are stored as they are: that is the scores' layout already
-                h = train_ops.linear(h, m.linear.weight, m.linear.bias, m.activation if head else None,
-                                     (m.scale if m.scale else None) if head else None, clamp, head and layout == "tnc")
-                if head:
-                    layout = "ntc"
-                i += 2 if clamp is not None else 1
-            elif isinstance(m, bnn.Clamp):
-                raise ValueError("forward_train: %s follows no convolution, linear or head to be fused into" % name)
-            else:                       # Permute / MakeContiguous: folded
-                i += 1
-        if layout != "ntc":
-            raise ValueError("forward_train: the encoder does not end in a linearcrfencoder")
-        return h
+    def forward_train(self, x, norm=None):
+        """The forward of a training step: x cuda fp16 [N,1,L] -> scores in the shape, layout and dtype of ``forward(x)``, INSIDE
+        autograd, so that ``self.loss(self.forward_train(x), targets, lengths).backward()`` leaves a gradient on every trainable
+        parameter. The parameters are the fp32 master weights on x's device; every layer rounds them to fp16 on the device in every
+        call (autocast's arithmetic: bonito_amd.train_ops, bonito_amd.rnn, bonito_amd.attn). Serves the LSTM family - conv x3 ->
+        permute -> LSTM x n -> [linear] -> linearcrfencoder [-> clamp] - and the transformer family - conv x n (no norm) ->
+        permute [0,2,1] -> TransformerEncoderLayer x depth -> LinearUpsample -> linearcrfencoder [-> clamp] - with the folding rules of
+        ``engine.lower``: a Clamp after a Convolution or the head is fused into it, Permute([2,0,1]) is folded into the producing
+        convolution's store, Permute([0,2,1]) is the layout the convolutions store anyway, Permute([1,0,2]) after the head is a no-op
+        (batch-major rows are the scores' layout already), a batch-first LinearUpsample is a linear layer whose [N][T][s D] output is
+        read as [N][s T][D]. Anything else is refused with a ValueError that names the layer, and every refusal comes before the first
+        launch: ``_train_plan`` judges the whole encoder and returns the steps, which are then only applied. The inference engine is
+        neither built nor dropped.
+
+        ``norm`` says what a Convolution that carries a norm gets. None: it is refused. ``"batch"``: a ``bonito_amd.nn.BatchNorm`` in
+        train mode normalises with the statistics of this batch, as the reference's training does (conv with no activation ->
+        ``train_ops.batchnorm`` with the layer's activation, the fused clamp and the time-major store) - and every call that is not
+        refused REWRITES the module's ``running_mean`` / ``running_var`` buffers and adds one to ``num_batches_tracked``, under
+        ``torch.no_grad()`` too; a refused call has no side effect. The inference engine holds the statistics of the moment it was
+        built: drop it (``_drop_engine``) before inference is to see the new ones. A BatchNorm in eval mode (frozen statistics) is refused."""
+        from bonito_amd._train import run
+        if getattr(self, "_quantize", False):
+            raise ValueError("forward_train: quantize (the 8-bit recurrent path) has no training forward; call use_hip(quantize=False)")
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float16 or x.dim() != 3 or x.shape[1] != 1:
+            raise ValueError("forward_train: x must be a float16 tensor [N,1,L], got %s"
+                             % ("%s %s" % (x.dtype, tuple(x.shape)) if isinstance(x, torch.Tensor) else type(x).__name__))
+        return run(self._train_plan(x, norm), x.reshape(x.shape[0], x.shape[2]))       # [N][L]: one input channel
 
     def decode_batch(self, x, blank_score=2.0):
         """Posterior decoding of engine scores [N, T, 4S] (cuda fp16) -> list of strings

@@ -18,7 +18,7 @@ parameter.
 import torch
 from torch.nn import BatchNorm1d, Conv1d, Dropout, Module, ModuleList, Sequential
 
-from bonito_amd.engine import HipEncoder, lower_ctc
+from bonito_amd.engine import EngineHolder, lower_ctc
 from bonito_amd.nn import NoTorchCompute, Permute, _no_forward, layers
 
 
@@ -121,7 +121,7 @@ class Decoder(Module):
     forward = _no_forward
 
 
-class Model(Module):
+class Model(EngineHolder, Module):
     """QuartzNet-style CTC model (https://arxiv.org/abs/1910.10261) from a ``[[block]]`` config."""
 
     def __init__(self, config):
@@ -135,61 +135,28 @@ class Model(Module):
         self.features = config["block"][-1]["filters"]
         self.encoder = Encoder(config)
         self.decoder = Decoder(self.features, len(self.alphabet))
-        self._hip = None
-        self._hip_args = None
 
-    def use_hip(self, batchsize=None, chunksize=None, quantize=None, **_):
-        self._hip_args = (batchsize, chunksize)
-        self._hip = None
-        return self
-
-    use_koi = use_hip     # the reference CLI calls use_koi unconditionally (cli/basecaller.py:59, util.py:292-296)
-
-    # the engine snapshots the weights at its first forward: parameter changes afterwards drop it (see crf/model.py)
-    def _drop_engine(self):
-        eng = self.__dict__.get("_hip")
-        if eng is not None:
-            eng.close()
-        self.__dict__["_hip"] = None
-
-    def load_state_dict(self, *args, **kwargs):
-        self._drop_engine()
-        return super().load_state_dict(*args, **kwargs)
-
-    def _apply(self, fn, *args, **kwargs):
-        self._drop_engine()
-        return super()._apply(fn, *args, **kwargs)
+    def _lowering(self):
+        return self, dict(lowering=lower_ctc)
 
     def forward(self, x):
         """x: cuda fp16 [N,1,L] -> log-probabilities fp16 [T, N, n_labels] (reference layout, a view)."""
         if not x.is_cuda:
             raise NoTorchCompute("bonito_amd models only run on a HIP device; got a %s tensor" % x.device)
-        N, L = x.shape[0], x.shape[-1]
-        if self._hip is not None and (N > self._hip.max_batch or L > self._hip.max_chunk or x.device != self._hip.device):
-            self._hip.close()
-            self._hip = None
-        if self._hip is None:
-            bs, cs = self._hip_args if self._hip_args is not None else (None, None)
-            self._hip = HipEncoder(self, max(int(bs or 0), N), max(int(cs or 0), L), device=x.device, lowering=lower_ctc)
-        return self._hip(x).permute(1, 0, 2)
+        return self._engine(x)(x).permute(1, 0, 2)
 
-    def _train_plan(self, x, norm):
-        """Every check of forward_train, in front of its first launch and its first side effect. -> the blocks as lists of
-        (TCSConv1d, BatchNorm1d) with their Dropout modules."""
-        from bonito_amd import train_ops
+    def _train_plan(self, x):
+        """Every check of forward_train about the model, in front of its first launch and its first side effect, and -> the steps to run
+        (bonito_amd._train), each with its decisions made: the separable, plain or wide convolution, the BatchNorm step behind it with the
+        activation it fuses, and the dropout sites in model order. A block that ends in a residual add or a dropout is one step."""
+        from bonito_amd import _lib, train_ops
+        from bonito_amd._train import batchnorm_step, pad_channels, run, unsupported_shape
         what = "forward_train"
-        if norm is None:
-            raise ValueError("forward_train: a bonito.ctc model has no forward_train without batch statistics: every block carries a "
-                             "BatchNorm; pass norm=\"batch\" / --norm batch")
-        if norm != "batch":
-            raise ValueError("forward_train: norm=%r is not served (\"batch\" for batch statistics)" % (norm,))
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float16 or x.dim() != 3 or x.shape[1] != 1 or x.shape[0] < 1:
-            raise ValueError("forward_train: x must be a float16 tensor [N,1,L], got %s"
-                             % ("%s %s" % (x.dtype, tuple(x.shape)) if isinstance(x, torch.Tensor) else type(x).__name__))
         N, L, C = int(x.shape[0]), int(x.shape[2]), 1
-        plan = []
+        plan, sites = [], 0
 
         def tcs_check(name, tcs, bn, Lin, Cin):
+            """-> (the steps of the convolution in front of bn, Lout, Cout)"""
             convs = [("depthwise", tcs.depthwise), ("pointwise", tcs.pointwise)] if tcs.separable else [("conv", tcs.conv)]
             for cname, c in convs:
                 if c.dilation[0] != 1:
@@ -214,6 +181,8 @@ class Model(Module):
                 train_ops._dw_check(torch.empty((N, Lin, Cin), dtype=torch.float16, device="meta"), dw.weight, pad,
                                     "%s: %s.depthwise" % (what, name), devices=False)
                 Lout = train_ops.conv_out_len(Lin, K, 1, pad)
+                steps = [lambda h, seed: train_ops.depthwise_conv1d(h, dw.weight, pad),
+                         lambda h, seed: train_ops.linear(h, pw.weight[:, :, 0])]
             else:
                 c = tcs.conv
                 wide = Cin == 1 and Cout > 256          # the single-channel kernel serves 256 filters: seven zero channels ride beside the signal
@@ -221,11 +190,15 @@ class Model(Module):
                 weight = torch.empty((Cout, 8, c.kernel_size[0]), dtype=c.weight.dtype, device="meta") if wide else c.weight
                 train_ops._conv_check(torch.empty(shape, dtype=torch.float16, device="meta"), weight, c.bias, c.stride[0], c.padding[0], None,
                                       None, "%s: %s.conv" % (what, name), devices=False)
-                from bonito_amd import _lib
                 if _lib.lib().bh_conv1d_train_workspace(N, Lin, 8 if wide else Cin, Cout, c.kernel_size[0], c.stride[0], c.padding[0]) == 0:
-                    raise ValueError("%s: %s.conv: shape N=%d Lin=%d Cin=%d Cout=%d K=%d stride=%d padding=%d is not supported"
-                                     % (what, name, N, Lin, Cin, Cout, c.kernel_size[0], c.stride[0], c.padding[0]))
+                    raise unsupported_shape("%s: %s.conv" % (what, name), N=N, Lin=Lin, Cin=Cin, Cout=Cout, K=c.kernel_size[0],
+                                            stride=c.stride[0], padding=c.padding[0])
                 Lout = train_ops.conv_out_len(Lin, c.kernel_size[0], c.stride[0], c.padding[0])
+                if wide:
+                    steps = [lambda h, seed: train_ops.conv1d(torch.nn.functional.pad(h.unsqueeze(-1), (0, 7)),
+                                                              pad_channels(c.weight, None, 7, 0)[0], c.bias, c.stride[0], c.padding[0])]
+                else:
+                    steps = [lambda h, seed: train_ops.conv1d(h, c.weight, c.bias, c.stride[0], c.padding[0])]
             if not isinstance(bn, BatchNorm1d) or bn.num_features != Cout:
                 raise ValueError("%s: %s is not followed by a BatchNorm1d over its %d channels" % (what, name, Cout))
             if not bn.training:
@@ -240,41 +213,57 @@ class Model(Module):
             if Cout > 2048 or N * Lout < 2:
                 raise ValueError("%s: %s normalises %d channels over %d values; up to 2048 channels and more than one value are served"
                                  % (what, name, Cout, N * Lout))
-            return Lout, Cout
+            return steps, Lout, Cout
+
+        def dropped(drop):
+            nonlocal sites
+            sites += 1
+            return (drop.p if drop.training else 0.0), sites - 1
 
         for bi, block in enumerate(self.encoder.encoder):
             bname = "encoder.encoder.%d" % bi
             mods = list(block.conv)
-            steps, i = [], 0
+            convs, i = [], 0            # per TCSConv1d: (its steps, its BatchNorm1d, the Dropout behind its activation or None)
             Lb, Cb = L, C
             while i < len(mods):
                 if not isinstance(mods[i], TCSConv1d) or i + 1 >= len(mods):
                     raise ValueError("%s: %s.conv.%d (%s) is no TCSConv1d followed by a BatchNorm1d" % (what, bname, i, type(mods[i]).__name__))
-                Lb, Cb = tcs_check("%s.conv.%d" % (bname, i), mods[i], mods[i + 1], Lb, Cb)
+                steps, Lb, Cb = tcs_check("%s.conv.%d" % (bname, i), mods[i], mods[i + 1], Lb, Cb)
                 drop = None
                 if i + 2 < len(mods):
                     if i + 3 >= len(mods) or not isinstance(mods[i + 3], Dropout):
                         raise ValueError("%s: %s.conv.%d is not followed by an activation and a Dropout" % (what, bname, i + 1))
                     train_ops._act(mods[i + 2], (None, "none", "swish", "tanh", "relu"), "%s: %s" % (what, bname))
                     drop = mods[i + 3]
-                steps.append((mods[i], mods[i + 1], drop))
+                convs.append((steps, mods[i + 1], drop))
                 i += 4
             act, drop = block.activation[0], block.activation[1]
             train_ops._act(act, (None, "none", "swish", "tanh", "relu"), "%s: %s" % (what, bname))
-            for d in [s[2] for s in steps[:-1]] + [drop]:
+            for d in [c[2] for c in convs[:-1]] + [drop]:
                 if not isinstance(d, Dropout) or not 0.0 <= d.p < 1.0:
                     raise ValueError("%s: %s has a dropout probability outside 0 <= p < 1" % (what, bname))
             res = None
             if block.use_res:
-                res = (block.residual[0], block.residual[1])
-                Lr, Cr = tcs_check("%s.residual" % bname, res[0], res[1], L, C)
+                steps, Lr, Cr = tcs_check("%s.residual" % bname, block.residual[0], block.residual[1], L, C)
                 if (Lr, Cr) != (Lb, Cb):
                     raise ValueError("%s: %s adds a residual of %d steps x %d channels to %d x %d" % (what, bname, Lr, Cr, Lb, Cb))
-            plan.append((steps, res, act, drop))
+                res = steps + [batchnorm_step(block.residual[1], None)]
+            main = []
+            for steps, bn, between in convs[:-1]:
+                main += steps + [batchnorm_step(bn, act)]
+                p, sid = dropped(between)
+                if p > 0.0:
+                    main.append(lambda h, seed, p=p, sid=sid: train_ops.residual_act(h, None, "none", p, seed, sid))
+            p, sid = dropped(drop)
+            fused = res is None and p == 0.0        # nothing but the activation follows the last BatchNorm, which fuses it
+            main += convs[-1][0] + [batchnorm_step(convs[-1][1], act if fused else None)]
+            plan += main if fused else [lambda h, seed, main=main, res=res, act=act, p=p, sid=sid: train_ops.residual_act(
+                run(main, h, seed), None if res is None else run(res, h, seed), act, p, seed, sid)]
             L, C = Lb, Cb
         head = self.decoder.layers[0]
         train_ops._head_check(torch.empty((N, L, C), dtype=torch.float16, device="meta"), head.weight, head.bias, "%s: decoder" % what,
                               devices=False)
+        plan.append(lambda h, seed: train_ops.ctc_head(h, head.weight, head.bias))
         if not x.is_cuda:
             raise NoTorchCompute("forward_train runs on a HIP device only; x is a %s tensor" % x.device)
         for pname, t in list(self.named_parameters()) + list(self.named_buffers()):
@@ -290,52 +279,27 @@ class Model(Module):
         its running statistics and ``num_batches_tracked``, as the reference's training does. ``norm=None`` is refused, like every
         other refusal (eval-mode BatchNorm, dilation, a separable convolution with a stride or K > 127, channel counts that are no
         multiples of 8, parameters that are not fp32, what train_ops.conv1d refuses in a plain convolution - K > 32, which is
-        dna_r9.4.1@v1's first layer) in front of the first launch and the first side effect. A single-channel first convolution with
-        more than 256 filters (dna_r9.4.1@v2: 344) gets seven zero channels beside the signal, which is what that layer serves.
+        dna_r9.4.1@v1's first layer) in front of the first launch and the first side effect: ``_train_plan`` judges the whole model
+        and returns the steps, which are then only applied. A single-channel first convolution with more than 256 filters
+        (dna_r9.4.1@v2: 344) gets seven zero channels beside the signal, which is what that layer serves.
 
         Dropout is not stored: site i of the model (every Dropout module, in model order) keeps an element iff a counter-based hash
         of (seed, i, element index) reaches p 2^32 (include/bonito_hip.h). ``seed``: one 64-bit number per call; None draws it from
-        torch's default CPU generator, so torch.manual_seed reproduces a run. A Dropout module in eval mode drops nothing."""
-        from bonito_amd import train_ops
-        plan = self._train_plan(x, norm)
+        torch's default CPU generator - after the plan, so a refused call draws nothing - and torch.manual_seed reproduces a run. A
+        Dropout module in eval mode drops nothing."""
+        from bonito_amd._train import run
+        if norm is None:
+            raise ValueError("forward_train: a bonito.ctc model has no forward_train without batch statistics: every block carries a "
+                             "BatchNorm; pass norm=\"batch\" / --norm batch")
+        if norm != "batch":
+            raise ValueError("forward_train: norm=%r is not served (\"batch\" for batch statistics)" % (norm,))
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float16 or x.dim() != 3 or x.shape[1] != 1 or x.shape[0] < 1:
+            raise ValueError("forward_train: x must be a float16 tensor [N,1,L], got %s"
+                             % ("%s %s" % (x.dtype, tuple(x.shape)) if isinstance(x, torch.Tensor) else type(x).__name__))
+        plan = self._train_plan(x)
         if seed is None:
             seed = int(torch.randint(-(1 << 63), (1 << 63) - 1, (1,), dtype=torch.int64).item())
-        seed = int(seed) & ((1 << 64) - 1)
-        site = [0]
-
-        def dropped(drop):
-            site[0] += 1
-            return (drop.p if drop.training else 0.0), site[0] - 1
-
-        def tcs_bn(tcs, bn, h, activation):
-            if tcs.separable:
-                h = train_ops.depthwise_conv1d(h, tcs.depthwise.weight, tcs.depthwise.padding[0])
-                h = train_ops.linear(h, tcs.pointwise.weight[:, :, 0])
-            else:
-                w = tcs.conv.weight
-                if w.shape[1] == 1 and w.shape[0] > 256:          # seven zero channels beside the signal (see _train_plan)
-                    h, w = torch.nn.functional.pad(h.unsqueeze(-1), (0, 7)), torch.nn.functional.pad(w, (0, 0, 0, 7))
-                h = train_ops.conv1d(h, w, tcs.conv.bias, tcs.conv.stride[0], tcs.conv.padding[0])
-            h = train_ops.batchnorm(h, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, activation)
-            if bn.num_batches_tracked is not None:
-                bn.num_batches_tracked.add_(1)
-            return h
-
-        h = x[:, 0, :].contiguous()
-        for steps, res, act, drop in plan:
-            inp = h
-            for tcs, bn, between in steps[:-1]:
-                h = tcs_bn(tcs, bn, h, act)
-                p, sid = dropped(between)
-                if p > 0.0:
-                    h = train_ops.residual_act(h, None, "none", p, seed, sid)
-            p, sid = dropped(drop)
-            fused = res is None and p == 0.0
-            h = tcs_bn(steps[-1][0], steps[-1][1], h, act if fused else None)
-            if not fused:
-                h = train_ops.residual_act(h, None if res is None else tcs_bn(res[0], res[1], inp, None), act, p, seed, sid)
-        head = self.decoder.layers[0]
-        return train_ops.ctc_head(h, head.weight, head.bias).permute(1, 0, 2)
+        return run(plan, x[:, 0, :].contiguous(), int(seed) & ((1 << 64) - 1)).permute(1, 0, 2)
 
     def decode(self, x, beamsize=5, threshold=1e-3, qscores=False, return_path=False):
         """x: log-probabilities [T, n_labels] of ONE read (any device). Greedy when beamsize == 1 or

@@ -16,6 +16,7 @@ import torch
 
 from bonito_amd import _lib
 from bonito_amd import nn as bnn
+from bonito_amd._train import act_name
 
 
 class LoweringError(RuntimeError):
@@ -51,11 +52,9 @@ class _Lowered:
 
 
 def _act_id(module):
-    if module is None:
+    name = act_name(module)
+    if name is None:
         return 0
-    name = getattr(module, "name", type(module).__name__.lower())
-    if name == "silu":
-        name = "swish"
     if name not in _lib.BH_ACT:
         raise LoweringError("activation %r is not supported by the HIP engine" % name)
     return _lib.BH_ACT[name]
@@ -303,3 +302,50 @@ class HipEncoder:
             self.close()
         except Exception:
             pass
+
+
+class EngineHolder:
+    """What a model object does with its HipEncoder, written once for crf.model.SeqdistModel and ctc.model.Model (a mixin in front of
+    Module). The model says what is lowered: ``_lowering()`` -> (the module tree, the keywords of HipEncoder)."""
+    _hip = None          # HipEncoder (plain object, not a submodule), built lazily
+    _hip_args = None     # (batchsize, chunksize) requested through use_koi / use_hip
+
+    def use_hip(self, batchsize=None, chunksize=None, quantize=None, **_):
+        """Route ``forward`` through the HIP engine. Same keywords as the reference's ``use_koi``.
+        ``quantize=True`` (cli/basecaller.py:186-189, crf/model.py:245) selects the 8-bit recurrent path Q8-1 for every LSTM
+        layer the int8 kernel covers (hidden sizes that are multiples of 48 or 64 up to 512, input size == hidden size);
+        other layers keep the fp16 kernels -- ``model._hip.describe()`` lists what runs where. The default stays fp16."""
+        self._hip_args = (batchsize, chunksize)
+        self._quantize = bool(quantize)
+        self._drop_engine()
+        return self
+
+    use_koi = use_hip     # the reference CLI calls use_koi unconditionally (cli/basecaller.py:59, util.py:292-296)
+
+    # The engine snapshots the weights when it is built (first forward). Anything that changes parameters afterwards --
+    # load_state_dict, .half() / .to() / .float() (Module._apply), apply(fuse_bn_) -- drops it, so the next forward lowers
+    # the current weights again instead of silently running stale ones.
+    def _drop_engine(self):
+        eng = self.__dict__.get("_hip")
+        if eng is not None:
+            eng.close()
+        self.__dict__["_hip"] = None
+
+    def load_state_dict(self, *args, **kwargs):
+        self._drop_engine()
+        return super().load_state_dict(*args, **kwargs)
+
+    def _apply(self, fn, *args, **kwargs):
+        self._drop_engine()
+        return super()._apply(fn, *args, **kwargs)
+
+    def _engine(self, x):
+        """The engine for signal x [N,1,L] or [N,L]: built on first use, rebuilt when x is larger than it was built for or elsewhere."""
+        N, L = x.shape[0], x.shape[-1]
+        if self._hip is not None and (N > self._hip.max_batch or L > self._hip.max_chunk or x.device != self._hip.device):
+            self._drop_engine()
+        if self._hip is None:
+            bs, cs = self._hip_args if self._hip_args is not None else (None, None)
+            what, keywords = self._lowering()
+            self._hip = HipEncoder(what, max(int(bs or 0), N), max(int(cs or 0), L), device=x.device, **keywords)
+        return self._hip

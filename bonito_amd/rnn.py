@@ -13,8 +13,7 @@ NoTorchCompute, an unsupported shape or dtype raises ValueError before anything 
 import torch
 
 from bonito_amd import _lib
-from bonito_amd._train import HalfLayer, devices, half, master, tensors
-from bonito_amd.nn import NoTorchCompute
+from bonito_amd._train import HalfLayer, devices, half_dev, master, tensors, workspace
 
 __all__ = ["lstm_forward", "lstm_backward", "lstm", "lstm_module", "supported_hidden_size"]
 
@@ -41,13 +40,6 @@ def _check(x, w_ih, w_hh, bias, what):
     return T, N, H
 
 
-def _half3(t, shape, name, what):
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise NoTorchCompute("%s runs on a HIP device only; %s is not a device tensor" % (what, name))
-    half(t, shape, name, what)
-    return t.contiguous()
-
-
 def lstm_forward(x, w_ih, w_hh, bias=None, reverse=False):
     """-> (h fp16 [T][N][H], saved): `saved` is the opaque byte buffer lstm_backward needs (the gates, c and the fp16 weights)."""
     if isinstance(x, torch.Tensor) and x.dtype != torch.float16:
@@ -56,9 +48,7 @@ def lstm_forward(x, w_ih, w_hh, bias=None, reverse=False):
     x, w_ih, w_hh = x.contiguous(), w_ih.detach().contiguous(), w_hh.detach().contiguous()
     bias = None if bias is None else bias.detach().contiguous()
     lib = _lib.lib()
-    nbytes = lib.bh_lstm_train_saved_bytes(T, N, H)
-    if nbytes == 0:
-        raise ValueError("lstm_forward: shape T=%d N=%d H=%d is not supported" % (T, N, H))
+    nbytes = workspace("bh_lstm_train_saved_bytes", "lstm_forward", T=T, N=N, H=H)
     with torch.cuda.device(x.device):
         h = torch.empty((T, N, H), dtype=torch.float16, device=x.device)
         saved = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
@@ -70,9 +60,9 @@ def lstm_forward(x, w_ih, w_hh, bias=None, reverse=False):
 def lstm_backward(x, w_ih, w_hh, h, saved, dh, reverse=False, need_bias=True):
     """-> (dx fp16 [T][N][H], dw_ih, dw_hh fp32 [4H][H], db fp32 [4H] or None) from the upstream gradient dh fp16 [T][N][H]."""
     T, N, H = _check(x, w_ih, w_hh, None, "lstm_backward")
-    x = _half3(x, (T, N, H), "x", "lstm_backward")
-    h = _half3(h, (T, N, H), "h", "lstm_backward")
-    dh = _half3(dh, (T, N, H), "dh", "lstm_backward")
+    x = half_dev(x, (T, N, H), "x", "lstm_backward")
+    h = half_dev(h, (T, N, H), "h", "lstm_backward")
+    dh = half_dev(dh, (T, N, H), "dh", "lstm_backward")
     w_ih, w_hh = w_ih.detach().contiguous(), w_hh.detach().contiguous()
     lib = _lib.lib()
     if not isinstance(saved, torch.Tensor) or saved.device != x.device or saved.dtype != torch.uint8 or \

@@ -42,7 +42,8 @@ import math
 import torch
 
 from bonito_amd import _lib
-from bonito_amd._train import HalfLayer, HalfLayer2, devices as _devices, half as _half, master as _master, tensors as _tensors
+from bonito_amd._train import (HalfLayer, HalfLayer2, act_name, devices as _devices, dtype_names as _dtype_names, half as _half,
+                               master as _master, tensors as _tensors, workspace as _workspace)
 
 __all__ = ["conv1d_forward", "conv1d_backward", "conv1d", "linear_forward", "linear_backward", "linear", "conv_out_len",
            "rmsnorm_residual_forward", "rmsnorm_residual_backward", "rmsnorm_residual",
@@ -60,9 +61,7 @@ def conv_out_len(Lin, K, stride, padding):
 
 
 def _act(activation, allowed, what):
-    name = activation if activation is None or isinstance(activation, str) else getattr(activation, "name", type(activation).__name__.lower())
-    if name == "silu":
-        name = "swish"
+    name = act_name(activation)
     if name not in allowed:
         raise ValueError("%s: activation %r is not supported (one of %s)" % (what, name, ", ".join(str(a) for a in allowed)))
     return _lib.BH_ACT[name]
@@ -85,7 +84,7 @@ def _conv_check(x, weight, bias, stride, padding, activation, clamp, what, dtype
         raise ValueError("%s: weight must be [Cout][Cin][K], got %s" % (what, tuple(weight.shape)))
     Cout, Cin, K = weight.shape
     if x.dtype not in dtypes:
-        raise ValueError("%s: x must be %s, got %s" % (what, " or ".join(str(d).replace("torch.", "") for d in dtypes), x.dtype))
+        raise ValueError("%s: x must be %s, got %s" % (what, _dtype_names(dtypes), x.dtype))
     if not ((x.dim() == 3 and x.shape[2] == Cin) or (x.dim() == 2 and Cin == 1)) or x.shape[0] < 1 or x.shape[1] < 1:
         raise ValueError("%s: x must be [N][Lin][%d]%s, got %s" % (what, Cin, " or [N][Lin]" if Cin == 1 else "", tuple(x.shape)))
     _master(weight, (Cout, Cin, K), "weight", what)
@@ -115,10 +114,7 @@ def conv1d_forward(x, weight, bias=None, stride=1, padding=0, activation=None, c
     x, weight = x.contiguous(), weight.detach().contiguous()
     bias = None if bias is None else bias.detach().contiguous()
     lib = _lib.lib()
-    nbytes = lib.bh_conv1d_train_workspace(N, Lin, Cin, Cout, K, stride, padding)
-    if nbytes == 0:
-        raise ValueError("conv1d_forward: shape N=%d Lin=%d Cin=%d Cout=%d K=%d stride=%d padding=%d is not supported"
-                         % (N, Lin, Cin, Cout, K, stride, padding))
+    nbytes = _workspace("bh_conv1d_train_workspace", "conv1d_forward", N=N, Lin=Lin, Cin=Cin, Cout=Cout, K=K, stride=stride, padding=padding)
     Lout = conv_out_len(Lin, K, stride, padding)
     os_n, os_t = _conv_strides(N, Lout, Cout, time_major)
     with torch.cuda.device(x.device):
@@ -145,10 +141,7 @@ def conv1d_backward(x, weight, bias, y, dy, stride=1, padding=0, activation=None
     x, weight, y, dy = x.contiguous(), weight.detach().contiguous(), y.contiguous(), dy.contiguous()
     bias = None if bias is None else bias.detach().contiguous()
     lib = _lib.lib()
-    nbytes = lib.bh_conv1d_train_workspace(N, Lin, Cin, Cout, K, stride, padding)
-    if nbytes == 0:
-        raise ValueError("%s: shape N=%d Lin=%d Cin=%d Cout=%d K=%d stride=%d padding=%d is not supported"
-                         % (what, N, Lin, Cin, Cout, K, stride, padding))
+    nbytes = _workspace("bh_conv1d_train_workspace", what, N=N, Lin=Lin, Cin=Cin, Cout=Cout, K=K, stride=stride, padding=padding)
     os_n, os_t = _conv_strides(N, Lout, Cout, time_major)
     with torch.cuda.device(x.device):
         dx = torch.empty(x.shape, dtype=torch.float16, device=x.device) if need_dx else None
@@ -198,7 +191,7 @@ def _linear_check(x, weight, bias, activation, scale, clamp, what, dtypes=(torch
         raise ValueError("%s: weight must be [C][K], got %s" % (what, tuple(weight.shape)))
     C, K = weight.shape
     if x.dtype not in dtypes:
-        raise ValueError("%s: x must be %s, got %s" % (what, " or ".join(str(d).replace("torch.", "") for d in dtypes), x.dtype))
+        raise ValueError("%s: x must be %s, got %s" % (what, _dtype_names(dtypes), x.dtype))
     if x.dim() != 3 or x.shape[2] != K or x.shape[0] < 1 or x.shape[1] < 1:
         raise ValueError("%s: x must be [T][N][%d] with T, N >= 1, got %s" % (what, K, tuple(x.shape)))
     _master(weight, (C, K), "weight", what)
@@ -222,9 +215,7 @@ def linear_forward(x, weight, bias=None, activation=None, scale=None, clamp=None
     x, weight = x.contiguous(), weight.detach().contiguous()
     bias = None if bias is None else bias.detach().contiguous()
     lib = _lib.lib()
-    nbytes = lib.bh_linear_train_workspace(T, N, K, C)
-    if nbytes == 0:
-        raise ValueError("linear_forward: shape T=%d N=%d K=%d C=%d is not supported" % (T, N, K, C))
+    nbytes = _workspace("bh_linear_train_workspace", "linear_forward", T=T, N=N, K=K, C=C)
     with torch.cuda.device(x.device):
         y = torch.empty((N, T, C) if batch_major_out else (T, N, C), dtype=torch.float16, device=x.device)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
@@ -245,9 +236,7 @@ def linear_backward(x, weight, y, dy, activation=None, scale=None, clamp=None, b
     _devices([("x", x), ("weight", weight), ("y", y), ("dy", dy)], what)
     x, weight, y, dy = x.contiguous(), weight.detach().contiguous(), y.contiguous(), dy.contiguous()
     lib = _lib.lib()
-    nbytes = lib.bh_linear_train_workspace(T, N, K, C)
-    if nbytes == 0:
-        raise ValueError("%s: shape T=%d N=%d K=%d C=%d is not supported" % (what, T, N, K, C))
+    nbytes = _workspace("bh_linear_train_workspace", what, T=T, N=N, K=K, C=C)
     with torch.cuda.device(x.device):
         dx = torch.empty((T, N, K), dtype=torch.float16, device=x.device) if need_dx else None
         dw = torch.empty((C, K), dtype=torch.float32, device=x.device)
@@ -277,10 +266,6 @@ def linear(x, weight, bias=None, activation=None, scale=None, clamp=None, batch_
 
 # ---- DeepNorm residual RMSNorm --------------------------------------------------------------------------------------------------------------
 _BOTH = (torch.float16, torch.float32)
-
-
-def _dtype_names(dtypes):
-    return " or ".join(str(d).replace("torch.", "") for d in dtypes)
 
 
 def _norm_check(a, x, weight, alpha, eps, what, dtypes=(torch.float16,), devices=True):
@@ -326,9 +311,7 @@ def rmsnorm_residual_backward(a, x, weight, dy, alpha, eps=1e-5, need_da=True, n
     _devices([("a", a), ("x", x), ("weight", weight), ("dy", dy)], what)
     a, x, weight, dy = a.contiguous(), x.contiguous(), weight.detach().contiguous(), dy.contiguous()
     lib = _lib.lib()
-    nbytes = lib.bh_rmsnorm_train_workspace(M, D)
-    if nbytes == 0:
-        raise ValueError("%s: shape M=%d D=%d is not supported" % (what, M, D))
+    nbytes = _workspace("bh_rmsnorm_train_workspace", what, M=M, D=D)
     with torch.cuda.device(a.device):
         da = torch.empty_like(a) if need_da else None
         dx = torch.empty_like(a) if need_dx else None
@@ -373,20 +356,13 @@ def _gated_check(x, weight, what, dtypes=(torch.float16,), devices=True):
     return x.numel() // D, D, F
 
 
-def _gated_workspace(M, D, F, what):
-    nbytes = _lib.lib().bh_gated_linear_train_workspace(M, D, F)
-    if nbytes == 0:
-        raise ValueError("%s: shape M=%d D=%d F=%d is not supported" % (what, M, D, F))
-    return nbytes
-
-
 def gated_linear_forward(x, weight):
     """-> h fp16 [...][F] = y gate sigmoid(gate), [y | gate] = x weight^T (x fp16 [...][D], weight fp32 [2F][D]): the bytes of bh_linear with
     gated = 1 on the rounded, row-interleaved weights, which is the engine's fc1."""
     what = "gated_linear_forward"
     M, D, F = _gated_check(x, weight, what)
     x, weight = x.contiguous(), weight.detach().contiguous()
-    nbytes = _gated_workspace(M, D, F, what)
+    nbytes = _workspace("bh_gated_linear_train_workspace", what, M=M, D=D, F=F)
     with torch.cuda.device(x.device):
         h = torch.empty(tuple(x.shape[:-1]) + (F,), dtype=torch.float16, device=x.device)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
@@ -404,7 +380,7 @@ def gated_linear_backward(x, weight, dh, need_dx=True):
     _half(dh, tuple(x.shape[:-1]) + (F,), "dh", what)
     _devices([("x", x), ("weight", weight), ("dh", dh)], what)
     x, weight, dh = x.contiguous(), weight.detach().contiguous(), dh.contiguous()
-    nbytes = _gated_workspace(M, D, F, what)
+    nbytes = _workspace("bh_gated_linear_train_workspace", what, M=M, D=D, F=F)
     with torch.cuda.device(x.device):
         dx = torch.empty_like(x) if need_dx else None
         dw = torch.empty((2 * F, D), dtype=torch.float32, device=x.device)
@@ -461,13 +437,6 @@ def _bn_strides(N, L, C, time_major):
     return (C, N * C) if time_major else (L * C, C)
 
 
-def _bn_workspace(N, L, C, what):
-    nbytes = _lib.lib().bh_batchnorm_train_workspace(N, L, C)
-    if nbytes == 0:
-        raise ValueError("%s: shape N=%d L=%d C=%d is not supported" % (what, N, L, C))
-    return nbytes
-
-
 def batchnorm_forward(z, weight, bias, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, activation=None, clamp=None,
                       time_major=False, channels=None):
     """-> (y fp16 [N][L][C], or [L][N][C] with time_major; mean fp32 [C]; rstd fp32 [C]) of torch.nn.BatchNorm1d in training mode on
@@ -497,7 +466,7 @@ def batchnorm_forward(z, weight, bias, running_mean=None, running_var=None, mome
     _devices(named, what)
     z = z.contiguous()
     weight, bias = (None, None) if weight is None else (weight.detach().contiguous(), bias.detach().contiguous())
-    nbytes = _bn_workspace(N, L, C, what)
+    nbytes = _workspace("bh_batchnorm_train_workspace", what, N=N, L=L, C=C)
     os_n, os_t = _bn_strides(N, L, C, time_major)
     with torch.cuda.device(z.device):
         y = torch.empty((L, N, C) if time_major else (N, L, C), dtype=torch.float16, device=z.device)
@@ -527,7 +496,7 @@ def batchnorm_backward(z, weight, bias, mean, rstd, y, dy, activation=None, clam
              + ([("weight", weight), ("bias", bias)] if weight is not None else []), what)
     z, mean, rstd, y, dy = z.contiguous(), mean.contiguous(), rstd.contiguous(), y.contiguous(), dy.contiguous()
     weight, bias = (None, None) if weight is None else (weight.detach().contiguous(), bias.detach().contiguous())
-    nbytes = _bn_workspace(N, L, C, what)
+    nbytes = _workspace("bh_batchnorm_train_workspace", what, N=N, L=L, C=C)
     os_n, os_t = _bn_strides(N, L, C, time_major)
     with torch.cuda.device(z.device):
         dz = torch.empty((N, L, C), dtype=torch.float16, device=z.device)
@@ -603,9 +572,7 @@ def depthwise_conv1d_backward(x, weight, dy, padding=0, need_dx=True, need_dw=Tr
     _devices([("x", x), ("weight", weight), ("dy", dy)], what)
     x, weight, dy = x.contiguous(), weight.detach().contiguous(), dy.contiguous()
     lib = _lib.lib()
-    nbytes = lib.bh_dwconv1d_train_workspace(N, L, C, K, padding)
-    if nbytes == 0:
-        raise ValueError("%s: shape N=%d L=%d C=%d K=%d padding=%d is not supported" % (what, N, L, C, K, padding))
+    nbytes = _workspace("bh_dwconv1d_train_workspace", what, N=N, L=L, C=C, K=K, padding=padding)
     with torch.cuda.device(x.device):
         dx = torch.empty_like(x) if need_dx else None
         dw = torch.empty((C, 1, K), dtype=torch.float32, device=x.device) if need_dw else None
@@ -760,9 +727,7 @@ def ctc_head_backward(x, weight, bias, dlp, need_dx=True, need_dw=True, need_db=
     _devices([("x", x), ("weight", weight), ("bias", bias), ("dlp", dlp)], what)
     x, weight, bias, dlp = x.contiguous(), weight.detach().contiguous(), bias.detach().contiguous(), dlp.contiguous()
     lib = _lib.lib()
-    nbytes = lib.bh_ctc_head_train_workspace(N * T, F, classes)
-    if nbytes == 0:
-        raise ValueError("%s: shape M=%d F=%d classes=%d is not supported" % (what, N * T, F, classes))
+    nbytes = _workspace("bh_ctc_head_train_workspace", what, M=N * T, F=F, classes=classes)
     with torch.cuda.device(x.device):
         dx = torch.empty_like(x) if need_dx else None
         dw = torch.empty((classes, F, 1), dtype=torch.float32, device=x.device) if need_dw else None

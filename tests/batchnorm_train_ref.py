@@ -236,6 +236,36 @@ def lstm_config():
                     "blank_score": 2.0, "expand_blanks": True, "permute": [1, 0, 2]}]}}
 
 
+def misbuilt_models():
+    """-> [(name, model, the refusal forward_train(x, norm="batch") owes it)]: five encoders that begin with a normalised convolution
+    and are wrong further on, in ways only the layout the activations have at a layer can tell. A refusal that came after the first
+    layer had run would have rewritten that convolution's BatchNorm buffers. x is [2, 1, 120]."""
+    from bonito_amd import nn as bnn
+    from bonito_amd.crf.model import CTC_CRF, SeqdistModel
+
+    def conv():
+        return bnn.Convolution(1, 32, 5, padding=2, activation="swish", norm="batchnorm")
+
+    def head():
+        return bnn.LinearCRFEncoder(32, 4, 3, blank_score=2.0)
+
+    encoders = (
+        ("no head", [conv(), bnn.Permute([2, 0, 1]), bnn.LSTM(32, 32)], "the encoder does not end in a linearcrfencoder"),
+        ("lstm without permute", [conv(), bnn.LSTM(32, 32), head()], r"layer 1 \(LSTM\) must follow permute \[2,0,1\]"),
+        ("conv after permute", [conv(), bnn.Permute([2, 0, 1]), bnn.Convolution(32, 32, 5, padding=2), head()],
+         r"layer 2 \(Convolution\) follows the permute to time-major activations"),
+        ("stray clamp", [conv(), bnn.Permute([2, 0, 1]), bnn.Clamp(-1, 1), bnn.LSTM(32, 32), head()],
+         r"layer 2 \(Clamp\) follows no convolution, linear or head to be fused into"),
+        ("second conv of one channel", [conv(), bnn.Convolution(1, 32, 5, padding=2), bnn.Permute([2, 0, 1]), bnn.LSTM(32, 32), head()],
+         r"layer 1 \(Convolution\) expects 1 input channels"))
+    return [(name, SeqdistModel(bnn.Serial(layers), CTC_CRF(3, ["N", "A", "C", "G", "T"])).train(), text) for name, layers, text in encoders]
+
+
+def batchnorm_buffers(model):
+    """Copies of running_mean, running_var and num_batches_tracked of every BatchNorm in the model."""
+    return {k: v.detach().clone() for k, v in model.named_buffers() if k.rsplit(".", 1)[-1] in ("running_mean", "running_var", "num_batches_tracked")}
+
+
 def lstm_model_names():
     """The encoder's parameter names in the order of train_layers_ref.chain_params(32, 4, 5, 19, 5, 256)."""
     names = [p + "conv." + k for p, _, _ in LSTM_CONVS for k in ("weight", "bias")]

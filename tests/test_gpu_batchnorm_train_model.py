@@ -177,6 +177,22 @@ def test_three_steps_of_statistics_and_the_inference_that_follows(kind):
         model.forward_train(x.to(DEV), norm="batch")
 
 
+def test_what_only_the_layout_tells_is_refused_before_the_statistics_are_touched():
+    """The five encoders of batchnorm_train_ref.misbuilt_models on the device: each begins with a normalised convolution, which a refusal
+    behind the first launch would already have run. The refusal names the layer and the three BatchNorm buffers keep their bits."""
+    x = torch.zeros(2, 1, 120, dtype=torch.float16, device=DEV)
+    for name, model, text in ref.misbuilt_models():
+        synthetic.randomise_batchnorm_(model, 3)
+        model = model.to(DEV).train()
+        before = ref.batchnorm_buffers(model)
+        assert len(before) == 3, name
+        with pytest.raises(ValueError, match=text):
+            model.forward_train(x, norm="batch")
+        torch.cuda.synchronize()
+        after = ref.batchnorm_buffers(model)
+        assert all(torch.equal(before[k].reshape(-1).view(torch.uint8), after[k].reshape(-1).view(torch.uint8)) for k in before), name
+
+
 @pytest.mark.parametrize("kind", ("lstm", "v5"))
 def test_twenty_adamw_steps_lower_the_loss(kind):
     model = _make(kind, 2)

@@ -313,7 +313,9 @@ def test_forward_train_refusals_name_the_block_and_change_nothing():
                     (cfg(0, filters=4104), "encoder.encoder.0.conv.0.conv: shape N=3 Lin=600 Cin=1 Cout=4104"),   # the library's own limit
                     (cfg(2, kernel=[4]), "encoder.encoder.2 adds a residual of 200 steps")]:
         m, _ = _model(c)
+        rng = torch.get_rng_state()
         _raises(lambda: m.forward_train(x, norm="batch"), text)
+        assert torch.equal(rng, torch.get_rng_state()), "a call that _train_plan refuses draws no seed: %s" % text
     six = {**base, "labels": {"labels": list("NACGTUXYZ")}}
     m, _ = _model(six)
     _raises(lambda: m.forward_train(x, norm="batch"), "decoder: classes <= 8")

@@ -328,6 +328,23 @@ def test_forward_train_refusals_name_the_layer_and_build_no_engine():
     assert model._hip is None
 
 
+def test_forward_train_refuses_what_only_the_layout_tells_before_anything_runs():
+    """Five encoders whose defect shows in the layout the activations have at a layer: the plan refuses them by name for a CPU x too,
+    in front of NoTorchCompute, and the normalised convolution they begin with keeps its statistics and its batch counter."""
+    import batchnorm_train_ref as bn
+    x = torch.zeros(2, 1, 120, dtype=torch.float16)
+    cases = bn.misbuilt_models()
+    assert [name for name, _, _ in cases] == ["no head", "lstm without permute", "conv after permute", "stray clamp", "second conv of one channel"]
+    for name, model, text in cases:
+        before = bn.batchnorm_buffers(model)
+        assert sorted(k.rsplit(".", 1)[-1] for k in before) == ["num_batches_tracked", "running_mean", "running_var"], name
+        with pytest.raises(ValueError, match=text):
+            model.forward_train(x, norm="batch")
+        assert model._hip is None, name
+        after = bn.batchnorm_buffers(model)
+        assert all(torch.equal(before[k], after[k]) for k in before), name
+
+
 def test_forward_train_refuses_a_transformer_by_name():
     from bonito_amd.crf.model import SeqdistModel, CTC_CRF
     from bonito_amd import nn as bnn

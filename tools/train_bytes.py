@@ -3,7 +3,7 @@
 
     python tools/train_bytes.py [--out FILE]
 
-Only the public functions of bonito_amd.rnn and bonito_amd.train_ops are called, so the same file runs in a checkout of an earlier
+Only the public functions of bonito_amd.rnn and bonito_amd.train_ops and the models' forward_train are called, so the same file runs in a checkout of an earlier
 commit; run it there and here on the same device and compare the two lines (hashes of device output depend on the toolchain and are
 not a committed golden). Inputs come from the generators of the tests (tests/lstm_ref.py, tests/lstm_train_ref.py,
 tests/train_layers_ref.py; fixed seeds).
@@ -18,6 +18,10 @@ tests/train_layers_ref.py; fixed seeds).
     batchnorm (N, L, C, pad)    batch-statistics BatchNorm behind a convolution (tests/batchnorm_train_ref.py), swish: one block of rows and
                                 several with a short last one, 65 vectors per row, zero-padded channels, clamp on and off, the time-major
                                 store; y, mean, rstd, running_mean, running_var, dz, dgamma, dbeta
+    model                       forward_train of the four small models of the model tests (the LSTM family with fused clamps and a linear
+                                layer, the transformer family, the LSTM family with norm="batch", QuartzNet with dropout 0.1 and a fixed
+                                seed), seeded weights, that test's batch, a seeded fp16 upstream gradient: the scores, every parameter's
+                                .grad and every BatchNorm buffer
 
 Prints one JSON line {case: {tensor: sha256}}."""
 import argparse
@@ -49,6 +53,27 @@ BATCHNORM_CASES = ((3, 5, 16, 4), (2, 257, 64, 0), (5, 1000, 520, 0))       # (N
 
 def sha(t):
     return None if t is None else hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def model_cases():
+    """-> (name, model with seeded weights, x, the keywords of forward_train): the four small configurations of the model tests, each on
+    that test's batch."""
+    import batchnorm_train_ref as bn
+    import conftest
+    import test_gpu_quartznet_train_model as tq
+    import test_gpu_train_model as tm
+    import transformer_train_ref as tt
+    from bonito_amd.crf.model import Model
+    from bonito_amd.ctc import Model as CtcModel
+    from bonito_amd.transformer import Model as TransformerModel
+    for name, make, x, kwargs in (
+            ("model lstm", lambda: Model(tm._new_config()), tm._batch(3)[0], {}),
+            ("model transformer", lambda: TransformerModel(tt.model_config()), tt.model_batch(3)[0], {}),
+            ("model lstm norm=batch", lambda: Model(bn.lstm_config()), tm._batch(3)[0], {"norm": "batch"}),
+            ("model quartznet dropout=0.1", lambda: CtcModel(tq._config(0.1)), conftest.load_ctc_fixture()[2].half(),
+             {"norm": "batch", "seed": tq.SEED})):
+        torch.manual_seed(7)
+        yield name, make(), x, kwargs
 
 
 def main():
@@ -112,6 +137,16 @@ def main():
                 res["batchnorm N=%d L=%d C=%d-%d %s" % (N, L, C, pad, "clamped tm" if clamp else "free")] = {
                     "y": sha(y), "mean": sha(mean), "rstd": sha(rstd), "running_mean": sha(rm), "running_var": sha(rv), "dz": sha(dz),
                     "dgamma": sha(dgamma), "dbeta": sha(dbeta)}
+    from bonito_amd.ctc import Model as CtcModel
+    if hasattr(CtcModel, "forward_train"):                     # new keys: a checkout from before the QuartzNet forward_train has none of them
+        for name, model, x, kwargs in model_cases():
+            model = model.to(dev).train()
+            scores = model.forward_train(x.to(dev), **kwargs)
+            scores.backward(torch.randn(scores.shape, generator=torch.Generator().manual_seed(11)).half().to(dev))
+            row = {"scores": sha(scores)}
+            row.update({"grad " + k: sha(p.grad) for k, p in model.named_parameters()})
+            row.update({k: sha(b) for k, b in model.named_buffers() if k.rsplit(".", 1)[-1] in ("running_mean", "running_var", "num_batches_tracked")})
+            res[name] = row
     torch.cuda.synchronize()
     line = json.dumps(res, sort_keys=True)
     print(line)
